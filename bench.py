@@ -9,7 +9,8 @@ with the four onesweep passes behind it as the device-side fallback; which of th
 read back from the device and stated, `roofline.plan_proof`) of one batch of synthetic input:
 N = 2^25 uniform-random u32 keys (BASELINE.json configs[1]); the key+value figure (configs[2]) is
 measured the same way and reported in the same JSON line under "key_value".  Inputs are resident
-in HBM before the timed region starts: every step sorts its own pre-generated array in place, so
+in HBM before the timed region starts: every step sorts a device-side copy of one of at most 32
+pre-generated arrays (the same array again only 32 steps later), made with the clock stopped, so
 the timed region holds exactly K sorts and nothing else (the reference likewise excludes upload
 and read-back: bench/vulkan_benchmark.cc:267-290,306-316, and uses fresh data per run:
 bench/bench.cc:83-84).
@@ -22,8 +23,11 @@ all-equal, all-0xFFFFFFFF, descending, ascending, few-distinct(4), 24-bit keys; 
 keys, the device's verdict, parity with values = iota -- under "adversarial".  The key+value half of the metric is
 `value_key_value` at the top level, next to `value`.
 
-Host memory is O(1) in --steps: the input streams are generated a few at a time on host threads, uploaded
-and freed; the pristine copies live on the device.
+Host and device memory are O(1) in --steps: the input streams are generated a few at a time on host threads,
+uploaded and freed; the pristine copies live on the device.
+
+--dump-outputs DIR writes what the last timed step returned (see parse_args); with the same arguments the inputs
+are the same in every run, so two builds' files compare output for output.
 
 With --gpus N > 1 this is the batched many-arrays variant (BASELINE.json configs[4]): one rank per
 GPU, every rank sorts its own independent arrays through vulkan_radix_sort_amd.batched
@@ -61,6 +65,10 @@ def parse_args():
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-sweep", action="store_true")   # only the headline region and the roofline
     p.add_argument("--no-adversarial", action="store_true")   # (with --no-sweep: every launch a profiler sees is a headline sort)
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed step of each mode returned (rank 0) as DIR/keys.npy, "
+                        "DIR/key_value_keys.npy and DIR/key_value_values.npy, float64; above 2^21 elements a fixed "
+                        "seeded sample of 2^21 positions, in ascending order")
     return p.parse_args()
 
 
@@ -87,6 +95,24 @@ def random_u32(torch, n, seed, device):
 
 
 GENERATOR_THREADS = 2   # streams in flight on the host at a time: 2 x 256 MiB at N = 2^25 (peak RSS 2.0 GiB, of which the runtime is most)
+STEP_STREAMS = 32       # input streams the warm-up and timed steps cycle through: 8 GiB pristine at N = 2^25, whatever --steps is
+STEP_ARRAYS = 128       # arrays the steps sort (copies of those streams): the clock stops to refill them every 128 steps
+DUMP_ELEMENTS = 1 << 21  # elements per --dump-outputs array: 3 x 16 MiB of float64
+
+
+def dump_positions(n):
+    """Positions of the output that --dump-outputs writes: all of them up to DUMP_ELEMENTS, else a fixed seeded sample
+    (the same for every build, so that two builds' files compare element for element)."""
+    import numpy as np
+    if n <= DUMP_ELEMENTS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, DUMP_ELEMENTS, replace=False))
+
+
+def write_outputs(directory, outputs):
+    import numpy as np
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float64))   # u32 is exact in float64
 
 
 def upload_streams(torch, n, seeds, device):
@@ -105,35 +131,59 @@ def upload_streams(torch, n, seeds, device):
     return keys, values
 
 
-def timed_sorts(torch, dist, executor, pristine, n, steps, warmup, key_value, device, distributed):
-    """Returns (wall_seconds_for_K_steps_max_over_ranks, per-step gpu ms list of this rank).
+def timed_sorts(torch, dist, executor, pristine, steps, warmup, key_value, device, distributed, dump_index=None):
+    """Returns (wall_seconds_for_K_steps_max_over_ranks, per-step gpu ms list of this rank, plan proof, outputs).
     Every sort goes through the batched front end's per-GPU executor (one array per step and rank).
-    pristine = (keys, values) device tensors, one pair per step: the keys-only measurement sorts device-side copies,
-    the key+value measurement (which runs last) the pristine arrays themselves."""
-    total = warmup + 2 * steps
-    if key_value:
-        keys, values = pristine[0][:total], pristine[1][:total]
-    else:
-        keys, values = [k.clone() for k in pristine[0][:total]], None
+    pristine = (keys, values) device tensors that are never sorted: step i sorts a device-side copy of pair
+    i % len(pristine[0]), held in work array i % STEP_ARRAYS.  The copies for a run of at most STEP_ARRAYS consecutive
+    steps are made before the run, with the clock stopped, so the timed region holds exactly K sorts and nothing else
+    and device memory does not grow with K.
+    outputs = what the last timed step computed, the keys (and the values for key+value) at the positions dump_index,
+    as host uint32 arrays; None without dump_index."""
+    streams = len(pristine[0])
+    slots = min(warmup + 2 * steps, STEP_ARRAYS)
+    keys = [torch.empty_like(pristine[0][0]) for _ in range(slots)]
+    values = [torch.empty_like(pristine[1][0]) for _ in range(slots)] if key_value else None
 
     def one(i):
-        executor.enqueue([(keys[i], values[i] if key_value else None)])  # vrdxCmdSort[KeyValue]: never blocks
+        s = i % slots
+        executor.enqueue([(keys[s], values[s] if key_value else None)])  # vrdxCmdSort[KeyValue]: never blocks
 
-    for i in range(warmup):
-        one(i)
+    def runs(lo, hi):
+        """Steps lo..hi-1 in runs of at most `slots` (no work array twice in a run), each run's inputs copied first."""
+        for a in range(lo, hi, slots):
+            b = min(hi, a + slots)
+            for i in range(a, b):
+                keys[i % slots].copy_(pristine[0][i % streams])
+                if key_value:
+                    values[i % slots].copy_(pristine[1][i % streams])
+            torch.cuda.synchronize()
+            yield a, b
+
+    for a, b in runs(0, warmup):
+        for i in range(a, b):
+            one(i)
     torch.cuda.synchronize()
     counters_before = executor.plan_counters()   # (outside the timed region)
-    if distributed:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for s in range(steps):      # the timed region: exactly K sorts, nothing else on the stream
-        one(warmup + s)
-    torch.cuda.synchronize()
-    if distributed:
-        dist.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    elapsed = 0.0
+    for a, b in runs(warmup, warmup + steps):
+        if distributed:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(a, b):      # the timed region: exactly these sorts, nothing else on the stream
+            one(i)
+        torch.cuda.synchronize()
+        if distributed:
+            dist.barrier()
+        torch.cuda.synchronize()
+        elapsed += time.perf_counter() - t0
+    outputs = None
+    if dump_index is not None:
+        last = (warmup + steps - 1) % slots
+        outputs = {"keys": keys[last][dump_index].cpu().numpy().view("uint32")}
+        if key_value:
+            outputs["values"] = values[last][dump_index].cpu().numpy().view("uint32")
     # What the DEVICE made of the plan the host recorded, for every sort of the timed region: the sorter counts the MSD plans
     # it records and the device counts those it turns down (vrdxHipReadPlanCounters); the last sort's verdict word as well.
     counters_after = executor.plan_counters()
@@ -144,10 +194,11 @@ def timed_sorts(torch, dist, executor, pristine, n, steps, warmup, key_value, de
     # the timed region, each between two events on the sort's stream
     starts = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
     ends = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
-    for s in range(steps):
-        starts[s].record()
-        one(warmup + steps + s)
-        ends[s].record()
+    for a, b in runs(warmup + steps, warmup + 2 * steps):
+        for i in range(a, b):
+            starts[i - warmup - steps].record()
+            one(i)
+            ends[i - warmup - steps].record()
     torch.cuda.synchronize()
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -159,12 +210,12 @@ def timed_sorts(torch, dist, executor, pristine, n, steps, warmup, key_value, de
         from vulkan_radix_sort_amd.batched import describe_status
         raise RuntimeError(f"sorter status 0x{status:08x}: {describe_status(status)}")
     # the last step's output must be sorted (cheap sanity check outside the timed region)
-    k = keys[-1].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    k = keys[(warmup + 2 * steps - 1) % slots].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
     if not bool((k[1:] >= k[:-1]).all()):
         raise RuntimeError("output not sorted")
-    del keys, values
+    del keys, values, k
     torch.cuda.empty_cache()
-    return elapsed, per_step_ms, proof
+    return elapsed, per_step_ms, proof, outputs
 
 
 def stage_profile(torch, sorter, pristine, n, key_value, device, repeats=5):
@@ -498,35 +549,22 @@ def kernel_source_digest():
 
 
 def visible_gpu_count():
-    """GPUs this process could use, WITHOUT touching a GPU runtime (torch.cuda.device_count() may initialise HIP in
-    the parent of the ranks): the KFD topology in sysfs (nodes with SIMDs are GPUs), narrowed by
-    HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES when set.  None when sysfs says nothing; the ranks then check
-    themselves (a world size that differs from --gpus is exit code 2, see main())."""
-    import glob
-    count = 0
-    if not os.path.isdir("/sys/class/kfd"):
-        return 0  # no amdgpu compute driver on this machine at all
-    nodes = glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties")
-    if not nodes:
+    """GPUs the ranks will see: torch.cuda.device_count() -- the count every rank checks itself against, see main() --
+    asked in a short-lived child process, so that this process never touches a GPU runtime.  (The KFD topology in sysfs
+    is no substitute: it lists every GPU of the node, also those this process cannot open.)  None when the child
+    fails; the ranks then check themselves (a world size that differs from --gpus is exit code 2)."""
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True,
+                       text=True, timeout=600)
+    try:
+        return int(r.stdout.split()[-1])
+    except (IndexError, ValueError):
         return None
-    for path in nodes:
-        try:
-            with open(path) as f:
-                for line in f:
-                    if line.startswith("simd_count") and int(line.split()[1]) > 0:
-                        count += 1
-        except (OSError, ValueError):
-            return None
-    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):
-        listed = os.environ.get(var)
-        if listed is not None:
-            count = min(count, len([x for x in listed.split(",") if x.strip() != ""]))
-    return count
 
 
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N ranks (torch.distributed.run) as a CHILD
-    process -- this process imports neither torch nor the HIP library (the GPUs are counted in sysfs), so it
+    process -- this process imports neither torch nor the HIP library (the GPUs are counted in a child process), so it
     never touches a GPU -- and exit with the child's code.  (Never exec from a process that holds a GPU context.)"""
     import socket
     import subprocess
@@ -583,20 +621,32 @@ def main():
     batch = BatchedSorter(executor=executor)
 
     # Inputs: seeds 1, 2, ... like the reference's runs (bench/bench.cc:83-84), other ranks continue the sequence;
-    # warm-up | the K timed steps | K more, each bracketed by events -- and, on the rank that reports the curve,
-    # CURVE_STREAMS more that are only ever copied from (size curve, stage profile, the 2^27 point).
+    # warm-up | the K timed steps | K more, each bracketed by events, cycling through at most STEP_STREAMS streams -- and,
+    # on the rank that reports the curve, CURVE_STREAMS more that are only ever copied from (size curve, stage profile,
+    # the 2^27 point).
     total = args.warmup + 2 * args.steps
+    streams = min(total, STEP_STREAMS)
     extras = rank == 0 and n_gpus == 1
     CURVE_STREAMS = 11
-    seed0 = 1 + (total + CURVE_STREAMS) * rank
+    seed0 = 1 + (streams + CURVE_STREAMS) * rank
+    dump_index = None
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)   # (a bad directory fails here, not after the measurement)
+        dump_index = torch.from_numpy(dump_positions(n)).to(device)
     t_setup = time.perf_counter()
-    pristine = upload_streams(torch, n, list(range(seed0, seed0 + total + (CURVE_STREAMS if extras else 2))), device)
+    pristine = upload_streams(torch, n, list(range(seed0, seed0 + streams + (CURVE_STREAMS if extras else 2))), device)
     setup_s = time.perf_counter() - t_setup
     to_first_region_s = time.perf_counter() - t_process   # start of main() -> inputs resident, first barrier next
     rss_inputs_mib = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
-    fresh = (pristine[0][total:], pristine[1][total:])   # never sorted in place
-    wall_keys, steps_keys, proof_keys = timed_sorts(torch, dist, executor, pristine, n, args.steps, args.warmup, False, device, distributed)
-    wall_kv, steps_kv, proof_kv = timed_sorts(torch, dist, executor, pristine, n, args.steps, args.warmup, True, device, distributed)
+    steps_in = (pristine[0][:streams], pristine[1][:streams])
+    fresh = (pristine[0][streams:], pristine[1][streams:])   # never sorted in place
+    wall_keys, steps_keys, proof_keys, out_keys = timed_sorts(torch, dist, executor, steps_in, args.steps, args.warmup, False,
+                                                              device, distributed, dump_index)
+    wall_kv, steps_kv, proof_kv, out_kv = timed_sorts(torch, dist, executor, steps_in, args.steps, args.warmup, True,
+                                                      device, distributed, dump_index)
+    if dump_index is not None:
+        write_outputs(args.dump_outputs, {"keys": out_keys["keys"], "key_value_keys": out_kv["keys"],
+                                          "key_value_values": out_kv["values"]})
     stamped_keys = stage_profile(torch, sorter, fresh, n, False, device, repeats=5 if extras else 1)
     stamped_kv = stage_profile(torch, sorter, fresh, n, True, device, repeats=5 if extras else 1)
     # ONE definition of a launch duration on this line: the event interval around the kernel minus what a pair of event
@@ -767,7 +817,7 @@ def main():
         result["sweep_protocol"] = ("bench/bench.cc:15-20,66-112: 1 warm-up + 10 timed sorts of fresh std::mt19937 data per "
                                     "size and mode, median, GPU time between two events around the sort; measured on " + box +
                                     " in %.1f s" % (time.perf_counter() - t_curve))
-    del pristine, fresh
+    del pristine, steps_in, fresh
     if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(n)
     result["setup"]["peak_rss_mib"] = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0   # (Linux: KiB; incl. the cpu_baseline leg)

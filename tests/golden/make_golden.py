@@ -67,6 +67,21 @@ def main():
         })
         print("hashed", seed, n, bits, flush=True)
 
+    # the reference's outputs on the inputs of tests/test_oracle.py's parity checks, as checksums
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_oracle import BENCH_STREAMS, reference_parity_inputs
+    parity = []
+    for case, (k, v) in reference_parity_inputs(ref.generate).items():
+        kk, kv, _ = ref.sort_key_value(k, v)
+        sk, _ = ref.sort_keys(k)
+        parity.append({"case": case, "input_keys_hash": f"{orc.hash(k):016x}", "input_values_hash": f"{orc.hash(v):016x}",
+                       "sorted_keys_hash": f"{orc.hash(kk):016x}", "sorted_values_hash": f"{orc.hash(kv):016x}",
+                       "keys_only_sorted_hash": f"{orc.hash(sk):016x}"})
+    streams = []
+    for seed, n in BENCH_STREAMS:
+        k, v = ref.generate(seed, n, 32)
+        streams.append({"seed": seed, "n": n, "keys_hash": f"{orc.hash(k):016x}", "values_hash": f"{orc.hash(v):016x}"})
+
     # storage-size table from the reference formulas (src/vk_radix_sort.h.in:279-308); the values
     # are also listed in SURVEY.md section 8(a3).  Computed here by the oracle restatement and
     # cross-checked against the survey's hand-derived numbers below.
@@ -84,7 +99,8 @@ def main():
         json.dump({"generator": "tests/golden/make_golden.py",
                    "source": "reference bench/cpu_benchmark.cc + bench/data_generator.cc via oracle/_ref",
                    "hash": "FNV-1a 64 over little-endian uint32 words",
-                   "vectors": index, "hashes": hashes, "storage_align16": storage, "usage": 0x22}, f, indent=1)
+                   "vectors": index, "hashes": hashes, "storage_align16": storage, "usage": 0x22,
+                   "reference_parity": parity, "reference_streams": streams}, f, indent=1)
     print("wrote", len(index), "vector cases,", len(hashes), "hash cases")
 
 

@@ -204,6 +204,33 @@ def test_bench_py_reports_the_ranks_it_ran_and_refuses_a_mismatch():
     assert line["roofline"]["bound"] == "hbm" and 0 < line["roofline"]["frac"] < 1
 
 
+def test_bench_py_dumps_what_its_last_timed_step_returned(tmp_path, oracle):
+    """`bench.py --dump-outputs DIR`: the keys-only and key+value outputs of the last timed step (step warmup + steps - 1,
+    i.e. seed 4 here), as float64 at bench.dump_positions(n), equal to the oracle's stable sort of that step's input."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--log2n", "22", "--no-cpu-baseline", "--no-sweep", "--no-adversarial", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    n = 1 << 22
+    at = bench.dump_positions(n)
+    assert len(at) == bench.DUMP_ELEMENTS < n
+    keys, values = bench.reference_stream(4, n)
+    ek, ev, _ = oracle.sort(keys, values)
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert sorted(files) == ["key_value_keys.npy", "key_value_values.npy", "keys.npy"]
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype == np.float64 and a.shape == at.shape for a in files.values())
+    assert np.array_equal(files["keys.npy"], ek[at]) and np.array_equal(files["key_value_keys.npy"], ek[at])
+    assert np.array_equal(files["key_value_values.npy"], ev[at])
+
+
 def test_bench_driver_batched_mode_in_cpp():
     """bench hip --devices G: one host process, one sorter + stream + storage per GPU, ncclAllGather of the
     per-GPU records; checked against the cpu backend (array 0 of every GPU) and by sortedness + checksum."""

@@ -2,8 +2,8 @@
 
 1. against the committed golden vectors, which were produced by the REFERENCE's own CPU backend
    (tests/golden/make_golden.py -> bench/cpu_benchmark.cc, bench/data_generator.cc);
-2. against oracle/_ref itself wherever that library exists (authoring container, or shipped to
-   the GPU box), on randomized inputs;
+2. against checksums of the reference's outputs on randomized and adversarial inputs (also produced by
+   make_golden.py), and against oracle/_ref itself wherever that library exists;
 3. against the storage-size table of SURVEY.md section 8(a3).
 """
 import os
@@ -123,41 +123,63 @@ def test_oracle_sentinel_keys_and_histogram(oracle):
         assert np.array_equal(hist[p].astype(np.int64), excl)
 
 
-def test_oracle_matches_reference_build(oracle, reference):
-    if reference is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
+BENCH_STREAMS = ((1, 1000), (42, 4097), (7, 65539))
+
+
+def reference_parity_inputs(generate):
+    """The inputs of the parity check against the reference's CPU backend, name -> (keys, values): seeded streams of
+    `generate(seed, n, bits)` (the oracle's DataGenerator port here, the reference's own in tests/golden/make_golden.py)
+    and adversarial keys with values = iota."""
     rng = np.random.default_rng(2)
+    cases = {}
     for seed, n, bits in [(3, 0, 32), (3, 1, 32), (9, 4097, 32), (9, 100003, 32), (4, 65539, 6), (4, 300000, 32)]:
-        k, v = oracle.generate(seed, n, bits)
-        rk, rv = reference.generate(seed, n, bits)
-        assert np.array_equal(k, rk) and np.array_equal(v, rv)
-        sk, sv, _ = oracle.sort(k, v)
-        rsk, rsv, _ = reference.sort_key_value(k, v)
-        assert np.array_equal(sk, rsk) and np.array_equal(sv, rsv)
-        assert np.array_equal(oracle.sort(k)[0], reference.sort_keys(k)[0])
-    # adversarial inputs
+        cases[f"s{seed}_n{n}_b{bits}"] = generate(seed, n, bits)
     n = 50000
-    for k in (np.full(n, 0x12345678, np.uint32), np.full(n, 0xFFFFFFFF, np.uint32),
-              np.arange(n, dtype=np.uint32)[::-1].copy(),
-              rng.choice(np.array([0, 1, 0x80000000, 0xFFFFFFFF], np.uint32), size=n)):
-        v = np.arange(n, dtype=np.uint32)
+    for name, k in (("all-equal", np.full(n, 0x12345678, np.uint32)), ("all-0xFFFFFFFF", np.full(n, 0xFFFFFFFF, np.uint32)),
+                    ("descending", np.arange(n, dtype=np.uint32)[::-1].copy()),
+                    ("four-distinct", rng.choice(np.array([0, 1, 0x80000000, 0xFFFFFFFF], np.uint32), size=n))):
+        cases[name] = (k, np.arange(n, dtype=np.uint32))
+    return cases
+
+
+def test_oracle_matches_reference_build(oracle, reference, golden):
+    """Against the reference's own outputs on the same inputs: their checksums in golden.json (make_golden.py ran the
+    reference's CPU backend), and oracle/_ref itself wherever that library exists."""
+    cases = reference_parity_inputs(oracle.generate)
+    rows = golden["reference_parity"]
+    assert [row["case"] for row in rows] == list(cases)
+    for row in rows:
+        k, v = cases[row["case"]]
+        # the same inputs the reference sorted (for the seeded cases: the reference's generator made them)
+        assert f"{oracle.hash(k):016x}" == row["input_keys_hash"], row["case"]
+        assert f"{oracle.hash(v):016x}" == row["input_values_hash"], row["case"]
         sk, sv, _ = oracle.sort(k, v)
-        rsk, rsv, _ = reference.sort_key_value(k, v)
-        assert np.array_equal(sk, rsk) and np.array_equal(sv, rsv)
+        assert f"{oracle.hash(sk):016x}" == row["sorted_keys_hash"], row["case"]
+        assert f"{oracle.hash(sv):016x}" == row["sorted_values_hash"], row["case"]
+        assert f"{oracle.hash(oracle.sort(k)[0]):016x}" == row["keys_only_sorted_hash"], row["case"]
+        if reference is not None:
+            rsk, rsv, _ = reference.sort_key_value(k, v)
+            assert np.array_equal(sk, rsk) and np.array_equal(sv, rsv)
+            assert np.array_equal(oracle.sort(k)[0], reference.sort_keys(k)[0])
 
 
-def test_bench_input_stream_is_the_reference_generator(oracle, reference):
+def test_bench_input_stream_is_the_reference_generator(oracle, reference, golden):
     """bench.py generates its inputs itself (it may touch the oracle only in its cpu_baseline leg): its stream must be
     the reference generator's -- keys = the first N raw mt19937(seed) outputs, values = the next N
-    (bench/data_generator.cc:20-25)."""
+    (bench/data_generator.cc:20-25): checksums of the reference generator's streams in golden.json, and oracle/_ref
+    itself wherever that library exists."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
-    for seed, n in ((1, 1000), (42, 4097), (7, 65539)):
+    rows = golden["reference_streams"]
+    assert [(row["seed"], row["n"]) for row in rows] == list(BENCH_STREAMS)
+    for row in rows:
+        seed, n = row["seed"], row["n"]
         k, v = bench.reference_stream(seed, n)
         ok, ov = oracle.generate(seed, n, 32)
         assert k.dtype == np.uint32 and np.array_equal(k, ok) and np.array_equal(v, ov)
+        assert f"{oracle.hash(k):016x}" == row["keys_hash"] and f"{oracle.hash(v):016x}" == row["values_hash"], row
         if reference is not None:
             rk, rv = reference.generate(seed, n, 32)
             assert np.array_equal(k, rk) and np.array_equal(v, rv)
