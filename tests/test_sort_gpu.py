@@ -657,7 +657,7 @@ def test_tail_split_tiles_at_their_boundaries(torch_mod, sorter, oracle, n, key_
                                          (12_000_001, False), (12_000_001, True), (MSD_HALF_UP_TO, True),
                                          (MSD_HALF_UP_TO + 1, False), (MSD_HALF_UP_TO + 1, True), (20_000_003, True),
                                          (1 << 25, False), (1 << 25, True), (36_500_000, False), (37_000_001, False),
-                                         (45_000_000, True)])
+                                         (45_000_000, True), (1 << 26, False), (1 << 26, True)])
 def test_msd_plan_and_its_fallback_at_the_bucket_capacity(torch_mod, sorter, oracle, n, key_value):
     """Sorts of 8.15 M elements and more record the MSD plan in front of their four passes (vrdx_kernels.hip, "MSD plan"):
     per-tile counts of the top ten or eleven bits, a spine, ONE stable scatter by those bits and one workgroup per bucket
@@ -666,7 +666,7 @@ def test_msd_plan_and_its_fallback_at_the_bucket_capacity(torch_mod, sorter, ora
     keys with ONE bucket brought to exactly the capacity (the plan applies: word 1 of the storage says 3) and to one more
     (it does not), keys-only or key+value (values = iota: the permutation itself), direct and indirect with a smaller
     device-side count; the first sizes of the plan, one round of tiles, both sides of the switch between the two bucket
-    kernels, the headline size, the last ten-bit and first eleven-bit sizes."""
+    kernels, the headline size, the last ten-bit and first eleven-bit sizes, and the plan's last size (2^26: 2048 tiles)."""
     info = sorter.describe_plan(n, key_value)
     assert info.name == "msd" and info.bits == (10 if n <= 36_600_000 else 11), (info.name, info.bits)
     bits = int(info.bits)

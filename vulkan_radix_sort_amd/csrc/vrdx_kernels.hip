@@ -1091,13 +1091,14 @@ __device__ __forceinline__ void OnesweepBody(const OnesweepArgs a) {
 
   // Launches 1-3 of a sort whose hybrid plan applies have nothing to do, and launch 0 has said so in one word: they
   // return after one load instead of after the table, the ticket, the votes and a barrier (4 -> 2 us per empty launch).
-  // (Not compiled into the key+value 1024x32 form with tiles of full capacity, the kernel of the 2^25 headline: the two
-  // lines cost it two registers and 1.7 % there, measured.  Key+value sorts of 4.4 ... 8.1 M pairs do meet that form
-  // with the hybrid plan recorded: their launches 1-3 take the long way to the same verdict, ~2 us each.  Running them on
-  // the form with run-time slot counts instead -- which has the word, but fetches its values late -- measured the same
-  // within 1 %, VRDX_EVEN_SPLIT=1, so they stay on this one.)
-  constexpr bool kVerdictWord = !(KV && KPT == 32 && !DYN);
-  if constexpr (kVerdictWord) {
+  // (That early return is not compiled into the key+value 1024x32 form with tiles of full capacity, the kernel of the 2^25
+  // headline: with it the form took two registers more and 1.7 % there, measured.  Key+value sorts of 4.4 ... 8.1 M pairs
+  // do meet that form with the hybrid plan recorded: their launches 1-3 take the long way to the same verdict, ~2 us each.
+  // Running them on the form with run-time slot counts instead -- which has the return, but fetches its values late --
+  // measured the same within 1 %, VRDX_EVEN_SPLIT=1, so they stay on this one.  Launch 0 of EVERY form writes the verdict
+  // below: vrdxHipReadPlanVerdict reports it.)
+  constexpr bool kVerdictReturn = !(KV && KPT == 32 && !DYN);
+  if constexpr (kVerdictReturn) {
     if (a.hybridCap != 0 && a.pass != 0 && *a.planWord == 1u) return;
   }
   // the MSD plan (recorded in front of launch 0) has taken the sort: nothing left for the passes
@@ -1122,10 +1123,8 @@ __device__ __forceinline__ void OnesweepBody(const OnesweepArgs a) {
 
   const uint32_t tile = misc[0];
   const PassPlan plan = ReadPassPlan(planFlags, a.pass, a.hybridCap);
-  if constexpr (kVerdictWord) {
-    if (a.hybridCap != 0 && a.pass == 0 && tile == 0 && tid == 0)  // the verdict, for the launches behind this one
-      *a.planWord = HybridByte(planFlags, a.hybridCap) >= 0 ? 1u : 2u;
-  }
+  if (a.hybridCap != 0 && a.pass == 0 && tile == 0 && tid == 0)  // the verdict, for the launches behind this one
+    *a.planWord = HybridByte(planFlags, a.hybridCap) >= 0 ? 1u : 2u;
   const uint32_t shift = 8u * plan.digit;
   const uint32_t* const keysIn = plan.fromScratch ? a.keysScratch : a.keysCaller;
   uint32_t* const keysOut = plan.fromScratch ? a.keysCaller : a.keysScratch;
