@@ -182,6 +182,44 @@ void vrdxCmdSortKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorte
                                  VkDeviceSize valuesOffset, VkBuffer storageBuffer,
                                  VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
 
+/**
+ * Segmented sort (not part of the reference API): segmentCount independent arrays in one recorded call.
+ *
+ * Offsets: offsetsBuffer + offsetsOffset holds segmentCount + 1 uint32 offsets o[] in CSR form; segment i is the elements
+ * [o[i], o[i+1]) of keysBuffer (and valuesBuffer).  The offsets are read ON THE DEVICE when the sort runs, never by the host:
+ * the call does not block, and a sort captured into a hipGraph may be replayed on another segmentation with the same
+ * segmentCount.
+ * Order: every segment is sorted ascending as uint32, stably; values travel with their keys.  Elements before o[0] and from
+ * o[segmentCount] on are not touched.
+ * Storage: what vrdxGetSorter[KeyValue]StorageRequirements(maxElementCount) returns; one sort in flight per storage.
+ * Bad offsets: a segment with o[i] > o[i+1] or o[i+1] > maxElementCount is left alone and the sort raises
+ * VRDX_HIP_STATUS_SEGMENTS_INVALID in the storage's failure word (vrdxHipReadStatus) and in the sorter's word
+ * (vrdxHipReadSorterStatus).  Any offsets that are not monotone raise it, so a clear bit means every segment was sorted (with
+ * the bit raised, valid segments that overlap each other are unspecified).  Nothing is ever written outside
+ * [0, maxElementCount) of the caller's arrays or outside the storage requirement.
+ * segmentCount == 0 or maxElementCount == 0 records nothing but the timestamps; maxElementCount > 2^30 - 4 is clamped
+ * (VRDX_HIP_STATUS_COUNT_CLAMPED).  Word 1 of the storage reads VRDX_HIP_VERDICT_NONE after the sort.
+ * Sizes are classed on the device: up to 4096 elements one 256-thread workgroup sorts the segment in LDS, up to 16384 one
+ * 1024-thread workgroup, beyond that one workgroup runs an LSD sort through memory (the segment's index range of the
+ * storage's scratch arrays) -- a few segments of millions of keys are faster with one vrdxCmdSort each.
+ *
+ * Timestamps (all 15 slots recorded; ts[14] - ts[0] is the sort):
+ *   [0,1] the fill of the storage header and list counters
+ *   [1,2] the 256-thread launch over every segment (sorts those of <= 4096 elements, lists the others)
+ *   [2,3] the 1024-thread in-LDS launch over the listed segments of 4097 ... 16384 elements (3 == 2 when maxElementCount < 4097)
+ *   [3,4] the launch over the listed segments of more than 16384 elements (4 == 3 when maxElementCount < 16385)
+ *   slots 5 ... 14 coincide with slot 4
+ */
+void vrdxHipCmdSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                             uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                             VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
+                             VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                     uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                     VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                     VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                     VkQueryPool queryPool, uint32_t query);
+
 /* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves
  * (vkCreateQueryPool / vkGetQueryPoolResults, bench/vulkan_benchmark.cc:195-198,318-321).
@@ -216,6 +254,7 @@ uint32_t vrdxHipReadSorterStatus(VrdxSorter sorter, VkCommandBuffer commandBuffe
  * them never read -- the vrdxCmdSort* entry points return void like the reference's, so nothing fails silently): */
 #define VRDX_HIP_STATUS_LOOKBACK_GAVE_UP 0x00000001u /* a bounded look-back spin expired: that sort's result is unspecified */
 #define VRDX_HIP_STATUS_RANK_ORDER       0x00000002u /* the periodic repeat of the LDS lane-order check failed: vrdxHipRecheck */
+#define VRDX_HIP_STATUS_SEGMENTS_INVALID 0x00000004u /* a segmented sort met offsets that decrease or end behind maxElementCount: those segments were left alone */
 #define VRDX_HIP_STATUS_COUNT_CLAMPED    0x40000000u /* elementCount > 2^30 - 4 (where the reference's uint32 size math wraps, src/vk_radix_sort.h.in:105-115): the first 2^30 - 4 elements were sorted, the rest left alone */
 #define VRDX_HIP_STATUS_ENQUEUE_REFUSED  0x80000000u /* the HIP runtime refused a fill, copy or launch of a sort */
 

@@ -68,6 +68,12 @@ def expected_kernels():
         for kv in (0, 1):
             for atomic in (0, 1):
                 names.append("_ZN4vrdx17small_sort_kernelILi%dELi16ELb%dELb%dEEEvPjS1_jPKjS1_" % (threads, kv, atomic))
+    # the segmented sort: in-LDS forms of 4096 and 16384 elements, one LSD sort through memory per large segment
+    names.append("_ZN4vrdx22segmented_clear_kernelENS_13SegmentedArgsE")
+    for kernel in ("22segmented_small_kernel", "20segmented_mid_kernel", "22segmented_large_kernel"):
+        for kv in (0, 1):
+            for atomic in (0, 1):
+                names.append("_ZN4vrdx%sILb%dELb%dEEEvNS_13SegmentedArgsE" % (kernel, kv, atomic))
     return names
 
 

@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""Times three ways of sorting many independent arrays packed back to back (CSR offsets) on one GPU:
+
+  segmented   one vrdxHipCmdSortSegmented[KeyValue] call (vulkan_radix_sort_amd.sort_segments)
+  per_array   one vrdxCmdSort[KeyValue] per segment on one stream and storage -- what HipShardExecutor.enqueue does today
+  torch_sort  torch.sort(stable=True) of the packed int64 (segment << 32) | key, unpacked again (values gathered by the
+              returned indices)
+
+Every step sorts fresh keys (seeded, generated on the device outside the timed region); the time of a step is the device
+event interval around the enqueue of the whole job, so a host-bound loop of enqueues is charged what it costs.  Each shape
+prints ONE JSON line; the segmented result of the last step is compared with the torch_sort result (`"match"`).
+
+usage: python tools/segmented_bench.py [--shapes 65536x256,8192x2048,...,mixed] [--steps 5] [--warmup 2] [--loop-steps 3]
+       [--modes keys,kv] [--only segmented] [--out FILE]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+DEFAULT_SHAPES = "65536x256,8192x2048,1024x16384,64x262144,4x4194304,mixed"
+
+
+def segment_sizes(shape, rng):
+    """Sizes of the segments of a shape: 'SxL' = S segments of L keys; 'mixed' = sizes log-uniform in [1, 100000] (every
+    16th segment empty) until about 2^24 keys."""
+    if shape == "mixed":
+        sizes, total = [], 0
+        while total < (1 << 24):
+            s = 0 if len(sizes) % 16 == 15 else int(math.exp(rng.uniform(0.0, math.log(100000.0))))
+            s = min(s, (1 << 24) - total) if total + s > (1 << 24) else s
+            sizes.append(s)
+            total += s
+        return np.array(sizes, dtype=np.int64)
+    count, length = (int(x) for x in shape.split("x"))
+    return np.full(count, length, dtype=np.int64)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default=DEFAULT_SHAPES)
+    ap.add_argument("--modes", default="keys,kv")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--loop-steps", type=int, default=3, help="timed steps of the per-array loop (slow for many segments)")
+    ap.add_argument("--only", default="", help="comma list of the ways to run (default: all three)")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+
+    import torch
+    import vulkan_radix_sort_amd as vrdx
+
+    if not torch.cuda.is_available():
+        sys.exit("segmented_bench.py needs a GPU (there is no CPU fallback)")
+    torch.cuda.set_device(0)
+    sorter = vrdx.Sorter(0)
+    ways = [w for w in ("segmented", "per_array", "torch_sort") if not args.only or w in args.only.split(",")]
+    out = open(args.out, "a") if args.out else None
+
+    for shape in args.shapes.split(","):
+        rng = np.random.default_rng(args.seed)
+        sizes = segment_sizes(shape, rng)
+        offsets_h = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        n = int(offsets_h[-1])
+        offsets = torch.from_numpy(offsets_h.astype(np.uint32).view(np.int32)).cuda()
+        seg_ids = torch.from_numpy(np.repeat(np.arange(len(sizes), dtype=np.int64), sizes)).cuda()
+        starts = [int(x) for x in offsets_h[:-1]]
+        lengths = [int(x) for x in sizes]
+        for mode in args.modes.split(","):
+            kv = mode == "kv"
+            keys = torch.empty(n, dtype=torch.int32, device="cuda")
+            values = torch.empty(n, dtype=torch.int32, device="cuda") if kv else None
+            req = (sorter.key_value_storage_requirements(n) if kv else sorter.storage_requirements(n)).size
+            storage = torch.empty(req, dtype=torch.uint8, device="cuda")
+            # the per-array loop's storage: the largest single sort's requirement
+            big = max(lengths) if lengths else 0
+            loop_storage = torch.empty(max(16, (sorter.key_value_storage_requirements(big) if kv
+                                                else sorter.storage_requirements(big)).size), dtype=torch.uint8, device="cuda")
+            gen = torch.Generator(device="cuda")
+            stream = torch.cuda.current_stream()
+
+            def fresh(step):
+                gen.manual_seed(args.seed * 1000003 + step)
+                keys.copy_(torch.randint(-(1 << 31), 1 << 31, (n,), dtype=torch.int64, device="cuda", generator=gen).to(torch.int32))
+                if kv:
+                    values.copy_(torch.arange(n, dtype=torch.int32, device="cuda"))
+
+            def run_segmented():
+                vrdx.sort_segments(sorter, keys, offsets, values=values, storage=storage)
+
+            def run_per_array():
+                s = stream.cuda_stream
+                kp, sp = keys.data_ptr(), loop_storage.data_ptr()
+                for b, m in zip(starts, lengths):
+                    if kv:
+                        sorter.cmd_sort_key_value(s, m, kp, 4 * b, values.data_ptr(), 4 * b, sp, 0)
+                    else:
+                        sorter.cmd_sort(s, m, kp, 4 * b, sp, 0)
+
+            torch_out = {}
+
+            def run_torch_sort():
+                packed = (seg_ids << 32) | (keys.to(torch.int64) & 0xFFFFFFFF)
+                sorted_packed, idx = torch.sort(packed, stable=True)
+                torch_out["keys"] = (sorted_packed & 0xFFFFFFFF).to(torch.int32)  # (wraps like the uint32 bit pattern)
+                if kv:
+                    torch_out["values"] = values[idx]
+
+            fns = {"segmented": run_segmented, "per_array": run_per_array, "torch_sort": run_torch_sort}
+            result = {"shape": shape, "segments": len(sizes), "keys": n, "key_value": kv,
+                      "max_segment": big, "empty_segments": int((sizes == 0).sum())}
+            outputs = {}
+            for way in ways:
+                steps = args.loop_steps if way == "per_array" else args.steps
+                times = []
+                for step in range(args.warmup + steps):
+                    fresh(step)
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fns[way]()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if step >= args.warmup:
+                        times.append(e0.elapsed_time(e1))
+                result[way + "_ms"] = float(np.median(times))
+                result[way + "_ms_min"] = float(np.min(times))
+                if way == "segmented":
+                    outputs["segmented"] = (keys.clone(), values.clone() if kv else None)
+                    result["status"] = sorter.read_status(stream.cuda_stream, storage.data_ptr(), 0)
+                elif way == "torch_sort":
+                    outputs["torch_sort"] = (torch_out["keys"], torch_out.get("values"))
+            if "segmented" in outputs and "torch_sort" in outputs:
+                (a, av), (b, bv) = outputs["segmented"], outputs["torch_sort"]
+                result["match"] = bool(torch.equal(a, b) and (not kv or torch.equal(av, bv)))  # (the same seeds: same input)
+            if "segmented_ms" in result:
+                for way in ("per_array", "torch_sort"):
+                    if way + "_ms" in result:
+                        result["speedup_vs_" + way] = result[way + "_ms"] / result["segmented_ms"]
+                result["segmented_gkeys_s"] = n / (result["segmented_ms"] * 1e6)
+            line = json.dumps(result)
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+            del keys, values, storage, loop_storage
+            torch.cuda.empty_cache()
+    if out:
+        out.close()
+    sorter.destroy()
+
+
+if __name__ == "__main__":
+    main()

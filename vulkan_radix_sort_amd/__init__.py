@@ -23,6 +23,7 @@ from .api import (  # noqa: F401
     PLAN_NAMES,
     STATUS_LOOKBACK_GAVE_UP,
     STATUS_RANK_ORDER,
+    STATUS_SEGMENTS_INVALID,
     STATUS_COUNT_CLAMPED,
     STATUS_ENQUEUE_REFUSED,
     VERDICT_NONE,
@@ -31,6 +32,7 @@ from .api import (  # noqa: F401
     VERDICT_MSD_RUNS,
     VERDICT_MSD_SORTED,
 )
+from .segmented import sort_segments  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -47,6 +49,7 @@ __all__ = [
     "PLAN_NAMES",
     "STATUS_LOOKBACK_GAVE_UP",
     "STATUS_RANK_ORDER",
+    "STATUS_SEGMENTS_INVALID",
     "STATUS_COUNT_CLAMPED",
     "STATUS_ENQUEUE_REFUSED",
     "VERDICT_NONE",
@@ -54,4 +57,5 @@ __all__ = [
     "VERDICT_HYBRID8_DECLINED",
     "VERDICT_MSD_RUNS",
     "VERDICT_MSD_SORTED",
+    "sort_segments",
 ]

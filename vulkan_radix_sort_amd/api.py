@@ -13,6 +13,8 @@ reference (C++ / Vulkan)                        here
 ``vrdxCmdSortIndirect``                         ``Sorter.cmd_sort_indirect(...)``
 ``vrdxCmdSortKeyValue``                         ``Sorter.cmd_sort_key_value(...)``
 ``vrdxCmdSortKeyValueIndirect``                 ``Sorter.cmd_sort_key_value_indirect(...)``
+``vrdxHipCmdSortSegmented`` (HIP only)          ``Sorter.cmd_sort_segmented(...)``
+``vrdxHipCmdSortSegmentedKeyValue`` (HIP only)  ``Sorter.cmd_sort_segmented_key_value(...)``
 =============================================  ==============================================
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
@@ -56,11 +58,15 @@ EXPORTED_SYMBOLS = (
     "vrdxHipReadPlanVerdict",
     "vrdxHipReadPlanCounters",
     "vrdxHipVersionString",
+    # many independent arrays in one call
+    "vrdxHipCmdSortSegmented",
+    "vrdxHipCmdSortSegmentedKeyValue",
 )
 
 # bits of vrdxHipReadSorterStatus (include/vk_radix_sort.h)
 STATUS_LOOKBACK_GAVE_UP = 0x00000001
 STATUS_RANK_ORDER = 0x00000002
+STATUS_SEGMENTS_INVALID = 0x00000004
 STATUS_COUNT_CLAMPED = 0x40000000
 STATUS_ENQUEUE_REFUSED = 0x80000000
 
@@ -165,6 +171,10 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxCmdSortKeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
     lib.vrdxCmdSortKeyValueIndirect.restype = None
     lib.vrdxCmdSortKeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortSegmented.restype = None
+    lib.vrdxHipCmdSortSegmented.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortSegmentedKeyValue.restype = None
+    lib.vrdxHipCmdSortSegmentedKeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
     lib.vrdxHipCreateQueryPool.argtypes = [u32, ctypes.POINTER(vp)]
     lib.vrdxHipDestroyQueryPool.restype = None
@@ -313,6 +323,23 @@ class Sorter:
                                               _handle(indirect), indirect_offset, _handle(keys), keys_offset,
                                               _handle(values), values_offset, _handle(storage),
                                               storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_segmented(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
+                           keys_offset, storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSortSegmented``: segment i = elements [o[i], o[i + 1]) of the keys, o = segment_count + 1 uint32
+        offsets read on the device; every segment sorted on its own, in place."""
+        self._lib.vrdxHipCmdSortSegmented(_handle(command_buffer), self.handle, max_element_count, segment_count,
+                                          _handle(offsets), offsets_offset, _handle(keys), keys_offset, _handle(storage),
+                                          storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_segmented_key_value(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset,
+                                     keys, keys_offset, values, values_offset, storage, storage_offset, query_pool=None,
+                                     query=0):
+        """``vrdxHipCmdSortSegmentedKeyValue``: the same with values that travel with their keys."""
+        self._lib.vrdxHipCmdSortSegmentedKeyValue(_handle(command_buffer), self.handle, max_element_count, segment_count,
+                                                  _handle(offsets), offsets_offset, _handle(keys), keys_offset,
+                                                  _handle(values), values_offset, _handle(storage), storage_offset,
+                                                  _pool(query_pool), query)
 
     # -- diagnostics ------------------------------------------------------------------------
     def read_status(self, command_buffer, storage, storage_offset=0) -> int:

@@ -407,6 +407,34 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
   return p;
 }
 
+// Launches go to the sorter's device (a Vulkan command buffer belongs to one device too); the
+// calling thread's current device is put back afterwards.
+struct DeviceScope {
+  int previous = -1;
+  explicit DeviceScope(int wanted) {
+    int current = -1;
+    if (hipGetDevice(&current) == hipSuccess && current != wanted && hipSetDevice(wanted) == hipSuccess)
+      previous = current;
+  }
+  ~DeviceScope() {
+    if (previous >= 0) (void)hipSetDevice(previous);
+  }
+};
+
+// Behind every 65536th sort: 8 workgroups repeat the lane-order check of vrdxCreateSorter (~20 us, never blocks; a
+// mismatch sets VRDX_HIP_STATUS_RANK_ORDER in the sorter's status word, which vrdxHipReadSorterStatus and
+// vrdxDestroySorter report).
+// Not into a stream capture: the check would be baked into the graph and run with every replay.  The count is not
+// advanced then, so the first sort recorded outside a capture makes up for it.
+void MaybeRecheckOrder(VrdxSorter sorter, hipStream_t stream, bool atomicRank) {
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (atomicRank && (sorter->sortsRecorded.load(std::memory_order_relaxed) & 0xFFFFu) == 0xFFFFu &&
+      (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone))
+    return;
+  if (atomicRank && (sorter->sortsRecorded.fetch_add(1u, std::memory_order_relaxed) & 0xFFFFu) == 0xFFFFu)
+    EnqueueCheck(sorter, "lds_order_check_kernel", vrdx::LaunchLdsOrderRecheck(stream, sorter->stickyStatus));
+}
+
 // reference: gpuSort, src/vk_radix_sort.h.in:344-507
 void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount,
                 VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
@@ -424,19 +452,7 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
     sorter->countClamped.store(1u, std::memory_order_relaxed);
   }
 
-  // Launches go to the sorter's device (a Vulkan command buffer belongs to one device too); the
-  // calling thread's current device is put back afterwards.
-  struct DeviceScope {
-    int previous = -1;
-    explicit DeviceScope(int wanted) {
-      int current = -1;
-      if (hipGetDevice(&current) == hipSuccess && current != wanted && hipSetDevice(wanted) == hipSuccess)
-        previous = current;
-    }
-    ~DeviceScope() {
-      if (previous >= 0) (void)hipSetDevice(previous);
-    }
-  } deviceScope(sorter->device);
+  DeviceScope deviceScope(sorter->device);
 
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
   const SortPlan plan = PlanSort(sorter, keyValue, elementCount, (uint64_t)reinterpret_cast<uintptr_t>(storage));
@@ -682,18 +698,83 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
     if (msdBits == 0 || pass != 0) Stamp(pool, query + 2 + 3 * pass + 2, stream);  // "downsweep"
   }
   StampSame(pool, query + 14, query + 13);  // end of the sort = end of the last pass
+  MaybeRecheckOrder(sorter, stream, atomicRank);
+}
 
-  // Behind every 65536th sort: 8 workgroups repeat the lane-order check of vrdxCreateSorter (~20 us, never blocks; a
-  // mismatch sets VRDX_HIP_STATUS_RANK_ORDER in the sorter's status word, which vrdxHipReadSorterStatus and
-  // vrdxDestroySorter report).
-  // Not into a stream capture: the check would be baked into the graph and run with every replay.  The count is not
-  // advanced then, so the first sort recorded outside a capture makes up for it.
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (atomicRank && (sorter->sortsRecorded.load(std::memory_order_relaxed) & 0xFFFFu) == 0xFFFFu &&
-      (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone))
+// The segmented sort (include/vk_radix_sort.h, vrdxHipCmdSortSegmented): a fill of the header and the two list counters, then
+// three launches whose work is decided on the device from the offsets -- the 256-thread in-LDS form over every segment (it
+// also lists the bigger ones), the 1024-thread in-LDS form over the mid list, one workgroup per large segment.
+// Grids depend on segmentCount, maxElementCount and the CU count only, so a captured call can be replayed on any segmentation
+// with the same segmentCount.
+void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
+                         VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
+                         VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                         VkQueryPool queryPool, uint32_t query) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
+  VrdxHipQueryPool* pool = reinterpret_cast<VrdxHipQueryPool*>(queryPool);
+  const bool keyValue = valuesBuffer != nullptr;
+  if (maxElementCount > VRDX_MAX_ELEMENTS) {
+    // as in RecordSort: no storage requirement exists beyond it; segments ending behind the clamped bound are left alone
+    // (and flagged on the device)
+    maxElementCount = VRDX_MAX_ELEMENTS;
+    sorter->countClamped.store(1u, std::memory_order_relaxed);
+  }
+  DeviceScope deviceScope(sorter->device);
+  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
+  Stamp(pool, query + 0, stream);
+  const vrdx::SegmentedLayout layout =
+      vrdx::MakeSegmentedLayout(maxElementCount, sorter->minStorageBufferOffsetAlignment, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (segmentCount == 0 || maxElementCount == 0 || !(keyValue ? layout.fitsKeyValue : layout.fitsKeys)) {
+    for (uint32_t s = 1; s < 15; ++s) StampSame(pool, query + s, query + 0);
+    if (segmentCount != 0 && maxElementCount != 0)  // (cannot happen for N >= 1: MakeSegmentedLayout fits every count)
+      EnqueueCheck(sorter, "segmented storage layout", hipErrorInvalidValue);
     return;
-  if (atomicRank && (sorter->sortsRecorded.fetch_add(1u, std::memory_order_relaxed) & 0xFFFFu) == 0xFFFFu)
-    EnqueueCheck(sorter, "lds_order_check_kernel", vrdx::LaunchLdsOrderRecheck(stream, sorter->stickyStatus));
+  }
+  const bool atomicRank = sorter->atomicRank.load(std::memory_order_relaxed);
+  vrdx::SegmentedArgs a;
+  a.keys = reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset));
+  a.values = keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
+  a.keysScratch = reinterpret_cast<uint32_t*>(storage + layout.keysScratchOffset);
+  a.valuesScratch = keyValue ? reinterpret_cast<uint32_t*>(storage + layout.valuesScratchOffset) : nullptr;
+  a.offsets = reinterpret_cast<const uint32_t*>(BufferAddress(offsetsBuffer, offsetsOffset));
+  a.segmentCount = segmentCount;
+  a.maxCount = maxElementCount;
+  a.midCount = reinterpret_cast<uint32_t*>(storage + layout.midCountOffset);
+  a.midList = reinterpret_cast<uint32_t*>(storage + layout.midListOffset);
+  a.midCap = layout.midCap;
+  a.largeCount = reinterpret_cast<uint32_t*>(storage + layout.largeCountOffset);
+  a.largeList = reinterpret_cast<uint32_t*>(storage + layout.largeListOffset);
+  a.largeCap = layout.largeCap;
+  a.failure = reinterpret_cast<uint32_t*>(storage + VRDX_OFF_FAILURE);
+  a.stickyFailure = sorter->stickyStatus;
+
+  // header (plan verdict = VRDX_HIP_VERDICT_NONE, failure word) and the two list counters, in front of the first launch: a
+  // one-wave kernel, not a memset (vrdx_kernels.hip, segmented_clear_kernel)
+  EnqueueCheck(sorter, "segmented_clear_kernel", vrdx::LaunchSegmentedClear(stream, a));
+  Stamp(pool, query + 1, stream);
+  // one workgroup per segment up to 2^20 of them (a grid-stride loop beyond); the other two launches take their lists by
+  // grid stride with at most as many workgroups as can be resident (the in-LDS form of 16384 keys and the large kernel
+  // hold one or two workgroups per CU)
+  const uint32_t cus = (uint32_t)sorter->computeUnits;
+  EnqueueCheck(sorter, "segmented_small_kernel",
+               vrdx::LaunchSegmentedSmall(stream, std::min<uint32_t>(segmentCount, 1u << 20), keyValue, atomicRank, a));
+  Stamp(pool, query + 2, stream);
+  const uint32_t midGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.midCap), 2u * cus);
+  if (midGrid != 0) {
+    EnqueueCheck(sorter, "segmented_mid_kernel", vrdx::LaunchSegmentedMid(stream, midGrid, keyValue, atomicRank, a));
+    Stamp(pool, query + 3, stream);
+  } else {
+    StampSame(pool, query + 3, query + 2);
+  }
+  const uint32_t largeGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.largeCap), 2u * cus);
+  if (largeGrid != 0) {
+    EnqueueCheck(sorter, "segmented_large_kernel", vrdx::LaunchSegmentedLarge(stream, largeGrid, keyValue, atomicRank, a));
+    Stamp(pool, query + 4, stream);
+  } else {
+    StampSame(pool, query + 4, query + 3);
+  }
+  for (uint32_t s = 5; s < 15; ++s) StampSame(pool, query + s, query + 4);
+  MaybeRecheckOrder(sorter, stream, atomicRank);
 }
 
 }  // namespace
@@ -730,6 +811,7 @@ VkResult vrdxCreateSorter(const VrdxSorterCreateInfo* pCreateInfo, VrdxSorter* p
   if (e == hipSuccess) e = vrdx::PrepareSmallSort();
   if (e == hipSuccess) e = vrdx::PrepareBucketSort();
   if (e == hipSuccess) e = vrdx::PrepareMsd();
+  if (e == hipSuccess) e = vrdx::PrepareSegmented();
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sorter->stickyStatus), 2 * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(sorter->stickyStatus, 0, 2 * sizeof(uint32_t));
   if (e == hipSuccess) sorter->declinedPlans = sorter->stickyStatus + 1;
@@ -789,9 +871,10 @@ void vrdxDestroySorter(VrdxSorter sorter) {
     if (sorter->countClamped.load(std::memory_order_relaxed) != 0) word |= VRDX_HIP_STATUS_COUNT_CLAMPED;
     if (word != 0)
       std::fprintf(stderr,
-                   "vrdx-hip: sorter destroyed with unreported failures (status 0x%08x:%s%s%s%s) -- see vrdxHipReadSorterStatus\n",
+                   "vrdx-hip: sorter destroyed with unreported failures (status 0x%08x:%s%s%s%s%s) -- see vrdxHipReadSorterStatus\n",
                    word, (word & VRDX_HIP_STATUS_LOOKBACK_GAVE_UP) ? " a look-back spin expired, that sort's result is unspecified;" : "",
                    (word & VRDX_HIP_STATUS_RANK_ORDER) ? " LDS atomics were seen out of lane order, call vrdxHipRecheck;" : "",
+                   (word & VRDX_HIP_STATUS_SEGMENTS_INVALID) ? " a segmented sort met offsets that decrease or end behind maxElementCount, those segments were left alone;" : "",
                    (word & VRDX_HIP_STATUS_COUNT_CLAMPED) ? " an element count beyond 2^30 - 4 was clamped, that sort's tail is unsorted;" : "",
                    (word & VRDX_HIP_STATUS_ENQUEUE_REFUSED) ? " the HIP runtime refused an enqueue;" : "");
     (void)hipFree(sorter->stickyStatus);
@@ -847,6 +930,23 @@ void vrdxCmdSortKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorte
                                  uint32_t query) {
   RecordSort(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer,
              keysOffset, valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                             uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                             VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
+                             VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                      nullptr, 0, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                     uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                     VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                     VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                     VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                      valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
 }
 
 VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {

@@ -215,6 +215,42 @@ hipError_t LaunchBucketSort2(hipStream_t stream, bool keyValue, const MsdArgs& a
 hipError_t LaunchMsdFused(hipStream_t stream, bool bucketLaunch, bool keyValue, const MsdArgs& args, const OnesweepArgs& pass,
                           uint32_t passGrid);
 
+// Segmented sort (vrdx_kernels.hip, "segmented sort"): segmentCount independent ranges [offsets[i], offsets[i + 1]) of
+// one array, every range sorted on its own, in place.  The host never learns the sizes; each segment's size class is decided
+// on the device:
+//   segmented_small_kernel  one 256-thread workgroup per segment (a grid-stride loop above the grid's cap): checks the
+//                           segment's offsets, sorts it in LDS when it holds at most kSegSmallMax elements, and otherwise
+//                           appends its id to the mid list (at most kSegMidMax) or to the large list;
+//   segmented_mid_kernel    1024 threads, takes the mid list by grid stride: one in-LDS sort per segment;
+//   segmented_large_kernel  1024 threads, takes the large list by grid stride: one stable LSD sort through memory per
+//                           segment, ping-ponging between the caller's range and the same index range of the scratch.
+constexpr uint32_t kSegSmallMax = 256u * 16u;  // the 256 x 16 form of SortInWorkgroup
+constexpr uint32_t kSegMidMax = 1024u * 16u;   // the 1024 x 16 form
+constexpr uint32_t kSegLargeTile = 1024u * 16u;  // keys per tile of the large kernel's passes
+struct SegmentedArgs {
+  uint32_t* keys;
+  uint32_t* values;             // KV only
+  uint32_t* keysScratch;        // large segments: the same index range as in keys
+  uint32_t* valuesScratch;      // KV only
+  const uint32_t* offsets;      // segmentCount + 1 words, read on the device
+  uint32_t segmentCount;
+  uint32_t maxCount;            // no segment may end behind it
+  uint32_t* midCount;           // appended to by the small kernel (zeroed by the fill in front of it)
+  uint32_t* midList;            // [midCap] segment ids
+  uint32_t midCap;
+  uint32_t* largeCount;
+  uint32_t* largeList;          // [largeCap] segment ids
+  uint32_t largeCap;
+  uint32_t* failure;            // the storage's failure word (word 3 of the header): VRDX_HIP_STATUS_SEGMENTS_INVALID
+  uint32_t* stickyFailure;      // the sorter's word
+};
+hipError_t PrepareSegmented();
+// The fill in front of the first launch (one wave): header words 0-3 (failure = word 3) and both list counters.
+hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args);
+hipError_t LaunchSegmentedSmall(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args);
+hipError_t LaunchSegmentedMid(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args);
+hipError_t LaunchSegmentedLarge(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args);
+
 // Runs the device self-check of the LDS same-address atomic ordering on the current device
 // (synchronous, ~1 ms).  *laneOrdered = true when returning atomics are served in lane order.
 hipError_t LdsOrderCheck(bool* laneOrdered);

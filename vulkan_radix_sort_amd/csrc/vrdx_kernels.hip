@@ -1770,6 +1770,274 @@ __global__ __launch_bounds__(THREADS) void bucket_sort_kernel(BucketSortArgs a) 
 }
 
 // ---------------------------------------------------------------------------------------------
+// segmented sort: many independent ranges of one array in one recorded call
+// ---------------------------------------------------------------------------------------------
+// Segment i is [offsets[i], offsets[i + 1]); the offsets are read here, never by the host, so every size class is decided on
+// the device (vrdx_kernels.h, SegmentedArgs):
+//   * segmented_small_kernel, one 256-thread workgroup per segment: checks the pair of offsets (a decreasing pair or an end
+//     behind maxCount leaves the segment alone and raises kSegmentsInvalid), sorts segments of 2 ... 4096 elements with
+//     SortInWorkgroup<256, 16>, and appends the id of a bigger one to the mid or the large list -- one global atomic per
+//     such segment, of which there are at most maxCount / 4097;
+//   * segmented_mid_kernel: SortInWorkgroup<1024, 16> for each id of the mid list.  Taking ids from a list rather than one
+//     workgroup per segment keeps 65536 segments of 256 keys from dispatching 65536 empty 1024-thread workgroups;
+//   * segmented_large_kernel: one workgroup per large segment, a stable LSD sort through memory (SegmentLsd below).
+// Segments never share elements when the offsets are monotone, so workgroups never share data or scratch.  A list slot beyond
+// its capacity (only non-monotone offsets, which raise the bit, can overlap segments and overfill a list) is dropped.
+constexpr uint32_t kSegmentsInvalid = 0x00000004u;  // VRDX_HIP_STATUS_SEGMENTS_INVALID (include/vk_radix_sort.h)
+
+// The segment's bounds, scalar (wave-uniform) loads; false when the pair is unusable (then the bit is raised if `flag`).
+__device__ __forceinline__ bool SegmentBounds(const SegmentedArgs& a, uint32_t segment, bool flag, uint32_t* begin,
+                                              uint32_t* end) {
+  const uint32_t b = a.offsets[segment];
+  const uint32_t e = a.offsets[segment + 1];
+  if (b <= e && e <= a.maxCount) {
+    *begin = b;
+    *end = e;
+    return true;
+  }
+  if (flag && threadIdx.x == 0) {
+    atomicOr(a.failure, kSegmentsInvalid);
+    if (a.stickyFailure != nullptr) atomicOr(a.stickyFailure, kSegmentsInvalid);
+  }
+  return false;
+}
+
+// The fill in front of the first launch: storage header (count, plan verdict = VRDX_HIP_VERDICT_NONE, MSD word, failure word)
+// and the two list counters.  A kernel rather than hipMemsetAsync: captured into a hipGraph, a memset node was seen to replay
+// with a wrong fill value once other copies had run between two replays, where kernel nodes replay their arguments as captured.
+__global__ __launch_bounds__(64) void segmented_clear_kernel(SegmentedArgs a) {
+  if (threadIdx.x < 4) a.failure[(int)threadIdx.x - 3] = 0u;  // words 0-3 (the failure word is word 3)
+  if (threadIdx.x == 4) *a.midCount = 0u;
+  if (threadIdx.x == 5) *a.largeCount = 0u;
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(256) void segmented_small_kernel(SegmentedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  for (uint32_t s = blockIdx.x; s < a.segmentCount; s += gridDim.x) {
+    uint32_t begin = 0, end = 0;
+    if (!SegmentBounds(a, s, true, &begin, &end)) continue;  // uniform
+    const uint32_t n = end - begin;
+    if (n > kSegSmallMax) {
+      if (threadIdx.x == 0) {
+        const bool mid = n <= kSegMidMax;
+        const uint32_t slot = atomicAdd(mid ? a.midCount : a.largeCount, 1u);
+        if (slot < (mid ? a.midCap : a.largeCap)) (mid ? a.midList : a.largeList)[slot] = s;
+      }
+      continue;
+    }
+    if (n < 2) continue;
+    LdsBarrier();  // the previous segment's read-back of the staging buffer is over
+    SortInWorkgroup<256, 16, KV, ATOMIC_RANK>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
+                                              KV ? a.values + begin : nullptr, n, VRDX_PASSES, smem);
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_mid_kernel(SegmentedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t listed = min(*a.midCount, a.midCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = a.midList[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    const uint32_t n = end - begin;
+    if (n <= kSegSmallMax || n > kSegMidMax) continue;
+    LdsBarrier();
+    SortInWorkgroup<1024, 16, KV, ATOMIC_RANK>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
+                                               KV ? a.values + begin : nullptr, n, VRDX_PASSES, smem);
+  }
+}
+
+// One large segment in one workgroup: a stable LSD sort through memory, the way one tile-sequential onesweep would do it.
+//   1. one read of the segment builds its four digit histograms (COPIES replicas per bin, like histogram_kernel, so that
+//      constant bytes do not serialise on one LDS address); a pass whose digit is the same for every key is skipped;
+//   2. every remaining pass walks the segment tile by tile IN ORDER: a tile of up to kSegLargeTile keys is loaded
+//      wave-striped, ranked by the digit (RankAtomic / RankBallot: stable), moved to the staging buffer in digit order and
+//      written out run by run to base[d] + (its position - the tile's start of digit d); base[d] then advances by the
+//      tile's count of d.  Tiles in input order and a stable order inside each tile make every pass stable;
+//   3. the passes alternate between the caller's range and the same index range of the scratch arrays; after an odd number
+//      of passes the result is copied back.
+// Global data written by one wave and read by another inside this workgroup only ever crosses a __syncthreads() (same CU:
+// the L1 is shared, the barrier's release waits for the stores).
+constexpr uint32_t kSegHistCopies = 8;
+template <bool KV>
+constexpr size_t SegmentLargeLdsWords() {
+  // staging (keys, values) | wave counters 16 x 256 | scan scratch 16 | bases 4 x 256 | tile starts 256 | tile counts 256 | 16
+  return (size_t)kSegLargeTile * (KV ? 2 : 1) + 16 * 256 + 16 + 4 * 256 + 256 + 256 + 16;
+}
+static_assert(4 * 256 * kSegHistCopies <= kSegLargeTile, "the histogram replicas alias the staging buffer");
+
+template <bool KV, bool ATOMIC_RANK>
+__device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uint32_t* keysScratch, uint32_t* valuesScratch,
+                                           uint32_t n, uint32_t* smem) {
+  constexpr int THREADS = 1024, KPT = 16, WAVES = THREADS / 64;
+  constexpr uint32_t TILE = kSegLargeTile;
+  uint32_t* const stagedKeys = smem;
+  uint32_t* const stagedValues = smem + TILE;  // KV only
+  uint32_t* const waveHist = smem + TILE * (KV ? 2 : 1);
+  uint32_t* const scanScratch = waveHist + WAVES * 256;
+  uint32_t* const bases = scanScratch + 16;      // [pass][digit]: where the next key of digit d goes, this pass
+  uint32_t* const tileStart = bases + 4 * 256;   // tile-local position of digit d's first key
+  uint32_t* const tileCount = tileStart + 256;
+  uint32_t* const misc = tileCount + 256;        // [0]: bit p = pass p is not trivial
+  uint32_t* const bins = smem;                   // [pass][digit][copy], before the passes (aliases the staging buffer)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // 1. histograms
+  for (uint32_t i = tid; i < 4 * 256 * kSegHistCopies; i += THREADS) bins[i] = 0;
+  if (tid == 0) misc[0] = 0;
+  LdsBarrier();
+  const uint32_t copy = tid & (kSegHistCopies - 1);
+  auto count = [&](uint32_t key) {
+#pragma unroll
+    for (uint32_t p = 0; p < 4; ++p) atomicAdd(&bins[(p * 256 + ((key >> (8 * p)) & 0xFFu)) * kSegHistCopies + copy], 1u);
+  };
+  {
+    constexpr uint32_t U = 8;  // loads in flight per lane
+    uint32_t i = tid;
+    for (; i + (U - 1) * THREADS < n; i += U * THREADS) {
+      uint32_t k[U];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) k[u] = keys[i + u * THREADS];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) count(k[u]);
+    }
+    for (; i < n; i += THREADS) count(keys[i]);
+  }
+  LdsBarrier();
+  {
+    // thread t: pass t / 256, digit t % 256 -- the exclusive scan over the 256 digits of each pass (four waves per pass)
+    const uint32_t p = (uint32_t)tid >> 8, d = (uint32_t)tid & 255u;
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kSegHistCopies; ++r) c += bins[(p * 256 + d) * kSegHistCopies + ((r + tid) & (kSegHistCopies - 1))];
+    const uint32_t x = WaveInclusiveScan(c);
+    if (lane == 63) scanScratch[wave] = x;
+    if (c != 0 && c != n) atomicOr(&misc[0], 1u << p);  // two digits at least: the pass moves keys
+    LdsBarrier();
+    uint32_t add = 0;
+    for (int w = wave & ~3; w < wave; ++w) add += scanScratch[w];
+    bases[p * 256 + d] = x - c + add;
+  }
+  LdsBarrier();
+  const uint32_t active = misc[0];
+
+  // 2. the passes
+  uint32_t* src = keys;
+  uint32_t* dst = keysScratch;
+  uint32_t* srcV = values;
+  uint32_t* dstV = valuesScratch;
+  uint32_t* const myHist = waveHist + wave * 256;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+#pragma unroll 1
+  for (uint32_t pass = 0; pass < 4; ++pass) {
+    if (((active >> pass) & 1u) == 0) continue;  // uniform
+    const uint32_t shift = 8 * pass;
+    uint32_t* const base = bases + pass * 256;
+#pragma unroll 1
+    for (uint32_t t0 = 0; t0 < n; t0 += TILE) {
+      const uint32_t m = min(TILE, n - t0);
+      // the chunks of four 64-key slots dealt out evenly over the waves, as in SortInWorkgroup: pads (the largest key) only
+      // in the last chunk, behind every real key of the tile
+      const uint32_t chunks = (m + 255u) / 256u;
+      const uint32_t per = chunks / WAVES, extra = chunks % WAVES;
+      const uint32_t slots = 4u * (per + (w < extra ? 1u : 0u));
+      const uint32_t first = 256u * (w * per + (w < extra ? w : extra)) + lane;
+      uint32_t key[KPT];
+      uint32_t val[KV ? KPT : 1];
+      LoadStriped<KPT, false, true>(src + t0, first, m, false, 0xFFFFFFFFu, key, slots);
+      if constexpr (KV) LoadStriped<KPT, false, true>(srcV + t0, first, m, false, 0u, val, slots);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;
+      uint32_t rank[KPT];
+      if constexpr (ATOMIC_RANK)
+        RankAtomic<KPT, false, true>(key, shift, myHist, lane, rank, slots);
+      else
+        RankBallot<KPT, false, true>(key, shift, myHist, lane, rank, slots);
+      LdsBarrier();
+      uint32_t c = 0;
+      if (tid < 256) {
+#pragma unroll
+        for (int v = 0; v < WAVES; ++v) c += waveHist[v * 256 + tid];
+      }
+      const uint32_t exclusive = BlockExclusiveScan256(tid < 256 ? c : 0u, scanScratch, tid);
+      if (tid < 256) {
+        uint32_t run = exclusive;
+#pragma unroll
+        for (int v = 0; v < WAVES; ++v) {
+          const uint32_t h = waveHist[v * 256 + tid];
+          waveHist[v * 256 + tid] = run;
+          run += h;
+        }
+        tileStart[tid] = exclusive;
+        tileCount[tid] = tid == 255 ? c - (256u * chunks - m) : c;  // (the pads are digit 255's last keys)
+      }
+      LdsBarrier();
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        if (i % 4 == 0 && (uint32_t)i >= slots) break;
+        const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[(key[i] >> shift) & 0xFFu]);
+        stagedKeys[slot] = key[i];
+        if constexpr (KV) stagedValues[slot] = val[i];
+      }
+      LdsBarrier();
+      // sorted position q of the tile -> base[d] + q - tileStart[d]: runs of one digit land contiguously
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        if (i % 4 == 0 && (uint32_t)i >= slots) break;
+        const uint32_t q = first + 64 * i;
+        if (q < m) {
+          const uint32_t slot = StagingSlot<TILE>(q);
+          const uint32_t k = stagedKeys[slot];
+          const uint32_t d = (k >> shift) & 0xFFu;
+          const uint32_t to = base[d] + q - tileStart[d];
+          // always < n while the segment is this workgroup's alone; segments that overlap (offsets that are not monotone,
+          // flagged by the small kernel) may change keys under the counts, and must still never write outside the range
+          if (to < n) {
+            dst[to] = k;
+            if constexpr (KV) dstV[to] = stagedValues[slot];
+          }
+        }
+      }
+      LdsBarrier();  // every lane has read base[] and tileStart[] of this tile
+      if (tid < 256) base[tid] += tileCount[tid];
+      // (the next tile reads base[] two barriers later, and writes the staging buffer and tileStart[] one barrier later)
+    }
+    __syncthreads();  // this pass's stores are complete before the next pass (or the copy back) reads them
+    uint32_t* const t = src;
+    src = dst;
+    dst = t;
+    uint32_t* const tv = srcV;
+    srcV = dstV;
+    dstV = tv;
+  }
+
+  // 3. an odd number of passes left the result in the scratch range
+  if (src != keys) {
+    for (uint32_t i = tid; i < n; i += THREADS) {
+      keys[i] = src[i];
+      if constexpr (KV) values[i] = srcV[i];
+    }
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_large_kernel(SegmentedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t listed = min(*a.largeCount, a.largeCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = a.largeList[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    if (end - begin <= kSegMidMax) continue;
+    __syncthreads();  // the previous segment is done (its copy back included)
+    SegmentLsd<KV, ATOMIC_RANK>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
+                                KV ? a.valuesScratch + begin : nullptr, end - begin, smem);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // MSD plan (round 5): three ranking steps of 10-11 bits, two trips through memory
 // ---------------------------------------------------------------------------------------------
 // A four-pass LSD sort moves every key through HBM four times, and each of the four passes costs a CU the same LDS work
@@ -3325,6 +3593,57 @@ hipError_t LaunchSmallSort(hipStream_t stream, bool atomicRank, uint32_t* keys, 
                            const uint32_t* countPtr, uint32_t* failure) {
   if (maxCount <= 256u * 16u) return LaunchSmall<256, 16>(stream, atomicRank, keys, values, maxCount, countPtr, failure);
   return LaunchSmall<1024, 16>(stream, atomicRank, keys, values, maxCount, countPtr, failure);
+}
+
+// ---- segmented sort ---------------------------------------------------------------------------------
+template <bool KV, bool ATOMIC_RANK>
+static const void* SegmentedKernel(int which) {  // 0 small, 1 mid, 2 large
+  if (which == 0) return reinterpret_cast<const void*>(&segmented_small_kernel<KV, ATOMIC_RANK>);
+  if (which == 1) return reinterpret_cast<const void*>(&segmented_mid_kernel<KV, ATOMIC_RANK>);
+  return reinterpret_cast<const void*>(&segmented_large_kernel<KV, ATOMIC_RANK>);
+}
+
+static size_t SegmentedLdsBytes(int which, bool keyValue) {
+  if (which == 0) return (keyValue ? SmallSortLdsWords<256, 16, true>() : SmallSortLdsWords<256, 16, false>()) * 4;
+  if (which == 1) return (keyValue ? SmallSortLdsWords<1024, 16, true>() : SmallSortLdsWords<1024, 16, false>()) * 4;
+  return (keyValue ? SegmentLargeLdsWords<true>() : SegmentLargeLdsWords<false>()) * 4;
+}
+
+static const void* SegmentedKernelFor(int which, bool keyValue, bool atomicRank) {
+  return keyValue ? (atomicRank ? SegmentedKernel<true, true>(which) : SegmentedKernel<true, false>(which))
+                  : (atomicRank ? SegmentedKernel<false, true>(which) : SegmentedKernel<false, false>(which));
+}
+
+hipError_t PrepareSegmented() {
+  for (int which = 0; which < 3; ++which)
+    for (int kv = 0; kv < 2; ++kv)
+      for (int atomic = 0; atomic < 2; ++atomic) {
+        const hipError_t e = hipFuncSetAttribute(SegmentedKernelFor(which, kv != 0, atomic != 0),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)SegmentedLdsBytes(which, kv != 0));
+        if (e != hipSuccess) return e;
+      }
+  return hipSuccess;
+}
+
+static hipError_t LaunchSegmented(int which, hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank,
+                                  const SegmentedArgs& args) {
+  if (grid == 0) return hipErrorInvalidValue;
+  return Launch(SegmentedKernelFor(which, keyValue, atomicRank), grid, which == 0 ? 256u : 1024u,
+                SegmentedLdsBytes(which, keyValue), stream, args);
+}
+
+hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args) {
+  return Launch(reinterpret_cast<const void*>(&segmented_clear_kernel), 1, 64, 0, stream, args);
+}
+hipError_t LaunchSegmentedSmall(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
+  return LaunchSegmented(0, stream, grid, keyValue, atomicRank, args);
+}
+hipError_t LaunchSegmentedMid(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
+  return LaunchSegmented(1, stream, grid, keyValue, atomicRank, args);
+}
+hipError_t LaunchSegmentedLarge(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
+  return LaunchSegmented(2, stream, grid, keyValue, atomicRank, args);
 }
 
 // ---- second half of the hybrid plan ---------------------------------------------------------------

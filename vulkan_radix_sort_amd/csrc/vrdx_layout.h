@@ -167,6 +167,41 @@ static inline bool LayoutFits(const StorageLayout& l, uint32_t maxElementCount) 
   return l.inoutOffset + bytes <= l.keysOnlySize && l.valuesOffset + bytes <= l.keyValueSize;
 }
 
+// The segmented sort's carving of the same bytes (vrdxHipCmdSortSegmented*; vrdx_kernels.hip, "segmented sort"):
+//   [0, 16)                        header: words 0-3 (plan verdict = word 1, failure word = word 3) zeroed by the fill kernel
+//   histogramOffset + 0            mid-list count   } in the reference's global-histogram area, zeroed by the same fill in
+//   histogramOffset + 256          large-list count }   front of the first launch (two different 128-byte lines)
+//   first 128-byte line behind the table: uint32 midList[N / 4097], then largeList[N / 16385] (segment ids; a segment of
+//                                  more than 4096 elements holds at least 4097 of the N, so the lists cannot overflow while
+//                                  segments are disjoint) -- in the reference's partition-histogram area (>= N / 16 words)
+//   keysScratch (128-byte aligned) uint[N] behind the lists, valuesScratch uint[N] behind it: a large segment's passes use
+//                                  the same index range as its elements
+struct SegmentedLayout {
+  uint64_t midCountOffset, largeCountOffset;
+  uint64_t midListOffset, largeListOffset;
+  uint32_t midCap, largeCap;
+  uint64_t keysScratchOffset, valuesScratchOffset;
+  bool fitsKeys, fitsKeyValue;  // every region lies inside the keys-only / key+value storage requirement
+};
+
+static inline SegmentedLayout MakeSegmentedLayout(uint32_t maxElementCount, uint32_t align, uint64_t storageAddress = 0) {
+  const StorageLayout l = MakeLayout(maxElementCount, align, 0, storageAddress);
+  SegmentedLayout s;
+  s.midCountOffset = l.histogramOffset;
+  s.largeCountOffset = l.histogramOffset + 256;
+  s.midCap = maxElementCount / (256u * 16u + 1u);
+  s.largeCap = maxElementCount / (1024u * 16u + 1u);
+  s.midListOffset = l.msdBucketOffset;
+  s.largeListOffset = s.midListOffset + 4ull * s.midCap;
+  const uint64_t listsEnd = s.largeListOffset + 4ull * s.largeCap;
+  s.keysScratchOffset = listsEnd + ((0 - (storageAddress + listsEnd)) & 127u);
+  s.valuesScratchOffset = s.keysScratchOffset + (((uint64_t)maxElementCount * sizeof(uint32_t) + 127u) & ~(uint64_t)127u);
+  const uint64_t bytes = (uint64_t)maxElementCount * sizeof(uint32_t);
+  s.fitsKeys = s.keysScratchOffset + bytes <= l.keysOnlySize;
+  s.fitsKeyValue = s.fitsKeys && s.valuesScratchOffset + bytes <= l.keyValueSize;
+  return s;
+}
+
 // The MSD plan's scatter (scatter_msd_kernel, one workgroup per CU and tile) cuts the sort into EQUAL tiles that fill whole
 // rounds of `cus` tiles: keys per tile, a multiple of 4096 (four 64-key slots per wave of its 1024 threads), at most 32768.
 // 520 tiles of 32768 keys would cost three rounds, the third for eight tiles; 768 tiles of 24576 cost three rounds of three

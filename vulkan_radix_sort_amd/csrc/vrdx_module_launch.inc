@@ -35,6 +35,8 @@ struct DeviceKernels {
   hipFunction_t bucket2[2][2] = {};                      // [10 | 11 bits][key-value]
   hipFunction_t bucket2Half[2] = {};                     // ten bits, buckets of <= 16384: [key-value]
   hipFunction_t fused[2][2][2][2] = {};                  // [10 | 11 bits][scatter-or-pass-0 | buckets-or-pass-1][key-value][full | split tiles]
+  hipFunction_t segmented[3][2][2] = {};                 // [small | mid | large][key-value][atomic rank]
+  hipFunction_t segmentedClear = nullptr;
   hipFunction_t orderCheck = nullptr;
   hipFunction_t orderCheckPacked = nullptr;
   hipFunction_t spin = nullptr;
@@ -376,6 +378,61 @@ hipError_t LaunchBucketSort2(hipStream_t stream, bool keyValue, const MsdArgs& a
   // (MsdBucketGrid of vrdx_kernels.hip: the full-size kernel takes two buckets per workgroup)
   return Launch(Handle(dev->bucket2[args.bits - 10][keyValue ? 1 : 0]), (1u << args.bits) / 2u, 1024, Bucket2LdsBytes(keyValue), stream,
                 params);
+}
+
+// ---- the segmented sort (vrdx_kernels.hip: PrepareSegmented, LaunchSegmented*) ----
+size_t SegmentedLdsBytesOf(int which, bool keyValue) {
+  if (which == 0) return SmallLdsBytes(256, keyValue);
+  if (which == 1) return SmallLdsBytes(1024, keyValue);
+  // SegmentLargeLdsWords: staging | wave counters | scan scratch | bases | tile starts | tile counts | 16
+  return ((size_t)kSegLargeTile * (keyValue ? 2 : 1) + 16 * 256 + 16 + 4 * 256 + 256 + 256 + 16) * 4;
+}
+
+hipError_t PrepareSegmented() {
+  DeviceKernels* dev = nullptr;
+  hipError_t e = CurrentDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(g_moduleMutex);
+  if ((e = Resolve(dev, "_ZN4vrdx22segmented_clear_kernelENS_13SegmentedArgsE", &dev->segmentedClear)) != hipSuccess) return e;
+  static const char* const kNames[3] = {"22segmented_small_kernel", "20segmented_mid_kernel", "22segmented_large_kernel"};
+  for (int which = 0; which < 3; ++which)
+    for (int kv = 0; kv < 2; ++kv)
+      for (int atomic = 0; atomic < 2; ++atomic) {
+        char name[128];
+        std::snprintf(name, sizeof(name), "_ZN4vrdx%sILb%dELb%dEEEvNS_13SegmentedArgsE", kNames[which], kv, atomic);
+        if ((e = Resolve(dev, name, &dev->segmented[which][kv][atomic])) != hipSuccess) return e;
+        RaiseLdsLimit(dev->segmented[which][kv][atomic], SegmentedLdsBytesOf(which, kv != 0));
+      }
+  return hipSuccess;
+}
+
+hipError_t LaunchSegmentedKernel(int which, hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank,
+                                 const SegmentedArgs& args) {
+  DeviceKernels* dev = nullptr;
+  const hipError_t e = CurrentDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (grid == 0) return hipErrorInvalidValue;
+  SegmentedArgs copy = args;
+  void* params[] = {&copy};
+  return Launch(Handle(dev->segmented[which][keyValue ? 1 : 0][atomicRank ? 1 : 0]), grid, which == 0 ? 256u : 1024u,
+                SegmentedLdsBytesOf(which, keyValue), stream, params);
+}
+hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args) {
+  DeviceKernels* dev = nullptr;
+  const hipError_t e = CurrentDevice(&dev);
+  if (e != hipSuccess) return e;
+  SegmentedArgs copy = args;
+  void* params[] = {&copy};
+  return Launch(Handle(dev->segmentedClear), 1, 64, 0, stream, params);
+}
+hipError_t LaunchSegmentedSmall(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
+  return LaunchSegmentedKernel(0, stream, grid, keyValue, atomicRank, args);
+}
+hipError_t LaunchSegmentedMid(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
+  return LaunchSegmentedKernel(1, stream, grid, keyValue, atomicRank, args);
+}
+hipError_t LaunchSegmentedLarge(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
+  return LaunchSegmentedKernel(2, stream, grid, keyValue, atomicRank, args);
 }
 
 hipError_t LaunchLdsOrderRecheck(hipStream_t stream, uint32_t* sticky) {
