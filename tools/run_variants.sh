@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs prebuilt variants (tools/build_variants.sh) ON the GPU box with the native selftest:
-#   gpurun -- 'bash tools/run_variants.sh "base h0" "auto 512x32x2" "bench 24 25" [out-name]'
+#   bash tools/run_variants.sh "base parent" "auto 1024x32x2" "bench 24 25" [out-name]
 # $1 variant names, $2 VRDX_TILE_CONFIG values ("auto" = size-adaptive), $3 selftest arguments.
 # PROF=1: under rocprofv3 --kernel-trace --stats, the per-kernel averages of the vrdx kernels are appended.
 set -u

@@ -191,13 +191,11 @@ uint32_t HybridCapacity(bool atomicRank, uint32_t elementCount) {
     return env == nullptr || env[0] != '0';
   }();
   if (!enabled || elementCount <= vrdx::kSmallSortMaxElements) return 0;
-  // percent of the mean bucket a bucket may hold (tools: VRDX_HYBRID_HEADROOM); the LARGEST capacity is tried with
-  // less room than the others: failing costs one empty launch, the plan is worth a fifth to a third of the sort
-  static const int knob = TuningKnob("VRDX_HYBRID_HEADROOM");
-  static const int knobLast = TuningKnob("VRDX_HYBRID_HEADROOM_LAST");
+  // a bucket may hold twice the mean bucket; the LARGEST capacity is tried with less room than the others (3 %): failing
+  // costs one empty launch, the plan is worth a fifth to a third of the sort (profiles/r03_hybrid_headroom.txt)
   const uint64_t mean = (elementCount + VRDX_RADIX - 1) / VRDX_RADIX;
-  const uint32_t need = (uint32_t)(mean * (uint64_t)(knob > 0 ? knob : 200) / 100u);
-  const uint32_t needLast = (uint32_t)(mean * (uint64_t)(knobLast > 0 ? knobLast : 103) / 100u);
+  const uint32_t need = (uint32_t)(mean * 200u / 100u);
+  const uint32_t needLast = (uint32_t)(mean * 103u / 100u);
   // 32768-element buckets: the one-atomic ranking only (the ballot forms of that kernel would spill); key+value stages
   // keys and values through one buffer there (SharedStage in vrdx_kernels.hip)
   const uint32_t largest = atomicRank ? 32768u : 16384u;
@@ -213,43 +211,30 @@ uint32_t HybridCapacity(bool atomicRank, uint32_t elementCount) {
 // and four.  Recorded, in front of the four passes (which return on its verdict), for sorts beyond the eight-bit
 // plan's reach whose mean bucket leaves 3 % of room in the bucket kernel's capacity (uniform keys spread by half a percent
 // at these sizes): ten bits up to 36.6 M keys / 32.5 M pairs, eleven bits up to twice that.  Returns the bits or 0.
-// One-atomic ranking only.  VRDX_MSD=0 switches it off (VRDX_HYBRID=0 and a forced tile geometry as well); VRDX_MSD_FROM=n
-// records it from n elements up instead (measurements: below its default range it replaces the other two plans).
-// Keys per tile of the MSD plan's histogram and scatter: equal tiles that fill whole rounds of one workgroup per CU
-// (vrdx_layout.h).  VRDX_MSD_EVEN=0: tiles of full capacity (measurements).
-// twoPerWorkgroup: keys-only sorts by ten bits (their scatter takes two consecutive tiles per workgroup, vrdx_kernels.hip)
-uint32_t MsdTileKeys(uint32_t elementCount, uint32_t cus, bool twoPerWorkgroup) {
-  static const int even = TuningKnob("VRDX_MSD_EVEN");
-  return even == 0 ? vrdx::kMsdTileKeys : vrdx::MsdTileKeysFor(elementCount, cus, vrdx::kMsdMaxTiles, twoPerWorkgroup);
-}
-
+// One-atomic ranking only.  VRDX_MSD=0 switches it off (VRDX_HYBRID=0 and a forced tile geometry as well).
 uint32_t MsdBits(bool atomicRank, bool keyValue, uint32_t elementCount, uint32_t hybridCap, uint32_t* capacity) {
   static const bool enabled = [] {
     const char* all = std::getenv("VRDX_HYBRID");
     const char* msd = std::getenv("VRDX_MSD");
     return (all == nullptr || all[0] != '0') && (msd == nullptr || msd[0] != '0');
   }();
-  static const int from = TuningKnob("VRDX_MSD_FROM");
-  static const int forcedBits = TuningKnob("VRDX_MSD_BITS");  // measurements: 10 | 11 wherever the capacity allows
-  static const int knobLast = TuningKnob("VRDX_HYBRID_HEADROOM_LAST");
   if (!enabled || !atomicRank) return 0;
   // From where the EIGHT-bit plan ends (8.1 M: hybridCap == 0), keys-only and key+value.  Up to 18.1 M elements the buckets
   // hold at most 18432 and the half-size bucket kernel sorts them, two workgroups to a CU: with it the plan is 8-15 % faster
   // than round 4's nine-bit hybrid plan and the four passes at one round of tiles, which key+value sorts of these sizes
   // took before (profiles/r05_msd_half_buckets.txt); that plan's kernels are gone since.
-  const uint32_t lowest = from > 0 ? (uint32_t)from : (hybridCap == 0 ? vrdx::kSmallSortMaxElements + 1u : ~0u);
-  if (elementCount < lowest || vrdx::RoundUp(elementCount, vrdx::kMsdTileKeys) > vrdx::kMsdMaxTiles) return 0;
+  if (hybridCap != 0 || elementCount <= vrdx::kSmallSortMaxElements ||
+      vrdx::RoundUp(elementCount, vrdx::kMsdTileKeys) > vrdx::kMsdMaxTiles)
+    return 0;
   const uint32_t cap = keyValue ? vrdx::kMsdCapKeyValue : vrdx::kMsdCapKeys;
   *capacity = cap;
   for (uint32_t bits = 10; bits <= 11; ++bits) {
-    if (forcedBits > 0 && (uint32_t)forcedBits != bits) continue;
     const uint64_t mean = ((uint64_t)elementCount + (1u << bits) - 1u) >> bits;
-    if (mean * (uint64_t)(knobLast > 0 ? knobLast : 103) / 100u <= cap) {
+    if (mean * 103u / 100u <= cap) {
       // buckets of half the size: the bucket kernel of 512 threads, two workgroups per CU (bucket_sort2_half_kernel)
-      static const int half = TuningKnob("VRDX_MSD_HALF");
       // (4 % of headroom here: 5.3 sigma of a uniform bucket of 17700; the 3 % of the full size would be 4 sigma at this
       // capacity, and with 1024 buckets one sort in thirty at the top of the range would be turned down)
-      if (bits == 10 && half != 0 && mean * (uint64_t)(knobLast > 0 ? knobLast : 104) / 100u <= vrdx::kMsdHalfCap)
+      if (bits == 10 && mean * 104u / 100u <= vrdx::kMsdHalfCap)
         *capacity = vrdx::kMsdHalfCap;
       return bits;
     }
@@ -314,16 +299,12 @@ void StampSame(VrdxHipQueryPool* pool, uint32_t slot, uint32_t same) {
 //   key+value 1024x32     NO even split (its split form fetches the values late, vrdx_kernels.hip: +2 ... +7 % at
 //                         0.55 < f < 1); tail split while the rest is at most half a round (f = 1.06: 0.184 / 0.193 ms,
 //                         2.06: 0.294 / 0.303, 3.06: 0.399 / 0.408, 4.06: 0.524 / 0.532; beyond half a round -1 ... +4 %)
-// VRDX_EVEN_SPLIT=0 / VRDX_TAIL_SPLIT=0 turn them off, VRDX_EVEN_SPLIT=1 / VRDX_TAIL_SPLIT=p (percent of a round) force
-// them wherever the forms exist (measurements).
 vrdx::TilePlan PlanTiles(const VrdxSorter_T* sorter, int configIndex, bool keyValue, uint32_t elementCount, bool atomicRank) {
-  static const int evenKnob = TuningKnob("VRDX_EVEN_SPLIT");
-  static const int tailKnob = TuningKnob("VRDX_TAIL_SPLIT");
   const vrdx::TileConfig& c = vrdx::kTileConfigs[configIndex];
   const bool pair = configIndex == kCfg1024x32x2;
   const bool splitForms = pair ? (!keyValue && atomicRank) : configIndex == kCfg1024x32;
-  const bool evenSplit = evenKnob >= 0 ? evenKnob != 0 : !keyValue;
-  const uint32_t tailPercent = tailKnob >= 0 ? (uint32_t)tailKnob : (pair ? 100u : (keyValue ? 50u : 0u));
+  const bool evenSplit = !keyValue;
+  const uint32_t tailPercent = pair ? 100u : (keyValue ? 50u : 0u);
   return vrdx::PlanTiles(elementCount, (uint32_t)sorter->computeUnits, (uint32_t)c.threads, (uint32_t)c.keysPerThread,
                          (uint32_t)c.subTiles, splitForms, evenSplit, tailPercent);
 }
@@ -361,7 +342,6 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
   }
   p.hybridCap = adaptive ? HybridCapacity(p.atomicRank, elementCount) : 0u;
   p.msdBits = adaptive ? MsdBits(p.atomicRank, keyValue, elementCount, p.hybridCap, &p.msdCap) : 0u;
-  if (p.hybridCap != 0) p.msdBits = 0;  // (VRDX_MSD_FROM below the eight-bit plan's end: that plan keeps its sizes)
   p.configIndex = ConfigIndex(sorter, keyValue, elementCount, p.atomicRank, p.msdBits != 0);
   p.tilePlan = PlanTiles(sorter, p.configIndex, keyValue, elementCount, p.atomicRank);
   // Block sums instead of the look-back chain: sorts of one round (PlanTiles) on the four-pass plan -- with a hybrid
@@ -369,7 +349,10 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
   // VRDX_BLOCK_SUMS=0 keeps the classic look-back (measurements).
   static const int blockSumsKnob = TuningKnob("VRDX_BLOCK_SUMS");
   p.blockSums = p.tilePlan.blockSums && p.hybridCap == 0 && blockSumsKnob != 0;
-  p.msdTileKeys = MsdTileKeys(elementCount, (uint32_t)sorter->computeUnits, !keyValue && p.msdBits == 10);
+  // keys per tile of the MSD plan's histogram and scatter: equal tiles that fill whole rounds of one workgroup per CU
+  // (vrdx_layout.h); keys-only sorts by ten bits take two consecutive tiles per scatter workgroup (vrdx_kernels.hip)
+  p.msdTileKeys = vrdx::MsdTileKeysFor(elementCount, (uint32_t)sorter->computeUnits, vrdx::kMsdMaxTiles,
+                                       !keyValue && p.msdBits == 10);
   p.msdTiles = vrdx::RoundUp(elementCount, p.msdTileKeys);
   const uint32_t align = sorter->minStorageBufferOffsetAlignment;
   p.layout = vrdx::MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, p.blockSums, p.msdBits, p.msdTiles);
@@ -380,11 +363,11 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
     p.layout = vrdx::MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, p.blockSums);
   }
   if (!vrdx::LayoutFits(p.layout, elementCount)) {
-    // EVERY sort of the general path is checked, not only those with a plan in front: the layout depends on the tile plan, and the
-    // measurement knobs (VRDX_TAIL_SPLIT, VRDX_EVEN_SPLIT, VRDX_TILE_CONFIG) can select plans the offline sweep of
-    // tests/native/layout_check.cpp never saw.  Tiles of the kernel's full capacity without block rows fit for every N
-    // (2 (tiles - 1) KiB <= (P - 1) KiB from 8192 keys per tile up); smaller tiles cannot be helped: the scratch arrays
-    // must not leave the caller's allocation, so that sort is refused and says so (VRDX_HIP_STATUS_ENQUEUE_REFUSED).
+    // EVERY sort of the general path is checked, not only those with a plan in front: the layout depends on the tile plan,
+    // and a forced tile geometry (VRDX_TILE_CONFIG) can select plans the offline sweep of tests/native/layout_check.cpp
+    // never saw.  Tiles of the kernel's full capacity without block rows fit for every N (2 (tiles - 1) KiB <= (P - 1) KiB
+    // from 8192 keys per tile up); smaller tiles cannot be helped: the scratch arrays must not leave the caller's
+    // allocation, so that sort is refused and says so (VRDX_HIP_STATUS_ENQUEUE_REFUSED).
     const vrdx::TileConfig& c = vrdx::kTileConfigs[p.configIndex];
     p.tilePlan = vrdx::PlanTiles(elementCount, (uint32_t)sorter->computeUnits, (uint32_t)c.threads, (uint32_t)c.keysPerThread,
                                  (uint32_t)c.subTiles, false, false, 0);
@@ -552,8 +535,8 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
   // upsweep of all four passes at once
   {
     // Every workgroup ends with up to 1024 global atomics on the same 1024 words, so few, long-lived
-    // workgroups win for large inputs: one per CU and at least two groups of 16384 keys each (tools/hist_grid.sh:
-    // 17.4 us with 256 workgroups against 21.1 us with 512 at N = 2^23; equal at 2^25).  Small inputs
+    // workgroups win for large inputs: one per CU and at least two groups of 16384 keys each (tools/hist_grid.sh, removed,
+    // last at commit 3645810: 17.4 us with 256 workgroups against 21.1 us with 512 at N = 2^23; equal at 2^25).  Small inputs
     // want the opposite -- the kernel is one memory latency long, so up to 128 workgroups of at least
     // 4096 keys share it: 6.9 instead of 9.7 us at 2^18, 7.9 instead of 9.8 us at 2^20, same at 2^22.
     uint32_t grid = vrdx::RoundUp(elementCount, 2 * vrdx::kHistGroupKeys);
@@ -562,12 +545,10 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
     const uint32_t cap = (uint32_t)sorter->computeUnits * vrdx::kHistWorkgroupsPerCu;
     if (grid > cap) grid = cap;
     if (grid == 0) grid = 1;
-    static const int forcedGrid = TuningKnob("VRDX_HIST_GRID");  // tools/hist_grid.sh
-    if (forcedGrid > 0) grid = (uint32_t)forcedGrid;
     if (msdBits != 0) {
       // the MSD plan's form: window-bits counts per tile of up to 32768 keys (a workgroup takes whole tiles); the spine
       // kernel clears status region 0
-      if (forcedGrid <= 0) grid = std::min<uint32_t>(msdTiles, cap);
+      grid = std::min<uint32_t>(msdTiles, cap);
       EnqueueCheck(sorter, "histogram_msd_kernel", vrdx::LaunchHistogramMsd(stream, grid, m));
     } else {
       EnqueueCheck(sorter, "histogram_kernel",
@@ -577,13 +558,6 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
   }
 
   const uint32_t tiles = tilePlan.tiles;
-  // Key+value tiles fetch their values early (right after the ranking: they land during the scan and the
-  // regroup) -- on the final kernels that is as fast as or faster than fetching them after the
-  // look-back at every size (0-8 %, vrdx_selftest sweep with VRDX_KV_EARLY_VALUES=0|1); the late form
-  // stays selectable for measurements.
-  bool earlyValues = true;
-  static const int forcedEarly = TuningKnob("VRDX_KV_EARLY_VALUES");  // 0 | 1: tuning/testing
-  if (forcedEarly >= 0) earlyValues = forcedEarly != 0;
   // the arguments of pass `pass` of the four passes (also handed to the MSD plan's launches, whose second role they are)
   auto passArgs = [&](uint32_t pass) {
     vrdx::OnesweepArgs args;
@@ -620,7 +594,7 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
     static const int testSpinLimit = TuningKnob("VRDX_TEST_SPIN_LIMIT");
     if (testSpinLimit >= 0) args.spinLimit = (uint32_t)testSpinLimit;
 #endif
-    args.earlyValues = earlyValues ? 1u : 0u;
+    args.earlyValues = 1u;
     args.planInFront = msdBits != 0 ? 1u : 0u;  // the MSD plan in front may have taken the sort (verdict 3)
     args.slots = tilePlan.slots;
     args.fullTiles = tilePlan.fullTiles;

@@ -37,48 +37,13 @@
 
 namespace vrdx {
 
-// Cache-policy switches for measurements (tools/variants.sh, tools/nt_sweep.sh).  VRDX_STREAMING_LOADS:
-// 0 never, 1 by size (the product, see StreamingLoads below), 2 always; VRDX_HIST_NT: the same three values
-// for the histogram's key loads.  VRDX_NT_STORES: the `nt` bit on the scatter stores (off: measured, a loss).
-#ifndef VRDX_STREAMING_LOADS
-#define VRDX_STREAMING_LOADS 1
-#endif
-#ifndef VRDX_NT_STORES
-#define VRDX_NT_STORES 0
-#endif
-#ifndef VRDX_HIST_NT
-#define VRDX_HIST_NT 1
-#endif
-// Measurement only (profiles/r04_histogram_busy_stream.txt): the LAST pass of a sort scatters with non-temporal stores, so
-// that its output does not sit dirty in the caches when the next sort's histogram starts.  Off in the product: a
-// consumer of the sorted data wants it cached.
-#ifndef VRDX_NT_LAST_PASS
-#define VRDX_NT_LAST_PASS 0
-#endif
 // (The timing ablations round 5 measured the four-pass formulation's ceiling with -- VRDX_ABLATE: no look-back, no ticket,
 // contiguous stores; results wrong by construction -- are gone from the source: profiles/r05_ceiling.txt has the numbers, commit
 // 9caa359 the build.)
-// Measurement switches of the MSD plan's kernels (tools/r05/ablate.sh builds the variants): VRDX_MSD_XCD = 0: tiles handed
-// out round-robin instead of in consecutive chunks per XCD; VRDX_MSD_NT_LOADS / VRDX_MSD_BUCKET_NT: non-temporal loads in
-// the scatter / the bucket kernel.
-#ifndef VRDX_MSD_XCD
-#define VRDX_MSD_XCD 1
-#endif
-#ifndef VRDX_MSD_NT_LOADS
-#define VRDX_MSD_NT_LOADS 1
-#endif
-#ifndef VRDX_MSD_BUCKET_NT
-#define VRDX_MSD_BUCKET_NT 0
-#endif
-#ifndef VRDX_MSD_SCATTER_DYN
-#define VRDX_MSD_SCATTER_DYN 1
-#endif
-#ifndef VRDX_MSD_EVEN_WAVES
-#define VRDX_MSD_EVEN_WAVES 1  // bucket_sort2_kernel deals a bucket's chunks out evenly over its waves
-#endif
-#ifndef VRDX_MSD_OUT_NT
-#define VRDX_MSD_OUT_NT 1  // the bucket kernel's output stores non-temporal: 0 never, 1 by mode and size (the product), 2 always
-#endif
+// (So are the compile-time measurement switches of rounds 2-6: the cache policy of the tile, histogram and bucket loads and
+// stores, the MSD scatter's tile order and tile size, the bucket kernel's old wave split, the look-back window, the LDS
+// swizzle and the histogram's geometry.  Only the product's choice of each is left; profiles/ has the numbers, commit
+// 3645810 the switches.)
 
 
 // Timing-only phase trace for tools/trace.sh (never defined in the product build): thread 0 of
@@ -189,12 +154,10 @@ __device__ __forceinline__ void LoadStriped(const uint32_t* base, uint32_t first
 // Key+value sorts whose four buffers (16 bytes per element) are between one and three times the
 // 256 MiB Infinity Cache read their tiles with NON-TEMPORAL loads: the reads then do not displace the
 // lines the previous pass has just written, which is what this pass reads.  Measured on MI355X
-// (tools/nt_sweep.sh, profiles/r02_streaming_loads.txt): +3 ... +11 % for 2^24 < N <= 3 * 2^24 pairs
-// (66 instead of 59 GItems/s at 2^25), nothing below, -3 ... -4 % above; keys-only sorts gain nothing at
-// any size.  The element count is the one the kernel sorts (indirect sorts included).
+// (profiles/r02_streaming_loads.txt; tools/nt_sweep.sh, removed, last at commit 3645810): +3 ... +11 % for
+// 2^24 < N <= 3 * 2^24 pairs (66 instead of 59 GItems/s at 2^25), nothing below, -3 ... -4 % above; keys-only
+// sorts gain nothing at any size.  The element count is the one the kernel sorts (indirect sorts included).
 __device__ __forceinline__ bool StreamingLoads(bool keyValue, uint32_t n) {
-  if (VRDX_STREAMING_LOADS == 0) return false;
-  if (VRDX_STREAMING_LOADS == 2) return true;
   return keyValue && n > kStreamingLoadsAbove && n <= kStreamingLoadsUpTo;
 }
 
@@ -455,11 +418,10 @@ __global__ __launch_bounds__(kHistThreads) void histogram_kernel(const uint32_t*
       HistFetch<NT>(keys4, g + 3 * step, tid, nvec, b);
     }
   };
-  const bool streamingInput = VRDX_HIST_NT == 2 || (VRDX_HIST_NT == 1 && n > kHistStreamingLoadsAbove);
   if (nvec == 0) {  // fewer than four keys
     for (uint32_t i = tid; i < kBinWords; i += kHistThreads) bins[i] = 0;
     LdsBarrier();
-  } else if (streamingInput) {
+  } else if (n > kHistStreamingLoadsAbove) {
     asm volatile("; non-temporal key loads" ::: "memory");  // keeps the two loops apart (see LoadTile)
     sweep(std::true_type{});
   } else {
@@ -530,24 +492,12 @@ __device__ __forceinline__ TileSpan SpanOfTile(uint32_t tile, uint32_t n, uint32
 // groups' partial sums together in order.  Returns the exclusive prefix in the threads tid < 256.
 //
 // lds: pos[256] | sum[GROUPS][256] | info[GROUPS][256]   (info = consumed | hitInclusive << 8)
-#ifndef VRDX_LOOKBACK_WINDOW
-#define VRDX_LOOKBACK_WINDOW 8
-#endif
-constexpr int kLookBackWindow = VRDX_LOOKBACK_WINDOW;
+constexpr int kLookBackWindow = 8;
 constexpr int32_t kLookBackDone = INT32_MIN;
 
 // One 16-byte store of a sorted quad to out[index .. index + 3] (4-byte aligned).
-__device__ __forceinline__ void StoreQuad(uint32_t* out, uint32_t index, u32x4 q, bool nt = false) {
-  u32x4_a4* const p = reinterpret_cast<u32x4_a4*>(reinterpret_cast<char*>(out) + (uint64_t)(index * 4u));
-  if (VRDX_NT_STORES) {
-    __builtin_nontemporal_store(q, p);
-  } else if (VRDX_NT_LAST_PASS && nt) {  // wave-uniform; the empty asm keeps the two kinds of store apart (see LoadTile)
-    asm volatile("; non-temporal scatter" ::: "memory");
-    __builtin_nontemporal_store(q, p);
-    asm volatile("" ::: "memory");
-  } else {
-    *p = q;
-  }
+__device__ __forceinline__ void StoreQuad(uint32_t* out, uint32_t index, u32x4 q) {
+  *reinterpret_cast<u32x4_a4*>(reinterpret_cast<char*>(out) + (uint64_t)(index * 4u)) = q;
 }
 
 // RADIX: digits per status row (256 in every kernel built today; THREADS / RADIX groups of threads share the look-back).
@@ -861,11 +811,7 @@ __device__ __forceinline__ uint32_t StagingSlot(uint32_t p) {
   constexpr uint32_t kPerDigit = TILE / 256;  // keys per digit in a flat tile
   constexpr int kLog = kPerDigit >= 128 ? 7 : 6;
   static_assert(TILE >= (1u << (kLog + 4)), "source bits inside the tile");
-#ifdef VRDX_NO_SWIZZLE
-  return p;
-#else
   return p ^ ((p >> (kLog - 2)) & 0x3Cu);
-#endif
 }
 
 // Regroup: sorted[StagingSlot(rank + waveBase[digit])] = key, eight keys at a time -- the eight
@@ -971,7 +917,7 @@ template <int THREADS, int KPT, bool KEEP_DIGITS, bool DYN = false>
 __device__ __forceinline__ void ScatterStagedKeys(const uint32_t* sorted, const uint32_t* offset, uint32_t* out,
                                                   uint32_t valid, uint32_t shift, int tid, uint32_t boundaryQuad,
                                                   uint32_t (&digits)[KEEP_DIGITS ? KPT / 4 : 1],
-                                                  uint32_t& boundaryDigits, bool nt = false) {
+                                                  uint32_t& boundaryDigits) {
   constexpr uint32_t STAGE = THREADS * KPT;
   constexpr int B = DYN ? (KPT % 16 == 0 ? 4 : 1) : ScatterBatch<KPT, KEEP_DIGITS>();
 #pragma unroll
@@ -993,7 +939,7 @@ __device__ __forceinline__ void ScatterStagedKeys(const uint32_t* sorted, const 
     }
 #pragma unroll
     for (int b = 0; b < B; ++b)
-      if (whole[b]) StoreQuad(out, o[b], k4[b], nt);
+      if (whole[b]) StoreQuad(out, o[b], k4[b]);
   }
   if (boundaryQuad != ~0u) {
     const u32x4 k4 = *reinterpret_cast<const u32x4*>(&sorted[StagingSlot<STAGE>(boundaryQuad)]);
@@ -1006,7 +952,7 @@ __device__ __forceinline__ void ScatterStagedKeys(const uint32_t* sorted, const 
 template <int THREADS, int KPT, bool DYN = false>
 __device__ __forceinline__ void ScatterStagedValues(const uint32_t* sorted, const uint32_t* offset, uint32_t* out,
                                                     uint32_t valid, int tid, uint32_t boundaryQuad,
-                                                    const uint32_t (&digits)[KPT / 4], uint32_t boundaryDigits, bool nt = false) {
+                                                    const uint32_t (&digits)[KPT / 4], uint32_t boundaryDigits) {
   constexpr uint32_t STAGE = THREADS * KPT;
   constexpr int B = DYN ? (KPT % 16 == 0 ? 4 : 1) : ScatterBatch<KPT, false>();
 #pragma unroll
@@ -1026,7 +972,7 @@ __device__ __forceinline__ void ScatterStagedValues(const uint32_t* sorted, cons
       const uint32_t p = StagingSlot<STAGE>(4u * (tid + (j0 + b) * THREADS));
       const uint32_t d0 = digits[j0 + b] & 0xFFu, d3 = digits[j0 + b] >> 8;
       if (p + 3 < valid && d0 == d3)
-        StoreQuad(out, o[b], v4[b], nt);
+        StoreQuad(out, o[b], v4[b]);
     }
   }
   if (boundaryQuad != ~0u)
@@ -1095,8 +1041,8 @@ __device__ __forceinline__ void OnesweepBody(const OnesweepArgs a) {
   // headline: with it the form took two registers more and 1.7 % there, measured.  Key+value sorts of 4.4 ... 8.1 M pairs
   // do meet that form with the hybrid plan recorded: their launches 1-3 take the long way to the same verdict, ~2 us each.
   // Running them on the form with run-time slot counts instead -- which has the return, but fetches its values late --
-  // measured the same within 1 %, VRDX_EVEN_SPLIT=1, so they stay on this one.  Launch 0 of EVERY form writes the verdict
-  // below: vrdxHipReadPlanVerdict reports it.)
+  // measured the same within 1 % (the even split forced by a tuning knob, removed, last at commit 3645810), so they stay
+  // on this one.  Launch 0 of EVERY form writes the verdict below: vrdxHipReadPlanVerdict reports it.)
   constexpr bool kVerdictReturn = !(KV && KPT == 32 && !DYN);
   if constexpr (kVerdictReturn) {
     if (a.hybridCap != 0 && a.pass != 0 && *a.planWord == 1u) return;
@@ -1189,7 +1135,8 @@ __device__ __forceinline__ void OnesweepBody(const OnesweepArgs a) {
   else
     RankBallot<KPT, PACKED, DYN>(key, shift, waveHist + wave * 256, lane, rank, slots);
   ForgetDerivedValues<KPT>(key);
-  // key+value, early form: the values start their trip now and land during the scan and the regroup
+  // key+value, early form: the values start their trip now and land during the scan and the regroup (as fast as fetching
+  // them after the look-back or faster, 0-8 %, at every size: profiles/r01_sweep_kv_early_values.txt)
   // (The form with run-time slot counts always fetches them late: its loops end in branches, the values would be live
   // across all of them and the kernel would need 140 registers -- 48 bytes of scratch per lane, 5-10 % slower, round 3.)
   constexpr bool kEarlyValuesBuilt = KV && !DYN;
@@ -1255,10 +1202,9 @@ __device__ __forceinline__ void OnesweepBody(const OnesweepArgs a) {
   LdsBarrier();
   VRDX_STAMP(5);
 
-  // Key+value, late form (measurements only, VRDX_KV_EARLY_VALUES=0): the values are fetched now and
-  // the key scatter covers their latency.  It used to win by 1-3 % for sorts of four and more rounds
-  // of tiles; on the final kernels the early form is as fast or faster everywhere.  Issued right
-  // before the look-back the loads queue in front of its agent-scope status reads (6 -> 9 us, measured).
+  // Key+value, late form (the form with run-time slot counts; a.earlyValues is always 1, see OnesweepArgs): the values are
+  // fetched now and the key scatter covers their latency.  Issued right before the look-back the loads would queue in front
+  // of its agent-scope status reads (6 -> 9 us, measured).
   if constexpr (KV) {
     if (!kEarlyValuesBuilt || !a.earlyValues)
       LoadTile<KPT, DYN>(valuesIn, loadBase, tileEnd, valid == frame, 0u, val, streaming, slots);
@@ -1268,9 +1214,8 @@ __device__ __forceinline__ void OnesweepBody(const OnesweepArgs a) {
   uint32_t digits[KV ? KPT / 4 : 1];  // key+value: first and last digit of every quad, for the value phase
   uint32_t boundaryDigits = 0;
   const uint32_t boundaryQuad = BoundaryQuad(tid, tileExclusive, count, valid);
-  const bool ntStores = VRDX_NT_LAST_PASS != 0 && a.pass == VRDX_PASSES - 1;
   ScatterStagedKeys<THREADS, KPT, KV, DYN>(sorted, tileOffset, keysOut, valid, shift, tid, boundaryQuad, digits,
-                                           boundaryDigits, ntStores);
+                                           boundaryDigits);
   if constexpr (KV) {
     LdsBarrier();  // every key has left the staging buffer
 #pragma unroll
@@ -1280,7 +1225,7 @@ __device__ __forceinline__ void OnesweepBody(const OnesweepArgs a) {
     }
     LdsBarrier();
     ScatterStagedValues<THREADS, KPT, DYN>(sorted, tileOffset, valuesOut, valid, tid, boundaryQuad, digits,
-                                           boundaryDigits, ntStores);
+                                           boundaryDigits);
   }
 #ifdef VRDX_TRACE
   VRDX_STAMP(6);
@@ -1517,16 +1462,15 @@ __device__ __forceinline__ void OnesweepPairBody(const OnesweepArgs a) {
   uint32_t boundaryDigits = 0;
   const uint32_t boundaryQuadA = BoundaryQuad(tid, localA, countA, validA);
   const uint32_t boundaryQuadB = BoundaryQuad(tid, localB, countB, validB);
-  const bool ntStores = VRDX_NT_LAST_PASS != 0 && a.pass == VRDX_PASSES - 1;
   ScatterStagedKeys<THREADS, KPT, false, DYN>(sorted, offsetA, keysOut, validA, shift, tid, boundaryQuadA, digits,
-                                              boundaryDigits, ntStores);
+                                              boundaryDigits);
   LdsBarrier();  // the staging buffer is free again
 
   // ---- B: regroup, scatter -----------------------------------------------------------------------
   RegroupKeys<KPT, SUB, PACKED, false, DYN>(keyB, rankB, shift, myHist, sorted, unusedSlots, slots);
   LdsBarrier();
   ScatterStagedKeys<THREADS, KPT, false, DYN>(sorted, offsetB, keysOut, validB, shift, tid, boundaryQuadB, digits,
-                                              boundaryDigits, ntStores);
+                                              boundaryDigits);
 #ifdef VRDX_TRACE
   VRDX_STAMP(6);
   if (a.trace != nullptr && tid == 0) {
@@ -2533,8 +2477,7 @@ __global__ __launch_bounds__(kHistThreads) void histogram_msd_kernel(MsdArgs a) 
     else
       loop(std::integral_constant<uint32_t, TABLES>{});
   };
-  const bool streamingInput = VRDX_HIST_NT == 2 || (VRDX_HIST_NT == 1 && n > kHistStreamingLoadsAbove);
-  if (streamingInput) {
+  if (n > kHistStreamingLoadsAbove) {
     asm volatile("; non-temporal key loads" ::: "memory");
     sweep(std::true_type{});
   } else {
@@ -2672,13 +2615,14 @@ __global__ __launch_bounds__(1024) void spine_msd_kernel(MsdArgs a) {
 // that owns the run (two runs per thread here).  The tile's 2^BITS bases arrive with the keys: one row of prefixes and the
 // bucket bases, loaded first.
 //
-// XCD-AWARE tile order.  A tile's run of bucket d is followed in memory by the NEXT tile's run of bucket d, and with runs of
-// 128 bytes (32768 keys over 1024 buckets) nearly every 128-byte line is written by two tiles.  The eight XCDs have an L2
-// each: written from two of them, a line leaves both as a partial line.  Measured at 2^25 keys (tools/r05/ablate.sh,
-// profiles/r05_msd_scatter.txt): no stores 48.6 us, contiguous stores 64.0, the real runs 98.6-106.9 with tiles handed out
-// round-robin -- and 91.3 with this order: XCD x (the workgroups b with b % 8 == x: observed dispatch order, for speed only,
-// nothing depends on it) takes the CONSECUTIVE tiles [x C, (x + 1) C), C = ceil(tiles / 8), so that the lines of a
-// bucket's range are completed inside one L2.  The grid is 8 C workgroups; one without a tile returns at once.
+// XCD-AWARE tile order.  A tile's run of bucket d is followed in memory by the NEXT tile's run of bucket d, and with runs
+// of 128 bytes (32768 keys over 1024 buckets) nearly every 128-byte line is written by two tiles.  The eight XCDs have an
+// L2 each: written from two of them, a line leaves both as a partial line.  Measured at 2^25 keys (tools/r05/ablate.sh,
+// removed, last at commit 3645810; profiles/r05_msd_scatter.txt): no stores 48.6 us, contiguous stores 64.0, the real runs
+// 98.6-106.9 with tiles handed out round-robin -- and 91.3 with this order: XCD x (the workgroups b with b % 8 == x:
+// observed dispatch order, for speed only, nothing depends on it) takes the CONSECUTIVE tiles [x C, (x + 1) C), C =
+// ceil(tiles / 8), so that the lines of a bucket's range are completed inside one L2.  The grid is 8 C workgroups; one
+// without a tile returns at once.
 // NON-TEMPORAL loads of the keys and values (read once): they then do not push the lines the scatter is still completing
 // out of that L2, nor the scattered data out of the caches before the bucket kernel reads them: 79.4 instead of 91.3 us,
 // and the bucket kernel behind it 112 instead of 116.
@@ -2708,13 +2652,12 @@ __device__ __forceinline__ void ScatterMsdBody(const MsdArgs a) {
   const uint32_t n = ElementCount(a.maxCount, a.countPtr);
   // the grid is 8 C workgroups, C = ceil(tiles / 8): workgroup b takes tile (b % 8) C + b / 8 of its XCD's chunk
   const uint32_t perXcd = gridDim.x / 8u;
-  const uint32_t tile = VRDX_MSD_XCD ? (blockIdx.x % 8u) * perXcd + blockIdx.x / 8u : blockIdx.x;
+  const uint32_t tile = (blockIdx.x % 8u) * perXcd + blockIdx.x / 8u;
   // EVEN-SPLIT tiles (MsdTilePlan in vrdx_api.cpp): every wave takes `slots` of its KPT slots of 64 keys (a multiple of four),
   // a tile is slots x 1024 keys, chosen so that the tiles fill whole rounds of one workgroup per CU -- 520 tiles of 32768 keys
   // cost three rounds, the third for eight tiles; 768 tiles of 24576 cost three rounds of three quarters the length.
-  constexpr bool DYN = VRDX_MSD_SCATTER_DYN != 0;  // (0: tiles of full capacity only, with VRDX_MSD_EVEN=0 -- measurements)
-  const uint32_t slots = DYN ? a.tileKeys / (uint32_t)THREADS : (uint32_t)KPT;
-  const uint32_t frame = DYN ? a.tileKeys : TILE;
+  const uint32_t slots = a.tileKeys / (uint32_t)THREADS;
+  const uint32_t frame = a.tileKeys;
   const uint32_t tileStart = tile * frame;
   // Verdict first, loads second: a wave cannot end with loads in flight, so a launch that is turned down (a bucket beyond the
   // capacity: the four passes behind it run) would still read every key -- 22 us at 2^25 for nothing, measured.
@@ -2734,7 +2677,7 @@ __device__ __forceinline__ void ScatterMsdBody(const MsdArgs a) {
   const uint32_t tileEnd = tileStart + valid;
   const uint32_t loadBase = tileStart + wave * (slots * 64) + lane;
   uint32_t key[KPT];
-  LoadStriped<KPT, VRDX_MSD_NT_LOADS != 0, DYN>(a.keysCaller, loadBase, tileEnd, valid == frame, 0xFFFFFFFFu, key, slots);  // pad: downsweep.slang:81
+  LoadStriped<KPT, true, true>(a.keysCaller, loadBase, tileEnd, valid == frame, 0xFFFFFFFFu, key, slots);  // pad: downsweep.slang:81
   uint32_t prefixWord = 0, base0 = 0, base1 = 0;
   if ((uint32_t)tid < ROW && valid != 0) {
     prefixWord = a.tileCounts[(size_t)tile * ROW + tid];
@@ -2748,7 +2691,7 @@ __device__ __forceinline__ void ScatterMsdBody(const MsdArgs a) {
 #pragma unroll
   for (uint32_t i = 0; i < ROW / 256u; ++i) reinterpret_cast<u32x4*>(myRow)[lane + 64 * i] = u32x4{0u, 0u, 0u, 0u};
   uint32_t rank[KPT / 2];  // ranks, then physical staging slots, two to a register
-  RankPacked16<KPT, DYN>(key, SHIFT, BITS, myRow, lane, rank, slots);
+  RankPacked16<KPT, true>(key, SHIFT, BITS, myRow, lane, rank, slots);
   ForgetDerivedValues<KPT>(key);
   LdsBarrier();
 
@@ -2764,18 +2707,18 @@ __device__ __forceinline__ void ScatterMsdBody(const MsdArgs a) {
     tileOffset[2 * tid + 1] = base1 + (prefixWord >> 16) - local1;
   }
   LdsBarrier();
-  PositionsPacked16<KPT, TILE, DYN>(key, SHIFT, BITS, myRow, rank, slots);
+  PositionsPacked16<KPT, TILE, true>(key, SHIFT, BITS, myRow, rank, slots);
   LdsBarrier();  // the counters are dead: the staging buffer takes their place
 #pragma unroll
   for (int i = 0; i < KPT; ++i) {
-    if (DYN && i % 4 == 0 && (uint32_t)i >= slots) break;
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
     sorted[(rank[i / 2] >> (16 * (i % 2))) & 0xFFFFu] = key[i];
   }
   LdsBarrier();
   // key+value: the values are fetched now and land while the keys are scattered (like the pass kernels' early value fetch)
   uint32_t val[KV ? KPT : 1];
   if constexpr (KV)
-    LoadStriped<KPT, VRDX_MSD_NT_LOADS != 0, DYN>(a.valuesCaller, loadBase, tileEnd, valid == frame, 0u, val, slots);  // pad: downsweep.slang:85
+    LoadStriped<KPT, true, true>(a.valuesCaller, loadBase, tileEnd, valid == frame, 0u, val, slots);  // pad: downsweep.slang:85
 
   // scatter: whole single-digit quads in the main loop, the quads around a run's start by the thread that owns the run
   constexpr int QUADS = KPT / 4;
@@ -2838,7 +2781,7 @@ __device__ __forceinline__ void ScatterMsdBody(const MsdArgs a) {
     LdsBarrier();  // every key has left the staging buffer
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
-      if (DYN && i % 4 == 0 && (uint32_t)i >= slots) break;
+      if (i % 4 == 0 && (uint32_t)i >= slots) break;
       sorted[(rank[i / 2] >> (16 * (i % 2))) & 0xFFFFu] = val[i];
     }
     LdsBarrier();
@@ -2899,8 +2842,8 @@ __device__ __forceinline__ void ScatterMsdPairBody(const MsdArgs a) {
   const uint32_t valid = validA + validB;
   const uint32_t baseA = startA + wave * (slots * 64) + lane, baseB = baseA + frame;
   uint32_t keyA[KPT], keyB[KPT];
-  LoadStriped<KPT, VRDX_MSD_NT_LOADS != 0, true>(a.keysCaller, baseA, startA + validA, validA == frame, 0xFFFFFFFFu, keyA, slots);
-  LoadStriped<KPT, VRDX_MSD_NT_LOADS != 0, true>(a.keysCaller, baseB, startB + validB, validB == frame, 0xFFFFFFFFu, keyB, slots);
+  LoadStriped<KPT, true, true>(a.keysCaller, baseA, startA + validA, validA == frame, 0xFFFFFFFFu, keyA, slots);
+  LoadStriped<KPT, true, true>(a.keysCaller, baseB, startB + validB, validB == frame, 0xFFFFFFFFu, keyB, slots);
   uint32_t prefixWord = 0, base0 = 0, base1 = 0;
   if ((uint32_t)tid < ROW && valid != 0) {
     prefixWord = a.tileCounts[(size_t)tileA * ROW + tid];
@@ -3053,28 +2996,16 @@ __device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_
   // base + (w < extra) chunks, consecutive in memory (waves in order, (slot, lane) order inside a wave: the ranking stays
   // stable).  With `slots` the same for every wave (SortInWorkgroup) a bucket of 16385 elements keeps thirteen waves busy
   // with twenty slots each, and every phase lasts as long as twenty slots take; dealt out evenly one wave has twenty and
-  // fifteen have sixteen (VRDX_MSD_EVEN_WAVES = 0: the old rule, measurements).
-  uint32_t slots, first;
-  if (VRDX_MSD_EVEN_WAVES) {
-    const uint32_t chunks = (n + 255u) / 256u;  // <= 144: n <= 36864
-    const uint32_t base = chunks / WAVES, extra = chunks % WAVES;
-    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
-    slots = 4u * (base + (w < extra ? 1u : 0u));
-    first = 256u * (w * base + (w < extra ? w : extra)) + lane;  // element i of this lane: first + 64 * i
-  } else {
-    slots = 4u * ((n + 4u * THREADS - 1u) / (4u * THREADS));
-    slots = slots < (uint32_t)KPT ? slots : (uint32_t)KPT;
-    first = wave * (slots * 64) + lane;
-    // a wave whose range starts at or behind n holds nothing but pads and skips every loop over its slots (SortInWorkgroup)
-    const uint32_t waveStart = (uint32_t)wave * (slots * 64);
-    const uint32_t mine = n > waveStart ? n - waveStart : 0u;
-    const uint32_t waveSlots = 4u * ((mine + 255u) / 256u);
-    slots = waveSlots < slots ? waveSlots : slots;
-  }
+  // fifteen have sixteen (the old rule: a measurement switch, removed, last at commit 3645810).
+  const uint32_t chunks = (n + 255u) / 256u;  // <= 144: n <= 36864
+  const uint32_t base = chunks / WAVES, extra = chunks % WAVES;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+  const uint32_t slots = 4u * (base + (w < extra ? 1u : 0u));
+  const uint32_t first = 256u * (w * base + (w < extra ? w : extra)) + lane;  // element i of this lane: first + 64 * i
   uint32_t key[KPT];
   uint32_t val[KV ? KPT : 1];
-  LoadStriped<KPT, VRDX_MSD_BUCKET_NT != 0, DYN>(keysIn, first, n, false, 0xFFFFFFFFu, key, slots);
-  if constexpr (KV) LoadStriped<KPT, VRDX_MSD_BUCKET_NT != 0, DYN>(valuesIn, first, n, false, 0u, val, slots);
+  LoadStriped<KPT, false, DYN>(keysIn, first, n, false, 0xFFFFFFFFu, key, slots);
+  if constexpr (KV) LoadStriped<KPT, false, DYN>(valuesIn, first, n, false, 0u, val, slots);
 
   uint32_t* const myRow = counters + wave * ROW;
 #pragma unroll 1
@@ -3148,13 +3079,12 @@ __device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_
   }
   // Key+value sorts of more than 2^24 pairs write their result with NON-TEMPORAL stores: 256 MiB and more of output is the
   // size of the Infinity Cache, and left dirty in the caches it is written back under the next kernel's reads -- the next
-  // sort's histogram in a batch of sorts.  Measured (tools/r05/out_nt2.sh, bench.py's loop of 20 sorts): key+value 82 ->
-  // 86.3 GItems/s at 2^25, a single sort on its own unchanged (0.4225 / 0.4239 ms).  Keys-only sorts keep plain stores:
-  // their loop gains the same 4 % but a single sort LOSES 4 % (its last kernel then waits for its own write-back), and a
-  // consumer of 128 MiB of sorted keys finds a good part of them in the cache.  (The empty asm statements keep the two
-  // kinds of store apart, see LoadTile.)
-  const bool streamOut = VRDX_MSD_OUT_NT == 2 || (VRDX_MSD_OUT_NT == 1 && KV && a.maxCount > kStreamingLoadsAbove);
-  if (streamOut) {
+  // sort's histogram in a batch of sorts.  Measured (tools/r05/out_nt2.sh, removed, last at commit 3645810; bench.py's loop
+  // of 20 sorts): key+value 82 -> 86.3 GItems/s at 2^25, a single sort on its own unchanged (0.4225 / 0.4239 ms).
+  // Keys-only sorts keep plain stores: their loop gains the same 4 % but a single sort LOSES 4 % (its last kernel then
+  // waits for its own write-back), and a consumer of 128 MiB of sorted keys finds a good part of them in the cache.  (The
+  // empty asm statements keep the two kinds of store apart, see LoadTile.)
+  if (KV && a.maxCount > kStreamingLoadsAbove) {
     asm volatile("; non-temporal output" ::: "memory");
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
@@ -3819,8 +3749,8 @@ hipError_t LaunchScatterMsd(hipStream_t stream, bool keyValue, const MsdArgs& ar
 
 // Workgroups of the plan's bucket launch.  The full-size kernel (one workgroup per CU) takes TWO buckets per workgroup, one
 // after the other (BucketSort2Body): half as many workgroups to start and to drain -- 107.4 instead of 110.9 us keys-only at
-// 2^25, 175-178 instead of 179-180 key+value (tools/r06/bucket_grid.sh, bucket_grid2.sh).  The half-size kernel (two
-// workgroups per CU) keeps one: 47.7 against 47.0 us keys-only at 2^24 with two.
+// 2^25, 175-178 instead of 179-180 key+value (tools/r06/bucket_grid.sh, bucket_grid2.sh, removed, last at commit
+// 3645810).  The half-size kernel (two workgroups per CU) keeps one: 47.7 against 47.0 us keys-only at 2^24 with two.
 static uint32_t MsdBucketGrid(uint32_t bits, bool halfSizeKernel) { return halfSizeKernel ? 1u << bits : (1u << bits) / 2u; }
 
 hipError_t LaunchBucketSort2(hipStream_t stream, bool keyValue, const MsdArgs& args) {
