@@ -69,7 +69,8 @@ def test_single_header_implementation_exports_the_segmented_entry_points(tmp_pat
 
 def test_code_object_holds_every_kernel_the_launcher_asks_for():
     """The gfx950 code object embedded in the single header (cross-compiled here) contains every mangled name
-    expected_kernels() lists -- the segmented kernels among them, both ranking modes, keys-only and key+value."""
+    expected_kernels() lists -- the segmented kernels among them, both ranking modes, keys-only and key+value -- and no
+    kernel the list (vrdx_launch.inc) leaves out."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
         import generate_single_header as gen
@@ -83,6 +84,8 @@ def test_code_object_holds_every_kernel_the_launcher_asks_for():
     blob = bytes(int(x) for x in array.replace("\n", "").split(","))
     missing = [n for n in names if n.encode() not in blob]
     assert not missing, missing
+    kernels = {k.decode() for k in re.findall(rb"(_ZN4vrdx\w+)\.kd\x00", blob)}
+    assert kernels == set(names) and len(names) == len(kernels), (sorted(kernels ^ set(names)), len(names))
 
 
 def test_segmented_storage_carving_fits_every_count(tmp_path):

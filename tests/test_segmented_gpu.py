@@ -368,7 +368,8 @@ int main() {
 
 def test_single_header_segmented_parity(tmp_path):
     """The segmented entry point through the single header's own launcher (vrdx_module_launch.inc: the kernels resolved by
-    mangled name, their LDS sizes restated there), compiled with plain g++: every size class in one key+value call."""
+    mangled name, with the LDS sizes of the launch layer it shares with the library), compiled with plain g++: every size
+    class in one key+value call."""
     header = os.path.join(ROOT, "build", "single_header", "vk_radix_sort.h")
     if not os.path.exists(header):
         subprocess.run(["python3", os.path.join(ROOT, "tools", "generate_single_header.py"), "-o", header], check=True)

@@ -58,8 +58,9 @@ def test_single_header_passes_the_native_parity_battery():
 @pytest.mark.gpu
 def test_single_header_passes_the_msd_battery():
     """The MSD plan through the single header's own launcher (vrdx_module_launch.inc: hipModuleLaunchKernel by mangled name,
-    its grids and LDS sizes restated there) -- the sizes the quick battery stops short of: both bucket kernels, both
-    windows, the plan's launches in their second role as passes 0 and 1 (keys-only and key+value), every verdict."""
+    with the grids and LDS sizes of the launch layer it shares with the library) -- the sizes the quick battery stops short
+    of: both bucket kernels, both windows, the plan's launches in their second role as passes 0 and 1 (keys-only and
+    key+value), every verdict."""
     _header()
     exe = os.path.join(NATIVE, "selftest_single_header")
     subprocess.run(["make", "-C", NATIVE, "selftest_single_header"], check=True, capture_output=True)

@@ -1071,7 +1071,7 @@ def test_small_sort_boundary_sizes(torch_mod, sorter, oracle, n):
     check_against_oracle(torch_mod, sorter, oracle, k, iota, count=max(n - 3, 0), indirect=True, max_count=n)
 
 
-ALL_TILE_CONFIGS = ["1024x8", "1024x16", "1024x32", "1024x32x2"]  # == kTileConfigs in vrdx_kernels.hip
+ALL_TILE_CONFIGS = ["1024x8", "1024x16", "1024x32", "1024x32x2"]  # == kTileConfigs in vrdx_launch.inc
 
 
 def _selftest(args, **env):

@@ -731,18 +731,21 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   // hold one or two workgroups per CU)
   const uint32_t cus = (uint32_t)sorter->computeUnits;
   EnqueueCheck(sorter, "segmented_small_kernel",
-               vrdx::LaunchSegmentedSmall(stream, std::min<uint32_t>(segmentCount, 1u << 20), keyValue, atomicRank, a));
+               vrdx::LaunchSegmented(stream, vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20), keyValue,
+                                     atomicRank, a));
   Stamp(pool, query + 2, stream);
   const uint32_t midGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.midCap), 2u * cus);
   if (midGrid != 0) {
-    EnqueueCheck(sorter, "segmented_mid_kernel", vrdx::LaunchSegmentedMid(stream, midGrid, keyValue, atomicRank, a));
+    EnqueueCheck(sorter, "segmented_mid_kernel",
+                 vrdx::LaunchSegmented(stream, vrdx::kSegmentMid, midGrid, keyValue, atomicRank, a));
     Stamp(pool, query + 3, stream);
   } else {
     StampSame(pool, query + 3, query + 2);
   }
   const uint32_t largeGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.largeCap), 2u * cus);
   if (largeGrid != 0) {
-    EnqueueCheck(sorter, "segmented_large_kernel", vrdx::LaunchSegmentedLarge(stream, largeGrid, keyValue, atomicRank, a));
+    EnqueueCheck(sorter, "segmented_large_kernel",
+                 vrdx::LaunchSegmented(stream, vrdx::kSegmentLarge, largeGrid, keyValue, atomicRank, a));
     Stamp(pool, query + 4, stream);
   } else {
     StampSame(pool, query + 4, query + 3);
@@ -781,11 +784,7 @@ VkResult vrdxCreateSorter(const VrdxSorterCreateInfo* pCreateInfo, VrdxSorter* p
   int previous = 0;
   (void)hipGetDevice(&previous);
   hipError_t e = hipSetDevice(ordinal);
-  for (int i = 0; i < vrdx::kNumTileConfigs && e == hipSuccess; ++i) e = vrdx::PrepareKernels(i);
-  if (e == hipSuccess) e = vrdx::PrepareSmallSort();
-  if (e == hipSuccess) e = vrdx::PrepareBucketSort();
-  if (e == hipSuccess) e = vrdx::PrepareMsd();
-  if (e == hipSuccess) e = vrdx::PrepareSegmented();
+  if (e == hipSuccess) e = vrdx::PrepareKernels();
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sorter->stickyStatus), 2 * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(sorter->stickyStatus, 0, 2 * sizeof(uint32_t));
   if (e == hipSuccess) sorter->declinedPlans = sorter->stickyStatus + 1;

@@ -4,6 +4,7 @@
 #define VRDX_KERNELS_H
 
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace vrdx {
@@ -31,7 +32,7 @@ struct TileConfig {
   uint32_t tileKeys() const { return (uint32_t)threads * (uint32_t)keysPerThread * (uint32_t)subTiles; }
 };
 constexpr int kNumTileConfigs = 4;
-extern const TileConfig kTileConfigs[kNumTileConfigs];
+extern const TileConfig kTileConfigs[kNumTileConfigs];  // vrdx_launch.inc
 
 // Every spin is bounded: a look-back that makes no progress for this many trips sets the failure word and goes on
 // (result unspecified) instead of hanging the GPU.
@@ -79,8 +80,8 @@ struct OnesweepArgs {
   uint32_t planInFront;
 };
 
-// Raises the dynamic-LDS limit of both instantiations (keys-only, key-value) of one tile config.
-hipError_t PrepareKernels(int configIndex);
+// Once per sorter, on the current device: raises the dynamic-LDS limit of every kernel (vrdx_launch.inc).
+hipError_t PrepareKernels();
 
 // Also zeroes the two tile tickets and status region 0 (statusClearBytes from statusClear, whole 1 KiB rows): they live
 // outside the prefix of the storage that the fill in front of this kernel clears.
@@ -95,7 +96,6 @@ hipError_t LaunchOnesweep(hipStream_t stream, int configIndex, uint32_t grid, bo
 // Small sorts (maxCount <= kSmallSortMaxElements): the whole sort in one workgroup and one launch,
 // in place in keys / values (values == nullptr: keys-only); of the storage only *failure is written (0).
 constexpr uint32_t kSmallSortMaxElements = 16384;
-hipError_t PrepareSmallSort();
 hipError_t LaunchSmallSort(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
                            const uint32_t* countPtr, uint32_t* failure);
 
@@ -113,7 +113,6 @@ struct BucketSortArgs {
   uint32_t hybridCap;              // elements one workgroup can take (selects the instantiation)
   const uint32_t* planWord;        // the verdict word in the storage (VRDX_OFF_PLAN), written by launch 0
 };
-hipError_t PrepareBucketSort();
 hipError_t LaunchBucketSort(hipStream_t stream, bool keyValue, bool atomicRank, const BucketSortArgs& args);
 
 // The MSD plan of large sorts (round 5; vrdx_kernels.hip, "MSD plan"): THREE ranking steps of 10-11 bits instead of four
@@ -194,7 +193,6 @@ struct MsdArgs {
   uint32_t* tickets;           // zeroed by the histogram kernel
   uint32_t* declinedPlans;     // the sorter's counter of plans the device turned down (vrdxHipReadPlanCounters), or nullptr
 };
-hipError_t PrepareMsd();
 hipError_t LaunchHistogramMsd(hipStream_t stream, uint32_t grid, const MsdArgs& args);
 hipError_t LaunchSpineMsd(hipStream_t stream, const MsdArgs& args);
 hipError_t LaunchScatterMsd(hipStream_t stream, bool keyValue, const MsdArgs& args);
@@ -235,12 +233,83 @@ struct SegmentedArgs {
   uint32_t* failure;            // the storage's failure word (word 3 of the header): VRDX_HIP_STATUS_SEGMENTS_INVALID
   uint32_t* stickyFailure;      // the sorter's word
 };
-hipError_t PrepareSegmented();
 // The fill in front of the first launch (one wave): header words 0-3 (failure = word 3) and both list counters.
 hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args);
-hipError_t LaunchSegmentedSmall(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args);
-hipError_t LaunchSegmentedMid(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args);
-hipError_t LaunchSegmentedLarge(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args);
+enum SegmentClass { kSegmentSmall = 0, kSegmentMid = 1, kSegmentLarge = 2 };  // segmented_small / mid / large_kernel
+hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                           const SegmentedArgs& args);
+
+// ---- the kernels' dynamic LDS and the MSD plan's grids: one definition for the kernels (vrdx_kernels.hip) and for both
+// launch backends (vrdx_launch.inc) ----
+// Key+value tiles replay the permutation for the values through the SAME staging buffer after the
+// keys have left it (like the reference, downsweep.slang:208-224): the LDS footprint equals the
+// keys-only one, so two workgroups fit per CU (keys and values staged together would need 128 KiB
+// at T = 16384: one workgroup per CU and nothing to overlap its waits with).
+constexpr size_t OnesweepLdsWords(int threads, int kpt) {
+  // staging buffer (keys, then values) | per-wave digit counters.  Everything else lives inside
+  // those two at times when they are idle: ticket + scan scratch at the front of the staging
+  // buffer (before the regroup), look-back scratch at the bottom and the per-digit scatter offsets
+  // in the top 256 words of the counters (after the regroup).  1024 x 16 is then exactly 80 KiB:
+  // two workgroups per CU.
+  return (size_t)threads * kpt + (size_t)(threads / 64) * 256;
+}
+
+// onesweep_pair_kernel: staging (THREADS*KPT) | wave counters (WAVES*256) | look-back scratch + scan scratch +
+// ticket | digit offsets of A and of B (2 x 256).
+constexpr size_t PairLdsWords(int threads, int kpt) {
+  return (size_t)threads * kpt + (size_t)(threads / 64) * 256 + (size_t)256 * (2 + 2 * (threads / 256)) + 512;
+}
+
+// SortInWorkgroup (small_sort_kernel, bucket_sort_kernel, the segmented sort's in-LDS forms).  Key+value with THREADS * KPT
+// = 32768 elements: two staging buffers of that size do not fit the CU's LDS, so keys and values take turns in ONE (like the
+// pass kernels, and like the reference, downsweep.slang:208-224): two more barriers per pass, the same LDS traffic.
+constexpr bool SharedStage(int threads, int kpt, bool kv) {
+  return kv && (size_t)threads * kpt * 2 * 4 + (size_t)(threads / 64) * 1024 + 64 > 160 * 1024;
+}
+
+constexpr size_t SmallSortLdsWords(int threads, int kpt, bool kv) {
+  return (size_t)threads * kpt * (kv && !SharedStage(threads, kpt, kv) ? 2 : 1) + (size_t)(threads / 64) * 256 + 16;
+}
+
+constexpr size_t SegmentLargeLdsWords(bool kv) {
+  // staging (keys, values) | wave counters 16 x 256 | scan scratch 16 | bases 4 x 256 | tile starts 256 | tile counts 256 | 16
+  return (size_t)kSegLargeTile * (kv ? 2 : 1) + 16 * 256 + 16 + 4 * 256 + 256 + 256 + 16;
+}
+
+// histogram_msd_kernel
+constexpr uint32_t kMsdTopBinWords = 8192;  // 32 KiB: 1024 bins x 8 replicas | 2048 x 4
+constexpr uint32_t HistMsdByte3Copies(uint32_t copies) { return copies < 16u ? copies : 16u; }
+constexpr uint32_t HistMsdLdsBytes(uint32_t copies, uint32_t bits) {
+  return (3u * 256u * copies + kMsdTopBinWords + (1u << bits) + 256u * HistMsdByte3Copies(copies) + 4u) * 4u;
+}
+
+constexpr size_t ScatterMsdLdsWords(uint32_t bits) { return (size_t)kMsdTileKeys + ((size_t)1 << bits) + 32; }
+
+// bucket_sort2_kernel (THREADS = 1024) and bucket_sort2_half_kernel (512)
+constexpr size_t BucketSort2LdsWords(int kpt, int threads = 1024) { return (size_t)threads * kpt + 32; }
+
+// msd_scatter_or_pass0_kernel / msd_buckets_or_pass1_kernel: the larger of the two roles'
+constexpr size_t MsdFusedLdsWords(bool kv, uint32_t bits, bool bucketLaunch) {
+  const size_t pass = kv ? OnesweepLdsWords(1024, 32) : PairLdsWords(1024, 32);
+  const size_t plan = bucketLaunch ? BucketSort2LdsWords((int)((kv ? kMsdCapKeyValue : kMsdCapKeys) / 1024))
+                                   : ScatterMsdLdsWords(bits);
+  return pass > plan ? pass : plan;
+}
+
+// lds_order_check_packed_kernel
+constexpr size_t kOrderCheckPackedLdsBytes = 2 * 16 * 1024 * sizeof(uint32_t);
+
+// workgroups of the plan's scatter: one per tile, or per two tiles (keys-only, ten bits), rounded up to a multiple of 8
+constexpr uint32_t MsdScatterGrid(uint32_t tiles, bool keyValue, uint32_t bits) {
+  const uint32_t units = !keyValue && bits == 10 ? (tiles + 1u) / 2u : tiles;
+  return 8u * ((units + 7u) / 8u);
+}
+
+// Workgroups of the plan's bucket launch.  The full-size kernel (one workgroup per CU) takes TWO buckets per workgroup, one
+// after the other (BucketSort2Body): half as many workgroups to start and to drain -- 107.4 instead of 110.9 us keys-only at
+// 2^25, 175-178 instead of 179-180 key+value (tools/r06/bucket_grid.sh, bucket_grid2.sh, removed, last at commit
+// 3645810).  The half-size kernel (two workgroups per CU) keeps one: 47.7 against 47.0 us keys-only at 2^24 with two.
+constexpr uint32_t MsdBucketGrid(uint32_t bits, bool halfSizeKernel) { return halfSizeKernel ? 1u << bits : (1u << bits) / 2u; }
 
 // Runs the device self-check of the LDS same-address atomic ordering on the current device
 // (synchronous, ~1 ms).  *laneOrdered = true when returning atomics are served in lane order.

@@ -979,26 +979,12 @@ __device__ __forceinline__ void ScatterStagedValues(const uint32_t* sorted, cons
     StoreBoundaryQuad<STAGE>(sorted, offset, out, boundaryQuad, valid, boundaryDigits);
 }
 
-// Key+value tiles replay the permutation for the values through the SAME staging buffer after the
-// keys have left it (like the reference, downsweep.slang:208-224): the LDS footprint equals the
-// keys-only one, so two workgroups fit per CU (keys and values staged together would need 128 KiB
-// at T = 16384: one workgroup per CU and nothing to overlap its waits with).
-template <int THREADS, int KPT, bool KV>
-constexpr size_t OnesweepLdsWords() {
-  // staging buffer (keys, then values) | per-wave digit counters.  Everything else lives inside
-  // those two at times when they are idle: ticket + scan scratch at the front of the staging
-  // buffer (before the regroup), look-back scratch at the bottom and the per-digit scatter offsets
-  // in the top 256 words of the counters (after the regroup).  1024 x 16 is then exactly 80 KiB:
-  // two workgroups per CU.
-  return (size_t)THREADS * KPT + (size_t)(THREADS / 64) * 256;
-}
-
 // Waves per SIMD the register allocation must leave room for: two workgroups per CU whenever the
 // LDS footprint allows two (every geometry except key+value tiles wider than 16384).
 template <int THREADS, int KPT>
 constexpr int MinWavesPerSimd() {
   // as many workgroups per CU as the LDS footprint allows (at most 8 waves per SIMD)
-  constexpr size_t lds = OnesweepLdsWords<THREADS, KPT, false>() * 4;
+  constexpr size_t lds = OnesweepLdsWords(THREADS, KPT) * 4;
   constexpr int workgroups = (int)((160 * 1024) / lds);
   constexpr int waves = workgroups * THREADS / 256;
   return waves > 8 ? 8 : (waves < 1 ? 1 : waves);
@@ -1263,16 +1249,11 @@ __global__ __launch_bounds__(THREADS, (MinWavesPerSimd<THREADS, KPT>())) void on
 // Keys-only sorts with the one-atomic ranking only (the key+value and the ballot forms spilled and were never
 // selected).
 //
-// LDS: staging (THREADS*KPT) | wave counters (WAVES*256) | look-back scratch + scan scratch +
-//      ticket | digit offsets of A and of B (2 x 256).
-template <int THREADS, int KPT>
-constexpr size_t PairLdsWords() {
-  return (size_t)THREADS * KPT + (size_t)(THREADS / 64) * 256 + (size_t)256 * (2 + 2 * (THREADS / 256)) + 512;
-}
+// LDS: PairLdsWords (vrdx_kernels.h).
 
 template <int THREADS, int KPT>
 constexpr int PairMinWavesPerSimd() {
-  constexpr int workgroups = (int)((160 * 1024) / (PairLdsWords<THREADS, KPT>() * 4));
+  constexpr int workgroups = (int)((160 * 1024) / (PairLdsWords(THREADS, KPT) * 4));
   constexpr int waves = workgroups * THREADS / 256;
   return waves > 8 ? 8 : (waves < 1 ? 1 : waves);
 }
@@ -1285,7 +1266,7 @@ __device__ __forceinline__ void OnesweepPairBody(const OnesweepArgs a) {
   static_assert(THREADS >= 256 && THREADS % 256 == 0, "one thread per digit, whole look-back groups");
   static_assert(KPT % 4 == 0, "quads");
   static_assert(SUB <= 65536, "packed 16-bit positions");
-  static_assert(PairLdsWords<THREADS, KPT>() * 4 <= 160 * 1024, "fits the CU's LDS");
+  static_assert(PairLdsWords(THREADS, KPT) * 4 <= 160 * 1024, "fits the CU's LDS");
 
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* const sorted = smem;                                // SUB
@@ -1498,18 +1479,8 @@ __global__ __launch_bounds__(THREADS, (PairMinWavesPerSimd<THREADS, KPT>())) voi
 // wave-striped order.  No global histogram, no tickets, no status words; of the storage only the failure word is written.
 // Positions >= n hold 0xFFFFFFFF pads (value 0): they are last in memory order and carry the
 // largest key, so the stable sort leaves them behind the n real elements, which are what is stored.
-// Key+value with THREADS * KPT = 32768 elements: two staging buffers of that size do not fit the CU's LDS, so keys and
-// values take turns in ONE (like the pass kernels, and like the reference, downsweep.slang:208-224): two more barriers
-// per pass, the same LDS traffic.
-template <int THREADS, int KPT, bool KV>
-constexpr bool SharedStage() {
-  return KV && (size_t)THREADS * KPT * 2 * 4 + (size_t)(THREADS / 64) * 1024 + 64 > 160 * 1024;
-}
-
-template <int THREADS, int KPT, bool KV>
-constexpr size_t SmallSortLdsWords() {
-  return (size_t)THREADS * KPT * (KV && !SharedStage<THREADS, KPT, KV>() ? 2 : 1) + (size_t)(THREADS / 64) * 256 + 16;
-}
+// Key+value with THREADS * KPT = 32768 elements: keys and values take turns in ONE staging buffer (SharedStage,
+// vrdx_kernels.h).  LDS: SmallSortLdsWords (vrdx_kernels.h).
 
 // The sort of n <= THREADS * KPT elements by the key bytes [0, bytes) inside one workgroup: in[0..n) -> out[0..n)
 // (in == out: in place).  Used by small_sort_kernel (the whole sort, bytes = 4) and by bucket_sort_kernel (one
@@ -1521,7 +1492,7 @@ __device__ __forceinline__ void SortInWorkgroup(const uint32_t* keysIn, uint32_t
                                                 uint32_t* valuesOut, uint32_t n, uint32_t bytes, uint32_t* smem) {
   constexpr int WAVES = THREADS / 64;
   constexpr uint32_t TILE = THREADS * KPT;
-  constexpr bool SHARED = SharedStage<THREADS, KPT, KV>();
+  constexpr bool SHARED = SharedStage(THREADS, KPT, KV);
   uint32_t* const stagedKeys = smem;                                  // TILE
   uint32_t* const stagedValues = SHARED ? smem : smem + TILE;         // TILE (key+value)
   uint32_t* const waveHist = smem + TILE * (KV && !SHARED ? 2 : 1);   // WAVES x 256
@@ -1804,12 +1775,8 @@ __global__ __launch_bounds__(1024) void segmented_mid_kernel(SegmentedArgs a) {
 //      of passes the result is copied back.
 // Global data written by one wave and read by another inside this workgroup only ever crosses a __syncthreads() (same CU:
 // the L1 is shared, the barrier's release waits for the stores).
+// LDS: SegmentLargeLdsWords (vrdx_kernels.h).
 constexpr uint32_t kSegHistCopies = 8;
-template <bool KV>
-constexpr size_t SegmentLargeLdsWords() {
-  // staging (keys, values) | wave counters 16 x 256 | scan scratch 16 | bases 4 x 256 | tile starts 256 | tile counts 256 | 16
-  return (size_t)kSegLargeTile * (KV ? 2 : 1) + 16 * 256 + 16 + 4 * 256 + 256 + 256 + 16;
-}
 static_assert(4 * 256 * kSegHistCopies <= kSegLargeTile, "the histogram replicas alias the staging buffer");
 
 template <bool KV, bool ATOMIC_RANK>
@@ -2236,12 +2203,7 @@ __device__ __forceinline__ uint32_t WaveOr(uint32_t v) {
 //             the overflow word;
 //   TABLES    the sample has turned the plan down, or every sampled key is identical: the four byte tables only, like
 //             histogram_kernel; in the second case any key that differs from the reference raises the overflow word.
-constexpr uint32_t kMsdTopBinWords = 8192;  // 32 KiB: 1024 bins x 8 replicas | 2048 x 4
-
-constexpr uint32_t HistMsdByte3Copies(uint32_t copies) { return copies < 16u ? copies : 16u; }
-constexpr uint32_t HistMsdLdsBytes(uint32_t copies, uint32_t bits) {
-  return (3u * 256u * copies + kMsdTopBinWords + (1u << bits) + 256u * HistMsdByte3Copies(copies) + 4u) * 4u;
-}
+// LDS: HistMsdLdsBytes, with kMsdTopBinWords and HistMsdByte3Copies (vrdx_kernels.h).
 
 template <uint32_t COPIES, uint32_t BITS>
 __global__ __launch_bounds__(kHistThreads) void histogram_msd_kernel(MsdArgs a) {
@@ -2630,11 +2592,7 @@ __global__ __launch_bounds__(1024) void spine_msd_kernel(MsdArgs a) {
 // the staged keys had left, every store a counted buffer store so that the prefetch could be waited for without draining the
 // scatter -- was built and measured: 91.3 against 86.0 us for one tile per workgroup.  Tiles of 16384 keys, two workgroups
 // per CU: 97.6 against 93.3.  Neither kept.)
-template <uint32_t BITS>
-constexpr size_t ScatterMsdLdsWords() {
-  return (size_t)kMsdTileKeys + (1u << BITS) + 32;
-}
-
+// LDS: ScatterMsdLdsWords (vrdx_kernels.h).
 template <uint32_t BITS, bool KV>
 __device__ __forceinline__ void ScatterMsdBody(const MsdArgs a) {
   constexpr int THREADS = 1024, KPT = 32, WAVES = THREADS / 64;
@@ -2955,10 +2913,7 @@ __device__ __forceinline__ void ScatterMsdRole(const MsdArgs a) {
 // range of the caller's arrays.  Keys (and values) stay in registers between the passes; the staging buffer -- up to
 // 144 KiB -- takes the counters' place inside each pass like in scatter_msd_kernel; key+value stages the values through
 // the same slots after the keys.  A wave takes only as many slots as the bucket needs (like SortInWorkgroup).
-template <int KPT, int THREADS = 1024>
-constexpr size_t BucketSort2LdsWords() {
-  return (size_t)THREADS * KPT + 32;
-}
+// LDS: BucketSort2LdsWords (vrdx_kernels.h).
 
 template <uint32_t BITS, int KPT, bool KV, int THREADS = 1024>
 __device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_t bucket, const uint32_t below) {
@@ -3159,13 +3114,7 @@ __device__ __forceinline__ void FallbackPassBody(const OnesweepArgs p) {
   else
     OnesweepPairBody<1024, 32, DYN>(p);
 }
-template <bool KV>
-constexpr size_t MsdFusedLdsWords(uint32_t bits, bool bucketLaunch) {
-  const size_t pass = KV ? OnesweepLdsWords<1024, 32, true>() : PairLdsWords<1024, 32>();
-  const size_t plan = bucketLaunch ? BucketSort2LdsWords<(KV ? kMsdCapKeyValue : kMsdCapKeys) / 1024>()
-                                   : (size_t)kMsdTileKeys + ((size_t)1 << bits) + 32;
-  return pass > plan ? pass : plan;
-}
+// LDS: MsdFusedLdsWords (vrdx_kernels.h).
 
 template <uint32_t BITS, bool KV, bool DYN>
 __global__ __launch_bounds__(1024) void msd_scatter_or_pass0_kernel(MsdArgs m, OnesweepArgs p) {
@@ -3326,498 +3275,27 @@ __global__ __launch_bounds__(64) void spin_kernel(unsigned long long* out, uint3
   }
 }
 
+
 // ---------------------------------------------------------------------------------------------
-// host-side launchers
+// host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs
 // ---------------------------------------------------------------------------------------------
-// Every launcher returns the hipError_t of ITS launch (hipLaunchKernel), so that the recorder never has to consult
-// the calling thread's sticky last-error state, which an unrelated earlier failure may have set.
-constexpr size_t kOrderCheckPackedLdsBytes = 2 * 16 * 1024 * sizeof(uint32_t);
+#include "vrdx_launch.inc"
 
-template <typename... Args>
-static hipError_t Launch(const void* kernel, uint32_t grid, uint32_t block, size_t ldsBytes, hipStream_t stream,
-                         Args... args) {
-  void* argv[] = {static_cast<void*>(&args)...};
-  return hipLaunchKernel(kernel, dim3(grid), dim3(block), argv, ldsBytes, stream);
-}
-
-template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK, bool DYN = false>
-static const void* OnesweepKernel() {
-  return reinterpret_cast<const void*>(&onesweep_kernel<THREADS, KPT, KV, ATOMIC_RANK, DYN>);
-}
-template <int THREADS, int KPT, bool DYN = false>
-static const void* PairKernel() {
-  return reinterpret_cast<const void*>(&onesweep_pair_kernel<THREADS, KPT, DYN>);
-}
-
-// EVEN: the forms with run-time slot counts (args.slots != 0: even-split and tail-split tiles, PlanTiles in
-// vrdx_api.cpp) are built for this geometry as well.
-template <int THREADS, int KPT, bool EVEN = false>
-static hipError_t PrepareConfig() {
-  const int keysBytes = (int)(OnesweepLdsWords<THREADS, KPT, false>() * sizeof(uint32_t));
-  const int kvBytes = (int)(OnesweepLdsWords<THREADS, KPT, true>() * sizeof(uint32_t));
-  const struct {
-    const void* fn;
-    int bytes;
-  } kernels[8] = {
-      {OnesweepKernel<THREADS, KPT, false, false>(), keysBytes},
-      {OnesweepKernel<THREADS, KPT, false, true>(), keysBytes},
-      {OnesweepKernel<THREADS, KPT, true, false>(), kvBytes},
-      {OnesweepKernel<THREADS, KPT, true, true>(), kvBytes},
-      {OnesweepKernel<THREADS, KPT, false, false, EVEN>(), keysBytes},
-      {OnesweepKernel<THREADS, KPT, false, true, EVEN>(), keysBytes},
-      {OnesweepKernel<THREADS, KPT, true, false, EVEN>(), kvBytes},
-      {OnesweepKernel<THREADS, KPT, true, true, EVEN>(), kvBytes},
-  };
-  for (int i = 0; i < (EVEN ? 8 : 4); ++i) {
-    const hipError_t e = hipFuncSetAttribute(kernels[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, kernels[i].bytes);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-template <int THREADS, int KPT, bool EVEN = false>
-static hipError_t LaunchConfig(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank,
-                               const OnesweepArgs& args) {
-  const size_t lds = (keyValue ? OnesweepLdsWords<THREADS, KPT, true>() : OnesweepLdsWords<THREADS, KPT, false>()) *
-                     sizeof(uint32_t);
-  const void* kernel =
-      keyValue ? (atomicRank ? OnesweepKernel<THREADS, KPT, true, true>() : OnesweepKernel<THREADS, KPT, true, false>())
-               : (atomicRank ? OnesweepKernel<THREADS, KPT, false, true>() : OnesweepKernel<THREADS, KPT, false, false>());
-  if (args.slots != 0) {  // run-time slot counts
-    if (!EVEN || args.slots % 4 != 0 || args.slots > (uint32_t)KPT || args.tailSlots % 4 != 0 || args.tailSlots == 0 ||
-        args.tailSlots > (uint32_t)KPT)
-      return hipErrorInvalidValue;
-    kernel = keyValue ? (atomicRank ? OnesweepKernel<THREADS, KPT, true, true, EVEN>()
-                                    : OnesweepKernel<THREADS, KPT, true, false, EVEN>())
-                      : (atomicRank ? OnesweepKernel<THREADS, KPT, false, true, EVEN>()
-                                    : OnesweepKernel<THREADS, KPT, false, false, EVEN>());
-  }
-  return Launch(kernel, grid, THREADS, lds, stream, args);
-}
-
-// The two-sub-tile kernel exists for keys-only sorts with the one-atomic ranking (the ballot form of it spills
-// 152 bytes per lane and ConfigIndex never selected it): its key+value form would hold sub-tile B's keys and
-// ranks, A's staging slots and A's values at once and spills (measured 40 GItems/s in round 1; a 768-thread
-// form with 168 registers and no spill measured 54.5 GItems/s against 67.2 for onesweep_kernel<1024, 32>,
-// profiles/r03_geometry.txt), so it is not built.
-template <int THREADS, int KPT>
-static hipError_t PreparePairConfig() {
-  const int bytes = (int)(PairLdsWords<THREADS, KPT>() * sizeof(uint32_t));
-  const hipError_t e = hipFuncSetAttribute(PairKernel<THREADS, KPT, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(PairKernel<THREADS, KPT>(), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-template <int THREADS, int KPT>
-static hipError_t LaunchPairConfig(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank,
-                                   const OnesweepArgs& args) {
-  if (keyValue || !atomicRank) return hipErrorInvalidValue;  // never selected (ConfigIndex)
-  const size_t lds = PairLdsWords<THREADS, KPT>() * sizeof(uint32_t);
-  if (args.slots != 0) {  // run-time slot counts
-    if (args.slots % 4 != 0 || args.slots > (uint32_t)KPT || args.tailSlots % 4 != 0 || args.tailSlots == 0 ||
-        args.tailSlots > (uint32_t)KPT)
-      return hipErrorInvalidValue;
-    return Launch(PairKernel<THREADS, KPT, true>(), grid, THREADS, lds, stream, args);
-  }
-  return Launch(PairKernel<THREADS, KPT>(), grid, THREADS, lds, stream, args);
-}
-
-// Every geometry here is selected by ConfigIndex (vrdx_api.cpp) for some size range; nothing else is built.
-const TileConfig kTileConfigs[kNumTileConfigs] = {
-    {1024, 8, 1}, {1024, 16, 1}, {1024, 32, 1}, {1024, 32, 2},
+static const void* const kStubs[kNumKernels] = {
+#define VRDX_KERNEL_STUB(id, stub, threads, ldsBytes, name) reinterpret_cast<const void*>(stub),
+    VRDX_KERNELS(VRDX_KERNEL_STUB)
+#undef VRDX_KERNEL_STUB
 };
 
-hipError_t PrepareKernels(int configIndex) {
-  if (configIndex == 0) {  // once per sorter: the histogram kernels' dynamic LDS
-    const struct {
-      const void* fn;
-      uint32_t bytes;
-    } kernels[2] = {
-        {reinterpret_cast<const void*>(&histogram_kernel<kHistCopies>), HistLdsBytes(kHistCopies)},
-        {reinterpret_cast<const void*>(&histogram_kernel<kHistCopiesLarge>), HistLdsBytes(kHistCopiesLarge)},
-    };
-    for (const auto& k : kernels) {
-      const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
-      if (e != hipSuccess) return e;
-    }
-  }
-  switch (configIndex) {
-    case 0: return PrepareConfig<1024, 8>();
-    case 1: return PrepareConfig<1024, 16>();
-    case 2: return PrepareConfig<1024, 32, true>();
-    case 3: return PreparePairConfig<1024, 32>();
-    default: return hipErrorInvalidValue;
-  }
+static hipError_t PrepareKernel(KernelId id) {
+  const uint32_t lds = kKernelShapes[id].ldsBytes;
+  if (lds == 0) return hipSuccess;
+  return hipFuncSetAttribute(kStubs[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
-hipError_t LdsOrderCheck(bool* laneOrdered) {
-  uint32_t* d = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(uint32_t));
-  if (e != hipSuccess) return e;
-  uint32_t h = 0xFFFFFFFFu;
-  e = hipMemset(d, 0, sizeof(uint32_t));
-  uint32_t* const noSticky = nullptr;
-  if (e == hipSuccess) e = Launch(reinterpret_cast<const void*>(&lds_order_check_kernel), 512, 1024, 0, nullptr, d, noSticky);
-  // the packed-counter shape of the MSD plan: two digits to a word (PrepareMsd has raised this kernel's LDS limit)
-  if (e == hipSuccess)
-    e = Launch(reinterpret_cast<const void*>(&lds_order_check_packed_kernel), 256, 1024, kOrderCheckPackedLdsBytes, nullptr, d, noSticky);
-  if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e == hipSuccess) *laneOrdered = h == 0;
-  return e;
-}
-
-hipError_t LaunchLdsOrderRecheck(hipStream_t stream, uint32_t* sticky) {
-  uint32_t* const noCount = nullptr;
-  const hipError_t e = Launch(reinterpret_cast<const void*>(&lds_order_check_kernel), 8, 1024, 0, stream, noCount, sticky);
-  if (e != hipSuccess) return e;
-  return Launch(reinterpret_cast<const void*>(&lds_order_check_packed_kernel), 8, 1024, kOrderCheckPackedLdsBytes, stream, noCount, sticky);
-}
-
-hipError_t LaunchSpin(hipStream_t stream, unsigned long long* out, uint32_t ticks) {
-  return Launch(reinterpret_cast<const void*>(&spin_kernel), 1, 64, 0, stream, out, ticks);
-}
-
-// ---- single-launch path for small sorts ---------------------------------------------------------
-template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK>
-static const void* SmallKernel() {
-  return reinterpret_cast<const void*>(&small_sort_kernel<THREADS, KPT, KV, ATOMIC_RANK>);
-}
-
-template <int THREADS, int KPT>
-static hipError_t PrepareSmall() {
-  const struct {
-    const void* fn;
-    size_t words;
-  } kernels[4] = {
-      {SmallKernel<THREADS, KPT, false, false>(), SmallSortLdsWords<THREADS, KPT, false>()},
-      {SmallKernel<THREADS, KPT, false, true>(), SmallSortLdsWords<THREADS, KPT, false>()},
-      {SmallKernel<THREADS, KPT, true, false>(), SmallSortLdsWords<THREADS, KPT, true>()},
-      {SmallKernel<THREADS, KPT, true, true>(), SmallSortLdsWords<THREADS, KPT, true>()},
-  };
-  for (const auto& k : kernels) {
-    const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(k.words * 4));
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-template <int THREADS, int KPT>
-static hipError_t LaunchSmall(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
-                              const uint32_t* countPtr, uint32_t* failure) {
-  const bool keyValue = values != nullptr;
-  const size_t lds = (keyValue ? SmallSortLdsWords<THREADS, KPT, true>() : SmallSortLdsWords<THREADS, KPT, false>()) * 4;
-  const void* const kernel =
-      keyValue ? (atomicRank ? SmallKernel<THREADS, KPT, true, true>() : SmallKernel<THREADS, KPT, true, false>())
-               : (atomicRank ? SmallKernel<THREADS, KPT, false, true>() : SmallKernel<THREADS, KPT, false, false>());
-  return Launch(kernel, 1, THREADS, lds, stream, keys, values, maxCount, countPtr, failure);
-}
-
-hipError_t PrepareSmallSort() {
-  hipError_t e = PrepareSmall<256, 16>();
-  if (e == hipSuccess) e = PrepareSmall<1024, 16>();
-  return e;
-}
-
-hipError_t LaunchSmallSort(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
-                           const uint32_t* countPtr, uint32_t* failure) {
-  if (maxCount <= 256u * 16u) return LaunchSmall<256, 16>(stream, atomicRank, keys, values, maxCount, countPtr, failure);
-  return LaunchSmall<1024, 16>(stream, atomicRank, keys, values, maxCount, countPtr, failure);
-}
-
-// ---- segmented sort ---------------------------------------------------------------------------------
-template <bool KV, bool ATOMIC_RANK>
-static const void* SegmentedKernel(int which) {  // 0 small, 1 mid, 2 large
-  if (which == 0) return reinterpret_cast<const void*>(&segmented_small_kernel<KV, ATOMIC_RANK>);
-  if (which == 1) return reinterpret_cast<const void*>(&segmented_mid_kernel<KV, ATOMIC_RANK>);
-  return reinterpret_cast<const void*>(&segmented_large_kernel<KV, ATOMIC_RANK>);
-}
-
-static size_t SegmentedLdsBytes(int which, bool keyValue) {
-  if (which == 0) return (keyValue ? SmallSortLdsWords<256, 16, true>() : SmallSortLdsWords<256, 16, false>()) * 4;
-  if (which == 1) return (keyValue ? SmallSortLdsWords<1024, 16, true>() : SmallSortLdsWords<1024, 16, false>()) * 4;
-  return (keyValue ? SegmentLargeLdsWords<true>() : SegmentLargeLdsWords<false>()) * 4;
-}
-
-static const void* SegmentedKernelFor(int which, bool keyValue, bool atomicRank) {
-  return keyValue ? (atomicRank ? SegmentedKernel<true, true>(which) : SegmentedKernel<true, false>(which))
-                  : (atomicRank ? SegmentedKernel<false, true>(which) : SegmentedKernel<false, false>(which));
-}
-
-hipError_t PrepareSegmented() {
-  for (int which = 0; which < 3; ++which)
-    for (int kv = 0; kv < 2; ++kv)
-      for (int atomic = 0; atomic < 2; ++atomic) {
-        const hipError_t e = hipFuncSetAttribute(SegmentedKernelFor(which, kv != 0, atomic != 0),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)SegmentedLdsBytes(which, kv != 0));
-        if (e != hipSuccess) return e;
-      }
-  return hipSuccess;
-}
-
-static hipError_t LaunchSegmented(int which, hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank,
-                                  const SegmentedArgs& args) {
-  if (grid == 0) return hipErrorInvalidValue;
-  return Launch(SegmentedKernelFor(which, keyValue, atomicRank), grid, which == 0 ? 256u : 1024u,
-                SegmentedLdsBytes(which, keyValue), stream, args);
-}
-
-hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args) {
-  return Launch(reinterpret_cast<const void*>(&segmented_clear_kernel), 1, 64, 0, stream, args);
-}
-hipError_t LaunchSegmentedSmall(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
-  return LaunchSegmented(0, stream, grid, keyValue, atomicRank, args);
-}
-hipError_t LaunchSegmentedMid(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
-  return LaunchSegmented(1, stream, grid, keyValue, atomicRank, args);
-}
-hipError_t LaunchSegmentedLarge(hipStream_t stream, uint32_t grid, bool keyValue, bool atomicRank, const SegmentedArgs& args) {
-  return LaunchSegmented(2, stream, grid, keyValue, atomicRank, args);
-}
-
-// ---- second half of the hybrid plan ---------------------------------------------------------------
-template <int KPT, bool KV, bool ATOMIC_RANK>
-static const void* BucketKernel() {
-  return reinterpret_cast<const void*>(&bucket_sort_kernel<1024, KPT, KV, ATOMIC_RANK>);
-}
-
-template <int KPT>
-static hipError_t PrepareBucket() {
-  const struct {
-    const void* fn;
-    size_t words;
-  } kernels[4] = {
-      {BucketKernel<KPT, false, false>(), SmallSortLdsWords<1024, KPT, false>()},
-      {BucketKernel<KPT, false, true>(), SmallSortLdsWords<1024, KPT, false>()},
-      {BucketKernel<KPT, true, false>(), SmallSortLdsWords<1024, KPT, true>()},
-      {BucketKernel<KPT, true, true>(), SmallSortLdsWords<1024, KPT, true>()},
-  };
-  for (const auto& k : kernels) {
-    const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(k.words * 4));
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-template <int KPT>
-static hipError_t LaunchBucket(hipStream_t stream, bool keyValue, bool atomicRank, const BucketSortArgs& args) {
-  const size_t lds = (keyValue ? SmallSortLdsWords<1024, KPT, true>() : SmallSortLdsWords<1024, KPT, false>()) * 4;
-  const void* const kernel = keyValue ? (atomicRank ? BucketKernel<KPT, true, true>() : BucketKernel<KPT, true, false>())
-                                      : (atomicRank ? BucketKernel<KPT, false, true>() : BucketKernel<KPT, false, false>());
-  return Launch(kernel, VRDX_RADIX, 1024, lds, stream, args);
-}
-
-hipError_t PrepareBucketSort() {
-  hipError_t e = PrepareBucket<4>();
-  if (e == hipSuccess) e = PrepareBucket<8>();
-  if (e == hipSuccess) e = PrepareBucket<16>();
-  // 32768-element buckets: with the one-atomic ranking only (the ballot forms would spill); key+value stages keys and
-  // values through ONE buffer (SharedStage)
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(BucketKernel<32, false, true>(), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(SmallSortLdsWords<1024, 32, false>() * 4));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(BucketKernel<32, true, true>(), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(SmallSortLdsWords<1024, 32, true>() * 4));
-  return e;
-}
-
-hipError_t LaunchBucketSort(hipStream_t stream, bool keyValue, bool atomicRank, const BucketSortArgs& args) {
-  switch (args.hybridCap) {
-    case 1024u * 4u: return LaunchBucket<4>(stream, keyValue, atomicRank, args);
-    case 1024u * 8u: return LaunchBucket<8>(stream, keyValue, atomicRank, args);
-    case 1024u * 16u: return LaunchBucket<16>(stream, keyValue, atomicRank, args);
-    case 1024u * 32u:
-      if (!atomicRank) return hipErrorInvalidValue;  // never recorded (HybridCapacity)
-      if (keyValue)
-        return Launch(BucketKernel<32, true, true>(), VRDX_RADIX, 1024, SmallSortLdsWords<1024, 32, true>() * 4, stream, args);
-      return Launch(BucketKernel<32, false, true>(), VRDX_RADIX, 1024, SmallSortLdsWords<1024, 32, false>() * 4, stream, args);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t LaunchHistogram(hipStream_t stream, uint32_t grid, const uint32_t* keys, uint32_t maxCount,
-                           const uint32_t* countPtr, uint32_t* globalHistogram, uint32_t* tickets, void* statusClear,
-                           uint32_t statusClearBytes) {
-  u32x4* const clear = reinterpret_cast<u32x4*>(statusClear);
-  const uint32_t vecs = statusClearBytes / 16u;  // whole status rows: a multiple of 1 KiB, 128-byte aligned
-  const bool many = maxCount >= kHistManyCopiesFrom;
-  const void* const kernel = many ? reinterpret_cast<const void*>(&histogram_kernel<kHistCopiesLarge>)
-                                  : reinterpret_cast<const void*>(&histogram_kernel<kHistCopies>);
-  return Launch(kernel, grid, kHistThreads, HistLdsBytes(many ? kHistCopiesLarge : kHistCopies), stream, keys, maxCount, countPtr,
-                globalHistogram, tickets, clear, vecs);
-}
-
-// ---- MSD plan -----------------------------------------------------------------------------------------
-template <uint32_t BITS>
-static hipError_t PrepareMsdBits() {
-  const struct {
-    const void* fn;
-    size_t bytes;
-  } kernels[] = {
-      {reinterpret_cast<const void*>(&histogram_msd_kernel<kHistCopies, BITS>), HistMsdLdsBytes(kHistCopies, BITS)},
-      {reinterpret_cast<const void*>(&histogram_msd_kernel<kHistCopiesLarge, BITS>), HistMsdLdsBytes(kHistCopiesLarge, BITS)},
-      {reinterpret_cast<const void*>(&scatter_msd_kernel<BITS, false>), ScatterMsdLdsWords<BITS>() * 4},
-      {reinterpret_cast<const void*>(&scatter_msd_kernel<BITS, true>), ScatterMsdLdsWords<BITS>() * 4},
-      {reinterpret_cast<const void*>(&bucket_sort2_kernel<BITS, kMsdCapKeys / 1024, false>), BucketSort2LdsWords<kMsdCapKeys / 1024>() * 4},
-      {reinterpret_cast<const void*>(&bucket_sort2_kernel<BITS, kMsdCapKeyValue / 1024, true>), BucketSort2LdsWords<kMsdCapKeyValue / 1024>() * 4},
-  };
-  for (const auto& k : kernels) {
-    const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
-    if (e != hipSuccess) return e;
-  }
-  const struct {
-    const void* fn;
-    size_t bytes;
-  } fused[] = {
-      {reinterpret_cast<const void*>(&msd_scatter_or_pass0_kernel<BITS, false, false>), MsdFusedLdsWords<false>(BITS, false) * 4},
-      {reinterpret_cast<const void*>(&msd_scatter_or_pass0_kernel<BITS, false, true>), MsdFusedLdsWords<false>(BITS, false) * 4},
-      {reinterpret_cast<const void*>(&msd_buckets_or_pass1_kernel<BITS, false, false>), MsdFusedLdsWords<false>(BITS, true) * 4},
-      {reinterpret_cast<const void*>(&msd_buckets_or_pass1_kernel<BITS, false, true>), MsdFusedLdsWords<false>(BITS, true) * 4},
-      {reinterpret_cast<const void*>(&msd_scatter_or_pass0_kernel<BITS, true, false>), MsdFusedLdsWords<true>(BITS, false) * 4},
-      {reinterpret_cast<const void*>(&msd_scatter_or_pass0_kernel<BITS, true, true>), MsdFusedLdsWords<true>(BITS, false) * 4},
-      {reinterpret_cast<const void*>(&msd_buckets_or_pass1_kernel<BITS, true, false>), MsdFusedLdsWords<true>(BITS, true) * 4},
-      {reinterpret_cast<const void*>(&msd_buckets_or_pass1_kernel<BITS, true, true>), MsdFusedLdsWords<true>(BITS, true) * 4},
-  };
-  for (const auto& k : fused) {
-    const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-hipError_t PrepareMsd() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lds_order_check_packed_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOrderCheckPackedLdsBytes);
-  if (e == hipSuccess) e = PrepareMsdBits<10>();
-  if (e == hipSuccess) e = PrepareMsdBits<11>();
-  for (int kv = 0; kv < 2 && e == hipSuccess; ++kv)
-    e = hipFuncSetAttribute(kv ? reinterpret_cast<const void*>(&bucket_sort2_half_kernel<10, true>)
-                               : reinterpret_cast<const void*>(&bucket_sort2_half_kernel<10, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BucketSort2LdsWords<kMsdHalfCap / 512, 512>() * 4));
-  return e;
-}
-
-hipError_t LaunchHistogramMsd(hipStream_t stream, uint32_t grid, const MsdArgs& args) {
-  const bool many = args.maxCount >= kHistManyCopiesFrom;
-  const void* kernel;
-  // tiles of rows x 4096 keys (the scatter's even-split tiles); a tile of full capacity is eight rows
-  if (args.tileKeys == 0 || args.tileKeys % 4096u != 0 || args.tileKeys > kMsdTileKeys) return hipErrorInvalidValue;
-  if (args.bits == 10)
-    kernel = many ? reinterpret_cast<const void*>(&histogram_msd_kernel<kHistCopiesLarge, 10>)
-                  : reinterpret_cast<const void*>(&histogram_msd_kernel<kHistCopies, 10>);
-  else if (args.bits == 11)
-    kernel = many ? reinterpret_cast<const void*>(&histogram_msd_kernel<kHistCopiesLarge, 11>)
-                  : reinterpret_cast<const void*>(&histogram_msd_kernel<kHistCopies, 11>);
-  else
-    return hipErrorInvalidValue;
-  return Launch(kernel, grid, kHistThreads, HistMsdLdsBytes(many ? kHistCopiesLarge : kHistCopies, args.bits), stream, args);
-}
-
-hipError_t LaunchSpineMsd(hipStream_t stream, const MsdArgs& args) {
-  if (args.tiles > kMsdMaxTiles) return hipErrorInvalidValue;
-  if (args.bits == 10) return Launch(reinterpret_cast<const void*>(&spine_msd_kernel<10>), 512 / 16, 1024, 0, stream, args);
-  if (args.bits == 11) return Launch(reinterpret_cast<const void*>(&spine_msd_kernel<11>), 1024 / 16, 1024, 0, stream, args);
-  return hipErrorInvalidValue;
-}
-
-// workgroups of the plan's scatter: one per tile, or per two tiles (keys-only, ten bits), rounded up to a multiple of 8
-static uint32_t MsdScatterGrid(uint32_t tiles, bool keyValue, uint32_t bits) {
-  const uint32_t units = !keyValue && bits == 10 ? (tiles + 1u) / 2u : tiles;
-  return 8u * ((units + 7u) / 8u);
-}
-
-hipError_t LaunchScatterMsd(hipStream_t stream, bool keyValue, const MsdArgs& args) {
-  const void* kernel;
-  size_t lds;
-  if (args.tileKeys == 0 || args.tileKeys % 4096u != 0 || args.tileKeys > kMsdTileKeys) return hipErrorInvalidValue;
-  if (args.bits == 10) {
-    kernel = keyValue ? reinterpret_cast<const void*>(&scatter_msd_kernel<10, true>)
-                      : reinterpret_cast<const void*>(&scatter_msd_kernel<10, false>);
-    lds = ScatterMsdLdsWords<10>() * 4;
-  } else if (args.bits == 11) {
-    kernel = keyValue ? reinterpret_cast<const void*>(&scatter_msd_kernel<11, true>)
-                      : reinterpret_cast<const void*>(&scatter_msd_kernel<11, false>);
-    lds = ScatterMsdLdsWords<11>() * 4;
-  } else {
-    return hipErrorInvalidValue;
-  }
-  // a multiple of 8 workgroups: eight chunks of consecutive tiles (keys-only: pairs of tiles), one per XCD (see the kernels)
-  return Launch(kernel, MsdScatterGrid(args.tiles, keyValue, args.bits), 1024, lds, stream, args);
-}
-
-// Workgroups of the plan's bucket launch.  The full-size kernel (one workgroup per CU) takes TWO buckets per workgroup, one
-// after the other (BucketSort2Body): half as many workgroups to start and to drain -- 107.4 instead of 110.9 us keys-only at
-// 2^25, 175-178 instead of 179-180 key+value (tools/r06/bucket_grid.sh, bucket_grid2.sh, removed, last at commit
-// 3645810).  The half-size kernel (two workgroups per CU) keeps one: 47.7 against 47.0 us keys-only at 2^24 with two.
-static uint32_t MsdBucketGrid(uint32_t bits, bool halfSizeKernel) { return halfSizeKernel ? 1u << bits : (1u << bits) / 2u; }
-
-hipError_t LaunchBucketSort2(hipStream_t stream, bool keyValue, const MsdArgs& args) {
-  constexpr int kKeys = kMsdCapKeys / 1024, kPairs = kMsdCapKeyValue / 1024;
-  if (args.cap == kMsdHalfCap && args.bits == 10) {
-    const void* half = keyValue ? reinterpret_cast<const void*>(&bucket_sort2_half_kernel<10, true>)
-                                : reinterpret_cast<const void*>(&bucket_sort2_half_kernel<10, false>);
-    return Launch(half, MsdBucketGrid(args.bits, true), 512, BucketSort2LdsWords<kMsdHalfCap / 512, 512>() * 4, stream, args);
-  }
-  if (args.cap != (keyValue ? kMsdCapKeyValue : kMsdCapKeys)) return hipErrorInvalidValue;
-  const void* kernel;
-  if (args.bits == 10)
-    kernel = keyValue ? reinterpret_cast<const void*>(&bucket_sort2_kernel<10, kPairs, true>)
-                      : reinterpret_cast<const void*>(&bucket_sort2_kernel<10, kKeys, false>);
-  else if (args.bits == 11)
-    kernel = keyValue ? reinterpret_cast<const void*>(&bucket_sort2_kernel<11, kPairs, true>)
-                      : reinterpret_cast<const void*>(&bucket_sort2_kernel<11, kKeys, false>);
-  else
-    return hipErrorInvalidValue;
-  const size_t lds = (keyValue ? BucketSort2LdsWords<kPairs>() : BucketSort2LdsWords<kKeys>()) * 4;
-  return Launch(kernel, MsdBucketGrid(args.bits, false), 1024, lds, stream, args);
-}
-
-// The plan's scatter / bucket launch with the fallback's pass 0 / pass 1 as its second role (bucketLaunch selects which).
-// passGrid: the grid LaunchOnesweep would have used for that pass.
-template <uint32_t BITS, bool KV>
-static hipError_t LaunchMsdFusedBits(hipStream_t stream, bool bucketLaunch, const MsdArgs& m, const OnesweepArgs& p, uint32_t passGrid) {
-  const bool dyn = p.slots != 0;
-  const void* kernel =
-      bucketLaunch ? (dyn ? reinterpret_cast<const void*>(&msd_buckets_or_pass1_kernel<BITS, KV, true>)
-                          : reinterpret_cast<const void*>(&msd_buckets_or_pass1_kernel<BITS, KV, false>))
-                   : (dyn ? reinterpret_cast<const void*>(&msd_scatter_or_pass0_kernel<BITS, KV, true>)
-                          : reinterpret_cast<const void*>(&msd_scatter_or_pass0_kernel<BITS, KV, false>));
-  // the larger of the two roles' grids, a multiple of 8 (the scatter derives its tile from the grid: eight chunks of tiles, one
-  // per XCD; a workgroup beyond its role's range returns)
-  // (the bucket launch: two buckets per workgroup, MsdBucketGrid -- a pass of up to 2^BITS / 2 tiles then has no idle workgroups)
-  const uint32_t planGrid = bucketLaunch ? MsdBucketGrid(BITS, false) : MsdScatterGrid(m.tiles, KV, BITS);
-  const uint32_t grid = 8u * (((planGrid > passGrid ? planGrid : passGrid) + 7u) / 8u);
-  // the pass's run-time slot counts, checked like LaunchPairConfig / LaunchConfig do
-  if (dyn && (p.slots % 4 != 0 || p.slots > 32u || p.tailSlots % 4 != 0 || p.tailSlots == 0 || p.tailSlots > 32u))
-    return hipErrorInvalidValue;
-  return Launch(kernel, grid, 1024, MsdFusedLdsWords<KV>(BITS, bucketLaunch) * 4, stream, m, p);
-}
-
-hipError_t LaunchMsdFused(hipStream_t stream, bool bucketLaunch, bool keyValue, const MsdArgs& m, const OnesweepArgs& p,
-                          uint32_t passGrid) {
-  if (m.tileKeys == 0 || m.tileKeys % 4096u != 0 || m.tileKeys > kMsdTileKeys ||
-      (bucketLaunch && m.cap != (keyValue ? kMsdCapKeyValue : kMsdCapKeys)))
-    return hipErrorInvalidValue;
-  if (m.bits == 10)
-    return keyValue ? LaunchMsdFusedBits<10, true>(stream, bucketLaunch, m, p, passGrid)
-                    : LaunchMsdFusedBits<10, false>(stream, bucketLaunch, m, p, passGrid);
-  if (m.bits == 11)
-    return keyValue ? LaunchMsdFusedBits<11, true>(stream, bucketLaunch, m, p, passGrid)
-                    : LaunchMsdFusedBits<11, false>(stream, bucketLaunch, m, p, passGrid);
-  return hipErrorInvalidValue;
-}
-
-hipError_t LaunchOnesweep(hipStream_t stream, int configIndex, uint32_t grid, bool keyValue, bool atomicRank,
-                          const OnesweepArgs& args) {
-  switch (configIndex) {
-    case 0: return LaunchConfig<1024, 8>(stream, grid, keyValue, atomicRank, args);
-    case 1: return LaunchConfig<1024, 16>(stream, grid, keyValue, atomicRank, args);
-    case 2: return LaunchConfig<1024, 32, true>(stream, grid, keyValue, atomicRank, args);
-    case 3: return LaunchPairConfig<1024, 32>(stream, grid, keyValue, atomicRank, args);
-    default: return hipErrorInvalidValue;
-  }
+static hipError_t LaunchKernel(KernelId id, uint32_t grid, hipStream_t stream, void** params) {
+  const KernelShape& k = kKernelShapes[id];
+  return hipLaunchKernel(kStubs[id], dim3(grid), dim3(k.threads), params, k.ldsBytes, stream);
 }
 
 }  // namespace vrdx

@@ -1,0 +1,400 @@
+// The launch layer of vrdx_kernels.h, written once for both backends:
+//   * VRDX_KERNELS lists every kernel instantiation a launcher can start, each once: its id, its host stub (the library),
+//     its block size, its dynamic LDS in bytes (0: none) and its mangled name (the single header;
+//     tools/generate_single_header.py reads the names from here and checks them against the code object);
+//   * every Launch* entry point picks an id, computes the grid, checks its arguments and starts the kernel.
+// A backend supplies the two primitives declared below and expands VRDX_KERNELS for what it needs to find a kernel:
+//   the library        (the end of vrdx_kernels.hip)      the host stub: hipFuncSetAttribute, hipLaunchKernel;
+//   the single header  (vrdx_module_launch.inc)           the name: hipModuleGetFunction, hipModuleLaunchKernel.
+// Included inside namespace vrdx.
+//
+// Order: the library instantiates the kernel templates where it expands the stubs, so the device code emits them in list
+// order; the list keeps the order they were emitted in before it existed.  A launcher picks a form by its offset from its
+// family's first id, in the order the family's comment gives, and refuses arguments it has no kernel for with
+// hipErrorInvalidValue.
+#define VRDX_KERNELS(X) \
+  /* histogram_kernel: kHistCopies | kHistCopiesLarge replicas */ \
+  X(kHistogram, (&histogram_kernel<kHistCopies>), kHistThreads, HistLdsBytes(kHistCopies), \
+    "_ZN4vrdx16histogram_kernelILj8EEEvPKjjS2_PjS3_PDv4_jj") \
+  X(kHistogramLarge, (&histogram_kernel<kHistCopiesLarge>), kHistThreads, HistLdsBytes(kHistCopiesLarge), \
+    "_ZN4vrdx16histogram_kernelILj32EEEvPKjjS2_PjS3_PDv4_jj") \
+  /* onesweep_kernel of tile configs 0-2, each [key-value][atomic rank] (V: key+value, A: one-atomic ranking); config 2 \
+     also with run-time slot counts (S) */ \
+  X(kOnesweep8, (&onesweep_kernel<1024, 8, false, false, false>), 1024, OnesweepLdsWords(1024, 8) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi8ELb0ELb0ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep8A, (&onesweep_kernel<1024, 8, false, true, false>), 1024, OnesweepLdsWords(1024, 8) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi8ELb0ELb1ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep8V, (&onesweep_kernel<1024, 8, true, false, false>), 1024, OnesweepLdsWords(1024, 8) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi8ELb1ELb0ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep8VA, (&onesweep_kernel<1024, 8, true, true, false>), 1024, OnesweepLdsWords(1024, 8) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi8ELb1ELb1ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep16, (&onesweep_kernel<1024, 16, false, false, false>), 1024, OnesweepLdsWords(1024, 16) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi16ELb0ELb0ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep16A, (&onesweep_kernel<1024, 16, false, true, false>), 1024, OnesweepLdsWords(1024, 16) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi16ELb0ELb1ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep16V, (&onesweep_kernel<1024, 16, true, false, false>), 1024, OnesweepLdsWords(1024, 16) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi16ELb1ELb0ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep16VA, (&onesweep_kernel<1024, 16, true, true, false>), 1024, OnesweepLdsWords(1024, 16) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi16ELb1ELb1ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep32, (&onesweep_kernel<1024, 32, false, false, false>), 1024, OnesweepLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi32ELb0ELb0ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep32A, (&onesweep_kernel<1024, 32, false, true, false>), 1024, OnesweepLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi32ELb0ELb1ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep32V, (&onesweep_kernel<1024, 32, true, false, false>), 1024, OnesweepLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi32ELb1ELb0ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep32VA, (&onesweep_kernel<1024, 32, true, true, false>), 1024, OnesweepLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi32ELb1ELb1ELb0EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep32S, (&onesweep_kernel<1024, 32, false, false, true>), 1024, OnesweepLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi32ELb0ELb0ELb1EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep32SA, (&onesweep_kernel<1024, 32, false, true, true>), 1024, OnesweepLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi32ELb0ELb1ELb1EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep32SV, (&onesweep_kernel<1024, 32, true, false, true>), 1024, OnesweepLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi32ELb1ELb0ELb1EEEvNS_12OnesweepArgsE") \
+  X(kOnesweep32SVA, (&onesweep_kernel<1024, 32, true, true, true>), 1024, OnesweepLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx15onesweep_kernelILi1024ELi32ELb1ELb1ELb1EEEvNS_12OnesweepArgsE") \
+  /* onesweep_pair_kernel (config 3; keys-only, one-atomic ranking): run-time slot counts | fixed */ \
+  X(kPair32S, (&onesweep_pair_kernel<1024, 32, true>), 1024, PairLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx20onesweep_pair_kernelILi1024ELi32ELb1EEEvNS_12OnesweepArgsE") \
+  X(kPair32, (&onesweep_pair_kernel<1024, 32, false>), 1024, PairLdsWords(1024, 32) * 4, \
+    "_ZN4vrdx20onesweep_pair_kernelILi1024ELi32ELb0EEEvNS_12OnesweepArgsE") \
+  /* small_sort_kernel [256 | 1024 threads][key-value][atomic rank] */ \
+  X(kSmall256, (&small_sort_kernel<256, 16, false, false>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx17small_sort_kernelILi256ELi16ELb0ELb0EEEvPjS1_jPKjS1_") \
+  X(kSmall256A, (&small_sort_kernel<256, 16, false, true>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx17small_sort_kernelILi256ELi16ELb0ELb1EEEvPjS1_jPKjS1_") \
+  X(kSmall256V, (&small_sort_kernel<256, 16, true, false>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx17small_sort_kernelILi256ELi16ELb1ELb0EEEvPjS1_jPKjS1_") \
+  X(kSmall256VA, (&small_sort_kernel<256, 16, true, true>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx17small_sort_kernelILi256ELi16ELb1ELb1EEEvPjS1_jPKjS1_") \
+  X(kSmall1024, (&small_sort_kernel<1024, 16, false, false>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx17small_sort_kernelILi1024ELi16ELb0ELb0EEEvPjS1_jPKjS1_") \
+  X(kSmall1024A, (&small_sort_kernel<1024, 16, false, true>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx17small_sort_kernelILi1024ELi16ELb0ELb1EEEvPjS1_jPKjS1_") \
+  X(kSmall1024V, (&small_sort_kernel<1024, 16, true, false>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx17small_sort_kernelILi1024ELi16ELb1ELb0EEEvPjS1_jPKjS1_") \
+  X(kSmall1024VA, (&small_sort_kernel<1024, 16, true, true>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx17small_sort_kernelILi1024ELi16ELb1ELb1EEEvPjS1_jPKjS1_") \
+  /* the segmented sort [key-value: yes | no][atomic rank: yes | no][small | mid | large] */ \
+  X(kSegmentedSmallVA, (&segmented_small_kernel<true, true>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx22segmented_small_kernelILb1ELb1EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedMidVA, (&segmented_mid_kernel<true, true>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx20segmented_mid_kernelILb1ELb1EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedLargeVA, (&segmented_large_kernel<true, true>), 1024, SegmentLargeLdsWords(true) * 4, \
+    "_ZN4vrdx22segmented_large_kernelILb1ELb1EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedSmallV, (&segmented_small_kernel<true, false>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx22segmented_small_kernelILb1ELb0EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedMidV, (&segmented_mid_kernel<true, false>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx20segmented_mid_kernelILb1ELb0EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedLargeV, (&segmented_large_kernel<true, false>), 1024, SegmentLargeLdsWords(true) * 4, \
+    "_ZN4vrdx22segmented_large_kernelILb1ELb0EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedSmallA, (&segmented_small_kernel<false, true>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx22segmented_small_kernelILb0ELb1EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedMidA, (&segmented_mid_kernel<false, true>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx20segmented_mid_kernelILb0ELb1EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedLargeA, (&segmented_large_kernel<false, true>), 1024, SegmentLargeLdsWords(false) * 4, \
+    "_ZN4vrdx22segmented_large_kernelILb0ELb1EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedSmall, (&segmented_small_kernel<false, false>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx22segmented_small_kernelILb0ELb0EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedMid, (&segmented_mid_kernel<false, false>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx20segmented_mid_kernelILb0ELb0EEEvNS_13SegmentedArgsE") \
+  X(kSegmentedLarge, (&segmented_large_kernel<false, false>), 1024, SegmentLargeLdsWords(false) * 4, \
+    "_ZN4vrdx22segmented_large_kernelILb0ELb0EEEvNS_13SegmentedArgsE") \
+  /* bucket_sort_kernel [4 | 8 | 16 keys per thread][key-value][atomic rank]; 32 keys per thread: one-atomic ranking only */ \
+  X(kBucket4, (&bucket_sort_kernel<1024, 4, false, false>), 1024, SmallSortLdsWords(1024, 4, false) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi4ELb0ELb0EEEvNS_14BucketSortArgsE") \
+  X(kBucket4A, (&bucket_sort_kernel<1024, 4, false, true>), 1024, SmallSortLdsWords(1024, 4, false) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi4ELb0ELb1EEEvNS_14BucketSortArgsE") \
+  X(kBucket4V, (&bucket_sort_kernel<1024, 4, true, false>), 1024, SmallSortLdsWords(1024, 4, true) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi4ELb1ELb0EEEvNS_14BucketSortArgsE") \
+  X(kBucket4VA, (&bucket_sort_kernel<1024, 4, true, true>), 1024, SmallSortLdsWords(1024, 4, true) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi4ELb1ELb1EEEvNS_14BucketSortArgsE") \
+  X(kBucket8, (&bucket_sort_kernel<1024, 8, false, false>), 1024, SmallSortLdsWords(1024, 8, false) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi8ELb0ELb0EEEvNS_14BucketSortArgsE") \
+  X(kBucket8A, (&bucket_sort_kernel<1024, 8, false, true>), 1024, SmallSortLdsWords(1024, 8, false) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi8ELb0ELb1EEEvNS_14BucketSortArgsE") \
+  X(kBucket8V, (&bucket_sort_kernel<1024, 8, true, false>), 1024, SmallSortLdsWords(1024, 8, true) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi8ELb1ELb0EEEvNS_14BucketSortArgsE") \
+  X(kBucket8VA, (&bucket_sort_kernel<1024, 8, true, true>), 1024, SmallSortLdsWords(1024, 8, true) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi8ELb1ELb1EEEvNS_14BucketSortArgsE") \
+  X(kBucket16, (&bucket_sort_kernel<1024, 16, false, false>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi16ELb0ELb0EEEvNS_14BucketSortArgsE") \
+  X(kBucket16A, (&bucket_sort_kernel<1024, 16, false, true>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi16ELb0ELb1EEEvNS_14BucketSortArgsE") \
+  X(kBucket16V, (&bucket_sort_kernel<1024, 16, true, false>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi16ELb1ELb0EEEvNS_14BucketSortArgsE") \
+  X(kBucket16VA, (&bucket_sort_kernel<1024, 16, true, true>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi16ELb1ELb1EEEvNS_14BucketSortArgsE") \
+  X(kBucket32A, (&bucket_sort_kernel<1024, 32, false, true>), 1024, SmallSortLdsWords(1024, 32, false) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi32ELb0ELb1EEEvNS_14BucketSortArgsE") \
+  X(kBucket32VA, (&bucket_sort_kernel<1024, 32, true, true>), 1024, SmallSortLdsWords(1024, 32, true) * 4, \
+    "_ZN4vrdx18bucket_sort_kernelILi1024ELi32ELb1ELb1EEEvNS_14BucketSortArgsE") \
+  /* the MSD plan's scatter and bucket launches with a pass of its fallback as a second role \
+     [10 | 11 bits][key-value][scatter | buckets][fixed | run-time slot counts] */ \
+  X(kMsdScatterOrPass0_10, (&msd_scatter_or_pass0_kernel<10, false, false>), 1024, MsdFusedLdsWords(false, 10, false) * 4, \
+    "_ZN4vrdx27msd_scatter_or_pass0_kernelILj10ELb0ELb0EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdScatterOrPass0_10S, (&msd_scatter_or_pass0_kernel<10, false, true>), 1024, MsdFusedLdsWords(false, 10, false) * 4, \
+    "_ZN4vrdx27msd_scatter_or_pass0_kernelILj10ELb0ELb1EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdBucketsOrPass1_10, (&msd_buckets_or_pass1_kernel<10, false, false>), 1024, MsdFusedLdsWords(false, 10, true) * 4, \
+    "_ZN4vrdx27msd_buckets_or_pass1_kernelILj10ELb0ELb0EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdBucketsOrPass1_10S, (&msd_buckets_or_pass1_kernel<10, false, true>), 1024, MsdFusedLdsWords(false, 10, true) * 4, \
+    "_ZN4vrdx27msd_buckets_or_pass1_kernelILj10ELb0ELb1EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdScatterOrPass0_10V, (&msd_scatter_or_pass0_kernel<10, true, false>), 1024, MsdFusedLdsWords(true, 10, false) * 4, \
+    "_ZN4vrdx27msd_scatter_or_pass0_kernelILj10ELb1ELb0EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdScatterOrPass0_10VS, (&msd_scatter_or_pass0_kernel<10, true, true>), 1024, MsdFusedLdsWords(true, 10, false) * 4, \
+    "_ZN4vrdx27msd_scatter_or_pass0_kernelILj10ELb1ELb1EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdBucketsOrPass1_10V, (&msd_buckets_or_pass1_kernel<10, true, false>), 1024, MsdFusedLdsWords(true, 10, true) * 4, \
+    "_ZN4vrdx27msd_buckets_or_pass1_kernelILj10ELb1ELb0EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdBucketsOrPass1_10VS, (&msd_buckets_or_pass1_kernel<10, true, true>), 1024, MsdFusedLdsWords(true, 10, true) * 4, \
+    "_ZN4vrdx27msd_buckets_or_pass1_kernelILj10ELb1ELb1EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdScatterOrPass0_11, (&msd_scatter_or_pass0_kernel<11, false, false>), 1024, MsdFusedLdsWords(false, 11, false) * 4, \
+    "_ZN4vrdx27msd_scatter_or_pass0_kernelILj11ELb0ELb0EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdScatterOrPass0_11S, (&msd_scatter_or_pass0_kernel<11, false, true>), 1024, MsdFusedLdsWords(false, 11, false) * 4, \
+    "_ZN4vrdx27msd_scatter_or_pass0_kernelILj11ELb0ELb1EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdBucketsOrPass1_11, (&msd_buckets_or_pass1_kernel<11, false, false>), 1024, MsdFusedLdsWords(false, 11, true) * 4, \
+    "_ZN4vrdx27msd_buckets_or_pass1_kernelILj11ELb0ELb0EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdBucketsOrPass1_11S, (&msd_buckets_or_pass1_kernel<11, false, true>), 1024, MsdFusedLdsWords(false, 11, true) * 4, \
+    "_ZN4vrdx27msd_buckets_or_pass1_kernelILj11ELb0ELb1EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdScatterOrPass0_11V, (&msd_scatter_or_pass0_kernel<11, true, false>), 1024, MsdFusedLdsWords(true, 11, false) * 4, \
+    "_ZN4vrdx27msd_scatter_or_pass0_kernelILj11ELb1ELb0EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdScatterOrPass0_11VS, (&msd_scatter_or_pass0_kernel<11, true, true>), 1024, MsdFusedLdsWords(true, 11, false) * 4, \
+    "_ZN4vrdx27msd_scatter_or_pass0_kernelILj11ELb1ELb1EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdBucketsOrPass1_11V, (&msd_buckets_or_pass1_kernel<11, true, false>), 1024, MsdFusedLdsWords(true, 11, true) * 4, \
+    "_ZN4vrdx27msd_buckets_or_pass1_kernelILj11ELb1ELb0EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  X(kMsdBucketsOrPass1_11VS, (&msd_buckets_or_pass1_kernel<11, true, true>), 1024, MsdFusedLdsWords(true, 11, true) * 4, \
+    "_ZN4vrdx27msd_buckets_or_pass1_kernelILj11ELb1ELb1EEEvNS_7MsdArgsENS_12OnesweepArgsE") \
+  /* the MSD plan: bucket_sort2_half_kernel (ten bits, buckets of at most kMsdHalfCap) [key-value: yes | no] */ \
+  X(kBucketMsdHalfV, (&bucket_sort2_half_kernel<10, true>), 512, BucketSort2LdsWords(kMsdHalfCap / 512, 512) * 4, \
+    "_ZN4vrdx24bucket_sort2_half_kernelILj10ELb1EEEvNS_7MsdArgsE") \
+  X(kBucketMsdHalf, (&bucket_sort2_half_kernel<10, false>), 512, BucketSort2LdsWords(kMsdHalfCap / 512, 512) * 4, \
+    "_ZN4vrdx24bucket_sort2_half_kernelILj10ELb0EEEvNS_7MsdArgsE") \
+  /* histogram_msd_kernel [10 | 11 bits][kHistCopiesLarge | kHistCopies replicas] */ \
+  X(kHistogramMsdLarge10, (&histogram_msd_kernel<kHistCopiesLarge, 10>), kHistThreads, HistMsdLdsBytes(kHistCopiesLarge, 10), \
+    "_ZN4vrdx20histogram_msd_kernelILj32ELj10EEEvNS_7MsdArgsE") \
+  X(kHistogramMsd10, (&histogram_msd_kernel<kHistCopies, 10>), kHistThreads, HistMsdLdsBytes(kHistCopies, 10), \
+    "_ZN4vrdx20histogram_msd_kernelILj8ELj10EEEvNS_7MsdArgsE") \
+  X(kHistogramMsdLarge11, (&histogram_msd_kernel<kHistCopiesLarge, 11>), kHistThreads, HistMsdLdsBytes(kHistCopiesLarge, 11), \
+    "_ZN4vrdx20histogram_msd_kernelILj32ELj11EEEvNS_7MsdArgsE") \
+  X(kHistogramMsd11, (&histogram_msd_kernel<kHistCopies, 11>), kHistThreads, HistMsdLdsBytes(kHistCopies, 11), \
+    "_ZN4vrdx20histogram_msd_kernelILj8ELj11EEEvNS_7MsdArgsE") \
+  /* spine_msd_kernel [10 | 11 bits] */ \
+  X(kSpineMsd10, (&spine_msd_kernel<10>), 1024, 0, \
+    "_ZN4vrdx16spine_msd_kernelILj10EEEvNS_7MsdArgsE") \
+  X(kSpineMsd11, (&spine_msd_kernel<11>), 1024, 0, \
+    "_ZN4vrdx16spine_msd_kernelILj11EEEvNS_7MsdArgsE") \
+  /* scatter_msd_kernel [10 | 11 bits][key-value: yes | no] */ \
+  X(kScatterMsd10V, (&scatter_msd_kernel<10, true>), 1024, ScatterMsdLdsWords(10) * 4, \
+    "_ZN4vrdx18scatter_msd_kernelILj10ELb1EEEvNS_7MsdArgsE") \
+  X(kScatterMsd10, (&scatter_msd_kernel<10, false>), 1024, ScatterMsdLdsWords(10) * 4, \
+    "_ZN4vrdx18scatter_msd_kernelILj10ELb0EEEvNS_7MsdArgsE") \
+  X(kScatterMsd11V, (&scatter_msd_kernel<11, true>), 1024, ScatterMsdLdsWords(11) * 4, \
+    "_ZN4vrdx18scatter_msd_kernelILj11ELb1EEEvNS_7MsdArgsE") \
+  X(kScatterMsd11, (&scatter_msd_kernel<11, false>), 1024, ScatterMsdLdsWords(11) * 4, \
+    "_ZN4vrdx18scatter_msd_kernelILj11ELb0EEEvNS_7MsdArgsE") \
+  /* bucket_sort2_kernel [10 | 11 bits][key-value: yes | no] */ \
+  X(kBucketMsd10V, (&bucket_sort2_kernel<10, kMsdCapKeyValue / 1024, true>), 1024, BucketSort2LdsWords(kMsdCapKeyValue / 1024) * 4, \
+    "_ZN4vrdx19bucket_sort2_kernelILj10ELi36ELb1EEEvNS_7MsdArgsE") \
+  X(kBucketMsd10, (&bucket_sort2_kernel<10, kMsdCapKeys / 1024, false>), 1024, BucketSort2LdsWords(kMsdCapKeys / 1024) * 4, \
+    "_ZN4vrdx19bucket_sort2_kernelILj10ELi36ELb0EEEvNS_7MsdArgsE") \
+  X(kBucketMsd11V, (&bucket_sort2_kernel<11, kMsdCapKeyValue / 1024, true>), 1024, BucketSort2LdsWords(kMsdCapKeyValue / 1024) * 4, \
+    "_ZN4vrdx19bucket_sort2_kernelILj11ELi36ELb1EEEvNS_7MsdArgsE") \
+  X(kBucketMsd11, (&bucket_sort2_kernel<11, kMsdCapKeys / 1024, false>), 1024, BucketSort2LdsWords(kMsdCapKeys / 1024) * 4, \
+    "_ZN4vrdx19bucket_sort2_kernelILj11ELi36ELb0EEEvNS_7MsdArgsE") \
+  /* no template: the segmented sort's fill, the two LDS order checks, the calibration spin */ \
+  X(kSegmentedClear, (&segmented_clear_kernel), 64, 0, \
+    "_ZN4vrdx22segmented_clear_kernelENS_13SegmentedArgsE") \
+  X(kOrderCheck, (&lds_order_check_kernel), 1024, 0, \
+    "_ZN4vrdx22lds_order_check_kernelEPjS0_") \
+  X(kOrderCheckPacked, (&lds_order_check_packed_kernel), 1024, kOrderCheckPackedLdsBytes, \
+    "_ZN4vrdx29lds_order_check_packed_kernelEPjS0_") \
+  X(kSpin, (&spin_kernel), 64, 0, \
+    "_ZN4vrdx11spin_kernelEPyj")
+
+enum KernelId : int {
+#define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
+  VRDX_KERNELS(VRDX_KERNEL_ID)
+#undef VRDX_KERNEL_ID
+  kNumKernels
+};
+
+struct KernelShape {
+  uint32_t threads;
+  uint32_t ldsBytes;
+};
+static constexpr KernelShape kKernelShapes[kNumKernels] = {
+#define VRDX_KERNEL_SHAPE(id, stub, threads, ldsBytes, name) {threads, (uint32_t)(ldsBytes)},
+    VRDX_KERNELS(VRDX_KERNEL_SHAPE)
+#undef VRDX_KERNEL_SHAPE
+};
+
+// The backend's primitives (defined behind this file).  PrepareKernel readies kernel `id` on the current device: it raises
+// the kernel's dynamic-LDS limit if it takes dynamic LDS.  LaunchKernel starts it with the list's block size and LDS and
+// returns the hipError_t of ITS launch, so that the recorder never has to consult the calling thread's sticky last-error
+// state, which an unrelated earlier failure may have set.
+static hipError_t PrepareKernel(KernelId id);
+static hipError_t LaunchKernel(KernelId id, uint32_t grid, hipStream_t stream, void** params);
+
+template <typename... Args>
+static hipError_t Launch(KernelId id, uint32_t grid, hipStream_t stream, Args... args) {
+  void* params[] = {static_cast<void*>(&args)...};
+  return LaunchKernel(id, grid, stream, params);
+}
+
+// a form of a family of four, listed as [key-value][atomic rank]
+static KernelId Form(KernelId first, bool keyValue, bool atomicRank) { return KernelId(first + 2 * keyValue + atomicRank); }
+
+// Every geometry here is selected by ConfigIndex (vrdx_api.cpp) for some size range; nothing else is built.
+const TileConfig kTileConfigs[kNumTileConfigs] = {
+    {1024, 8, 1}, {1024, 16, 1}, {1024, 32, 1}, {1024, 32, 2},
+};
+
+hipError_t PrepareKernels() {
+  for (int id = 0; id < kNumKernels; ++id) {
+    const hipError_t e = PrepareKernel(KernelId(id));
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// run-time slot counts (even-split and tail-split tiles, PlanTiles in vrdx_api.cpp): multiples of 4, at most the geometry's
+static bool SlotsFit(const OnesweepArgs& a, uint32_t keysPerThread) {
+  return a.slots % 4 == 0 && a.slots <= keysPerThread && a.tailSlots % 4 == 0 && a.tailSlots != 0 &&
+         a.tailSlots <= keysPerThread;
+}
+
+// tiles of rows x 4096 keys (the scatter's even-split tiles); a tile of full capacity is eight rows
+static bool MsdShapeFits(const MsdArgs& a) {
+  return (a.bits == 10 || a.bits == 11) && a.tileKeys != 0 && a.tileKeys % 4096u == 0 && a.tileKeys <= kMsdTileKeys;
+}
+
+hipError_t LaunchHistogram(hipStream_t stream, uint32_t grid, const uint32_t* keys, uint32_t maxCount,
+                           const uint32_t* countPtr, uint32_t* globalHistogram, uint32_t* tickets, void* statusClear,
+                           uint32_t statusClearBytes) {
+  const uint32_t vecs = statusClearBytes / 16u;  // whole status rows: a multiple of 1 KiB, 128-byte aligned
+  return Launch(maxCount >= kHistManyCopiesFrom ? kHistogramLarge : kHistogram, grid, stream, keys, maxCount, countPtr,
+                globalHistogram, tickets, statusClear, vecs);
+}
+
+// The two-sub-tile kernel exists for keys-only sorts with the one-atomic ranking (the ballot form of it spills
+// 152 bytes per lane and ConfigIndex never selected it): its key+value form would hold sub-tile B's keys and
+// ranks, A's staging slots and A's values at once and spills (measured 40 GItems/s in round 1; a 768-thread
+// form with 168 registers and no spill measured 54.5 GItems/s against 67.2 for onesweep_kernel<1024, 32>,
+// profiles/r03_geometry.txt), so it is not built.
+hipError_t LaunchOnesweep(hipStream_t stream, int configIndex, uint32_t grid, bool keyValue, bool atomicRank,
+                          const OnesweepArgs& args) {
+  // kTileConfigs: configs 0-2 are onesweep_kernel of 8, 16 and 32 keys per thread, config 3 the two-sub-tile kernel; only
+  // the geometries of 32 keys per thread (2, 3) have forms with run-time slot counts
+  if (configIndex < 0 || configIndex >= kNumTileConfigs) return hipErrorInvalidValue;
+  const bool split = args.slots != 0;
+  if (split && (configIndex < 2 || !SlotsFit(args, 32))) return hipErrorInvalidValue;
+  if (configIndex == 3) {
+    if (keyValue || !atomicRank) return hipErrorInvalidValue;  // never selected (ConfigIndex)
+    return Launch(split ? kPair32S : kPair32, grid, stream, args);
+  }
+  const KernelId first = split ? kOnesweep32S : configIndex == 0 ? kOnesweep8 : configIndex == 1 ? kOnesweep16 : kOnesweep32;
+  return Launch(Form(first, keyValue, atomicRank), grid, stream, args);
+}
+
+hipError_t LaunchSmallSort(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
+                           const uint32_t* countPtr, uint32_t* failure) {
+  const KernelId first = maxCount <= 256u * 16u ? kSmall256 : kSmall1024;
+  return Launch(Form(first, values != nullptr, atomicRank), 1, stream, keys, values, maxCount, countPtr, failure);
+}
+
+hipError_t LaunchBucketSort(hipStream_t stream, bool keyValue, bool atomicRank, const BucketSortArgs& args) {
+  KernelId id;
+  switch (args.hybridCap) {
+    case 1024u * 4u: id = Form(kBucket4, keyValue, atomicRank); break;
+    case 1024u * 8u: id = Form(kBucket8, keyValue, atomicRank); break;
+    case 1024u * 16u: id = Form(kBucket16, keyValue, atomicRank); break;
+    case 1024u * 32u:
+      // the one-atomic ranking only (the ballot forms would spill; never recorded: HybridCapacity); key+value stages keys
+      // and values through ONE buffer (SharedStage)
+      if (!atomicRank) return hipErrorInvalidValue;
+      id = keyValue ? kBucket32VA : kBucket32A;
+      break;
+    default: return hipErrorInvalidValue;
+  }
+  return Launch(id, VRDX_RADIX, stream, args);
+}
+
+// ---- MSD plan -----------------------------------------------------------------------------------------
+hipError_t LaunchHistogramMsd(hipStream_t stream, uint32_t grid, const MsdArgs& args) {
+  if (!MsdShapeFits(args)) return hipErrorInvalidValue;
+  const bool many = args.maxCount >= kHistManyCopiesFrom;
+  return Launch(KernelId(kHistogramMsd10 + 2 * ((int)args.bits - 10) - many), grid, stream, args);
+}
+
+hipError_t LaunchSpineMsd(hipStream_t stream, const MsdArgs& args) {
+  if ((args.bits != 10 && args.bits != 11) || args.tiles > kMsdMaxTiles) return hipErrorInvalidValue;
+  return Launch(KernelId(kSpineMsd10 + ((int)args.bits - 10)), (1u << args.bits) / 32u, stream, args);
+}
+
+hipError_t LaunchScatterMsd(hipStream_t stream, bool keyValue, const MsdArgs& args) {
+  if (!MsdShapeFits(args)) return hipErrorInvalidValue;
+  // a multiple of 8 workgroups: eight chunks of consecutive tiles (keys-only: pairs of tiles), one per XCD (see the kernels)
+  const uint32_t grid = MsdScatterGrid(args.tiles, keyValue, args.bits);
+  return Launch(KernelId(kScatterMsd10 + 2 * ((int)args.bits - 10) - keyValue), grid, stream, args);
+}
+
+hipError_t LaunchBucketSort2(hipStream_t stream, bool keyValue, const MsdArgs& args) {
+  if (args.cap == kMsdHalfCap && args.bits == 10)
+    return Launch(keyValue ? kBucketMsdHalfV : kBucketMsdHalf, MsdBucketGrid(args.bits, true), stream, args);
+  if ((args.bits != 10 && args.bits != 11) || args.cap != (keyValue ? kMsdCapKeyValue : kMsdCapKeys))
+    return hipErrorInvalidValue;
+  return Launch(KernelId(kBucketMsd10 + 2 * ((int)args.bits - 10) - keyValue), MsdBucketGrid(args.bits, false), stream, args);
+}
+
+// The plan's scatter / bucket launch with the fallback's pass 0 / pass 1 as its second role (bucketLaunch selects which).
+// passGrid: the grid LaunchOnesweep would have used for that pass.
+hipError_t LaunchMsdFused(hipStream_t stream, bool bucketLaunch, bool keyValue, const MsdArgs& m, const OnesweepArgs& p,
+                          uint32_t passGrid) {
+  if (!MsdShapeFits(m) || (bucketLaunch && m.cap != (keyValue ? kMsdCapKeyValue : kMsdCapKeys))) return hipErrorInvalidValue;
+  const bool split = p.slots != 0;  // the pass's run-time slot counts, checked like LaunchOnesweep does
+  if (split && !SlotsFit(p, 32)) return hipErrorInvalidValue;
+  // the larger of the two roles' grids, a multiple of 8 (the scatter derives its tile from the grid: eight chunks of tiles,
+  // one per XCD; a workgroup beyond its role's range returns).  The bucket launch takes two buckets per workgroup
+  // (MsdBucketGrid): a pass of up to 2^bits / 2 tiles then has no idle workgroups.
+  const uint32_t planGrid = bucketLaunch ? MsdBucketGrid(m.bits, false) : MsdScatterGrid(m.tiles, keyValue, m.bits);
+  const uint32_t grid = 8u * (((planGrid > passGrid ? planGrid : passGrid) + 7u) / 8u);
+  const int form = 8 * ((int)m.bits - 10) + 4 * keyValue + 2 * bucketLaunch + split;
+  return Launch(KernelId(kMsdScatterOrPass0_10 + form), grid, stream, m, p);
+}
+
+// ---- segmented sort ---------------------------------------------------------------------------------
+hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args) {
+  return Launch(kSegmentedClear, 1, stream, args);
+}
+
+hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                           const SegmentedArgs& args) {
+  if (grid == 0) return hipErrorInvalidValue;
+  return Launch(KernelId(kSegmentedSmall - 3 * (2 * keyValue + atomicRank) + sizeClass), grid, stream, args);
+}
+
+// ---- the LDS order check and the calibration spin -----------------------------------------------------
+hipError_t LdsOrderCheck(bool* laneOrdered) {
+  uint32_t* d = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(uint32_t));
+  if (e != hipSuccess) return e;
+  uint32_t h = 0xFFFFFFFFu;
+  e = hipMemset(d, 0, sizeof(uint32_t));
+  uint32_t* const noSticky = nullptr;
+  if (e == hipSuccess) e = Launch(kOrderCheck, 512, nullptr, d, noSticky);
+  // the packed-counter shape of the MSD plan: two digits to a word
+  if (e == hipSuccess) e = Launch(kOrderCheckPacked, 256, nullptr, d, noSticky);
+  if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e == hipSuccess) *laneOrdered = h == 0;
+  return e;
+}
+
+hipError_t LaunchLdsOrderRecheck(hipStream_t stream, uint32_t* sticky) {
+  uint32_t* const noCount = nullptr;
+  const hipError_t e = Launch(kOrderCheck, 8, stream, noCount, sticky);
+  if (e != hipSuccess) return e;
+  return Launch(kOrderCheckPacked, 8, stream, noCount, sticky);
+}
+
+hipError_t LaunchSpin(hipStream_t stream, unsigned long long* out, uint32_t ticks) {
+  return Launch(kSpin, 1, stream, out, ticks);
+}
