@@ -1,7 +1,7 @@
 """A plain-Python model of what the DEVICE decides about a sort whose host recorded a two-trip plan in front of the four
 passes -- restated from vrdx_kernels.hip, not derived from the kernels' output:
 
-  MSD plan (histogram_msd_kernel, spine_msd_kernel, scatter_msd_kernel):
+  MSD plan (histogram_msd_kernel, spine_msd_kernel, the scatter role of msd_scatter_or_pass0_kernel):
     wave 0 samples 64 keys at indices t (n - 1) / 63 of the DEVICE count n; `varying` = one past the highest bit in which
     two sampled keys differ; the window of BITS bits starts at lowest = max(varying, BITS + 2) - BITS; spread = the varying
     bits inside it.  Then, in this order:

@@ -112,19 +112,20 @@ int ConfigIndex(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCount
   // (the two-sub-tile kernel is keys-only: a key+value sort under a forced 1024x32x2 takes 1024x32)
   if (forced >= 0) return forced == kCfg1024x32x2 && (keyValue || !atomicRank) ? kCfg1024x32 : forced;
   const double f = (double)elementCount / ((double)sorter->computeUnits * 32768.0);
+  // Behind the MSD plan the passes are the fallback only, and the plan's own launches double as its first two (one kernel, two
+  // roles): those kernels exist for 1024x32 key+value and the two-sub-tile geometry keys-only (the plan is recorded with the
+  // one-atomic ranking only), which are then taken at every size -- keys-only at one round of tiles and below as even-split
+  // tiles of two half-size sub-tiles.
+  if (msd) return keyValue ? kCfg1024x32 : kCfg1024x32x2;
   if (keyValue) {
     if (f <= 0.26) return kCfg1024x8;
     if (f <= 0.53) return kCfg1024x16;
     // just past one round of 32768-element tiles, two workgroups of 16384 per CU fill the second round's gap
     // (1.2-2.6 % at 1.07 <= f <= 1.32, profiles/r03_sweep_by_geometry.txt; still so with the tail split of round 4,
     // profiles/r04_tail_split_kv.txt)
-    if (f > 1.0 && f <= 1.35 && !msd) return kCfg1024x16;
+    if (f > 1.0 && f <= 1.35) return kCfg1024x16;
     return kCfg1024x32;
   }
-  // Behind the MSD plan the passes are the fallback only, and the plan's own launches double as its first two (one kernel, two
-  // roles): those fused kernels exist for the two-sub-tile geometry, which is then taken at every size (at one round of tiles
-  // and below as even-split tiles of two half-size sub-tiles).
-  if (msd && atomicRank) return kCfg1024x32x2;
   if (f <= 0.125) return kCfg1024x8;
   if (f <= 0.5) return kCfg1024x16;   // beyond: even-split 1024x32 tiles (PlanTiles), 7 % faster at f = 0.536
   if (f <= 1.0) return kCfg1024x32;
@@ -317,10 +318,9 @@ struct SortPlan {
   bool oneWorkgroup = false;    // small_sort_kernel: one launch, no storage layout
   uint32_t hybridCap = 0;       // the eight-bit hybrid plan is recorded with this bucket capacity
   uint32_t msdBits = 0;         // the MSD plan is recorded in front of the passes (10 | 11)
-  uint32_t msdCap = 0;
+  uint32_t msdCap = 0;          // kMsdHalfCap: bucket_sort2_half_kernel, and pass 1 a launch of its own
   uint32_t msdTileKeys = 0;
   uint32_t msdTiles = 0;
-  uint32_t msdFused = 0;        // how many of the plan's launches double as the fallback's first passes (0 | 1 | 2)
   int configIndex = 0;
   vrdx::TilePlan tilePlan{};
   bool blockSums = false;
@@ -377,16 +377,13 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
     p.fits = vrdx::LayoutFits(p.layout, elementCount);
   }
   // The MSD plan's scatter launch is ALSO pass 0 of the fallback and its bucket launch pass 1 (one branch on the verdict, on
-  // the device): only passes 2 and 3 remain as launches that return when the plan runs.  The fused kernels exist for the
-  // geometries the recorder selects at these sizes (ConfigIndex: the two-sub-tile kernel keys-only, 1024x32 key+value --
-  // since round 6: vrdx_kernels.hip, msd_scatter_or_pass0_kernel); with buckets of the half-size kernel (512 threads; the
-  // passes' bodies need 1024) only the scatter launch has a second role.  VRDX_MSD_FUSED=0: none (measurements).
-  static const int fusedKnob = TuningKnob("VRDX_MSD_FUSED");
-  if (p.msdBits != 0 && fusedKnob != 0 && p.configIndex == (keyValue ? kCfg1024x32 : kCfg1024x32x2))
-    p.msdFused = p.msdCap == (keyValue ? vrdx::kMsdCapKeyValue : vrdx::kMsdCapKeys) ? 2u : 1u;
-  // kernels: histogram + four passes (+ the eight-bit plan's bucket launch); the MSD plan: + spine, and those of its scatter
-  // and bucket launches that are not also a pass
-  p.launches = 1u + VRDX_PASSES + (p.msdBits != 0 ? 3u - p.msdFused : 0u) + (p.hybridCap != 0 ? 1u : 0u);
+  // the device; vrdx_kernels.hip, msd_scatter_or_pass0_kernel): only passes 2 and 3 remain as launches that return when the
+  // plan runs.  With buckets of the half-size kernel (512 threads; the passes' bodies need 1024) only the scatter launch has
+  // a second role.
+  // kernels: histogram + four passes (+ the eight-bit plan's bucket launch); the MSD plan: + spine (+ the half-size bucket
+  // kernel)
+  const uint32_t msdLaunches = p.msdBits == 0 ? 0u : p.msdCap == vrdx::kMsdHalfCap ? 2u : 1u;
+  p.launches = 1u + VRDX_PASSES + msdLaunches + (p.hybridCap != 0 ? 1u : 0u);
   return p;
 }
 
@@ -605,9 +602,10 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
 #endif
     return args;
   };
-  const uint32_t msdFused = plan.msdFused;  // how many of the plan's launches double as the fallback's first passes (PlanSort)
   // The MSD plan, recorded in front of the passes: spine (prefixes over the tiles, bucket table,
-  // verdict), scatter by the window bits, one workgroup per bucket.  The passes behind return on the verdict word.
+  // verdict), scatter by the window bits -- also pass 0 --, one workgroup per bucket -- also pass 1, unless the buckets are
+  // half-size (PlanSort).  The passes behind return on the verdict word.
+  const bool halfBuckets = msdCap == vrdx::kMsdHalfCap;
   if (msdBits != 0) {
     // Timestamps: the plan's own three stages take the names they have in the reference -- slot 2 "upsweep" = the
     // histogram, 3 "spine", 4 "downsweep" = the scatter -- and the bucket sorts are pass 1's "upsweep" (slot 5, like the
@@ -615,31 +613,27 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
     Stamp(pool, query + 2, stream);
     EnqueueCheck(sorter, "spine_msd_kernel", vrdx::LaunchSpineMsd(stream, m));
     Stamp(pool, query + 3, stream);
-    if (msdFused >= 1)
-      EnqueueCheck(sorter, "msd_scatter_or_pass0_kernel", vrdx::LaunchMsdFused(stream, false, keyValue, m, passArgs(0), tilePlan.tiles));
-    else
-      EnqueueCheck(sorter, "scatter_msd_kernel", vrdx::LaunchScatterMsd(stream, keyValue, m));
+    EnqueueCheck(sorter, "msd_scatter_or_pass0_kernel", vrdx::LaunchMsdFused(stream, false, keyValue, m, passArgs(0), tilePlan.tiles));
     Stamp(pool, query + 4, stream);
-    if (msdFused >= 2)
-      EnqueueCheck(sorter, "msd_buckets_or_pass1_kernel", vrdx::LaunchMsdFused(stream, true, keyValue, m, passArgs(1), tilePlan.tiles));
+    if (halfBuckets)
+      EnqueueCheck(sorter, "bucket_sort2_half_kernel", vrdx::LaunchBucketSortHalf(stream, keyValue, m));
     else
-      EnqueueCheck(sorter, "bucket_sort2_kernel", vrdx::LaunchBucketSort2(stream, keyValue, m));
+      EnqueueCheck(sorter, "msd_buckets_or_pass1_kernel", vrdx::LaunchMsdFused(stream, true, keyValue, m, passArgs(1), tilePlan.tiles));
     Stamp(pool, query + 5, stream);
   }
   for (uint32_t pass = 0; pass < VRDX_PASSES; ++pass) {
-    if (pass < msdFused) {  // ran (or returned) inside the plan's own launches
-      if (pass == 1) {
-        StampSame(pool, query + 6, query + 5);
-        StampSame(pool, query + 7, query + 5);
-      }
-      continue;
-    }
     // "upsweep" of this pass: the fused histogram kernel for pass 0, nothing for the others -- the same
     // point of the stream as the previous pass's "downsweep" stamp
     if (msdBits != 0) {
-      // (slots 2-5 are the MSD plan's, above; launch 0 and launch 1 fall into slot 7)
-      if (pass == 1) StampSame(pool, query + 6, query + 5);
-      if (pass >= 2) {
+      // (slots 2-5 are the MSD plan's, above: the bucket launch is pass 1's "upsweep")
+      if (pass == 0) continue;  // ran (or returned) inside the scatter launch
+      if (pass == 1) {
+        StampSame(pool, query + 6, query + 5);
+        if (!halfBuckets) {  // ran (or returned) inside the bucket launch
+          StampSame(pool, query + 7, query + 5);
+          continue;
+        }
+      } else {
         StampSame(pool, query + 2 + 3 * pass + 0, query + 2 + 3 * (pass - 1) + 2);
         StampSame(pool, query + 2 + 3 * pass + 1, query + 2 + 3 * pass + 0);
       }
@@ -669,7 +663,7 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
     EnqueueCheck(sorter, "onesweep_kernel",
                  vrdx::LaunchOnesweep(stream, configIndex, tiles, keyValue, atomicRank, args));
 
-    if (msdBits == 0 || pass != 0) Stamp(pool, query + 2 + 3 * pass + 2, stream);  // "downsweep"
+    Stamp(pool, query + 2 + 3 * pass + 2, stream);  // "downsweep"
   }
   StampSame(pool, query + 14, query + 13);  // end of the sort = end of the last pass
   MaybeRecheckOrder(sorter, stream, atomicRank);

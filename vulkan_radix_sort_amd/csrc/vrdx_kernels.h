@@ -127,13 +127,16 @@ hipError_t LaunchBucketSort(hipStream_t stream, bool keyValue, bool atomicRank, 
 //                         overflow word -- the sample is the guess, the count stays the proof;
 //   spine_msd_kernel      turns the counts, in place, into exclusive prefixes over the tiles and leaves every bucket's base;
 //                         a bucket beyond `cap` elements sets *overflowWord;
-//   scatter_msd_kernel    one stable scatter by the window bits, caller -> scratch: no ticket, no look-back, no status words --
+//   the scatter launch    one stable scatter by the window bits, caller -> scratch: no ticket, no look-back, no status words --
 //                         a tile's bases are bucketBase[d] + its row of prefixes; keys-only sorts take TWO consecutive tiles per
 //                         workgroup (round 6: runs of 256 bytes instead of 128);
-//   bucket_sort2_kernel   one workgroup per bucket sorts it by the bits below the window (none, one or two stable passes of
+//   the bucket launch     one workgroup per bucket sorts it by the bits below the window (none, one or two stable passes of
 //                         up to 11 bits) inside its LDS, scratch -> caller.
+// The scatter launch is also pass 0 of the fallback and the bucket launch, with full-size buckets, pass 1 (LaunchMsdFused);
+// buckets of half the size take bucket_sort2_half_kernel (LaunchBucketSortHalf), and pass 1 is a launch of its own.
 // All of it with wave-private counters of 16 bits, two to a word.  The device decides (the overflow word): with a bucket
-// beyond the capacity or a key outside the prefix the last two return at once and the four passes recorded behind them run.
+// beyond the capacity or a key outside the prefix the last two run their pass instead (the half-size bucket kernel returns at
+// once) and the passes recorded behind them follow.
 constexpr uint32_t kMsdTileKeys = 32768;   // a scatter tile's capacity: 1024 threads x 32 keys
 constexpr uint32_t kMsdMaxTiles = 2048;    // spine_msd_kernel: 64 chunks of at most 32 rows
 constexpr uint32_t kMsdCapKeys = 36864;    // bucket capacity, keys-only: 1024 threads x 36 keys (144 KiB of staging)
@@ -195,8 +198,8 @@ struct MsdArgs {
 };
 hipError_t LaunchHistogramMsd(hipStream_t stream, uint32_t grid, const MsdArgs& args);
 hipError_t LaunchSpineMsd(hipStream_t stream, const MsdArgs& args);
-hipError_t LaunchScatterMsd(hipStream_t stream, bool keyValue, const MsdArgs& args);
-hipError_t LaunchBucketSort2(hipStream_t stream, bool keyValue, const MsdArgs& args);
+// The bucket launch of buckets of at most kMsdHalfCap (ten bits): bucket_sort2_half_kernel.
+hipError_t LaunchBucketSortHalf(hipStream_t stream, bool keyValue, const MsdArgs& args);
 // The scatter (bucketLaunch = false) or bucket (true) launch of the plan with pass 0 / pass 1 of its fallback as a second
 // role, chosen on the device by the plan's verdict: saves two of the four returning launches.  `pass` = the arguments and
 // passGrid the grid LaunchOnesweep would have been given for that pass (the two-sub-tile kernel keys-only, 1024x32
@@ -285,7 +288,7 @@ constexpr uint32_t HistMsdLdsBytes(uint32_t copies, uint32_t bits) {
 
 constexpr size_t ScatterMsdLdsWords(uint32_t bits) { return (size_t)kMsdTileKeys + ((size_t)1 << bits) + 32; }
 
-// bucket_sort2_kernel (THREADS = 1024) and bucket_sort2_half_kernel (512)
+// the bucket role of msd_buckets_or_pass1_kernel (THREADS = 1024) and bucket_sort2_half_kernel (512)
 constexpr size_t BucketSort2LdsWords(int kpt, int threads = 1024) { return (size_t)threads * kpt + 32; }
 
 // msd_scatter_or_pass0_kernel / msd_buckets_or_pass1_kernel: the larger of the two roles'

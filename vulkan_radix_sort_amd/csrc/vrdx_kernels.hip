@@ -22,9 +22,10 @@
 //     see ConfigIndex in vrdx_api.cpp).
 //   * small_sort_kernel / bucket_sort_kernel -- sorts of up to 16384 elements in one workgroup; the hybrid plan of
 //     mid-size sorts (one scatter by the highest varying byte, then every bucket in LDS).
-//   * histogram_msd_kernel / spine_msd_kernel / scatter_msd_kernel / bucket_sort2[_half]_kernel -- the MSD plan of sorts
-//     of 8.14 M ... 67 M elements: one chain-free scatter by a window of 10-11 bits (the top ones for uniform keys, chosen on
-//     the device below the keys' common prefix otherwise), then every bucket in LDS in two passes.
+//   * histogram_msd_kernel / spine_msd_kernel / msd_scatter_or_pass0_kernel / msd_buckets_or_pass1_kernel /
+//     bucket_sort2_half_kernel -- the MSD plan of sorts of 8.14 M ... 67 M elements: one chain-free scatter by a window of
+//     10-11 bits (the top ones for uniform keys, chosen on the device below the keys' common prefix otherwise), then every
+//     bucket in LDS in two passes.
 //   Tile ids are handed out by an atomic ticket in ARRIVAL order, so a look-back only ever waits
 //   on a tile that is already running; every spin is bounded (failure word, never a hang).
 #include <hip/hip_runtime.h>
@@ -1963,12 +1964,14 @@ __global__ __launch_bounds__(1024) void segmented_large_kernel(SegmentedArgs a) 
 //                          their sum) -- the reference's upsweep (upsweep.slang:10-45) for this one digit;
 //   spine_msd_kernel       exclusive prefix over the tiles, in place; base and size of every bucket; a bucket beyond
 //                          the capacity raises the overflow word (spine.slang:11-84);
-//   scatter_msd_kernel     stable scatter by the top bits: base = bucketBase[d] + prefix[tile][d] + rank in the tile
+//   the scatter role       stable scatter by the top bits: base = bucketBase[d] + prefix[tile][d] + rank in the tile
 //                          (downsweep.slang:41-224).  No ticket, no status words, no look-back, no spin: tiles are
 //                          independent, which is what a row of 2048 status words per tile would have made expensive;
-//   bucket_sort2_kernel    every bucket (<= 36864 elements) by its remaining 21-22 bits: two stable passes of <= 11 bits
+//   the bucket role        every bucket (<= 36864 elements) by its remaining 21-22 bits: two stable passes of <= 11 bits
 //                          through the LDS staging buffer; bucket_sort2_half_kernel: the same in 512 threads for buckets
 //                          of <= 18432 elements (sorts of up to 18.1 M), two workgroups to a CU.
+// The scatter role is msd_scatter_or_pass0_kernel and the full-size bucket role msd_buckets_or_pass1_kernel: each is also a
+// pass of the fallback (below, "the plan's launches double as ...").
 //
 // A stable scatter by the top bits followed by a stable sort of each bucket by the bits below is the permutation of
 // four stable LSD passes.  If any bucket exceeds the capacity (skewed or few-distinct keys, keys below 2^21) the last two
@@ -2487,9 +2490,10 @@ __global__ __launch_bounds__(kHistThreads) void histogram_msd_kernel(MsdArgs a) 
 // each, every load in flight at once, 64 bytes per row and workgroup -- the 64 chunk sums of a word are scanned by one
 // wave, and the thread walks its rows again from registers.  Totals are kept in 32 bits per digit: a bucket beyond 65535
 // must not go unnoticed because its half wrapped (the prefixes it leaves are garbage then, and nobody reads them).
-// The first bucket's base is the number of keys in the buckets below it: the histogram kernel has added up every bucket's
-// size (bucketCount).  A plan that is already turned down (the sample's prediction, a key outside the sampled prefix) or
-// has nothing to scatter (all keys identical) leaves only the fallback's status region to clear.
+// The first bucket's base is the number of keys in the buckets below it: below a prefix the histogram kernel has added up
+// every bucket's size (bucketCount), under the top window byte 3's table has it and this kernel writes the sizes.  A plan
+// that is already turned down (the sample's prediction, a key outside the sampled prefix) or has nothing to scatter (all
+// keys identical) leaves only the fallback's status region to clear.
 template <uint32_t BITS>
 __global__ __launch_bounds__(1024) void spine_msd_kernel(MsdArgs a) {
   constexpr uint32_t D = 1u << BITS, ROW = D / 2;
@@ -2524,7 +2528,8 @@ __global__ __launch_bounds__(1024) void spine_msd_kernel(MsdArgs a) {
 #pragma unroll
   for (uint32_t k = 0; k < MAXROWS; ++k) v[k] = (k < rows && r0 + k < a.tiles) ? column[(size_t)(r0 + k) * ROW] : 0u;
   if ((decided & kMsdDeclineMask) != 0u || ((decided >> kMsdModeShift) & kMsdModeMask) != kMsdModePlan) return;  // nothing to scan
-  uint32_t under = ((decided >> kMsdShiftShift) & kMsdShiftMask) == 32u - BITS ? underTop : underSizes;
+  const bool topWindow = ((decided >> kMsdShiftShift) & kMsdShiftMask) == 32u - BITS;
+  uint32_t under = topWindow ? underTop : underSizes;
   uint32_t lo = 0, hi = 0;
 #pragma unroll
   for (uint32_t k = 0; k < MAXROWS; ++k) {
@@ -2564,13 +2569,15 @@ __global__ __launch_bounds__(1024) void spine_msd_kernel(MsdArgs a) {
 #pragma unroll
       for (uint32_t q = 0; q < 16; ++q) base += below[q];
       a.bucketBase[firstBucket + tid] = base;
-      a.bucketCount[firstBucket + tid] = mine;  // (what the histogram kernel has added up below a prefix, the same number)
+      // The bucket sizes: under the top window the histogram kernel leaves them to this kernel; below a prefix it has added
+      // them up, and they are left alone -- so no workgroup of this launch writes the sizes another one reads (underSizes).
+      if (topWindow) a.bucketCount[firstBucket + tid] = mine;
       if (mine > a.cap) atomicOr(a.overflowWord, kMsdDeclineBucket);
     }
   }
 }
 
-// ---- scatter_msd_kernel -----------------------------------------------------------------------------
+// ---- the plan's scatter role ------------------------------------------------------------------------
 // One tile of 32768 keys: load (wave-striped), rank by the top BITS bits with packed counters, scan, positions, regroup
 // through the staging buffer -- which takes the counters' place once every wave knows its positions: 128 KiB of staging
 // and 64 KiB of counters would not fit side by side -- and out in quads like the pass kernels, boundary quads by the thread
@@ -2756,7 +2763,7 @@ __device__ __forceinline__ void ScatterMsdBody(const MsdArgs a) {
 // kernel's trick), ranked with a counter row per (sub-tile, wave) -- the column scan walks A's sixteen rows, then B's: inside a
 // bucket all of A precedes all of B, the stable order -- and staged through the 128 KiB buffer in two halves BY POSITION
 // ([0, H) then [H, 2H), H = a tile's keys: whatever the keys are, a half fits), each half written out in quads like
-// scatter_msd_kernel does.  A run that straddles H is cut in two, like any run at a tile's end.
+// the one-tile scatter does.  A run that straddles H is cut in two, like any run at a tile's end.
 // Measured against the one-tile form (profiles/r06_scatter_pair.txt, rocprofv3, ten sorts back to back): 70.4 instead of 83.0 us
 // at 2^25, 36.8 instead of 43.1 at 2^24; WRITE_SIZE 157.9 MB per launch instead of 193.2 (1.18 x instead of 1.44 x of what must
 // be written), reads unchanged.
@@ -2776,7 +2783,7 @@ __device__ __forceinline__ void ScatterMsdPairBody(const MsdArgs a) {
   const int wave = tid >> 6;
   const uint32_t n = ElementCount(a.maxCount, a.countPtr);
   const uint32_t pairs = (a.tiles + 1u) / 2u;
-  // XCD x takes the consecutive super-tiles [x C, (x + 1) C), C = ceil(pairs / 8) (scatter_msd_kernel)
+  // XCD x takes the consecutive super-tiles [x C, (x + 1) C), C = ceil(pairs / 8) (ScatterMsdBody)
   const uint32_t perXcd = (pairs + 7u) / 8u;
   const uint32_t pair = (blockIdx.x % 8u) * perXcd + blockIdx.x / 8u;
   const uint32_t slots = a.tileKeys / (uint32_t)THREADS;
@@ -2842,7 +2849,7 @@ __device__ __forceinline__ void ScatterMsdPairBody(const MsdArgs a) {
 
   constexpr int QUADS = KPT / 4;
   constexpr int B = 2;  // (four at a time: 128 registers and 48 bytes of scratch)
-  // the quads around a run's start, by the thread that owns the run (two runs per thread, scatter_msd_kernel)
+  // the quads around a run's start, by the thread that owns the run (two runs per thread, ScatterMsdBody)
   uint32_t boundaryQuad[2] = {~0u, ~0u};
   if ((uint32_t)tid < ROW) {
     if (count0 != 0 && (local0 & 3u) != 0 && local0 < valid) boundaryQuad[0] = local0 & ~3u;
@@ -2907,11 +2914,11 @@ __device__ __forceinline__ void ScatterMsdRole(const MsdArgs a) {
     ScatterMsdBody<BITS, KV>(a);
 }
 
-// ---- bucket_sort2_kernel ----------------------------------------------------------------------------
+// ---- the plan's bucket role -------------------------------------------------------------------------
 // Workgroup b sorts bucket b = [bucketBase[b], + bucketCount[b]) of the scratch arrays by the 32 - BITS bits below the
 // scatter's, in two stable passes (11 bits, then the rest) with 2048 packed counters per wave, and writes it to the same
 // range of the caller's arrays.  Keys (and values) stay in registers between the passes; the staging buffer -- up to
-// 144 KiB -- takes the counters' place inside each pass like in scatter_msd_kernel; key+value stages the values through
+// 144 KiB -- takes the counters' place inside each pass like in the scatter role; key+value stages the values through
 // the same slots after the keys.  A wave takes only as many slots as the bucket needs (like SortInWorkgroup).
 // LDS: BucketSort2LdsWords (vrdx_kernels.h).
 
@@ -3077,18 +3084,10 @@ __device__ __forceinline__ void BucketSort2Body(const MsdArgs a, const uint32_t 
   for (uint32_t bucket = blockIdx.x; bucket < (1u << BITS); bucket += workgroups) BucketSort2Bucket<BITS, KPT, KV, THREADS>(a, bucket, below);
 }
 
-template <uint32_t BITS, bool KV>
-__global__ __launch_bounds__(1024) void scatter_msd_kernel(MsdArgs a) {
-  ScatterMsdRole<BITS, KV>(a);
-}
-template <uint32_t BITS, int KPT, bool KV>
-__global__ __launch_bounds__(1024) void bucket_sort2_kernel(MsdArgs a) {
-  BucketSort2Body<BITS, KPT, KV>(a, gridDim.x);
-}
 // Buckets of no more than 18432 elements (sorts of up to 18.1 M elements by ten bits): workgroups of 512 threads and
 // 72 KiB of LDS, TWO to a CU -- one loads or scans while the other ranks.  A bucket has a fixed cost of 5.7 us in the
-// kernel above (load latency, two column scans, eight barriers), half the time of a bucket of 8192 keys, and with one
-// workgroup per CU nothing runs beside it.
+// full-size form (1024 threads; load latency, two column scans, eight barriers), half the time of a bucket of 8192 keys,
+// and with one workgroup per CU nothing runs beside it.
 // (__launch_bounds__' second argument is WAVES PER SIMD here: two workgroups of eight waves on four SIMDs = 4, i.e. at most
 // 128 registers; the kernels take 85 keys-only and 121 key+value.)
 template <uint32_t BITS, bool KV>

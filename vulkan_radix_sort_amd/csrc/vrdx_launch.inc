@@ -181,24 +181,6 @@
     "_ZN4vrdx16spine_msd_kernelILj10EEEvNS_7MsdArgsE") \
   X(kSpineMsd11, (&spine_msd_kernel<11>), 1024, 0, \
     "_ZN4vrdx16spine_msd_kernelILj11EEEvNS_7MsdArgsE") \
-  /* scatter_msd_kernel [10 | 11 bits][key-value: yes | no] */ \
-  X(kScatterMsd10V, (&scatter_msd_kernel<10, true>), 1024, ScatterMsdLdsWords(10) * 4, \
-    "_ZN4vrdx18scatter_msd_kernelILj10ELb1EEEvNS_7MsdArgsE") \
-  X(kScatterMsd10, (&scatter_msd_kernel<10, false>), 1024, ScatterMsdLdsWords(10) * 4, \
-    "_ZN4vrdx18scatter_msd_kernelILj10ELb0EEEvNS_7MsdArgsE") \
-  X(kScatterMsd11V, (&scatter_msd_kernel<11, true>), 1024, ScatterMsdLdsWords(11) * 4, \
-    "_ZN4vrdx18scatter_msd_kernelILj11ELb1EEEvNS_7MsdArgsE") \
-  X(kScatterMsd11, (&scatter_msd_kernel<11, false>), 1024, ScatterMsdLdsWords(11) * 4, \
-    "_ZN4vrdx18scatter_msd_kernelILj11ELb0EEEvNS_7MsdArgsE") \
-  /* bucket_sort2_kernel [10 | 11 bits][key-value: yes | no] */ \
-  X(kBucketMsd10V, (&bucket_sort2_kernel<10, kMsdCapKeyValue / 1024, true>), 1024, BucketSort2LdsWords(kMsdCapKeyValue / 1024) * 4, \
-    "_ZN4vrdx19bucket_sort2_kernelILj10ELi36ELb1EEEvNS_7MsdArgsE") \
-  X(kBucketMsd10, (&bucket_sort2_kernel<10, kMsdCapKeys / 1024, false>), 1024, BucketSort2LdsWords(kMsdCapKeys / 1024) * 4, \
-    "_ZN4vrdx19bucket_sort2_kernelILj10ELi36ELb0EEEvNS_7MsdArgsE") \
-  X(kBucketMsd11V, (&bucket_sort2_kernel<11, kMsdCapKeyValue / 1024, true>), 1024, BucketSort2LdsWords(kMsdCapKeyValue / 1024) * 4, \
-    "_ZN4vrdx19bucket_sort2_kernelILj11ELi36ELb1EEEvNS_7MsdArgsE") \
-  X(kBucketMsd11, (&bucket_sort2_kernel<11, kMsdCapKeys / 1024, false>), 1024, BucketSort2LdsWords(kMsdCapKeys / 1024) * 4, \
-    "_ZN4vrdx19bucket_sort2_kernelILj11ELi36ELb0EEEvNS_7MsdArgsE") \
   /* no template: the segmented sort's fill, the two LDS order checks, the calibration spin */ \
   X(kSegmentedClear, (&segmented_clear_kernel), 64, 0, \
     "_ZN4vrdx22segmented_clear_kernelENS_13SegmentedArgsE") \
@@ -329,19 +311,9 @@ hipError_t LaunchSpineMsd(hipStream_t stream, const MsdArgs& args) {
   return Launch(KernelId(kSpineMsd10 + ((int)args.bits - 10)), (1u << args.bits) / 32u, stream, args);
 }
 
-hipError_t LaunchScatterMsd(hipStream_t stream, bool keyValue, const MsdArgs& args) {
-  if (!MsdShapeFits(args)) return hipErrorInvalidValue;
-  // a multiple of 8 workgroups: eight chunks of consecutive tiles (keys-only: pairs of tiles), one per XCD (see the kernels)
-  const uint32_t grid = MsdScatterGrid(args.tiles, keyValue, args.bits);
-  return Launch(KernelId(kScatterMsd10 + 2 * ((int)args.bits - 10) - keyValue), grid, stream, args);
-}
-
-hipError_t LaunchBucketSort2(hipStream_t stream, bool keyValue, const MsdArgs& args) {
-  if (args.cap == kMsdHalfCap && args.bits == 10)
-    return Launch(keyValue ? kBucketMsdHalfV : kBucketMsdHalf, MsdBucketGrid(args.bits, true), stream, args);
-  if ((args.bits != 10 && args.bits != 11) || args.cap != (keyValue ? kMsdCapKeyValue : kMsdCapKeys))
-    return hipErrorInvalidValue;
-  return Launch(KernelId(kBucketMsd10 + 2 * ((int)args.bits - 10) - keyValue), MsdBucketGrid(args.bits, false), stream, args);
+hipError_t LaunchBucketSortHalf(hipStream_t stream, bool keyValue, const MsdArgs& args) {
+  if (args.cap != kMsdHalfCap || args.bits != 10) return hipErrorInvalidValue;
+  return Launch(keyValue ? kBucketMsdHalfV : kBucketMsdHalf, MsdBucketGrid(args.bits, true), stream, args);
 }
 
 // The plan's scatter / bucket launch with the fallback's pass 0 / pass 1 as its second role (bucketLaunch selects which).

@@ -202,7 +202,7 @@ static inline SegmentedLayout MakeSegmentedLayout(uint32_t maxElementCount, uint
   return s;
 }
 
-// The MSD plan's scatter (scatter_msd_kernel, one workgroup per CU and tile) cuts the sort into EQUAL tiles that fill whole
+// The MSD plan's scatter (msd_scatter_or_pass0_kernel, one workgroup per CU and tile) cuts the sort into EQUAL tiles that fill whole
 // rounds of `cus` tiles: keys per tile, a multiple of 4096 (four 64-key slots per wave of its 1024 threads), at most 32768.
 // 520 tiles of 32768 keys would cost three rounds, the third for eight tiles; 768 tiles of 24576 cost three rounds of three
 // quarters the length.  maxTiles: the spine kernel's reach; beyond it, tiles of full capacity.
