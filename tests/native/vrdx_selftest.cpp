@@ -255,6 +255,67 @@ bool GraphCase(Harness& h, bool kv, uint32_t n) {
   return ok;
 }
 
+// vrdxHipCmdSortSegmentedKeyValue: segments of every size class (in-LDS small and mid, through memory) in one call, o[0] > 0
+// and a tail behind the last segment, 16-bit keys (equal keys in every segment), compared with std::stable_sort by key per
+// segment; nothing outside the segments, behind the bound or behind the storage requirement may change.
+bool SegmentedCase(Harness& h) {
+  const std::vector<uint32_t> sizes = {7, 40000, 0, 4096, 1, 9000, 16384, 300, 16385, 2, 4097, 70001, 5};
+  std::vector<uint32_t> offsets = {5};
+  for (uint32_t s : sizes) offsets.push_back(offsets.back() + s);
+  const uint32_t n = offsets.back() + 11;
+  std::vector<uint32_t> keys = Mt(n, 31, 16, nullptr), values(n);
+  for (uint32_t i = 0; i < n; ++i) values[i] = i ^ 0x80000000u;
+
+  const uint32_t inout = Align16((n + kGuard) * 4u);
+  const uint32_t offsetsBytes = Align16((uint32_t)offsets.size() * 4u);
+  VrdxSorterStorageRequirements req;
+  vrdxGetSorterKeyValueStorageRequirements(h.sorter, n, &req);
+  const size_t guardBytes = 256;
+  h.reserve((size_t)2 * inout + offsetsBytes, (size_t)req.size + guardBytes);
+  std::vector<uint32_t> hk(inout / 4, kGuardWord), hv(inout / 4, kGuardWord);
+  std::copy(keys.begin(), keys.end(), hk.begin());
+  std::copy(values.begin(), values.end(), hv.begin());
+  HIP_OK(hipMemcpy(h.dKeys, hk.data(), inout, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h.dKeys + inout, hv.data(), inout, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h.dKeys + 2 * (size_t)inout, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemset(h.dStorage, 0xA5, (size_t)req.size));
+  HIP_OK(hipMemset(h.dStorage + req.size, 0x5A, guardBytes));
+
+  VkCommandBuffer cmd = (VkCommandBuffer)h.stream;
+  VkBuffer buf = (VkBuffer)h.dKeys;
+  VkBuffer sto = (VkBuffer)h.dStorage;
+  vrdxHipCmdSortSegmentedKeyValue(cmd, h.sorter, n, (uint32_t)sizes.size(), buf, 2 * (VkDeviceSize)inout, buf, 0, buf, inout,
+                                  sto, 0, h.pool, 0);
+  HIP_OK(hipStreamSynchronize(h.stream));
+  const uint32_t failure = vrdxHipReadStatus(cmd, sto, 0);
+
+  std::vector<uint32_t> gk(inout / 4), gv(inout / 4), go(offsets.size());
+  std::vector<uint8_t> guard(guardBytes);
+  HIP_OK(hipMemcpy(gk.data(), h.dKeys, inout, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(gv.data(), h.dKeys + inout, inout, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(go.data(), h.dKeys + 2 * (size_t)inout, offsets.size() * 4, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(guard.data(), h.dStorage + req.size, guardBytes, hipMemcpyDeviceToHost));
+
+  std::vector<uint32_t> idx(n);
+  for (uint32_t i = 0; i < n; ++i) idx[i] = i;
+  for (size_t s = 0; s < sizes.size(); ++s)
+    std::stable_sort(idx.begin() + offsets[s], idx.begin() + offsets[s + 1],
+                     [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+  long firstBad = -1;
+  for (uint32_t i = 0; i < n && firstBad < 0; ++i)
+    if (gk[i] != keys[idx[i]] || gv[i] != values[idx[i]]) firstBad = i;
+  bool tailOk = go == offsets;
+  for (uint32_t i = n; i < inout / 4; ++i)
+    if (gk[i] != kGuardWord || gv[i] != kGuardWord) tailOk = false;
+  for (uint8_t b : guard)
+    if (b != 0x5A) tailOk = false;
+  const bool ok = failure == 0 && firstBad < 0 && tailOk;
+  if (!ok)
+    std::printf("FAIL segmented kv, %zu segments n=%u failure=%u firstBad=%ld tailOk=%d\n", sizes.size(), n, failure, firstBad,
+                (int)tailOk);
+  return ok;
+}
+
 int Parity(Harness& h, bool quick) {
   int failures = 0, cases = 0;
   auto run = [&](Mode m, const std::vector<uint32_t>& k, const std::vector<uint32_t>& v, uint32_t maxCount,
@@ -359,6 +420,9 @@ int Parity(Harness& h, bool quick) {
       ++cases;
       if (!GraphCase(h, kv != 0, n)) ++failures;
     }
+  // the segmented entry point: every size class in one key+value call
+  ++cases;
+  if (!SegmentedCase(h)) ++failures;
   std::printf("parity: %d cases, %d failures\n", cases, failures);
   return failures;
 }

@@ -588,7 +588,7 @@ def test_hybrid_plan_and_its_fallback_at_the_bucket_capacity(torch_mod, sorter, 
 
 
 def test_four_pass_plan_at_mid_sizes_with_the_hybrid_plan_switched_off():
-    """VRDX_HYBRID=0: the native parity battery (255 cases up to 3 M elements) on the four-pass plan alone."""
+    """VRDX_HYBRID=0: the native parity battery (256 cases up to 3 M elements, the segmented one among them) on the four-pass plan alone."""
     exe = os.path.join(ROOT, "tests", "native", "vrdx_selftest")
     out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=1200, env=dict(os.environ, VRDX_HYBRID="0"))
     assert out.returncode == 0 and ", 0 failures" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
