@@ -76,6 +76,27 @@ def check(torch, sorter, oracle, keys, count=None, indirect=False, expect=None, 
     return want
 
 
+# ---- 1. what the host records: plan and launch count by size -----------------------------------------------------------
+
+# (n, plan, launches): one size inside each shape of a recorded sort and the sizes either side of each switch, the same
+# keys-only and key+value with the one-atomic ranking.  Launches are kernels (the state fill and the copy of an indirect
+# count are not): the one kernel; histogram + bucket sort + four passes; histogram, spine, scatter (also pass 0), half-size
+# buckets, passes 1-3; the same with full-size buckets that are also pass 1; histogram + four passes.
+PLAN_TABLE = [(1, "one-workgroup", 1), (4096, "one-workgroup", 1), (16384, "one-workgroup", 1),
+              (16385, "hybrid-8", 6), (1 << 20, "hybrid-8", 6), (8_144_384, "hybrid-8", 6),
+              (8_144_385, "msd", 7), (12_000_001, "msd", 7), (18_149_376, "msd", 7),
+              (18_149_377, "msd", 6), (1 << 25, "msd", 6), (LAST, "msd", 6),
+              (LAST + 1, "four-passes", 5), (100_000_000, "four-passes", 5)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key_value", [False, True])
+@pytest.mark.parametrize("n,plan,launches", PLAN_TABLE)
+def test_recorded_plan_and_launch_count_by_size(sorter, n, plan, launches, key_value):
+    info = sorter.describe_plan(n, key_value)
+    assert (info.name, int(info.launches)) == (plan, launches), (n, key_value)
+
+
 # ---- 2. the window at every position -----------------------------------------------------------------------------------
 
 SWEEP = ([(HALF, v, model.PREFIX) for v in range(2, 33)] + [(HALF, v, 0) for v in (12, 17, 24)]

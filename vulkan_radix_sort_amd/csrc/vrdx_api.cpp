@@ -53,12 +53,15 @@ struct VrdxSorter_T {
 };
 
 struct VrdxHipQueryPool {
-  uint32_t count = 0;
-  hipEvent_t* events = nullptr;
-  uint8_t* recorded = nullptr;
-  // source[slot]: the slot whose event holds this slot's time.  Slots the sort writes back to back, with
-  // no device work between them, share ONE event record (an event record costs the stream ~3 us).
-  uint32_t* source = nullptr;
+  struct Slot {
+    hipEvent_t event = nullptr;
+    bool recorded = false;
+    // the slot whose event holds this slot's time.  Slots the sort writes back to back, with no device work between
+    // them, share ONE event record (an event record costs the stream ~3 us).
+    uint32_t source = 0;
+  };
+  uint32_t count = 0;  // slots whose event exists
+  Slot* slots = nullptr;
 };
 
 namespace {
@@ -77,19 +80,52 @@ void ConfigName(const vrdx::TileConfig& c, char* out, size_t size) {
     std::snprintf(out, size, "%dx%dx%d", c.threads, c.keysPerThread, c.subTiles);
 }
 
-int ForcedConfigIndex() {
-  static const int forced = [] {
-    const char* env = std::getenv("VRDX_TILE_CONFIG");  // e.g. "512x16": one geometry for everything (tuning/testing)
-    if (env == nullptr) return -1;
-    for (int i = 0; i < vrdx::kNumTileConfigs; ++i) {
-      char name[32];
-      ConfigName(vrdx::kTileConfigs[i], name, sizeof(name));
-      if (std::strcmp(env, name) == 0) return i;
+// The environment knobs (tuning / testing only), read once.  VRDX_RANK is not among them: it is read
+// whenever a sorter is created or re-checked (RankModeIs).
+struct Knobs {
+  int forcedConfig = -1;   // VRDX_TILE_CONFIG, e.g. "1024x16": one geometry for everything, and the general path at every size
+  bool hybrid = true;      // VRDX_HYBRID=0: always the four-pass plan
+  bool msd = true;         // VRDX_MSD=0 (or VRDX_HYBRID=0): no MSD plan
+  bool smallSort = true;   // VRDX_SMALL_SORT=0: always the general path
+  bool blockSums = true;   // VRDX_BLOCK_SUMS=0: sorts of one round keep the classic look-back (measurements)
+  bool debug = false;      // VRDX_DEBUG: report HIP errors of the enqueues on stderr (the entry points themselves return
+                           // void and validate nothing, like the reference's vrdxCmd*)
+#ifdef VRDX_TESTING
+  // test build only.  VRDX_TEST_INJECT_ENQUEUE_ERROR: every EnqueueCheck reports a refusal, the work itself is enqueued as
+  // usual (tests/enqueue_error_check.py).  VRDX_TEST_SPIN_LIMIT >= 0: the passes' spin limit; 0 makes the first look-back trip
+  // that has to wait give up, how tests/sticky_status_check.py sees the device-side failure path (failure + sticky word)
+  bool injectEnqueueError = false;
+  int testSpinLimit = -1;
+#endif
+};
+
+const Knobs& EnvKnobs() {
+  static const Knobs knobs = [] {
+    Knobs k;
+    const auto off = [](const char* name) {
+      const char* env = std::getenv(name);
+      return env != nullptr && env[0] == '0';
+    };
+    if (const char* env = std::getenv("VRDX_TILE_CONFIG")) {
+      for (int i = 0; i < vrdx::kNumTileConfigs && k.forcedConfig < 0; ++i) {
+        char name[32];
+        ConfigName(vrdx::kTileConfigs[i], name, sizeof(name));
+        if (std::strcmp(env, name) == 0) k.forcedConfig = i;
+      }
+      if (k.forcedConfig < 0) std::fprintf(stderr, "vrdx-hip: unknown VRDX_TILE_CONFIG '%s', using the defaults\n", env);
     }
-    std::fprintf(stderr, "vrdx-hip: unknown VRDX_TILE_CONFIG '%s', using the defaults\n", env);
-    return -1;
+    k.hybrid = !off("VRDX_HYBRID");
+    k.msd = k.hybrid && !off("VRDX_MSD");
+    k.smallSort = !off("VRDX_SMALL_SORT");
+    if (const char* env = std::getenv("VRDX_BLOCK_SUMS")) k.blockSums = std::atoi(env) != 0;
+    k.debug = std::getenv("VRDX_DEBUG") != nullptr;
+#ifdef VRDX_TESTING
+    k.injectEnqueueError = std::getenv("VRDX_TEST_INJECT_ENQUEUE_ERROR") != nullptr;
+    if (const char* env = std::getenv("VRDX_TEST_SPIN_LIMIT")) k.testSpinLimit = std::atoi(env);
+#endif
+    return k;
   }();
-  return forced;
+  return knobs;
 }
 
 // Tile geometry by problem size, measured on MI355X (tools: `vrdx_selftest sweep`, tables in
@@ -108,7 +144,7 @@ enum : int { kCfg1024x8 = 0, kCfg1024x16 = 1, kCfg1024x32 = 2, kCfg1024x32x2 = 3
 // msd: the MSD plan is recorded in front of the passes, which are then only the fallback for skewed keys; its per-tile counts
 // take a quarter to a half of the reference's partition-histogram area, so the passes must not take tiles of 16384.
 int ConfigIndex(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCount, bool atomicRank, bool msd = false) {
-  const int forced = ForcedConfigIndex();
+  const int forced = EnvKnobs().forcedConfig;
   // (the two-sub-tile kernel is keys-only: a key+value sort under a forced 1024x32x2 takes 1024x32)
   if (forced >= 0) return forced == kCfg1024x32x2 && (keyValue || !atomicRank) ? kCfg1024x32 : forced;
   const double f = (double)elementCount / ((double)sorter->computeUnits * 32768.0);
@@ -171,12 +207,6 @@ void DumpTrace() {
 }
 #endif
 
-// Integer environment knob for the tuning scripts (read once); -1 when unset.
-int TuningKnob(const char* name) {
-  const char* env = std::getenv(name);
-  return env != nullptr ? std::atoi(env) : -1;
-}
-
 // Mid-size sorts record the hybrid plan (vrdx_kernels.hip, PassPlan) next to the four passes: launch 0 scatters by the
 // keys' highest byte that varies and bucket_sort_kernel finishes every bucket inside one workgroup -- if the DEVICE finds that no bucket
 // exceeds the capacity returned here; otherwise the four passes run as usual and the bucket launch is empty.  The
@@ -187,11 +217,7 @@ int TuningKnob(const char* name) {
 // launch, 3 us, where one that does saves 17-25 %): N <= 8.1 M elements (4.0 M with the ballot ranking).
 // 0 = the plan is not recorded (larger N, a forced tile geometry, VRDX_HYBRID=0).
 uint32_t HybridCapacity(bool atomicRank, uint32_t elementCount) {
-  static const bool enabled = [] {
-    const char* env = std::getenv("VRDX_HYBRID");  // "0": always the four-pass plan (testing / measurements)
-    return env == nullptr || env[0] != '0';
-  }();
-  if (!enabled || elementCount <= vrdx::kSmallSortMaxElements) return 0;
+  if (!EnvKnobs().hybrid || elementCount <= vrdx::kSmallSortMaxElements) return 0;
   // a bucket may hold twice the mean bucket; the LARGEST capacity is tried with less room than the others (3 %): failing
   // costs one empty launch, the plan is worth a fifth to a third of the sort (profiles/r03_hybrid_headroom.txt)
   const uint64_t mean = (elementCount + VRDX_RADIX - 1) / VRDX_RADIX;
@@ -214,12 +240,7 @@ uint32_t HybridCapacity(bool atomicRank, uint32_t elementCount) {
 // at these sizes): ten bits up to 36.6 M keys / 32.5 M pairs, eleven bits up to twice that.  Returns the bits or 0.
 // One-atomic ranking only.  VRDX_MSD=0 switches it off (VRDX_HYBRID=0 and a forced tile geometry as well).
 uint32_t MsdBits(bool atomicRank, bool keyValue, uint32_t elementCount, uint32_t hybridCap, uint32_t* capacity) {
-  static const bool enabled = [] {
-    const char* all = std::getenv("VRDX_HYBRID");
-    const char* msd = std::getenv("VRDX_MSD");
-    return (all == nullptr || all[0] != '0') && (msd == nullptr || msd[0] != '0');
-  }();
-  if (!enabled || !atomicRank) return 0;
+  if (!EnvKnobs().msd || !atomicRank) return 0;
   // From where the EIGHT-bit plan ends (8.1 M: hybridCap == 0), keys-only and key+value.  Up to 18.1 M elements the buckets
   // hold at most 18432 and the half-size bucket kernel sorts them, two workgroups to a CU: with it the plan is 8-15 % faster
   // than round 4's nine-bit hybrid plan and the four passes at one round of tiles, which key+value sorts of these sizes
@@ -243,52 +264,57 @@ uint32_t MsdBits(bool atomicRank, bool keyValue, uint32_t elementCount, uint32_t
   return 0;
 }
 
-bool SmallSortEnabled() {
-  static const bool enabled = [] {
-    const char* env = std::getenv("VRDX_SMALL_SORT");  // "0": always take the general path (testing)
-    return env == nullptr || env[0] != '0';
-  }();
-  return enabled;
-}
-
 inline uint8_t* BufferAddress(VkBuffer buffer, VkDeviceSize offset) {
   return reinterpret_cast<uint8_t*>(buffer) + offset;
 }
 
-// VRDX_DEBUG=1: report HIP errors of the enqueues on stderr (the entry points themselves return
-// void and validate nothing, like the reference's vrdxCmd*).
-bool DebugEnabled() {
-  static const bool enabled = std::getenv("VRDX_DEBUG") != nullptr;
-  return enabled;
-}
 // After every enqueue of a sort: a launch / fill / copy the runtime REFUSED is latched in the sorter (and
 // printed under VRDX_DEBUG).  Only the value returned by that very call is looked at -- never the calling
 // thread's last-error state, which is sticky on ROCm and may hold an unrelated, older failure of the caller's.
 void EnqueueCheck(const VrdxSorter_T* sorter, const char* what, hipError_t returned) {
 #ifdef VRDX_TESTING
-  // test build only (tests/enqueue_error_check.py builds it): every check reports a refusal, the work itself is
-  // enqueued as usual
-  static const bool inject = std::getenv("VRDX_TEST_INJECT_ENQUEUE_ERROR") != nullptr;
-  if (inject) returned = hipErrorUnknown;
+  if (EnvKnobs().injectEnqueueError) returned = hipErrorUnknown;
 #endif
   if (returned == hipSuccess) return;
   sorter->enqueueFailed.store(1u, std::memory_order_relaxed);
-  if (DebugEnabled()) std::fprintf(stderr, "vrdx-hip: %s -> %s\n", what, hipGetErrorString(returned));
+  if (EnvKnobs().debug) std::fprintf(stderr, "vrdx-hip: %s -> %s\n", what, hipGetErrorString(returned));
 }
 
-void Stamp(VrdxHipQueryPool* pool, uint32_t slot, hipStream_t stream) {
-  if (pool == nullptr || slot >= pool->count) return;
-  if (hipEventRecord(pool->events[slot], stream) == hipSuccess) {
-    pool->recorded[slot] = 1;
-    pool->source[slot] = slot;
+// The 15 timestamp slots of one sort, [query, query + 15) of the pool, written front to back: every slot is either
+// stamped by an event of its own behind the step that ends there, or is the same point of the stream as the slot before
+// it (nothing enqueued since) and shares that slot's event.
+constexpr uint32_t kTimestampSlots = 15;
+class StampCursor {
+ public:
+  StampCursor(VrdxHipQueryPool* pool, uint32_t query, hipStream_t stream) : pool_(pool), query_(query), stream_(stream) { Stamp(0); }
+  // everything enqueued so far ends at `slot`: the slots in between coincide with their predecessor
+  void AdvanceTo(uint32_t slot) {
+    while (++slot_ < slot) StampSame(slot_);
+    Stamp(slot);
   }
-}
-// The same point of the stream as slot `same` (stamped just before, nothing enqueued since): no second event.
-void StampSame(VrdxHipQueryPool* pool, uint32_t slot, uint32_t same) {
-  if (pool == nullptr || slot >= pool->count || same >= pool->count || !pool->recorded[same]) return;
-  pool->recorded[slot] = 1;
-  pool->source[slot] = pool->source[same];
-}
+  void Finish() {  // the end of the sort = the end of its last step
+    while (++slot_ < kTimestampSlots) StampSame(slot_);
+  }
+ private:
+  void Stamp(uint32_t slot) {
+    const uint32_t q = query_ + slot;
+    if (pool_ == nullptr || q >= pool_->count) return;
+    if (hipEventRecord(pool_->slots[q].event, stream_) == hipSuccess) {
+      pool_->slots[q].recorded = true;
+      pool_->slots[q].source = q;
+    }
+  }
+  void StampSame(uint32_t slot) {
+    const uint32_t q = query_ + slot;
+    if (pool_ == nullptr || q >= pool_->count || !pool_->slots[q - 1].recorded) return;
+    pool_->slots[q].recorded = true;
+    pool_->slots[q].source = pool_->slots[q - 1].source;
+  }
+  VrdxHipQueryPool* pool_;
+  uint32_t query_;
+  hipStream_t stream_;
+  uint32_t slot_ = 0;
+};
 
 // The tile plan of a sort (vrdx_layout.h, PlanTiles): even-split tiles for sorts of one round, tail-split tiles behind
 // the whole rounds of a longer one -- where the kernels' forms with run-time slot counts exist and where they were
@@ -310,10 +336,30 @@ vrdx::TilePlan PlanTiles(const VrdxSorter_T* sorter, int configIndex, bool keyVa
                          (uint32_t)c.subTiles, splitForms, evenSplit, tailPercent);
 }
 
+// The steps of a sort in the order they are enqueued, each with the timestamp slot it ends.  The slots carry the
+// reference's names (include/vk_radix_sort.h): 0 start, 1 "transfer", 2 + 3 p "upsweep" / 3 + 3 p "spine" / 4 + 3 p
+// "downsweep" of pass p, 14 end; a slot no step ends coincides with the one before it (StampCursor).
+enum class Step : uint8_t {
+  kFill,               // slot 1: state fill, and the copy of an indirect count (not counted as a launch)
+  kHistogram,          // slot 2, pass 0's "upsweep": the fused histogram of all four passes
+  kHistogramMsd,       // slot 2: the MSD plan's form of it
+  kSpineMsd,           // slot 3: a real "spine"
+  kMsdScatterOrPass0,  // slot 4, pass 0's "downsweep": the MSD plan's scatter, whose second role is pass 0
+  kMsdBucketsOrPass1,  // slot 5, pass 1's "upsweep": the MSD plan's full-size buckets, whose second role is pass 1
+  kBucketSortHalf,     // slot 5: its half-size buckets
+  kBucketSort,         // slot 5: the eight-bit plan's buckets
+  kPass,               // slot 4 + 3 p, "downsweep": pass p, look-back fused into it ("spine" = "upsweep" = the slot before)
+  kSmallSort,          // slot 14: the one-workgroup sort
+};
+struct SortStep { Step what; uint8_t pass, slot; const char* name; };  // (pass: kPass only; name: what EnqueueCheck reports)
+constexpr uint32_t kMaxSortSteps = 8;  // fill, histogram, spine, scatter, half-size buckets, passes 1-3
+
 // Everything the host decides about a sort, in ONE place: RecordSort records it and vrdxHipDescribePlan reports it.
 // storageAddress: the absolute address the storage is handed over at -- only its low seven bits matter (the pads in front
 // of the 128-byte aligned regions); 0 is the worst case for what fits, which is what vrdxHipDescribePlan assumes.
 struct SortPlan {
+  bool keyValue = false;
+  uint32_t elementCount = 0;
   bool atomicRank = false;
   bool oneWorkgroup = false;    // small_sort_kernel: one launch, no storage layout
   uint32_t hybridCap = 0;       // the eight-bit hybrid plan is recorded with this bucket capacity
@@ -326,18 +372,55 @@ struct SortPlan {
   bool blockSums = false;
   bool fits = true;             // false: not even tiles of full capacity fit the caller's storage (refused)
   vrdx::StorageLayout layout{};
-  uint32_t launches = 0;        // kernels + fills enqueued
+  SortStep steps[kMaxSortSteps];  // none: the empty sort and the refused one
+  uint32_t stepCount = 0;
+  uint32_t launches = 0;        // kernels among the steps
 };
+
+// The MSD plan's scatter launch is ALSO pass 0 of the fallback and its bucket launch pass 1 (one branch on the verdict, on
+// the device; vrdx_kernels.hip, msd_scatter_or_pass0_kernel): only passes 2 and 3 remain as launches that return when the
+// plan runs.  With buckets of the half-size kernel (512 threads; the passes' bodies need 1024) only the scatter launch has
+// a second role.  The eight-bit plan's bucket sort sits between launch 0 and launch 1 (which is empty when the plan applies).
+void ListSteps(SortPlan& p) {
+  const auto add = [&p](Step what, const char* name, uint32_t slot, uint32_t pass = 0) {
+    p.steps[p.stepCount++] = SortStep{what, (uint8_t)pass, (uint8_t)slot, name};
+    if (what != Step::kFill) ++p.launches;
+  };
+  const bool msd = p.msdBits != 0, halfBuckets = msd && p.msdCap == vrdx::kMsdHalfCap;
+  if (p.oneWorkgroup) return add(Step::kSmallSort, "small_sort_kernel", 14);
+  add(Step::kFill, "hipMemcpyAsync(count)", 1);
+  if (msd)
+    add(Step::kHistogramMsd, "histogram_msd_kernel", 2);
+  else
+    add(Step::kHistogram, "histogram_kernel", 2);
+  if (msd) {
+    add(Step::kSpineMsd, "spine_msd_kernel", 3);
+    add(Step::kMsdScatterOrPass0, "msd_scatter_or_pass0_kernel", 4);
+    if (halfBuckets)
+      add(Step::kBucketSortHalf, "bucket_sort2_half_kernel", 5);
+    else
+      add(Step::kMsdBucketsOrPass1, "msd_buckets_or_pass1_kernel", 5);
+  }
+  for (uint32_t pass = !msd ? 0u : halfBuckets ? 1u : 2u; pass < VRDX_PASSES; ++pass) {
+    if (pass == 1 && p.hybridCap != 0) add(Step::kBucketSort, "bucket_sort_kernel", 5);
+    add(Step::kPass, "onesweep_kernel", 4 + 3 * pass, pass);
+  }
+}
 
 SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCount, uint64_t storageAddress) {
   SortPlan p;
+  p.keyValue = keyValue;
+  p.elementCount = elementCount;
   p.atomicRank = sorter->atomicRank.load(std::memory_order_relaxed);  // one answer for the whole sort
-  const bool adaptive = ForcedConfigIndex() < 0;
+  const bool adaptive = EnvKnobs().forcedConfig < 0;
   if (elementCount == 0) return p;
-  if (elementCount <= vrdx::kSmallSortMaxElements && adaptive && SmallSortEnabled()) {
+  // Small sorts: one workgroup, one launch, nothing but the caller's keys / values and the failure word touched (the
+  // general path costs six launches = 30-45 us however small N is).  Forcing a tile geometry (VRDX_TILE_CONFIG) also
+  // forces the general path, which is how the tests reach it at small sizes.
+  if (elementCount <= vrdx::kSmallSortMaxElements && adaptive && EnvKnobs().smallSort) {
     p.oneWorkgroup = true;
-    p.launches = 1;
     p.layout = vrdx::MakeLayout(elementCount, sorter->minStorageBufferOffsetAlignment, 0, storageAddress);  // (the failure word)
+    ListSteps(p);
     return p;
   }
   p.hybridCap = adaptive ? HybridCapacity(p.atomicRank, elementCount) : 0u;
@@ -346,9 +429,7 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
   p.tilePlan = PlanTiles(sorter, p.configIndex, keyValue, elementCount, p.atomicRank);
   // Block sums instead of the look-back chain: sorts of one round (PlanTiles) on the four-pass plan -- with a hybrid
   // plan recorded, launch 0 may rank by another byte than its pass index, which the block-sum form does not look up.
-  // VRDX_BLOCK_SUMS=0 keeps the classic look-back (measurements).
-  static const int blockSumsKnob = TuningKnob("VRDX_BLOCK_SUMS");
-  p.blockSums = p.tilePlan.blockSums && p.hybridCap == 0 && blockSumsKnob != 0;
+  p.blockSums = p.tilePlan.blockSums && p.hybridCap == 0 && EnvKnobs().blockSums;
   // keys per tile of the MSD plan's histogram and scatter: equal tiles that fill whole rounds of one workgroup per CU
   // (vrdx_layout.h); keys-only sorts by ten bits take two consecutive tiles per scatter workgroup (vrdx_kernels.hip)
   p.msdTileKeys = vrdx::MsdTileKeysFor(elementCount, (uint32_t)sorter->computeUnits, vrdx::kMsdMaxTiles,
@@ -376,14 +457,7 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
     p.layout = vrdx::MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, false, 0);
     p.fits = vrdx::LayoutFits(p.layout, elementCount);
   }
-  // The MSD plan's scatter launch is ALSO pass 0 of the fallback and its bucket launch pass 1 (one branch on the verdict, on
-  // the device; vrdx_kernels.hip, msd_scatter_or_pass0_kernel): only passes 2 and 3 remain as launches that return when the
-  // plan runs.  With buckets of the half-size kernel (512 threads; the passes' bodies need 1024) only the scatter launch has
-  // a second role.
-  // kernels: histogram + four passes (+ the eight-bit plan's bucket launch); the MSD plan: + spine (+ the half-size bucket
-  // kernel)
-  const uint32_t msdLaunches = p.msdBits == 0 ? 0u : p.msdCap == vrdx::kMsdHalfCap ? 2u : 1u;
-  p.launches = 1u + VRDX_PASSES + msdLaunches + (p.hybridCap != 0 ? 1u : 0u);
+  if (p.fits) ListSteps(p);
   return p;
 }
 
@@ -391,15 +465,37 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
 // calling thread's current device is put back afterwards.
 struct DeviceScope {
   int previous = -1;
+  bool onDevice = false;  // the calling thread's current device is the wanted one
   explicit DeviceScope(int wanted) {
     int current = -1;
-    if (hipGetDevice(&current) == hipSuccess && current != wanted && hipSetDevice(wanted) == hipSuccess)
+    if (hipGetDevice(&current) != hipSuccess) return;
+    onDevice = current == wanted;
+    if (!onDevice && hipSetDevice(wanted) == hipSuccess) {
       previous = current;
+      onDevice = true;
+    }
   }
   ~DeviceScope() {
     if (previous >= 0) (void)hipSetDevice(previous);
   }
 };
+
+// VRDX_RANK=ballot|atomic|auto, read whenever a sorter is created or re-checked: a process may set it between two sorters.
+bool RankModeIs(const char* mode) {
+  const char* env = std::getenv("VRDX_RANK");
+  return env != nullptr && std::strcmp(env, mode) == 0;
+}
+
+// One device word, copied behind everything enqueued on the stream so far (and then cleared in the same stream, if asked
+// to), and waited for: the copy targets the caller's variable, so this never returns while it may still be in flight.
+// All ones and false when anything failed.
+bool ReadDeviceWord(hipStream_t stream, uint32_t* address, uint32_t* word, bool clear = false) {
+  const bool copied = hipMemcpyAsync(word, address, sizeof(*word), hipMemcpyDeviceToHost, stream) == hipSuccess;
+  const bool cleared = copied && (!clear || hipMemsetAsync(address, 0, sizeof(*word), stream) == hipSuccess);
+  const bool ok = copied && hipStreamSynchronize(stream) == hipSuccess && cleared;
+  if (!ok) *word = 0xFFFFFFFFu;
+  return ok;
+}
 
 // Behind every 65536th sort: 8 workgroups repeat the lane-order check of vrdxCreateSorter (~20 us, never blocks; a
 // mismatch sets VRDX_HIP_STATUS_RANK_ORDER in the sorter's status word, which vrdxHipReadSorterStatus and
@@ -415,6 +511,168 @@ void MaybeRecheckOrder(VrdxSorter sorter, hipStream_t stream, bool atomicRank) {
     EnqueueCheck(sorter, "lds_order_check_kernel", vrdx::LaunchLdsOrderRecheck(stream, sorter->stickyStatus));
 }
 
+// The addresses a sort works on: the caller's arrays, the regions of its storage (vrdx_layout.h) and the sorter's two
+// device words.  values / valuesScratch: nullptr for a keys-only sort.
+struct SortBuffers {
+  uint8_t* storage;
+  uint32_t *keys, *values;
+  const uint32_t* countPtr;  // device-side element count (indirect) or nullptr
+  uint32_t *histogram, *status, *tickets, *failure, *planWord, *keysScratch, *valuesScratch;  // regions of the storage
+  uint32_t *stickyStatus, *declinedPlans;                                                     // the sorter's device words
+};
+
+SortBuffers ResolveBuffers(const VrdxSorter_T* sorter, const vrdx::StorageLayout& layout, uint8_t* storage, uint32_t* keys,
+                           uint32_t* values, const uint32_t* countPtr) {
+  const auto at = [storage](uint64_t offset) { return reinterpret_cast<uint32_t*>(storage + offset); };
+  SortBuffers b;
+  b.storage = storage;
+  b.keys = keys;
+  b.values = values;
+  b.countPtr = countPtr;
+  b.histogram = at(layout.histogramOffset);
+  b.status = at(layout.statusOffset);
+  b.tickets = at(layout.ticketOffset);
+  b.failure = at(layout.failureOffset);
+  b.planWord = at(VRDX_OFF_PLAN);
+  b.keysScratch = at(layout.inoutOffset);
+  b.valuesScratch = values != nullptr ? at(layout.valuesOffset) : nullptr;
+  b.stickyStatus = sorter->stickyStatus;
+  b.declinedPlans = sorter->declinedPlans;
+  return b;
+}
+
+// The arguments of pass `pass` of the four passes (also handed to the MSD plan's launches, whose second role they are).
+vrdx::OnesweepArgs PassArgs(const SortPlan& plan, const SortBuffers& b, uint32_t pass) {
+  vrdx::OnesweepArgs args;
+  // which pair of arrays the pass reads is settled on the device (vrdx_kernels.h); the reference
+  // switches in->out to out->in for pass 1, pass 3 (:417-427) and so do four ranking passes here
+  args.keysCaller = b.keys;
+  args.keysScratch = b.keysScratch;
+  args.valuesCaller = b.values;
+  args.valuesScratch = b.valuesScratch;
+  args.maxCount = plan.elementCount;
+  args.countPtr = b.countPtr;
+  args.histogramTable = b.histogram;
+  // region r of the two: [statusRows tile rows][blockRows block rows]
+  const size_t regionWords = (size_t)(plan.layout.regionBytes / sizeof(uint32_t));
+  const uint32_t statusRows = (uint32_t)plan.layout.statusRows;
+  uint32_t* const regionCur = b.status + (size_t)(pass & 1u) * regionWords;
+  uint32_t* const regionNext = b.status + (size_t)((pass + 1) & 1u) * regionWords;
+  args.statusCur = regionCur;
+  args.statusNext = pass + 1 < VRDX_PASSES ? regionNext : nullptr;
+  args.statusRows = statusRows;
+  args.blockCur = plan.blockSums ? regionCur + (size_t)statusRows * VRDX_RADIX : nullptr;
+  args.blockNext = plan.blockSums ? regionNext + (size_t)statusRows * VRDX_RADIX : nullptr;
+  args.blockRows = plan.blockSums ? (uint32_t)plan.layout.blockRows : 0u;
+  args.ticketCur = b.tickets + (pass & 1u);
+  args.ticketNext = b.tickets + ((pass + 1) & 1u);
+  args.failure = b.failure;
+  args.stickyFailure = b.stickyStatus;
+  args.pass = pass;
+  args.hybridCap = plan.hybridCap;
+  args.planWord = b.planWord;
+  args.spinLimit = vrdx::kSpinLimit;
+#ifdef VRDX_TESTING
+  if (EnvKnobs().testSpinLimit >= 0) args.spinLimit = (uint32_t)EnvKnobs().testSpinLimit;
+#endif
+  args.earlyValues = 1u;
+  args.planInFront = plan.msdBits != 0 ? 1u : 0u;  // the MSD plan in front may have taken the sort (verdict 3)
+  args.slots = plan.tilePlan.slots;
+  args.fullTiles = plan.tilePlan.fullTiles;
+  args.tailSlots = plan.tilePlan.tailSlots;
+  args.trace = nullptr;
+#ifdef VRDX_TRACE
+  args.trace = TraceBuffer(pass, plan.tilePlan.tiles);
+#endif
+  return args;
+}
+
+// The MSD plan's arguments: spine (prefixes over the tiles, bucket table, verdict), scatter by the window bits, one
+// workgroup per bucket; the histogram kernel takes the same structure.
+vrdx::MsdArgs MsdArgsOf(const SortPlan& plan, const SortBuffers& b) {
+  vrdx::MsdArgs m{};
+  m.keysCaller = b.keys;
+  m.keysScratch = b.keysScratch;
+  m.valuesCaller = b.values;
+  m.valuesScratch = b.valuesScratch;
+  m.maxCount = plan.elementCount;
+  m.countPtr = b.countPtr;
+  m.histogramTable = b.histogram;
+  m.tileCounts = reinterpret_cast<uint32_t*>(b.storage + plan.layout.msdCountsOffset);
+  m.bucketCount = reinterpret_cast<uint32_t*>(b.storage + plan.layout.msdBucketOffset);
+  m.bucketBase = m.bucketCount + ((size_t)1 << plan.msdBits);
+  m.overflowWord = reinterpret_cast<uint32_t*>(b.storage + VRDX_OFF_MSD_OVERFLOW);
+  m.planWord = b.planWord;
+  m.bits = plan.msdBits;
+  m.cap = plan.msdCap;
+  m.tiles = plan.msdTiles;
+  m.tileKeys = plan.msdTileKeys;
+  m.statusClear = b.storage + plan.layout.statusClearOffset;
+  m.statusVecs = (uint32_t)(plan.layout.statusClearBytes / 16u);
+  m.tickets = b.tickets;
+  m.declinedPlans = b.declinedPlans;
+  return m;
+}
+
+vrdx::BucketSortArgs BucketSortArgsOf(const SortPlan& plan, const SortBuffers& b) {
+  vrdx::BucketSortArgs a;
+  a.keysScratch = b.keysScratch;
+  a.keysCaller = b.keys;
+  a.valuesScratch = b.valuesScratch;
+  a.valuesCaller = b.values;
+  a.maxCount = plan.elementCount;
+  a.countPtr = b.countPtr;
+  a.histogramTable = b.histogram;
+  a.hybridCap = plan.hybridCap;
+  a.planWord = b.planWord;
+  return a;
+}
+
+// Grid of the fused histogram.  Every workgroup ends with up to 1024 global atomics on the same 1024 words, so few, long-lived
+// workgroups win for large inputs: one per CU and at least two groups of 16384 keys each (tools/hist_grid.sh, removed, last at
+// commit 3645810: 17.4 us with 256 workgroups against 21.1 us with 512 at N = 2^23; equal at 2^25).  Small inputs want the
+// opposite -- the kernel is one memory latency long, so up to 128 workgroups of at least 4096 keys share it: 6.9 instead of 9.7 us
+// at 2^18, 7.9 instead of 9.8 us at 2^20, same at 2^22.  The MSD plan's form takes whole tiles of up to 32768 keys per workgroup.
+uint32_t HistogramGrid(const VrdxSorter_T* sorter, const SortPlan& plan) {
+  const uint32_t cap = (uint32_t)sorter->computeUnits * vrdx::kHistWorkgroupsPerCu;
+  if (plan.msdBits != 0) return std::min<uint32_t>(plan.msdTiles, cap);
+  const uint32_t wide = std::min<uint32_t>(128u, vrdx::RoundUp(plan.elementCount, 4096u));
+  const uint32_t grid = std::max(vrdx::RoundUp(plan.elementCount, 2 * vrdx::kHistGroupKeys), wide);
+  return std::max(std::min(grid, cap), 1u);
+}
+
+// Enqueues one step of the list; the value the runtime returned for it goes to EnqueueCheck.
+hipError_t EnqueueStep(const VrdxSorter_T* sorter, hipStream_t stream, const SortPlan& plan, const SortBuffers& b,
+                       const vrdx::MsdArgs& msd, const SortStep& step) {
+  const bool keyValue = plan.keyValue, atomicRank = plan.atomicRank;
+  const uint32_t tiles = plan.tilePlan.tiles;
+  switch (step.what) {
+    case Step::kFill:
+      // Clear count / plan / failure word and the 4x256 global histogram (reference :382) in one fill of 4112 bytes;
+      // status region 0 is zeroed by the histogram kernel behind it (MSD plan: by the spine kernel).  With the MSD plan
+      // recorded the fill also covers the plan's bucket sizes, 4-8 KiB behind the table: its histogram kernel adds them up.
+      // Indirect: also copy the device-side count to where the reference keeps it (:368-379); the kernels themselves
+      // read it straight from the caller's buffer.  (Direct: the count travels as a kernel argument, the slot stays 0 --
+      // storage contents are scratch.)
+      EnqueueCheck(sorter, "hipMemsetAsync(state)", hipMemsetAsync(b.storage, 0, plan.layout.clearBytes, stream));
+      if (b.countPtr == nullptr) return hipSuccess;
+      return hipMemcpyAsync(b.storage + plan.layout.countOffset, b.countPtr, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    case Step::kHistogram:
+      return vrdx::LaunchHistogram(stream, HistogramGrid(sorter, plan), b.keys, plan.elementCount, b.countPtr, b.histogram, b.tickets,
+                                   b.storage + plan.layout.statusClearOffset, (uint32_t)plan.layout.statusClearBytes);
+    case Step::kHistogramMsd: return vrdx::LaunchHistogramMsd(stream, HistogramGrid(sorter, plan), msd);
+    case Step::kSpineMsd: return vrdx::LaunchSpineMsd(stream, msd);
+    case Step::kMsdScatterOrPass0: return vrdx::LaunchMsdFused(stream, false, keyValue, msd, PassArgs(plan, b, 0), tiles);
+    case Step::kMsdBucketsOrPass1: return vrdx::LaunchMsdFused(stream, true, keyValue, msd, PassArgs(plan, b, 1), tiles);
+    case Step::kBucketSortHalf: return vrdx::LaunchBucketSortHalf(stream, keyValue, msd);
+    case Step::kBucketSort: return vrdx::LaunchBucketSort(stream, keyValue, atomicRank, BucketSortArgsOf(plan, b));
+    case Step::kPass: return vrdx::LaunchOnesweep(stream, plan.configIndex, tiles, keyValue, atomicRank, PassArgs(plan, b, step.pass));
+    case Step::kSmallSort:
+      return vrdx::LaunchSmallSort(stream, atomicRank, b.keys, b.values, plan.elementCount, b.countPtr, b.failure);
+  }
+  return hipErrorInvalidValue;
+}
+
 // reference: gpuSort, src/vk_radix_sort.h.in:344-507
 void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount,
                 VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
@@ -422,7 +680,6 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
                 VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
                 uint32_t query) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
-  VrdxHipQueryPool* pool = reinterpret_cast<VrdxHipQueryPool*>(queryPool);
   const bool keyValue = valuesBuffer != nullptr;
   if (elementCount > VRDX_MAX_ELEMENTS) {
     // The reference's uint32 byte math wraps above 2^30 - 4 elements (src/vk_radix_sort.h.in:105-115): no storage
@@ -436,237 +693,28 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
 
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
   const SortPlan plan = PlanSort(sorter, keyValue, elementCount, (uint64_t)reinterpret_cast<uintptr_t>(storage));
-  const bool atomicRank = plan.atomicRank;
-  const uint32_t hybridCap = plan.hybridCap, msdBits = plan.msdBits, msdCap = plan.msdCap;
-  const int configIndex = plan.configIndex;
-  const vrdx::TilePlan& tilePlan = plan.tilePlan;
-  const bool blockSums = plan.blockSums;
-  const uint32_t msdTileKeys = plan.msdTileKeys, msdTiles = plan.msdTiles;
-  const vrdx::StorageLayout& layout = plan.layout;
-  uint32_t* const keys = reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset));
-  uint32_t* const values =
-      keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
-  const uint32_t* const countPtr =
-      indirectBuffer != nullptr
-          ? reinterpret_cast<const uint32_t*>(BufferAddress(indirectBuffer, indirectOffset))
-          : nullptr;
-
-  Stamp(pool, query + 0, stream);
-
-  if (elementCount == 0) {
-    // reference: zero partitions -> every dispatch is empty (:353,448,465,487)
-    for (uint32_t s = 1; s < 15; ++s) StampSame(pool, query + s, query + 0);
-    return;
-  }
-
-  // Small sorts: one workgroup, one launch, nothing but the caller's keys / values and the failure
-  // word touched (the
-  // general path below costs six launches = 30-45 us however small N is).  Forcing a tile geometry
-  // (VRDX_TILE_CONFIG) also forces the general path, which is how the tests reach it at small sizes.
-  if (plan.oneWorkgroup) {
-    for (uint32_t s = 1; s < 14; ++s) StampSame(pool, query + s, query + 0);
-    EnqueueCheck(sorter, "small_sort_kernel",
-                 vrdx::LaunchSmallSort(stream, atomicRank, keys, values, elementCount, countPtr,
-                                       reinterpret_cast<uint32_t*>(storage + layout.failureOffset)));
-    Stamp(pool, query + 14, stream);
-    return;
-  }
-
-  // (behind the empty sort and the one-workgroup sort above: neither touches the scratch arrays)
-  if (!plan.fits) {
-    // every slot of the timestamp contract is recorded, like in the empty sort: a caller that reads the pool after a
-    // refused sort must not wait on events that never were
-    for (uint32_t s = 1; s < 15; ++s) StampSame(pool, query + s, query + 0);
-    EnqueueCheck(sorter, "storage layout (status rows do not fit the reference's partition-histogram area)", hipErrorInvalidValue);
-    return;
-  }
-  uint32_t* const globalHistogram = reinterpret_cast<uint32_t*>(storage + layout.histogramOffset);
-  uint32_t* const status = reinterpret_cast<uint32_t*>(storage + layout.statusOffset);
-  uint32_t* const tickets = reinterpret_cast<uint32_t*>(storage + layout.ticketOffset);
-  uint32_t* const failure = reinterpret_cast<uint32_t*>(storage + layout.failureOffset);
-  uint32_t* const keysScratch = reinterpret_cast<uint32_t*>(storage + layout.inoutOffset);
-  uint32_t* const valuesScratch = reinterpret_cast<uint32_t*>(storage + layout.valuesOffset);
-  const uint32_t statusRows = (uint32_t)layout.statusRows;
-
-  // the MSD plan's arguments: spine (prefixes over the tiles, bucket table, verdict), scatter by the window bits, one
-  // workgroup per bucket; the histogram kernel takes the same structure
-  vrdx::MsdArgs m;
-  std::memset(&m, 0, sizeof(m));
-  if (msdBits != 0) {
-    m.keysCaller = keys;
-    m.keysScratch = keysScratch;
-    m.valuesCaller = keyValue ? values : nullptr;
-    m.valuesScratch = keyValue ? valuesScratch : nullptr;
-    m.maxCount = elementCount;
-    m.countPtr = countPtr;
-    m.histogramTable = globalHistogram;
-    m.tileCounts = reinterpret_cast<uint32_t*>(storage + layout.msdCountsOffset);
-    m.bucketCount = reinterpret_cast<uint32_t*>(storage + layout.msdBucketOffset);
-    m.bucketBase = m.bucketCount + ((size_t)1 << msdBits);
-    m.overflowWord = reinterpret_cast<uint32_t*>(storage + VRDX_OFF_MSD_OVERFLOW);
-    m.planWord = reinterpret_cast<uint32_t*>(storage + VRDX_OFF_PLAN);
-    m.bits = msdBits;
-    m.cap = msdCap;
-    m.tiles = msdTiles;
-    m.tileKeys = msdTileKeys;
-    m.statusClear = storage + layout.statusClearOffset;
-    m.statusVecs = (uint32_t)(layout.statusClearBytes / 16u);
-    m.tickets = tickets;
-    m.declinedPlans = sorter->declinedPlans;
+  const SortBuffers b = ResolveBuffers(
+      sorter, plan.layout, storage, reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset)),
+      keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr,
+      indirectBuffer != nullptr ? reinterpret_cast<const uint32_t*>(BufferAddress(indirectBuffer, indirectOffset)) : nullptr);
+  vrdx::MsdArgs msd{};
+  if (plan.msdBits != 0) {
+    msd = MsdArgsOf(plan, b);
     sorter->plansRecorded.fetch_add(1u, std::memory_order_relaxed);
   }
 
-  // Clear count / plan / failure word and the 4x256 global histogram (reference :382) in one fill of 4112 bytes; status
-  // region 0 is zeroed by the histogram kernel behind it.  Indirect: also copy the device-side count to where the reference keeps
-  // it (:368-379); the kernels themselves read it straight from the caller's buffer.  (Direct: the
-  // count travels as a kernel argument, the slot stays 0 -- storage contents are scratch.)
-  // (With the MSD plan recorded the fill also covers the plan's bucket sizes, 4-8 KiB behind the table: its histogram kernel
-  // adds them up.)
-  EnqueueCheck(sorter, "hipMemsetAsync(state)", hipMemsetAsync(storage, 0, layout.clearBytes, stream));
-  if (countPtr != nullptr)
-    EnqueueCheck(sorter, "hipMemcpyAsync(count)",
-                 hipMemcpyAsync(storage + layout.countOffset, countPtr, sizeof(uint32_t), hipMemcpyDeviceToDevice,
-                                stream));
-  Stamp(pool, query + 1, stream);
-
-  // upsweep of all four passes at once
-  {
-    // Every workgroup ends with up to 1024 global atomics on the same 1024 words, so few, long-lived
-    // workgroups win for large inputs: one per CU and at least two groups of 16384 keys each (tools/hist_grid.sh, removed,
-    // last at commit 3645810: 17.4 us with 256 workgroups against 21.1 us with 512 at N = 2^23; equal at 2^25).  Small inputs
-    // want the opposite -- the kernel is one memory latency long, so up to 128 workgroups of at least
-    // 4096 keys share it: 6.9 instead of 9.7 us at 2^18, 7.9 instead of 9.8 us at 2^20, same at 2^22.
-    uint32_t grid = vrdx::RoundUp(elementCount, 2 * vrdx::kHistGroupKeys);
-    const uint32_t wide = std::min<uint32_t>(128u, vrdx::RoundUp(elementCount, 4096u));
-    if (grid < wide) grid = wide;
-    const uint32_t cap = (uint32_t)sorter->computeUnits * vrdx::kHistWorkgroupsPerCu;
-    if (grid > cap) grid = cap;
-    if (grid == 0) grid = 1;
-    if (msdBits != 0) {
-      // the MSD plan's form: window-bits counts per tile of up to 32768 keys (a workgroup takes whole tiles); the spine
-      // kernel clears status region 0
-      grid = std::min<uint32_t>(msdTiles, cap);
-      EnqueueCheck(sorter, "histogram_msd_kernel", vrdx::LaunchHistogramMsd(stream, grid, m));
-    } else {
-      EnqueueCheck(sorter, "histogram_kernel",
-                   vrdx::LaunchHistogram(stream, grid, keys, elementCount, countPtr, globalHistogram, tickets,
-                                         storage + layout.statusClearOffset, (uint32_t)layout.statusClearBytes));
-    }
+  // Every slot of the timestamp contract is recorded whatever the plan -- also by the empty sort (reference: zero
+  // partitions -> every dispatch is empty, :353,448,465,487) and the refused one, neither of which has a step or touches
+  // the scratch arrays: a caller that reads the pool afterwards must not wait on events that never were.
+  StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
+  if (!plan.fits)
+    EnqueueCheck(sorter, "storage layout (status rows do not fit the reference's partition-histogram area)", hipErrorInvalidValue);
+  for (uint32_t i = 0; i < plan.stepCount; ++i) {
+    EnqueueCheck(sorter, plan.steps[i].name, EnqueueStep(sorter, stream, plan, b, msd, plan.steps[i]));
+    stamps.AdvanceTo(plan.steps[i].slot);
   }
-
-  const uint32_t tiles = tilePlan.tiles;
-  // the arguments of pass `pass` of the four passes (also handed to the MSD plan's launches, whose second role they are)
-  auto passArgs = [&](uint32_t pass) {
-    vrdx::OnesweepArgs args;
-    // which pair of arrays the pass reads is settled on the device (vrdx_kernels.h); the reference
-    // switches in->out to out->in for pass 1, pass 3 (:417-427) and so do four ranking passes here
-    args.keysCaller = keys;
-    args.keysScratch = keysScratch;
-    args.valuesCaller = keyValue ? values : nullptr;
-    args.valuesScratch = keyValue ? valuesScratch : nullptr;
-    args.maxCount = elementCount;
-    args.countPtr = countPtr;
-    args.histogramTable = globalHistogram;
-    // region r of the two: [statusRows tile rows][blockRows block rows]
-    const size_t regionWords = (size_t)(layout.regionBytes / sizeof(uint32_t));
-    uint32_t* const regionCur = status + (size_t)(pass & 1u) * regionWords;
-    uint32_t* const regionNext = status + (size_t)((pass + 1) & 1u) * regionWords;
-    args.statusCur = regionCur;
-    args.statusNext = pass + 1 < VRDX_PASSES ? regionNext : nullptr;
-    args.statusRows = statusRows;
-    args.blockCur = blockSums ? regionCur + (size_t)statusRows * VRDX_RADIX : nullptr;
-    args.blockNext = blockSums ? regionNext + (size_t)statusRows * VRDX_RADIX : nullptr;
-    args.blockRows = blockSums ? (uint32_t)layout.blockRows : 0u;
-    args.ticketCur = tickets + (pass & 1u);
-    args.ticketNext = tickets + ((pass + 1) & 1u);
-    args.failure = failure;
-    args.stickyFailure = sorter->stickyStatus;
-    args.pass = pass;
-    args.hybridCap = hybridCap;
-    args.planWord = reinterpret_cast<uint32_t*>(storage + VRDX_OFF_PLAN);
-    args.spinLimit = vrdx::kSpinLimit;
-#ifdef VRDX_TESTING
-    // test build only: VRDX_TEST_SPIN_LIMIT=0 makes the first look-back trip that has to wait give up, which is how
-    // tests/sticky_status_check.py sees the device-side failure path (failure word + the sorter's sticky word)
-    static const int testSpinLimit = TuningKnob("VRDX_TEST_SPIN_LIMIT");
-    if (testSpinLimit >= 0) args.spinLimit = (uint32_t)testSpinLimit;
-#endif
-    args.earlyValues = 1u;
-    args.planInFront = msdBits != 0 ? 1u : 0u;  // the MSD plan in front may have taken the sort (verdict 3)
-    args.slots = tilePlan.slots;
-    args.fullTiles = tilePlan.fullTiles;
-    args.tailSlots = tilePlan.tailSlots;
-    args.trace = nullptr;
-#ifdef VRDX_TRACE
-    args.trace = TraceBuffer(pass, tiles);
-#endif
-    return args;
-  };
-  // The MSD plan, recorded in front of the passes: spine (prefixes over the tiles, bucket table,
-  // verdict), scatter by the window bits -- also pass 0 --, one workgroup per bucket -- also pass 1, unless the buckets are
-  // half-size (PlanSort).  The passes behind return on the verdict word.
-  const bool halfBuckets = msdCap == vrdx::kMsdHalfCap;
-  if (msdBits != 0) {
-    // Timestamps: the plan's own three stages take the names they have in the reference -- slot 2 "upsweep" = the
-    // histogram, 3 "spine", 4 "downsweep" = the scatter -- and the bucket sorts are pass 1's "upsweep" (slot 5, like the
-    // eight-bit plan's); the four returning passes share the slots behind.
-    Stamp(pool, query + 2, stream);
-    EnqueueCheck(sorter, "spine_msd_kernel", vrdx::LaunchSpineMsd(stream, m));
-    Stamp(pool, query + 3, stream);
-    EnqueueCheck(sorter, "msd_scatter_or_pass0_kernel", vrdx::LaunchMsdFused(stream, false, keyValue, m, passArgs(0), tilePlan.tiles));
-    Stamp(pool, query + 4, stream);
-    if (halfBuckets)
-      EnqueueCheck(sorter, "bucket_sort2_half_kernel", vrdx::LaunchBucketSortHalf(stream, keyValue, m));
-    else
-      EnqueueCheck(sorter, "msd_buckets_or_pass1_kernel", vrdx::LaunchMsdFused(stream, true, keyValue, m, passArgs(1), tilePlan.tiles));
-    Stamp(pool, query + 5, stream);
-  }
-  for (uint32_t pass = 0; pass < VRDX_PASSES; ++pass) {
-    // "upsweep" of this pass: the fused histogram kernel for pass 0, nothing for the others -- the same
-    // point of the stream as the previous pass's "downsweep" stamp
-    if (msdBits != 0) {
-      // (slots 2-5 are the MSD plan's, above: the bucket launch is pass 1's "upsweep")
-      if (pass == 0) continue;  // ran (or returned) inside the scatter launch
-      if (pass == 1) {
-        StampSame(pool, query + 6, query + 5);
-        if (!halfBuckets) {  // ran (or returned) inside the bucket launch
-          StampSame(pool, query + 7, query + 5);
-          continue;
-        }
-      } else {
-        StampSame(pool, query + 2 + 3 * pass + 0, query + 2 + 3 * (pass - 1) + 2);
-        StampSame(pool, query + 2 + 3 * pass + 1, query + 2 + 3 * pass + 0);
-      }
-    } else if (pass == 0) {
-      Stamp(pool, query + 2, stream);
-    } else if (pass == 1 && hybridCap != 0) {
-      // the hybrid plan's second half, between launch 0 and launch 1 (which is empty when the plan applies): its time
-      // is this pass's "upsweep" slot
-      vrdx::BucketSortArgs b;
-      b.keysScratch = keysScratch;
-      b.keysCaller = keys;
-      b.valuesScratch = keyValue ? valuesScratch : nullptr;
-      b.valuesCaller = keyValue ? values : nullptr;
-      b.maxCount = elementCount;
-      b.countPtr = countPtr;
-      b.histogramTable = globalHistogram;
-      b.hybridCap = hybridCap;
-      b.planWord = reinterpret_cast<const uint32_t*>(storage + VRDX_OFF_PLAN);
-      EnqueueCheck(sorter, "bucket_sort_kernel", vrdx::LaunchBucketSort(stream, keyValue, atomicRank, b));
-      Stamp(pool, query + 2 + 3 * pass + 0, stream);
-    } else {
-      StampSame(pool, query + 2 + 3 * pass + 0, query + 2 + 3 * (pass - 1) + 2);
-    }
-    if (msdBits == 0) StampSame(pool, query + 2 + 3 * pass + 1, query + 2 + 3 * pass + 0);  // "spine" (fused into the look-back)
-
-    const vrdx::OnesweepArgs args = passArgs(pass);
-    EnqueueCheck(sorter, "onesweep_kernel",
-                 vrdx::LaunchOnesweep(stream, configIndex, tiles, keyValue, atomicRank, args));
-
-    Stamp(pool, query + 2 + 3 * pass + 2, stream);  // "downsweep"
-  }
-  StampSame(pool, query + 14, query + 13);  // end of the sort = end of the last pass
-  MaybeRecheckOrder(sorter, stream, atomicRank);
+  stamps.Finish();
+  if (plan.stepCount > 1) MaybeRecheckOrder(sorter, stream, plan.atomicRank);  // (the general path)
 }
 
 // The segmented sort (include/vk_radix_sort.h, vrdxHipCmdSortSegmented): a fill of the header and the two list counters, then
@@ -679,7 +727,6 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
                          VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                          VkQueryPool queryPool, uint32_t query) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
-  VrdxHipQueryPool* pool = reinterpret_cast<VrdxHipQueryPool*>(queryPool);
   const bool keyValue = valuesBuffer != nullptr;
   if (maxElementCount > VRDX_MAX_ELEMENTS) {
     // as in RecordSort: no storage requirement exists beyond it; segments ending behind the clamped bound are left alone
@@ -689,11 +736,11 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   }
   DeviceScope deviceScope(sorter->device);
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
-  Stamp(pool, query + 0, stream);
+  StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
   const vrdx::SegmentedLayout layout =
       vrdx::MakeSegmentedLayout(maxElementCount, sorter->minStorageBufferOffsetAlignment, (uint64_t)reinterpret_cast<uintptr_t>(storage));
   if (segmentCount == 0 || maxElementCount == 0 || !(keyValue ? layout.fitsKeyValue : layout.fitsKeys)) {
-    for (uint32_t s = 1; s < 15; ++s) StampSame(pool, query + s, query + 0);
+    stamps.Finish();
     if (segmentCount != 0 && maxElementCount != 0)  // (cannot happen for N >= 1: MakeSegmentedLayout fits every count)
       EnqueueCheck(sorter, "segmented storage layout", hipErrorInvalidValue);
     return;
@@ -719,7 +766,7 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   // header (plan verdict = VRDX_HIP_VERDICT_NONE, failure word) and the two list counters, in front of the first launch: a
   // one-wave kernel, not a memset (vrdx_kernels.hip, segmented_clear_kernel)
   EnqueueCheck(sorter, "segmented_clear_kernel", vrdx::LaunchSegmentedClear(stream, a));
-  Stamp(pool, query + 1, stream);
+  stamps.AdvanceTo(1);
   // one workgroup per segment up to 2^20 of them (a grid-stride loop beyond); the other two launches take their lists by
   // grid stride with at most as many workgroups as can be resident (the in-LDS form of 16384 keys and the large kernel
   // hold one or two workgroups per CU)
@@ -727,24 +774,21 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   EnqueueCheck(sorter, "segmented_small_kernel",
                vrdx::LaunchSegmented(stream, vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20), keyValue,
                                      atomicRank, a));
-  Stamp(pool, query + 2, stream);
+  stamps.AdvanceTo(2);
+  // (a launch that is not recorded leaves its slot to coincide with the one before)
   const uint32_t midGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.midCap), 2u * cus);
   if (midGrid != 0) {
     EnqueueCheck(sorter, "segmented_mid_kernel",
                  vrdx::LaunchSegmented(stream, vrdx::kSegmentMid, midGrid, keyValue, atomicRank, a));
-    Stamp(pool, query + 3, stream);
-  } else {
-    StampSame(pool, query + 3, query + 2);
+    stamps.AdvanceTo(3);
   }
   const uint32_t largeGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.largeCap), 2u * cus);
   if (largeGrid != 0) {
     EnqueueCheck(sorter, "segmented_large_kernel",
                  vrdx::LaunchSegmented(stream, vrdx::kSegmentLarge, largeGrid, keyValue, atomicRank, a));
-    Stamp(pool, query + 4, stream);
-  } else {
-    StampSame(pool, query + 4, query + 3);
+    stamps.AdvanceTo(4);
   }
-  for (uint32_t s = 5; s < 15; ++s) StampSame(pool, query + s, query + 4);
+  stamps.Finish();
   MaybeRecheckOrder(sorter, stream, atomicRank);
 }
 
@@ -775,18 +819,15 @@ VkResult vrdxCreateSorter(const VrdxSorterCreateInfo* pCreateInfo, VrdxSorter* p
   sorter->device = ordinal;
   sorter->computeUnits = prop.multiProcessorCount;
 
-  int previous = 0;
-  (void)hipGetDevice(&previous);
-  hipError_t e = hipSetDevice(ordinal);
-  if (e == hipSuccess) e = vrdx::PrepareKernels();
+  DeviceScope deviceScope(ordinal);
+  hipError_t e = deviceScope.onDevice ? vrdx::PrepareKernels() : hipErrorInvalidDevice;
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sorter->stickyStatus), 2 * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(sorter->stickyStatus, 0, 2 * sizeof(uint32_t));
   if (e == hipSuccess) sorter->declinedPlans = sorter->stickyStatus + 1;
   if (e == hipSuccess) {
     // Ranking mode: the single-atomic form needs a hardware property the ISA manual does not
     // promise, so it is verified here, once, on this very device; VRDX_RANK=ballot|atomic|auto.
-    const char* mode = std::getenv("VRDX_RANK");
-    if (mode != nullptr && std::strcmp(mode, "ballot") == 0) {
+    if (RankModeIs("ballot")) {
       sorter->atomicRank = false;
     } else {
       bool ordered = false;
@@ -797,11 +838,10 @@ VkResult vrdxCreateSorter(const VrdxSorterCreateInfo* pCreateInfo, VrdxSorter* p
         std::fprintf(stderr,
                      "vrdx-hip: LDS returning atomics are not lane-ordered on device %d: ranking with wave ballots "
                      "instead (same results, 1.2-1.7x the time)%s\n",
-                     ordinal, mode != nullptr && std::strcmp(mode, "atomic") == 0 ? "; VRDX_RANK=atomic refused" : "");
+                     ordinal, RankModeIs("atomic") ? "; VRDX_RANK=atomic refused" : "");
       }
     }
   }
-  (void)hipSetDevice(previous);
   if (e != hipSuccess) {
     if (sorter->stickyStatus != nullptr) (void)hipFree(sorter->stickyStatus);
     delete sorter;  // reference cleanup(): nothing half-built survives (:153-158)
@@ -822,16 +862,7 @@ void vrdxDestroySorter(VrdxSorter sorter) {
   // lane-order re-check failed or that the runtime refused an enqueue.  One line on stderr, only if something did.
   if (sorter->stickyStatus != nullptr) {
     // on the sorter's device, whatever the calling thread's current one is (one thread may own a sorter per GPU)
-    int previous = -1;
-    const bool switched = hipGetDevice(&previous) == hipSuccess && previous != sorter->device &&
-                          hipSetDevice(sorter->device) == hipSuccess;
-    struct Restore {
-      bool on;
-      int device;
-      ~Restore() {
-        if (on) (void)hipSetDevice(device);
-      }
-    } restore{switched, previous};
+    DeviceScope deviceScope(sorter->device);
     uint32_t word = 0;
     if (hipMemcpy(&word, sorter->stickyStatus, sizeof(word), hipMemcpyDeviceToHost) != hipSuccess) word = 0;  // (synchronises)
     if (sorter->enqueueFailed.load(std::memory_order_relaxed) != 0) word |= VRDX_HIP_STATUS_ENQUEUE_REFUSED;
@@ -919,29 +950,18 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
 VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {
   if (pQueryPool == nullptr || queryCount == 0) return VK_ERROR_INITIALIZATION_FAILED;
   VrdxHipQueryPool* pool = new (std::nothrow) VrdxHipQueryPool;
-  if (pool == nullptr) return VK_ERROR_OUT_OF_HOST_MEMORY;
-  pool->events = new (std::nothrow) hipEvent_t[queryCount];
-  pool->recorded = new (std::nothrow) uint8_t[queryCount];
-  pool->source = new (std::nothrow) uint32_t[queryCount];
-  if (pool->events == nullptr || pool->recorded == nullptr || pool->source == nullptr) {
-    delete[] pool->events;
-    delete[] pool->recorded;
-    delete[] pool->source;
-    delete pool;
-    return VK_ERROR_OUT_OF_HOST_MEMORY;
+  if (pool != nullptr) pool->slots = new (std::nothrow) VrdxHipQueryPool::Slot[queryCount];
+  VkResult result = pool != nullptr && pool->slots != nullptr ? VK_SUCCESS : VK_ERROR_OUT_OF_HOST_MEMORY;
+  for (uint32_t i = 0; result == VK_SUCCESS && i < queryCount; ++i) {
+    pool->slots[i].source = i;
+    if (hipEventCreate(&pool->slots[i].event) == hipSuccess)
+      pool->count = i + 1;
+    else
+      result = VK_ERROR_INITIALIZATION_FAILED;
   }
-  std::memset(pool->recorded, 0, queryCount);
-  for (uint32_t i = 0; i < queryCount; ++i) pool->source[i] = i;
-  for (uint32_t i = 0; i < queryCount; ++i) {
-    if (hipEventCreate(&pool->events[i]) != hipSuccess) {
-      for (uint32_t j = 0; j < i; ++j) (void)hipEventDestroy(pool->events[j]);
-      delete[] pool->events;
-      delete[] pool->recorded;
-      delete[] pool->source;
-      delete pool;
-      return VK_ERROR_INITIALIZATION_FAILED;
-    }
-    pool->count = i + 1;
+  if (result != VK_SUCCESS) {
+    vrdxHipDestroyQueryPool(reinterpret_cast<VkQueryPool>(pool));  // (whatever part of it exists)
+    return result;
   }
   *pQueryPool = reinterpret_cast<VkQueryPool>(pool);
   return VK_SUCCESS;
@@ -950,10 +970,8 @@ VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {
 void vrdxHipDestroyQueryPool(VkQueryPool queryPool) {
   VrdxHipQueryPool* pool = reinterpret_cast<VrdxHipQueryPool*>(queryPool);
   if (pool == nullptr) return;
-  for (uint32_t i = 0; i < pool->count; ++i) (void)hipEventDestroy(pool->events[i]);
-  delete[] pool->events;
-  delete[] pool->recorded;
-  delete[] pool->source;
+  for (uint32_t i = 0; i < pool->count; ++i) (void)hipEventDestroy(pool->slots[i].event);
+  delete[] pool->slots;
   delete pool;
 }
 
@@ -963,10 +981,10 @@ VkResult vrdxHipGetQueryPoolResults(VkQueryPool queryPool, uint32_t firstQuery, 
   if (pool == nullptr || pData == nullptr || firstQuery + queryCount > pool->count)
     return VK_ERROR_INITIALIZATION_FAILED;
   for (uint32_t i = 0; i < queryCount; ++i) {
-    if (!pool->recorded[firstQuery + i]) return VK_NOT_READY;
+    if (!pool->slots[firstQuery + i].recorded) return VK_NOT_READY;
     float ms = 0.0f;
-    const hipError_t e = hipEventElapsedTime(&ms, pool->events[pool->source[firstQuery]],
-                                             pool->events[pool->source[firstQuery + i]]);
+    const hipError_t e = hipEventElapsedTime(&ms, pool->slots[pool->slots[firstQuery].source].event,
+                                             pool->slots[pool->slots[firstQuery + i].source].event);
     if (e == hipErrorNotReady) return VK_NOT_READY;
     if (e != hipSuccess) return VK_ERROR_DEVICE_LOST;
     pData[i] = ms <= 0.0f ? 0ull : (uint64_t)((double)ms * 1.0e6 + 0.5);
@@ -976,24 +994,16 @@ VkResult vrdxHipGetQueryPoolResults(VkQueryPool queryPool, uint32_t firstQuery, 
 
 uint32_t vrdxHipReadStatus(VkCommandBuffer commandBuffer, VkBuffer storageBuffer,
                            VkDeviceSize storageOffset) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
-  uint32_t word = 0xFFFFFFFFu;
-  if (hipMemcpyAsync(&word, BufferAddress(storageBuffer, storageOffset) + VRDX_OFF_FAILURE,
-                     sizeof(word), hipMemcpyDeviceToHost, stream) != hipSuccess)
-    return 0xFFFFFFFFu;
-  if (hipStreamSynchronize(stream) != hipSuccess) return 0xFFFFFFFFu;
+  uint32_t word;
+  ReadDeviceWord(reinterpret_cast<hipStream_t>(commandBuffer),
+                 reinterpret_cast<uint32_t*>(BufferAddress(storageBuffer, storageOffset) + VRDX_OFF_FAILURE), &word);
   return word;
 }
 
 uint32_t vrdxHipReadSorterStatus(VrdxSorter sorter, VkCommandBuffer commandBuffer) {
   if (sorter == nullptr || sorter->stickyStatus == nullptr) return 0xFFFFFFFFu;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
-  uint32_t word = 0xFFFFFFFFu;
-  if (hipMemcpyAsync(&word, sorter->stickyStatus, sizeof(word), hipMemcpyDeviceToHost, stream) != hipSuccess)
-    return 0xFFFFFFFFu;
-  const hipError_t cleared = hipMemsetAsync(sorter->stickyStatus, 0, sizeof(word), stream);
-  // the copy above targets `word` on this stack frame: never return while it may still be in flight
-  if (hipStreamSynchronize(stream) != hipSuccess || cleared != hipSuccess) return 0xFFFFFFFFu;
+  uint32_t word;
+  if (!ReadDeviceWord(reinterpret_cast<hipStream_t>(commandBuffer), sorter->stickyStatus, &word, true)) return word;
   if (sorter->enqueueFailed.exchange(0u, std::memory_order_relaxed) != 0) word |= VRDX_HIP_STATUS_ENQUEUE_REFUSED;
   if (sorter->countClamped.exchange(0u, std::memory_order_relaxed) != 0) word |= VRDX_HIP_STATUS_COUNT_CLAMPED;
   return word;
@@ -1001,15 +1011,10 @@ uint32_t vrdxHipReadSorterStatus(VrdxSorter sorter, VkCommandBuffer commandBuffe
 
 VkResult vrdxHipRecheck(VrdxSorter sorter) {
   if (sorter == nullptr) return VK_ERROR_INITIALIZATION_FAILED;
-  const char* mode = std::getenv("VRDX_RANK");
-  if (mode != nullptr && std::strcmp(mode, "ballot") == 0) return VK_SUCCESS;  // nothing rests on the property
-  int previous = 0;
-  (void)hipGetDevice(&previous);
-  if (hipSetDevice(sorter->device) != hipSuccess) return VK_ERROR_DEVICE_LOST;
+  if (RankModeIs("ballot")) return VK_SUCCESS;  // nothing rests on the property
+  DeviceScope deviceScope(sorter->device);
   bool ordered = false;
-  const hipError_t e = vrdx::LdsOrderCheck(&ordered);
-  (void)hipSetDevice(previous);
-  if (e != hipSuccess) return VK_ERROR_DEVICE_LOST;
+  if (!deviceScope.onDevice || vrdx::LdsOrderCheck(&ordered) != hipSuccess) return VK_ERROR_DEVICE_LOST;
   const bool was = sorter->atomicRank.exchange(ordered, std::memory_order_relaxed);
   if (was && !ordered)
     std::fprintf(stderr,
@@ -1029,16 +1034,7 @@ uint64_t vrdxHipEventOverheadNs(VkCommandBuffer commandBuffer) {
   if ((stream != nullptr ? hipStreamGetDevice(stream, &device) : hipGetDevice(&device)) != hipSuccess ||
       hipDeviceGetAttribute(&clockKhz, hipDeviceAttributeWallClockRate, device) != hipSuccess || clockKhz <= 0)
     return result;
-  int previousDevice = -1;
-  const bool switchedDevice = hipGetDevice(&previousDevice) == hipSuccess && previousDevice != device &&
-                              hipSetDevice(device) == hipSuccess;
-  struct RestoreDevice {
-    bool on;
-    int device;
-    ~RestoreDevice() {
-      if (on) (void)hipSetDevice(device);
-    }
-  } restoreDevice{switchedDevice, previousDevice};
+  DeviceScope deviceScope(device);
   if (hipMalloc(reinterpret_cast<void**>(&stamps), 2 * sizeof(unsigned long long)) != hipSuccess) return result;
   if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
     // a kernel that demonstrably runs 40 us, right behind another one (a busy stream, like the passes of a sort)
@@ -1097,22 +1093,17 @@ void vrdxHipDescribePlan(VrdxSorter sorter, uint32_t elementCount, int keyValue,
 }
 
 uint32_t vrdxHipReadPlanVerdict(VkCommandBuffer commandBuffer, VkBuffer storageBuffer, VkDeviceSize storageOffset) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
-  uint32_t word = 0xFFFFFFFFu;
-  if (hipMemcpyAsync(&word, BufferAddress(storageBuffer, storageOffset) + VRDX_OFF_PLAN, sizeof(word), hipMemcpyDeviceToHost,
-                     stream) != hipSuccess)
-    return 0xFFFFFFFFu;
-  if (hipStreamSynchronize(stream) != hipSuccess) return 0xFFFFFFFFu;
+  uint32_t word;
+  if (!ReadDeviceWord(reinterpret_cast<hipStream_t>(commandBuffer),
+                      reinterpret_cast<uint32_t*>(BufferAddress(storageBuffer, storageOffset) + VRDX_OFF_PLAN), &word))
+    return word;
   return word & vrdx::kMsdVerdictMask;  // (the MSD plan's scatter also notes its window's shift there, bits 8-13)
 }
 
 VkResult vrdxHipReadPlanCounters(VrdxSorter sorter, VkCommandBuffer commandBuffer, uint32_t* pRecorded, uint32_t* pDeclined) {
   if (sorter == nullptr || sorter->declinedPlans == nullptr) return VK_ERROR_INITIALIZATION_FAILED;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
-  uint32_t declined = 0;
-  if (hipMemcpyAsync(&declined, sorter->declinedPlans, sizeof(declined), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-      hipStreamSynchronize(stream) != hipSuccess)  // (the copy targets this stack frame: never return while it may be in flight)
-    return VK_ERROR_DEVICE_LOST;
+  uint32_t declined;
+  if (!ReadDeviceWord(reinterpret_cast<hipStream_t>(commandBuffer), sorter->declinedPlans, &declined)) return VK_ERROR_DEVICE_LOST;
   if (pRecorded != nullptr) *pRecorded = sorter->plansRecorded.load(std::memory_order_relaxed);
   if (pDeclined != nullptr) *pDeclined = declined;
   return VK_SUCCESS;
@@ -1132,7 +1123,7 @@ const char* vrdxHipVersionString(void) {
       ConfigName(kv, kvName, sizeof(kvName));
       std::snprintf(text, sizeof(text), "vrdx-hip %d.%d.%d gfx950 tiles at 2^25: keys=%s key-value=%s%s",
                     VRDX_VERSION_MAJOR, VRDX_VERSION_MINOR, VRDX_VERSION_PATCH, kName, kvName,
-                    ForcedConfigIndex() >= 0 ? " (forced)" : " (size-adaptive)");
+                    EnvKnobs().forcedConfig >= 0 ? " (forced)" : " (size-adaptive)");
     }
   };
   static const Text once;
