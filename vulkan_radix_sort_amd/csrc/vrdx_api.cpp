@@ -589,7 +589,7 @@ vrdx::OnesweepArgs PassArgs(const SortPlan& plan, const SortBuffers& b, uint32_t
 
 // The MSD plan's arguments: spine (prefixes over the tiles, bucket table, verdict), scatter by the window bits, one
 // workgroup per bucket; the histogram kernel takes the same structure.
-vrdx::MsdArgs MsdArgsOf(const SortPlan& plan, const SortBuffers& b) {
+vrdx::MsdArgs MsdArgsOf(const VrdxSorter_T* sorter, const SortPlan& plan, const SortBuffers& b) {
   vrdx::MsdArgs m{};
   m.keysCaller = b.keys;
   m.keysScratch = b.keysScratch;
@@ -609,6 +609,7 @@ vrdx::MsdArgs MsdArgsOf(const SortPlan& plan, const SortBuffers& b) {
   m.tileKeys = plan.msdTileKeys;
   m.statusClear = b.storage + plan.layout.statusClearOffset;
   m.statusVecs = (uint32_t)(plan.layout.statusClearBytes / 16u);
+  m.plainTail = vrdx::MsdPlainTail((uint32_t)sorter->computeUnits, plan.elementCount, plan.msdBits);
   m.tickets = b.tickets;
   m.declinedPlans = b.declinedPlans;
   return m;
@@ -699,7 +700,7 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
       indirectBuffer != nullptr ? reinterpret_cast<const uint32_t*>(BufferAddress(indirectBuffer, indirectOffset)) : nullptr);
   vrdx::MsdArgs msd{};
   if (plan.msdBits != 0) {
-    msd = MsdArgsOf(plan, b);
+    msd = MsdArgsOf(sorter, plan, b);
     sorter->plansRecorded.fetch_add(1u, std::memory_order_relaxed);
   }
 

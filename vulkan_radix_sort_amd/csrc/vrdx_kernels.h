@@ -193,6 +193,10 @@ struct MsdArgs {
   // bandwidth to spare, instead of by the histogram kernel (which it cost 1.9 us at 2^25, round 4)
   void* statusClear;
   uint32_t statusVecs;
+  // The bucket launch's output policy (BucketSort2Body): keys-only sorts of more than kStreamingLoadsAbove elements write
+  // their buckets with non-temporal stores, all but the last plainTail buckets in the order the launch takes them (the
+  // highest indices), which keep plain stores.  MsdPlainTail (2^bits: every bucket plain); in the padding behind statusVecs: no argument moves.
+  uint32_t plainTail;
   uint32_t* tickets;           // zeroed by the histogram kernel
   uint32_t* declinedPlans;     // the sorter's counter of plans the device turned down (vrdxHipReadPlanCounters), or nullptr
 };
@@ -313,6 +317,19 @@ constexpr uint32_t MsdScatterGrid(uint32_t tiles, bool keyValue, uint32_t bits) 
 // 2^25, 175-178 instead of 179-180 key+value (tools/r06/bucket_grid.sh, bucket_grid2.sh, removed, last at commit
 // 3645810).  The half-size kernel (two workgroups per CU) keeps one: 47.7 against 47.0 us keys-only at 2^24 with two.
 constexpr uint32_t MsdBucketGrid(uint32_t bits, bool halfSizeKernel) { return halfSizeKernel ? 1u << bits : (1u << bits) / 2u; }
+
+// MsdArgs::plainTail: the buckets at the end of the bucket launch that keep plain output stores -- one per CU, the last
+// bucket each CU sorts.  Only their stores lie on the kernel's tail; the write-back of every earlier bucket streams out
+// behind the LDS work of the buckets that follow it on the same CU (vrdx_kernels.hip, BucketSort2Body).  Only from
+// kMsdStreamedOutputFrom = 2^25 elements, the size the rule was measured at, to the end of the ten-bit plan: buckets of
+// 32 K keys and more, whose LDS work is at least as long as the measured one.  Below it (18.1 M ... 2^25: buckets down to
+// 18 K keys, half the LDS work to hide a write-back behind) nothing was measured and every bucket keeps plain stores
+// (DESIGN.md 5.B).
+constexpr uint32_t kMsdStreamedOutputFrom = 1u << 25;
+constexpr uint32_t kMsdStreamedOutputUpTo = 36649984u;  // the ten-bit plan's last size (vrdx_api.cpp, MsdBits)
+constexpr uint32_t MsdPlainTail(uint32_t computeUnits, uint32_t elementCount, uint32_t bits) {
+  return elementCount >= kMsdStreamedOutputFrom && elementCount <= kMsdStreamedOutputUpTo ? computeUnits : 1u << bits;
+}
 
 // Runs the device self-check of the LDS same-address atomic ordering on the current device
 // (synchronous, ~1 ms).  *laneOrdered = true when returning atomics are served in lane order.

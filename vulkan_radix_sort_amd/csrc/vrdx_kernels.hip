@@ -2923,7 +2923,7 @@ __device__ __forceinline__ void ScatterMsdRole(const MsdArgs a) {
 // LDS: BucketSort2LdsWords (vrdx_kernels.h).
 
 template <uint32_t BITS, int KPT, bool KV, int THREADS = 1024>
-__device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_t bucket, const uint32_t below) {
+__device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_t bucket, const uint32_t below, const bool streamOut) {
   constexpr int WAVES = THREADS / 64;
   static_assert(THREADS == 1024 || THREADS == 512, "one or two words of a counter row per thread");
   constexpr uint32_t TILE = THREADS * KPT;
@@ -3043,10 +3043,11 @@ __device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_
   // size of the Infinity Cache, and left dirty in the caches it is written back under the next kernel's reads -- the next
   // sort's histogram in a batch of sorts.  Measured (tools/r05/out_nt2.sh, removed, last at commit 3645810; bench.py's loop
   // of 20 sorts): key+value 82 -> 86.3 GItems/s at 2^25, a single sort on its own unchanged (0.4225 / 0.4239 ms).
-  // Keys-only sorts keep plain stores: their loop gains the same 4 % but a single sort LOSES 4 % (its last kernel then
-  // waits for its own write-back), and a consumer of 128 MiB of sorted keys finds a good part of them in the cache.  (The
-  // empty asm statements keep the two kinds of store apart, see LoadTile.)
-  if (KV && a.maxCount > kStreamingLoadsAbove) {
+  // Keys-only sorts with ALL their stores non-temporal gain the same 4 % in the loop, but a single sort LOSES 4 % (its last
+  // kernel then waits for its own write-back): for them the caller decides per bucket (BucketSort2Body; streamOut is
+  // wave-uniform and not looked at by the key+value form, whose code stays what it was).
+  // (The empty asm statements keep the two kinds of store apart, see LoadTile.)
+  if (KV ? a.maxCount > kStreamingLoadsAbove : streamOut) {
     asm volatile("; non-temporal output" ::: "memory");
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
@@ -3080,8 +3081,20 @@ __device__ __forceinline__ void BucketSort2Body(const MsdArgs a, const uint32_t 
   const uint32_t verdict = *a.planWord;
   if ((verdict & kMsdVerdictMask) != kMsdVerdictRuns) return;  // the plan does not apply (the four passes are running), or nothing needs sorting
   const uint32_t below = (verdict >> kMsdShiftShift) & kMsdShiftMask;
+  // The output policy of KEYS-ONLY sorts, per bucket (key+value: BucketSort2Bucket).  The full-size kernel by ten bits, above
+  // kStreamingLoadsAbove elements: a CU sorts four buckets one after the other (512 workgroups of two), and only the LAST
+  // one's stores lie on the kernel's tail, where a single sort waits for their write-back.  The buckets in front of it are
+  // followed by the LDS work of the next bucket on the same CU, behind which a streamed write-back disappears, so they take
+  // non-temporal stores and leave nothing dirty for the next kernel's reads to push out; the last a.plainTail buckets in the
+  // launch's order (the highest indices) keep plain stores.  The host sets plainTail (vrdx_kernels.h, MsdPlainTail): one
+  // bucket per CU in the range of sizes where this measured a gain, every bucket outside it.
+  // (The half-size kernel and the eleven-bit plan keep plain stores throughout: not measured with this rule.)
+  uint32_t streamedBuckets = 0u;
+  if constexpr (!KV && THREADS == 1024 && BITS == 10)
+    if (a.maxCount > kStreamingLoadsAbove) streamedBuckets = (1u << BITS) - min(a.plainTail, 1u << BITS);
 #pragma unroll 1
-  for (uint32_t bucket = blockIdx.x; bucket < (1u << BITS); bucket += workgroups) BucketSort2Bucket<BITS, KPT, KV, THREADS>(a, bucket, below);
+  for (uint32_t bucket = blockIdx.x; bucket < (1u << BITS); bucket += workgroups)
+    BucketSort2Bucket<BITS, KPT, KV, THREADS>(a, bucket, below, bucket < streamedBuckets);
 }
 
 // Buckets of no more than 18432 elements (sorts of up to 18.1 M elements by ten bits): workgroups of 512 threads and
