@@ -219,6 +219,56 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
                                      VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                                      VkQueryPool queryPool, uint32_t query);
 
+/**
+ * 64-bit keys (not part of the reference API): elementCount uint64 keys, with or without one uint32 value each.
+ *
+ * Keys and values: keysBuffer + keysOffset holds uint64 keys and is a multiple of 8; valuesBuffer + valuesOffset holds uint32
+ * values and is a multiple of 4.
+ * Order: ascending as unsigned 64-bit, stable; results land back in the caller's arrays.  Elements from elementCount on are
+ * never touched, and nothing is written outside the storage requirement.
+ * How: two of this library's stable 32-bit key+value sorts, the low words first and the high words second, each carrying the
+ * other word (keys-only) or the element's index (key+value) as its value -- four trips through memory where the plans of
+ * vrdxHipDescribePlan(elementCount, 1) take two each, and a word that is the same in every key costs next to nothing.
+ *   keys-only   split (A = low words, B = high words); sort (A, B); sort (B, A); merge (keys = B << 32 | A)
+ *   key+value   split (A = low words, I = 0, 1, 2, ...); sort (A, I); gather (A = high word of keys[I]); sort (A, I);
+ *               permute (T = A << 32 | low word of keys[I], A = values[I]); copy back (keys = T, values = A)
+ * Storage: vrdxHipGetSorter64[KeyValue]StorageRequirements(maxElementCount); storageOffset is a multiple of 16 as for every
+ * sort, one sort in flight per storage.  It is vrdxGetSorterKeyValueStorageRequirements(maxElementCount) bytes, used by
+ * both inner sorts, then up to 112 bytes of padding, then the word arrays on 128-byte lines: A and B / I (4 bytes per
+ * element each), and for key+value T (8 bytes per element).  On top of the 32-bit key+value requirement that is 8 bytes per
+ * element keys-only and 16 bytes per element key+value.
+ * Recording: the call never blocks and reads no data on the host; with a NULL query pool it is legal inside a stream capture,
+ * and the captured graph may be replayed on other data of the same count.
+ * Counts: elementCount == 0 records nothing but the timestamps; elementCount > 2^30 - 4 is clamped
+ * (VRDX_HIP_STATUS_COUNT_CLAMPED).
+ * Status: the inner sorts' header is the front of this storage, and each inner sort clears it, so vrdxHipReadStatus and
+ * vrdxHipReadPlanVerdict on this storage report the SECOND inner sort (the high words).  vrdxHipReadSorterStatus covers both,
+ * as it does for any two sorts.
+ *
+ * Timestamps (all 15 slots recorded; ts[14] - ts[0] is the call; the inner sorts are recorded without a pool):
+ *   [0,1] the split
+ *   [1,2] the first sort (low words)
+ *   [2,3] key+value: the gather of the high words (keys-only: 3 == 2)
+ *   [3,4] the second sort (high words)
+ *   [4,5] keys-only: the merge; key+value: the permutation of keys and values into the storage
+ *   [5,6] key+value: the copy back into the caller's arrays (keys-only: 6 == 5)
+ *   slots 7 ... 14 coincide with slot 6
+ *
+ * Out of scope, each left to the caller: indirect counts (no vrdxHipCmdSort64Indirect); segmented 64-bit sorts; signed and
+ * floating-point orders (flip the sign bit, or the IEEE bits, before and after); descending order (complement the keys); values
+ * wider than 32 bits (sort an index as the value and gather by it).
+ */
+void vrdxHipGetSorter64StorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
+                                           VrdxSorterStorageRequirements* requirements);
+void vrdxHipGetSorter64KeyValueStorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
+                                                   VrdxSorterStorageRequirements* requirements);
+void vrdxHipCmdSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                      VkDeviceSize keysOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                      uint32_t query);
+void vrdxHipCmdSort64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                              VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                              VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+
 /* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves
  * (vkCreateQueryPool / vkGetQueryPoolResults, bench/vulkan_benchmark.cc:195-198,318-321).

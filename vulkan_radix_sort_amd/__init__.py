@@ -33,6 +33,7 @@ from .api import (  # noqa: F401
     VERDICT_MSD_SORTED,
 )
 from .segmented import sort_segments  # noqa: F401
+from .sort64 import sort64  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -58,4 +59,5 @@ __all__ = [
     "VERDICT_MSD_RUNS",
     "VERDICT_MSD_SORTED",
     "sort_segments",
+    "sort64",
 ]

@@ -15,6 +15,9 @@ reference (C++ / Vulkan)                        here
 ``vrdxCmdSortKeyValueIndirect``                 ``Sorter.cmd_sort_key_value_indirect(...)``
 ``vrdxHipCmdSortSegmented`` (HIP only)          ``Sorter.cmd_sort_segmented(...)``
 ``vrdxHipCmdSortSegmentedKeyValue`` (HIP only)  ``Sorter.cmd_sort_segmented_key_value(...)``
+``vrdxHipGetSorter64[KeyValue]Storage...``      ``Sorter.storage_requirements64(n, key_value=False)``
+``vrdxHipCmdSort64`` (HIP only)                 ``Sorter.cmd_sort64(...)``
+``vrdxHipCmdSort64KeyValue`` (HIP only)         ``Sorter.cmd_sort64_key_value(...)``
 =============================================  ==============================================
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
@@ -61,6 +64,11 @@ EXPORTED_SYMBOLS = (
     # many independent arrays in one call
     "vrdxHipCmdSortSegmented",
     "vrdxHipCmdSortSegmentedKeyValue",
+    # uint64 keys
+    "vrdxHipGetSorter64StorageRequirements",
+    "vrdxHipGetSorter64KeyValueStorageRequirements",
+    "vrdxHipCmdSort64",
+    "vrdxHipCmdSort64KeyValue",
 )
 
 # bits of vrdxHipReadSorterStatus (include/vk_radix_sort.h)
@@ -159,7 +167,8 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxCreateSorter.argtypes = [ctypes.POINTER(VrdxSorterCreateInfo), ctypes.POINTER(vp)]
     lib.vrdxDestroySorter.restype = None
     lib.vrdxDestroySorter.argtypes = [vp]
-    for name in ("vrdxGetSorterStorageRequirements", "vrdxGetSorterKeyValueStorageRequirements"):
+    for name in ("vrdxGetSorterStorageRequirements", "vrdxGetSorterKeyValueStorageRequirements",
+                 "vrdxHipGetSorter64StorageRequirements", "vrdxHipGetSorter64KeyValueStorageRequirements"):
         fn = getattr(lib, name)
         fn.restype = None
         fn.argtypes = [vp, u32, ctypes.POINTER(VrdxSorterStorageRequirements)]
@@ -175,6 +184,10 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxHipCmdSortSegmented.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u32]
     lib.vrdxHipCmdSortSegmentedKeyValue.restype = None
     lib.vrdxHipCmdSortSegmentedKeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
+    lib.vrdxHipCmdSort64.restype = None
+    lib.vrdxHipCmdSort64.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u32]
+    lib.vrdxHipCmdSort64KeyValue.restype = None
+    lib.vrdxHipCmdSort64KeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
     lib.vrdxHipCreateQueryPool.argtypes = [u32, ctypes.POINTER(vp)]
     lib.vrdxHipDestroyQueryPool.restype = None
@@ -298,6 +311,14 @@ class Sorter:
         self._lib.vrdxGetSorterKeyValueStorageRequirements(self.handle, max_element_count, ctypes.byref(req))
         return req
 
+    def storage_requirements64(self, max_element_count: int, key_value: bool = False) -> VrdxSorterStorageRequirements:
+        """``vrdxHipGetSorter64[KeyValue]StorageRequirements``: the storage of a sort of uint64 keys."""
+        req = VrdxSorterStorageRequirements()
+        fn = (self._lib.vrdxHipGetSorter64KeyValueStorageRequirements if key_value
+              else self._lib.vrdxHipGetSorter64StorageRequirements)
+        fn(self.handle, max_element_count, ctypes.byref(req))
+        return req
+
     # -- recording --------------------------------------------------------------------------
     def cmd_sort(self, command_buffer, element_count, keys, keys_offset, storage, storage_offset,
                  query_pool=None, query=0):
@@ -340,6 +361,21 @@ class Sorter:
                                                   _handle(offsets), offsets_offset, _handle(keys), keys_offset,
                                                   _handle(values), values_offset, _handle(storage), storage_offset,
                                                   _pool(query_pool), query)
+
+    def cmd_sort64(self, command_buffer, element_count, keys, keys_offset, storage, storage_offset, query_pool=None,
+                   query=0):
+        """``vrdxHipCmdSort64``: uint64 keys (``keys_offset`` a multiple of 8), ascending and stable, in place; storage of
+        ``storage_requirements64(n)`` bytes."""
+        self._lib.vrdxHipCmdSort64(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
+                                   _handle(storage), storage_offset, _pool(query_pool), query)
+
+    def cmd_sort64_key_value(self, command_buffer, element_count, keys, keys_offset, values, values_offset, storage,
+                             storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSort64KeyValue``: the same with one uint32 value per key; storage of
+        ``storage_requirements64(n, key_value=True)`` bytes."""
+        self._lib.vrdxHipCmdSort64KeyValue(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
+                                           _handle(values), values_offset, _handle(storage), storage_offset,
+                                           _pool(query_pool), query)
 
     # -- diagnostics ------------------------------------------------------------------------
     def read_status(self, command_buffer, storage, storage_offset=0) -> int:

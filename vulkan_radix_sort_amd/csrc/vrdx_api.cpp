@@ -793,6 +793,66 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   MaybeRecheckOrder(sorter, stream, atomicRank);
 }
 
+// The 64-bit sorts (include/vk_radix_sort.h, vrdxHipCmdSort64[KeyValue]): two stable 32-bit key+value sorts, low words first
+// and high words second, each through RecordSort on word arrays inside the storage (vrdx_layout.h, MakeSort64Layout), with
+// the streaming kernels of vrdx_kernels.hip ("64-bit keys") around them:
+//   keys-only   split (A = lo, B = hi) | sort (A, B) | sort (B, A) | merge (keys = B << 32 | A)
+//   key+value   split (A = lo, I = iota) | sort (A, I) | gather (A = hi of keys[I]) | sort (A, I) |
+//               permute (T = A << 32 | lo of keys[I], A = values[I]) | copy back (keys = T, values = A)
+// The inner sorts are recorded without a query pool; each step of this list ends one slot.  Nothing is decided from the
+// data on the host, so a captured call can be replayed on other data of the same count.
+void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                  VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer,
+                  VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
+  const bool keyValue = valuesBuffer != nullptr;
+  if (elementCount > VRDX_MAX_ELEMENTS) {
+    // as in RecordSort: no storage requirement exists beyond it, the tail is left alone
+    elementCount = VRDX_MAX_ELEMENTS;
+    sorter->countClamped.store(1u, std::memory_order_relaxed);
+  }
+  DeviceScope deviceScope(sorter->device);
+  StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
+  if (elementCount == 0) {
+    stamps.Finish();
+    return;
+  }
+  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
+  const vrdx::Sort64Layout layout = vrdx::MakeSort64Layout(elementCount, sorter->minStorageBufferOffsetAlignment,
+                                                           (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  uint64_t* const keys = reinterpret_cast<uint64_t*>(BufferAddress(keysBuffer, keysOffset));
+  uint32_t* const values = keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
+  uint32_t* const lo = reinterpret_cast<uint32_t*>(storage + layout.loOffset);
+  uint32_t* const other = reinterpret_cast<uint32_t*>(storage + layout.otherOffset);
+  uint64_t* const keysTemp = reinterpret_cast<uint64_t*>(storage + layout.keysTempOffset);
+  // an inner sort: the words at `sortKeys` with those at `payload` as their values, in the storage's front part
+  auto sortWords = [&](uint64_t sortKeys, uint64_t payload) {
+    RecordSort(commandBuffer, sorter, elementCount, nullptr, 0, storageBuffer, storageOffset + sortKeys, storageBuffer,
+               storageOffset + payload, storageBuffer, storageOffset, nullptr, 0);
+  };
+
+  EnqueueCheck(sorter, "split64_kernel", vrdx::LaunchSplit64(stream, keyValue, keys, lo, other, elementCount));
+  stamps.AdvanceTo(1);
+  sortWords(layout.loOffset, layout.otherOffset);
+  stamps.AdvanceTo(2);
+  if (keyValue) {
+    EnqueueCheck(sorter, "gather_hi64_kernel", vrdx::LaunchGatherHi64(stream, keys, other, lo, elementCount));
+    stamps.AdvanceTo(3);
+    sortWords(layout.loOffset, layout.otherOffset);
+    stamps.AdvanceTo(4);
+    EnqueueCheck(sorter, "permute64_kernel", vrdx::LaunchPermute64(stream, keys, values, other, lo, keysTemp, elementCount));
+    stamps.AdvanceTo(5);
+    EnqueueCheck(sorter, "copy_back64_kernel", vrdx::LaunchCopyBack64(stream, keys, values, keysTemp, lo, elementCount));
+    stamps.AdvanceTo(6);
+  } else {
+    sortWords(layout.otherOffset, layout.loOffset);  // (slot 3 coincides with slot 2: no step between the sorts)
+    stamps.AdvanceTo(4);
+    EnqueueCheck(sorter, "merge64_kernel", vrdx::LaunchMerge64(stream, keys, lo, other, elementCount));
+    stamps.AdvanceTo(5);
+  }
+  stamps.Finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -946,6 +1006,32 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
                                      VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
                       valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipGetSorter64StorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
+                                           VrdxSorterStorageRequirements* requirements) {
+  requirements->size = vrdx::MakeSort64Layout(maxElementCount, sorter->minStorageBufferOffsetAlignment).keysOnlySize;
+  requirements->usage = VK_BUFFER_USAGE_STORAGE_BUFFER_BIT | VK_BUFFER_USAGE_TRANSFER_DST_BIT;
+}
+
+void vrdxHipGetSorter64KeyValueStorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
+                                                   VrdxSorterStorageRequirements* requirements) {
+  requirements->size = vrdx::MakeSort64Layout(maxElementCount, sorter->minStorageBufferOffsetAlignment).keyValueSize;
+  requirements->usage = VK_BUFFER_USAGE_STORAGE_BUFFER_BIT | VK_BUFFER_USAGE_TRANSFER_DST_BIT;
+}
+
+void vrdxHipCmdSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                      VkDeviceSize keysOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                      uint32_t query) {
+  RecordSort64(commandBuffer, sorter, elementCount, keysBuffer, keysOffset, nullptr, 0, storageBuffer, storageOffset,
+               queryPool, query);
+}
+
+void vrdxHipCmdSort64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                              VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                              VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSort64(commandBuffer, sorter, elementCount, keysBuffer, keysOffset, valuesBuffer, valuesOffset, storageBuffer,
+               storageOffset, queryPool, query);
 }
 
 VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {

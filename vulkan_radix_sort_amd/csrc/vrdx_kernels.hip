@@ -3287,6 +3287,130 @@ __global__ __launch_bounds__(64) void spin_kernel(unsigned long long* out, uint3
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// 64-bit keys (vrdxHipCmdSort64[KeyValue]): the streaming steps around the two stable 32-bit key+value sorts
+// ---------------------------------------------------------------------------------------------
+// A 64-bit sort is two stable 32-bit sorts, low words first and high words second (RecordSort64 in vrdx_api.cpp); these
+// kernels take the keys apart in front of them and put them together behind them.  Every thread owns four consecutive
+// elements (kSort64Threads x 4 per workgroup): the caller's keys move as two 16-byte accesses of two keys each, which need
+// the keys' own 8-byte alignment only, the caller's values as one that needs 4-byte alignment, and the word arrays inside
+// the storage (128-byte aligned, MakeSort64Layout) as one aligned 16-byte access.  The last n mod 4 elements go one by
+// one, so nothing from element n on is read or written.  Gathers read ONE word of a key: the other word of its 8 bytes
+// comes along in the same sector for nothing, but would cost registers.
+typedef u32x4 u32x4_a8 __attribute__((aligned(8)));  // two uint64 keys {lo, hi, lo, hi}: 16-byte access, 8-byte aligned
+
+__device__ __forceinline__ uint32_t Sort64First(uint32_t n, bool* whole) {
+  const uint32_t i = (blockIdx.x * kSort64Threads + threadIdx.x) * 4u;  // (n <= 2^30 - 4: no wrap)
+  *whole = i + 4u <= n;
+  return i;
+}
+
+// lo[i] = low word; other[i] = high word, or i itself (IOTA: the index the key+value form sorts along)
+template <bool IOTA>
+__global__ __launch_bounds__(kSort64Threads) void split64_kernel(const uint64_t* __restrict__ keys, uint32_t* __restrict__ lo,
+                                                                 uint32_t* __restrict__ other, uint32_t n) {
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4_a8* const pairs = reinterpret_cast<const u32x4_a8*>(keys + i);
+    const u32x4 a = pairs[0], b = pairs[1];
+    *reinterpret_cast<u32x4*>(lo + i) = u32x4{a.x, a.z, b.x, b.z};
+    *reinterpret_cast<u32x4*>(other + i) = IOTA ? u32x4{i, i + 1u, i + 2u, i + 3u} : u32x4{a.y, a.w, b.y, b.w};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    const uint64_t k = keys[j];
+    lo[j] = (uint32_t)k;
+    other[j] = IOTA ? j : (uint32_t)(k >> 32);
+  }
+}
+
+// keys[i] = hi[i] << 32 | lo[i]
+__global__ __launch_bounds__(kSort64Threads) void merge64_kernel(uint64_t* __restrict__ keys, const uint32_t* __restrict__ lo,
+                                                                 const uint32_t* __restrict__ hi, uint32_t n) {
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4 l = *reinterpret_cast<const u32x4*>(lo + i), h = *reinterpret_cast<const u32x4*>(hi + i);
+    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(keys + i);
+    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
+    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) keys[j] = (uint64_t)hi[j] << 32 | lo[j];
+}
+
+// hi[j] = high word of keys[index[j]]: the keys of the second sort, in the order the first one left
+__global__ __launch_bounds__(kSort64Threads) void gather_hi64_kernel(const uint64_t* __restrict__ keys,
+                                                                     const uint32_t* __restrict__ index,
+                                                                     uint32_t* __restrict__ hi, uint32_t n) {
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
+  if (whole) {
+    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
+    *reinterpret_cast<u32x4*>(hi + i) = u32x4{words[2ull * at.x + 1u], words[2ull * at.y + 1u], words[2ull * at.z + 1u],
+                                              words[2ull * at.w + 1u]};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) hi[j] = words[2ull * index[j] + 1u];
+}
+
+// keysOut[j] = hiThenValues[j] << 32 | low word of keys[index[j]], then hiThenValues[j] = values[index[j]]: the sorted high
+// words are what the second sort left as its keys, and their array takes the permuted values once they are read (every
+// element of it is read and written by the same thread)
+__global__ __launch_bounds__(kSort64Threads) void permute64_kernel(const uint64_t* __restrict__ keys,
+                                                                   const uint32_t* __restrict__ values,
+                                                                   const uint32_t* __restrict__ index,
+                                                                   uint32_t* __restrict__ hiThenValues,
+                                                                   uint64_t* __restrict__ keysOut, uint32_t n) {
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
+  if (whole) {
+    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
+    const u32x4 h = *reinterpret_cast<const u32x4*>(hiThenValues + i);
+    const u32x4 l = u32x4{words[2ull * at.x], words[2ull * at.y], words[2ull * at.z], words[2ull * at.w]};
+    const u32x4 v = u32x4{values[at.x], values[at.y], values[at.z], values[at.w]};
+    u32x4* const pairs = reinterpret_cast<u32x4*>(keysOut + i);
+    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
+    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
+    *reinterpret_cast<u32x4*>(hiThenValues + i) = v;
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    const uint32_t at = index[j];
+    keysOut[j] = (uint64_t)hiThenValues[j] << 32 | words[2ull * at];
+    hiThenValues[j] = values[at];
+  }
+}
+
+// keys[i] = keysIn[i], values[i] = valuesIn[i]: the permuted arrays back into the caller's
+__global__ __launch_bounds__(kSort64Threads) void copy_back64_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ values,
+                                                                     const uint64_t* __restrict__ keysIn,
+                                                                     const uint32_t* __restrict__ valuesIn, uint32_t n) {
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4* const in = reinterpret_cast<const u32x4*>(keysIn + i);
+    const u32x4 a = in[0], b = in[1], v = *reinterpret_cast<const u32x4*>(valuesIn + i);
+    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(keys + i);
+    pairs[0] = a;
+    pairs[1] = b;
+    *reinterpret_cast<u32x4_a4*>(values + i) = v;
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    keys[j] = keysIn[j];
+    values[j] = valuesIn[j];
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs

@@ -202,6 +202,36 @@ static inline SegmentedLayout MakeSegmentedLayout(uint32_t maxElementCount, uint
   return s;
 }
 
+// The 64-bit sorts' storage (vrdxHipCmdSort64[KeyValue]; RecordSort64 in vrdx_api.cpp): the unchanged 32-bit key+value
+// storage for N first -- both inner sorts use it, so its header is the 64-bit storage's header -- and behind it the word
+// arrays, each on a 128-byte line of the absolute address:
+//   [0, innerSize)                     vrdxGetSorterKeyValueStorageRequirements(N), carved by MakeLayout as ever
+//   loOffset     (128-byte aligned)    uint32 A[N]: the keys of both inner sorts (low words, then high words); key+value:
+//                                      the permuted values at the very end
+//   otherOffset  = loOffset + Align(4 N, 128)     uint32 B[N] (keys-only: the other word) | I[N] (key+value: the index)
+//   keysTempOffset = otherOffset + Align(4 N, 128) key+value only: uint64[N], the permuted keys before they are copied back
+// The sizes do not depend on the address: the pad in front of A is counted at its largest, 112 bytes for storage that is
+// 16-byte aligned like the inner storage asks.  Per element: 8 bytes on top of the inner storage keys-only, 16 key+value.
+struct Sort64Layout {
+  uint64_t innerSize;
+  uint64_t loOffset, otherOffset, keysTempOffset;
+  uint64_t keysOnlySize, keyValueSize;  // what the caller allocates
+};
+
+static inline Sort64Layout MakeSort64Layout(uint32_t maxElementCount, uint32_t align, uint64_t storageAddress = 0) {
+  Sort64Layout s;
+  s.innerSize = MakeLayout(maxElementCount, align, 0).keyValueSize;
+  const uint64_t words = ((uint64_t)maxElementCount * sizeof(uint32_t) + 127u) & ~(uint64_t)127u;
+  const uint64_t longs = ((uint64_t)maxElementCount * sizeof(uint64_t) + 127u) & ~(uint64_t)127u;
+  s.loOffset = s.innerSize + ((0 - (storageAddress + s.innerSize)) & 127u);
+  s.otherOffset = s.loOffset + words;
+  s.keysTempOffset = s.otherOffset + words;
+  const uint64_t maxPad = align < 128u ? 128u - align : 0u;  // (innerSize is a multiple of align, like the address)
+  s.keysOnlySize = s.innerSize + maxPad + 2 * words;
+  s.keyValueSize = s.keysOnlySize + longs;
+  return s;
+}
+
 // The MSD plan's scatter (msd_scatter_or_pass0_kernel, one workgroup per CU and tile) cuts the sort into EQUAL tiles that fill whole
 // rounds of `cus` tiles: keys per tile, a multiple of 4096 (four 64-key slots per wave of its 1024 threads), at most 32768.
 // 520 tiles of 32768 keys would cost three rounds, the third for eight tiles; 768 tiles of 24576 cost three rounds of three

@@ -1,0 +1,69 @@
+"""Sort of 64-bit keys held in torch tensors.
+
+``sort64(sorter, keys)`` sorts a one-dimensional ``torch.int64`` (or ``torch.uint64``) tensor ascending as uint64 and stably,
+in place, on torch's current stream (``vrdxHipCmdSort64[KeyValue]``); ``values``, 4-byte integers of the same length, travel
+with their keys.  An ``int64`` tensor with negative entries therefore ends with them behind the others: flip bit 63 before
+and after for the signed order.  Everything is checked on the host before anything is recorded, no data is read, so the
+call does not synchronise and can be captured into a ``torch.cuda.graph``.
+"""
+from __future__ import annotations
+
+from .api import Sorter
+from .segmented import MAX_ELEMENTS, _four_byte_integer_dtypes
+
+
+def _eight_byte_integer_dtypes(torch):
+    dtypes = [torch.int64]
+    if hasattr(torch, "uint64"):
+        dtypes.append(torch.uint64)
+    return tuple(dtypes)
+
+
+def _check_array(torch, name, t, dtypes, what, device=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must hold {what}, got {t.dtype}")
+    if t.dim() != 1:
+        raise ValueError(f"{name} must be one-dimensional, got shape {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} must live on a GPU, got {t.device}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name} is on {t.device}, keys are on {device}")
+
+
+def sort64(sorter: Sorter, keys, values=None, storage=None):
+    """Sorts ``keys`` in place as uint64 (``values``, if given, travel with their keys).  ``storage``: a uint8 tensor of at
+    least ``sorter.storage_requirements64(keys.numel(), key_value=values is not None)`` bytes on the keys' device whose
+    address is a multiple of 16, allocated here when omitted.  Returns the storage used (one sort in flight per storage)."""
+    import torch
+
+    _check_array(torch, "keys", keys, _eight_byte_integer_dtypes(torch), "8-byte integers (int64 or uint64, sorted as uint64)")
+    if values is not None:
+        _check_array(torch, "values", values, _four_byte_integer_dtypes(torch), "4-byte integers (int32 or uint32)",
+                     keys.device)
+        if values.numel() != keys.numel():
+            raise ValueError(f"values hold {values.numel()} elements, keys {keys.numel()}")
+    n = keys.numel()
+    if n > MAX_ELEMENTS:
+        raise ValueError(f"{n} keys: at most {MAX_ELEMENTS} per call")
+    if storage is not None:
+        if not isinstance(storage, torch.Tensor) or storage.dtype != torch.uint8 or not storage.is_contiguous():
+            raise TypeError("storage must be a contiguous uint8 torch.Tensor")
+        if storage.device != keys.device:
+            raise ValueError(f"storage is on {storage.device}, keys are on {keys.device}")
+        if storage.data_ptr() % 16 != 0:
+            raise ValueError("storage must start on a 16-byte boundary")
+    required = sorter.storage_requirements64(n, key_value=values is not None).size
+    if storage is None:
+        storage = torch.empty(required, dtype=torch.uint8, device=keys.device)
+    elif storage.numel() < required:
+        raise ValueError(f"storage holds {storage.numel()} bytes, the sort needs {required}")
+    stream = torch.cuda.current_stream(keys.device).cuda_stream
+    if values is None:
+        sorter.cmd_sort64(stream, n, keys.data_ptr(), 0, storage.data_ptr(), 0)
+    else:
+        sorter.cmd_sort64_key_value(stream, n, keys.data_ptr(), 0, values.data_ptr(), 0, storage.data_ptr(), 0)
+    return storage
