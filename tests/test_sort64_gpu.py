@@ -1,7 +1,9 @@
 """GPU tests of the 64-bit sorts (vrdxHipCmdSort64[KeyValue], vulkan_radix_sort_amd.sort64), through the C ABI and element
 for element against numpy: keys-only against np.sort of the uint64 keys, key+value against np.argsort(kind="stable")
-applied to keys and to values (values = iota over duplicate-heavy keys prove stability).  Every case runs with guard words
-around the keys, the values and the storage requirement, and reads the status words afterwards."""
+applied to keys and to values (distinct values over duplicate-heavy keys prove stability; where a test says payload64 they
+are nowhere their own index, which a sort that hands out the index for the value needs to pass).  Every case runs with
+guard words around the keys, the values and the storage requirement, and reads the status words afterwards.  The key
+patterns, the values and the reference are those of tests/sort64_model.py."""
 import os
 import subprocess
 import zlib
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 
 from segmented_cases import ballot_sorter, sorter, torch_mod  # noqa: F401
+from sort64_model import check64, expected64, make_keys64, payload64  # noqa: F401 (shared with test_sort64_edges_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -18,37 +21,6 @@ SIZES = [0, 1, 2, 1000, 16384, 16385, (1 << 18) + 3, 1 << 22, 8_200_000]  # ever
 PATTERNS = ["uniform", "high-constant", "low-constant", "identical", "descending", "8-distinct", "bit63-mixed", "tile-depth"]
 GUARD = 0xA5
 STORAGE_GUARD = 0x5A
-
-
-def make_keys64(pattern, n, rng):
-    if pattern == "uniform":
-        return rng.integers(0, 1 << 64, size=n, dtype=np.uint64)
-    low = rng.integers(0, 1 << 32, size=n, dtype=np.uint64)
-    if pattern == "high-constant":
-        return np.uint64(0xDEADBEEF << 32) | low
-    if pattern == "low-constant":
-        return (low << np.uint64(32)) | np.uint64(0x12345678)
-    if pattern == "identical":
-        return np.full(n, 0x8000000100000002, dtype=np.uint64)
-    if pattern == "descending":  # strictly decreasing in both words
-        return np.uint64(0xFFFFFFFFFFFFFFFF) - np.arange(n, dtype=np.uint64) * np.uint64(0x100000001)
-    if pattern == "8-distinct":
-        return rng.integers(0, 1 << 64, size=8, dtype=np.uint64)[rng.integers(0, 8, size=n)]
-    if pattern == "bit63-mixed":  # the unsigned order: keys with bit 63 come last, whatever int64 makes of them
-        small = rng.integers(0, 1 << 20, size=n, dtype=np.uint64)
-        return small | (rng.integers(0, 2, size=n, dtype=np.uint64) << np.uint64(63))
-    if pattern == "tile-depth":  # a 16-bit tile id over the bits of a positive float depth
-        tile = rng.integers(0, 1 << 16, size=n, dtype=np.uint64)
-        depth = (rng.random(n, dtype=np.float32) * np.float32(100.0) + np.float32(0.1)).view(np.uint32).astype(np.uint64)
-        return (tile << np.uint64(32)) | depth
-    raise ValueError(pattern)
-
-
-def expected64(keys, values):
-    if values is None:
-        return np.sort(keys), None
-    order = np.argsort(keys, kind="stable")
-    return keys[order], values[order]
 
 
 def _guarded(torch, payload, offset, tail):
@@ -65,9 +37,10 @@ def _unguard(buffer, offset, nbytes, dtype):
     return raw[offset:offset + nbytes].copy().view(dtype)
 
 
-def run64(torch, s, keys, values=None, keys_off=0, values_off=0, storage_off=0, pool=None, count=None):
+def run64(torch, s, keys, values=None, keys_off=0, values_off=0, storage_off=0, pool=None, count=None, storage_out=None):
     """One call through the C ABI.  count (default: all of keys) elements are sorted; the rest of `keys` / `values` and 256
-    bytes more are guard words.  Returns the whole arrays as the device left them."""
+    bytes more are guard words.  Returns the whole arrays as the device left them; storage_out: a list that receives the
+    storage tensor (its header is at storage_off)."""
     stream = torch.cuda.current_stream().cuda_stream
     n = len(keys) if count is None else count
     key_value = values is not None
@@ -75,9 +48,10 @@ def run64(torch, s, keys, values=None, keys_off=0, values_off=0, storage_off=0, 
     storage = torch.full((storage_off + required + 256,), STORAGE_GUARD, dtype=torch.uint8, device="cuda")
     assert storage.data_ptr() % 16 == 0
     dk = _guarded(torch, keys, keys_off, 256)
-    assert (dk.data_ptr() + keys_off) % 8 == 0
+    assert dk.data_ptr() % 16 == 0 and keys_off % 8 == 0
     if key_value:
         dv = _guarded(torch, values, values_off, 256)
+        assert dv.data_ptr() % 16 == 0 and values_off % 4 == 0
         s.cmd_sort64_key_value(stream, n, dk.data_ptr(), keys_off, dv.data_ptr(), values_off, storage.data_ptr(), storage_off,
                                pool, 0)
     else:
@@ -92,17 +66,9 @@ def run64(torch, s, keys, values=None, keys_off=0, values_off=0, storage_off=0, 
     assert (back == STORAGE_GUARD).all(), "the storage buffer behind the requirement was written"
     got_keys = _unguard(dk, keys_off, keys.nbytes, np.uint64)
     got_values = _unguard(dv, values_off, values.nbytes, np.uint32) if key_value else None
+    if storage_out is not None:
+        storage_out.append(storage)
     return got_keys, got_values
-
-
-def check64(got_keys, got_values, keys, values, count=None):
-    n = len(keys) if count is None else count
-    want_keys, want_values = expected64(keys[:n], None if values is None else values[:n])
-    assert np.array_equal(got_keys[:n], want_keys)
-    assert np.array_equal(got_keys[n:], keys[n:]), "keys behind elementCount changed"
-    if values is not None:
-        assert np.array_equal(got_values[:n], want_values)
-        assert np.array_equal(got_values[n:], values[n:]), "values behind elementCount changed"
 
 
 @pytest.mark.parametrize("key_value", [False, True], ids=["keys", "pairs"])
@@ -111,7 +77,7 @@ def check64(got_keys, got_values, keys, values, count=None):
 def test_sort64_matches_numpy(torch_mod, sorter, n, pattern, key_value):
     rng = np.random.default_rng(zlib.crc32(f"{n}/{pattern}/{key_value}".encode()))
     keys = make_keys64(pattern, n + 5, rng)  # five elements behind elementCount
-    values = np.arange(n + 5, dtype=np.uint32) if key_value else None
+    values = payload64(n + 5) if key_value else None
     got_keys, got_values = run64(torch_mod, sorter, keys, values, count=n)
     check64(got_keys, got_values, keys, values, count=n)
 
@@ -214,17 +180,17 @@ def test_captured_graph_replays_on_new_data(torch_mod, sorter, key_value):
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         vrdx.sort64(sorter, dk, dv, storage=storage)
-    iota = np.arange(n, dtype=np.uint32)
+    values = payload64(n)
     for pattern in ("uniform", "high-constant", "8-distinct"):
         keys = make_keys64(pattern, n, rng)
         dk.copy_(torch.from_numpy(keys.view(np.int64)))
         if key_value:
-            dv.copy_(torch.from_numpy(iota.view(np.int32)))
+            dv.copy_(torch.from_numpy(values.view(np.int32)))
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
         check64(dk.cpu().numpy().view(np.uint64), dv.cpu().numpy().view(np.uint32) if key_value else None, keys,
-                iota if key_value else None)
+                values if key_value else None)
         stream = torch.cuda.current_stream().cuda_stream
         assert sorter.read_status(stream, storage.data_ptr(), 0) == 0
         assert sorter.read_sorter_status(stream) == 0
@@ -278,7 +244,7 @@ static size_t Run(VrdxSorter sorter, uint32_t n, bool keyValue) {
   for (uint32_t i = 0; i < n; ++i) {
     x ^= x << 13; x ^= x >> 7; x ^= x << 17;
     keys[i] = (i % 3 == 0) ? (x & 0xFFFF0000000000FFull) : x;  // duplicates of both words
-    values[i] = i;
+    values[i] = i * 2654435761u ^ 0x80000000u;  // not the index: a sort that hands out I[j] for values[I[j]] fails
   }
   VrdxSorterStorageRequirements req;
   if (keyValue) vrdxHipGetSorter64KeyValueStorageRequirements(sorter, n, &req);
