@@ -254,9 +254,9 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
  *   [5,6] key+value: the copy back into the caller's arrays (keys-only: 6 == 5)
  *   slots 7 ... 14 coincide with slot 6
  *
- * Out of scope, each left to the caller: indirect counts (no vrdxHipCmdSort64Indirect); segmented 64-bit sorts; signed and
- * floating-point orders (flip the sign bit, or the IEEE bits, before and after); descending order (complement the keys); values
- * wider than 32 bits (sort an index as the value and gather by it).
+ * Out of scope, each left to the caller: segmented 64-bit sorts; signed and floating-point orders (flip the sign bit, or the
+ * IEEE bits, before and after); descending order (complement the keys); values wider than 32 bits (sort an index as the value
+ * and gather by it).
  */
 void vrdxHipGetSorter64StorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
                                            VrdxSorterStorageRequirements* requirements);
@@ -268,6 +268,38 @@ void vrdxHipCmdSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t
 void vrdxHipCmdSort64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
                               VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                               VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+
+/**
+ * 64-bit keys by a device-side count: vrdxHipCmdSort64[KeyValue] with the element count read on the device, parameters in
+ * the order of vrdxCmdSort[KeyValue]Indirect.  A pipeline that learns its count on the GPU (a prefix sum, a compaction) sorts
+ * without reading it back, and one captured call serves every count up to the bound.
+ *
+ * Count: one uint32 at indirectBuffer + indirectOffset, a multiple of 4.  Every step reads it on the device when it runs; the
+ * host never reads it.  Values above maxElementCount are clamped to it, silently, as vrdxCmdSort*Indirect does.  The word may
+ * share a buffer with the keys or the values at another offset; it must not lie inside the storage range.  Nothing writes
+ * it.
+ * Effect: with n = min(count, maxElementCount), elements [0, n) of the keys (and values) end up sorted ascending as unsigned
+ * 64-bit and stable -- exactly what vrdxHipCmdSort64[KeyValue](..., n, ...) leaves.  Elements from n on are neither read nor
+ * written, also where n == 0, and nothing is written outside the storage requirement.
+ * Storage: vrdxHipGetSorter64[KeyValue]StorageRequirements(maxElementCount), carved as for the direct forms.
+ * Plans and grids depend on maxElementCount only: the inner sorts take the plan of maxElementCount, as vrdxCmdSort*Indirect
+ * does, and the steps around them start one thread per four elements of the bound, of which those from n on return.  With a
+ * NULL query pool the call is legal inside a stream capture, and the captured graph may be replayed on any count up to the
+ * bound and any data.
+ * Counts: maxElementCount == 0 records nothing but the timestamps; maxElementCount > 2^30 - 4 is clamped
+ * (VRDX_HIP_STATUS_COUNT_CLAMPED).
+ * Timestamps and status: as for the direct forms -- the same assignment of slots [0,6], all 15 recorded; vrdxHipReadStatus and
+ * vrdxHipReadPlanVerdict on this storage report the second inner sort.
+ */
+void vrdxHipCmdSort64Indirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                              VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                              VkDeviceSize keysOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                              VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSort64KeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                      VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                      VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                      VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                                      uint32_t query);
 
 /* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the 64-bit sorts (vrdxHipCmdSort64[KeyValue]) on one GPU, step by step, against two yardsticks outside them:
+"""Times the 64-bit sorts (vrdxHipCmdSort64[KeyValue], with --indirect vrdxHipCmdSort64[KeyValue]Indirect) on one GPU, step by step, against two yardsticks outside them:
 
   sort64      one vrdxHipCmdSort64[KeyValue] call, stamped with a 15-slot query pool: the call (slot 14 - slot 0) and each of
               its steps (split | first sort | gather | second sort | merge or permute | copy back)
@@ -13,8 +13,12 @@ streaming steps are also given as achieved bytes per second, priced with the byt
 merge 16, gather 12 (index, one word of the key, the word out), permute 28 (index, high word, low word and value in; key and
 value out), copy back 24.  Each shape prints ONE JSON line; the sort64 result of the last step is compared with torch's.
 
+--indirect records the sort64 step through the indirect forms instead, with N as the bound and a count equal to N held in
+a device word, and adds "indirect": true to every line: the same work by the same kernels and grids, so its sort64_ms over
+that of a run without the flag is the price of reading the count on the device.
+
 usage: python tools/sort64_bench.py [--sizes 1048576,4194304,33554432] [--patterns uniform,bits32,tile_depth]
-       [--modes keys,kv] [--steps 7] [--warmup 2] [--out FILE]
+       [--modes keys,kv] [--steps 7] [--warmup 2] [--indirect] [--out FILE]
 """
 import argparse
 import json
@@ -52,6 +56,7 @@ def main():
     ap.add_argument("--steps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--indirect", action="store_true")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -81,6 +86,7 @@ def main():
                 inner = torch.empty(sorter.key_value_storage_requirements(n).size, dtype=torch.uint8, device="cuda")
                 lo = torch.empty(n, dtype=torch.int32, device="cuda")
                 hi = torch.empty(n, dtype=torch.int32, device="cuda")
+                count = torch.tensor([n], dtype=torch.int32, device="cuda") if args.indirect else None
                 slots, torch_ms, floor_ms = [], [], []
                 torch_keys = torch_values = None
                 for step in range(args.warmup + args.steps):
@@ -90,9 +96,15 @@ def main():
                     if kv:
                         values.copy_(iota)
                     torch.cuda.synchronize()
-                    if kv:
+                    if kv and args.indirect:
+                        sorter.cmd_sort64_key_value_indirect(stream, n, count.data_ptr(), 0, keys.data_ptr(), 0,
+                                                             values.data_ptr(), 0, storage.data_ptr(), 0, pool, 0)
+                    elif kv:
                         sorter.cmd_sort64_key_value(stream, n, keys.data_ptr(), 0, values.data_ptr(), 0, storage.data_ptr(), 0,
                                                     pool, 0)
+                    elif args.indirect:
+                        sorter.cmd_sort64_indirect(stream, n, count.data_ptr(), 0, keys.data_ptr(), 0, storage.data_ptr(), 0,
+                                                   pool, 0)
                     else:
                         sorter.cmd_sort64(stream, n, keys.data_ptr(), 0, storage.data_ptr(), 0, pool, 0)
                     torch.cuda.synchronize()
@@ -126,6 +138,8 @@ def main():
                 names = (["split", "sort_low", "gather", "sort_high", "permute", "copy_back"] if kv
                          else ["split", "sort_low", None, "sort_high", "merge"])
                 result = {"n": n, "pattern": pattern, "key_value": kv, "sort64_ms": float(ts[14])}
+                if args.indirect:
+                    result["indirect"] = True
                 for i, name in enumerate(names):
                     if name is not None:
                         result[name + "_ms"] = float(ts[i + 1] - ts[i])
@@ -143,7 +157,7 @@ def main():
                 if out:
                     out.write(line + "\n")
                     out.flush()
-                del keys, values, storage, inner, lo, hi, torch_keys, torch_values
+                del keys, values, storage, inner, lo, hi, count, torch_keys, torch_values
                 torch.cuda.empty_cache()
             del master
     if out:

@@ -18,6 +18,8 @@ reference (C++ / Vulkan)                        here
 ``vrdxHipGetSorter64[KeyValue]Storage...``      ``Sorter.storage_requirements64(n, key_value=False)``
 ``vrdxHipCmdSort64`` (HIP only)                 ``Sorter.cmd_sort64(...)``
 ``vrdxHipCmdSort64KeyValue`` (HIP only)         ``Sorter.cmd_sort64_key_value(...)``
+``vrdxHipCmdSort64Indirect`` (HIP only)         ``Sorter.cmd_sort64_indirect(...)``
+``vrdxHipCmdSort64KeyValueIndirect`` (HIP only) ``Sorter.cmd_sort64_key_value_indirect(...)``
 =============================================  ==============================================
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
@@ -69,6 +71,8 @@ EXPORTED_SYMBOLS = (
     "vrdxHipGetSorter64KeyValueStorageRequirements",
     "vrdxHipCmdSort64",
     "vrdxHipCmdSort64KeyValue",
+    "vrdxHipCmdSort64Indirect",
+    "vrdxHipCmdSort64KeyValueIndirect",
 )
 
 # bits of vrdxHipReadSorterStatus (include/vk_radix_sort.h)
@@ -188,6 +192,10 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxHipCmdSort64.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u32]
     lib.vrdxHipCmdSort64KeyValue.restype = None
     lib.vrdxHipCmdSort64KeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
+    lib.vrdxHipCmdSort64Indirect.restype = None
+    lib.vrdxHipCmdSort64Indirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
+    lib.vrdxHipCmdSort64KeyValueIndirect.restype = None
+    lib.vrdxHipCmdSort64KeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
     lib.vrdxHipCreateQueryPool.argtypes = [u32, ctypes.POINTER(vp)]
     lib.vrdxHipDestroyQueryPool.restype = None
@@ -376,6 +384,24 @@ class Sorter:
         self._lib.vrdxHipCmdSort64KeyValue(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
                                            _handle(values), values_offset, _handle(storage), storage_offset,
                                            _pool(query_pool), query)
+
+    def cmd_sort64_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys, keys_offset, storage,
+                            storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSort64Indirect``: ``cmd_sort64`` of the first min(count, ``max_element_count``) keys, the count
+        one uint32 at ``indirect + indirect_offset`` that is read on the device; storage of
+        ``storage_requirements64(max_element_count)`` bytes."""
+        self._lib.vrdxHipCmdSort64Indirect(_handle(command_buffer), self.handle, max_element_count, _handle(indirect),
+                                           indirect_offset, _handle(keys), keys_offset, _handle(storage), storage_offset,
+                                           _pool(query_pool), query)
+
+    def cmd_sort64_key_value_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys, keys_offset,
+                                      values, values_offset, storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSort64KeyValueIndirect``: the same with one uint32 value per key; storage of
+        ``storage_requirements64(max_element_count, key_value=True)`` bytes."""
+        self._lib.vrdxHipCmdSort64KeyValueIndirect(_handle(command_buffer), self.handle, max_element_count,
+                                                   _handle(indirect), indirect_offset, _handle(keys), keys_offset,
+                                                   _handle(values), values_offset, _handle(storage), storage_offset,
+                                                   _pool(query_pool), query)
 
     # -- diagnostics ------------------------------------------------------------------------
     def read_status(self, command_buffer, storage, storage_offset=0) -> int:

@@ -793,7 +793,7 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   MaybeRecheckOrder(sorter, stream, atomicRank);
 }
 
-// The 64-bit sorts (include/vk_radix_sort.h, vrdxHipCmdSort64[KeyValue]): two stable 32-bit key+value sorts, low words first
+// The 64-bit sorts (include/vk_radix_sort.h, vrdxHipCmdSort64[KeyValue][Indirect]): two stable 32-bit key+value sorts, low words first
 // and high words second, each through RecordSort on word arrays inside the storage (vrdx_layout.h, MakeSort64Layout), with
 // the streaming kernels of vrdx_kernels.hip ("64-bit keys") around them:
 //   keys-only   split (A = lo, B = hi) | sort (A, B) | sort (B, A) | merge (keys = B << 32 | A)
@@ -801,9 +801,13 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
 //               permute (T = A << 32 | lo of keys[I], A = values[I]) | copy back (keys = T, values = A)
 // The inner sorts are recorded without a query pool; each step of this list ends one slot.  Nothing is decided from the
 // data on the host, so a captured call can be replayed on other data of the same count.
-void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
-                  VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer,
-                  VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+// Indirect (indirectBuffer != nullptr): elementCount is the bound; layout, plans and grids come from it alone, and every
+// step -- the streaming kernels and, through RecordSort, the inner sorts -- reads the count from the caller's word when it
+// runs, so a captured call can be replayed on any count up to the bound.
+void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer indirectBuffer,
+                  VkDeviceSize indirectOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                  VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                  uint32_t query) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
   const bool keyValue = valuesBuffer != nullptr;
   if (elementCount > VRDX_MAX_ELEMENTS) {
@@ -825,29 +829,33 @@ void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t ele
   uint32_t* const lo = reinterpret_cast<uint32_t*>(storage + layout.loOffset);
   uint32_t* const other = reinterpret_cast<uint32_t*>(storage + layout.otherOffset);
   uint64_t* const keysTemp = reinterpret_cast<uint64_t*>(storage + layout.keysTempOffset);
+  const uint32_t* const countPtr =
+      indirectBuffer != nullptr ? reinterpret_cast<const uint32_t*>(BufferAddress(indirectBuffer, indirectOffset)) : nullptr;
   // an inner sort: the words at `sortKeys` with those at `payload` as their values, in the storage's front part
   auto sortWords = [&](uint64_t sortKeys, uint64_t payload) {
-    RecordSort(commandBuffer, sorter, elementCount, nullptr, 0, storageBuffer, storageOffset + sortKeys, storageBuffer,
-               storageOffset + payload, storageBuffer, storageOffset, nullptr, 0);
+    RecordSort(commandBuffer, sorter, elementCount, indirectBuffer, indirectOffset, storageBuffer, storageOffset + sortKeys,
+               storageBuffer, storageOffset + payload, storageBuffer, storageOffset, nullptr, 0);
   };
 
-  EnqueueCheck(sorter, "split64_kernel", vrdx::LaunchSplit64(stream, keyValue, keys, lo, other, elementCount));
+  EnqueueCheck(sorter, "split64_kernel", vrdx::LaunchSplit64(stream, keyValue, keys, lo, other, elementCount, countPtr));
   stamps.AdvanceTo(1);
   sortWords(layout.loOffset, layout.otherOffset);
   stamps.AdvanceTo(2);
   if (keyValue) {
-    EnqueueCheck(sorter, "gather_hi64_kernel", vrdx::LaunchGatherHi64(stream, keys, other, lo, elementCount));
+    EnqueueCheck(sorter, "gather_hi64_kernel", vrdx::LaunchGatherHi64(stream, keys, other, lo, elementCount, countPtr));
     stamps.AdvanceTo(3);
     sortWords(layout.loOffset, layout.otherOffset);
     stamps.AdvanceTo(4);
-    EnqueueCheck(sorter, "permute64_kernel", vrdx::LaunchPermute64(stream, keys, values, other, lo, keysTemp, elementCount));
+    EnqueueCheck(sorter, "permute64_kernel",
+                 vrdx::LaunchPermute64(stream, keys, values, other, lo, keysTemp, elementCount, countPtr));
     stamps.AdvanceTo(5);
-    EnqueueCheck(sorter, "copy_back64_kernel", vrdx::LaunchCopyBack64(stream, keys, values, keysTemp, lo, elementCount));
+    EnqueueCheck(sorter, "copy_back64_kernel",
+                 vrdx::LaunchCopyBack64(stream, keys, values, keysTemp, lo, elementCount, countPtr));
     stamps.AdvanceTo(6);
   } else {
     sortWords(layout.otherOffset, layout.loOffset);  // (slot 3 coincides with slot 2: no step between the sorts)
     stamps.AdvanceTo(4);
-    EnqueueCheck(sorter, "merge64_kernel", vrdx::LaunchMerge64(stream, keys, lo, other, elementCount));
+    EnqueueCheck(sorter, "merge64_kernel", vrdx::LaunchMerge64(stream, keys, lo, other, elementCount, countPtr));
     stamps.AdvanceTo(5);
   }
   stamps.Finish();
@@ -1023,15 +1031,32 @@ void vrdxHipGetSorter64KeyValueStorageRequirements(VrdxSorter sorter, uint32_t m
 void vrdxHipCmdSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
                       VkDeviceSize keysOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
                       uint32_t query) {
-  RecordSort64(commandBuffer, sorter, elementCount, keysBuffer, keysOffset, nullptr, 0, storageBuffer, storageOffset,
-               queryPool, query);
+  RecordSort64(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, nullptr, 0, storageBuffer,
+               storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSort64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
                               VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                               VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
-  RecordSort64(commandBuffer, sorter, elementCount, keysBuffer, keysOffset, valuesBuffer, valuesOffset, storageBuffer,
-               storageOffset, queryPool, query);
+  RecordSort64(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, valuesBuffer, valuesOffset,
+               storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSort64Indirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                              VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                              VkDeviceSize keysOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                              VkQueryPool queryPool, uint32_t query) {
+  RecordSort64(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, nullptr, 0,
+               storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSort64KeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                      VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                      VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                      VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                                      uint32_t query) {
+  RecordSort64(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, valuesBuffer,
+               valuesOffset, storageBuffer, storageOffset, queryPool, query);
 }
 
 VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {

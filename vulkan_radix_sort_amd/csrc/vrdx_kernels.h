@@ -246,22 +246,27 @@ enum SegmentClass { kSegmentSmall = 0, kSegmentMid = 1, kSegmentLarge = 2 };  //
 hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
                            const SegmentedArgs& args);
 
-// ---- 64-bit keys (vrdxHipCmdSort64[KeyValue]): the steps around the two 32-bit sorts (vrdx_kernels.hip, "64-bit keys") ----
-// Every thread takes four consecutive elements; count <= VRDX_MAX_ELEMENTS.  keys: the caller's, 8-byte aligned; values:
-// the caller's, 4-byte aligned; every other array lies inside the storage on a 16-byte boundary (MakeSort64Layout).
+// ---- 64-bit keys (vrdxHipCmdSort64[KeyValue][Indirect]): the steps around the two 32-bit sorts (vrdx_kernels.hip, "64-bit
+// keys") ----
+// Every thread takes four consecutive elements; 0 < maxCount <= VRDX_MAX_ELEMENTS sizes the grid, and the kernels work on
+// min(*countPtr, maxCount) elements (countPtr == nullptr: on maxCount).  keys: the caller's, 8-byte aligned; values: the
+// caller's, 4-byte aligned; every other array lies inside the storage on a 16-byte boundary (MakeSort64Layout).
 constexpr uint32_t kSort64Threads = 256;
 // lo[i] = low word of keys[i]; other[i] = its high word, or i (iota)
-hipError_t LaunchSplit64(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other, uint32_t count);
+hipError_t LaunchSplit64(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other, uint32_t maxCount,
+                         const uint32_t* countPtr);
 // keys[i] = hi[i] << 32 | lo[i]
-hipError_t LaunchMerge64(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t count);
+hipError_t LaunchMerge64(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
+                         const uint32_t* countPtr);
 // hi[j] = high word of keys[index[j]]
-hipError_t LaunchGatherHi64(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi, uint32_t count);
+hipError_t LaunchGatherHi64(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi, uint32_t maxCount,
+                            const uint32_t* countPtr);
 // keysOut[j] = hiThenValues[j] << 32 | low word of keys[index[j]]; then hiThenValues[j] = values[index[j]]
 hipError_t LaunchPermute64(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
-                           uint32_t* hiThenValues, uint64_t* keysOut, uint32_t count);
+                           uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr);
 // keys[i] = keysIn[i]; values[i] = valuesIn[i]
 hipError_t LaunchCopyBack64(hipStream_t stream, uint64_t* keys, uint32_t* values, const uint64_t* keysIn,
-                            const uint32_t* valuesIn, uint32_t count);
+                            const uint32_t* valuesIn, uint32_t maxCount, const uint32_t* countPtr);
 
 // ---- the kernels' dynamic LDS and the MSD plan's grids: one definition for the kernels (vrdx_kernels.hip) and for both
 // launch backends (vrdx_launch.inc) ----

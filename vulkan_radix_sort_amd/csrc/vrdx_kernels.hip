@@ -3296,7 +3296,9 @@ __global__ __launch_bounds__(64) void spin_kernel(unsigned long long* out, uint3
 // the keys' own 8-byte alignment only, the caller's values as one that needs 4-byte alignment, and the word arrays inside
 // the storage (128-byte aligned, MakeSort64Layout) as one aligned 16-byte access.  The last n mod 4 elements go one by
 // one, so nothing from element n on is read or written.  Gathers read ONE word of a key: the other word of its 8 bytes
-// comes along in the same sector for nothing, but would cost registers.
+// comes along in the same sector for nothing, but would cost registers.  n is ElementCount(maxCount, countPtr) like in every
+// other kernel: the grid covers maxCount (Sort64Grid), and with a device-side count (vrdxHipCmdSort64[KeyValue]Indirect) the
+// workgroups from element n on return.
 typedef u32x4 u32x4_a8 __attribute__((aligned(8)));  // two uint64 keys {lo, hi, lo, hi}: 16-byte access, 8-byte aligned
 
 __device__ __forceinline__ uint32_t Sort64First(uint32_t n, bool* whole) {
@@ -3308,7 +3310,9 @@ __device__ __forceinline__ uint32_t Sort64First(uint32_t n, bool* whole) {
 // lo[i] = low word; other[i] = high word, or i itself (IOTA: the index the key+value form sorts along)
 template <bool IOTA>
 __global__ __launch_bounds__(kSort64Threads) void split64_kernel(const uint64_t* __restrict__ keys, uint32_t* __restrict__ lo,
-                                                                 uint32_t* __restrict__ other, uint32_t n) {
+                                                                 uint32_t* __restrict__ other, uint32_t maxCount,
+                                                                 const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
   bool whole;
   const uint32_t i = Sort64First(n, &whole);
   if (i >= n) return;
@@ -3328,7 +3332,9 @@ __global__ __launch_bounds__(kSort64Threads) void split64_kernel(const uint64_t*
 
 // keys[i] = hi[i] << 32 | lo[i]
 __global__ __launch_bounds__(kSort64Threads) void merge64_kernel(uint64_t* __restrict__ keys, const uint32_t* __restrict__ lo,
-                                                                 const uint32_t* __restrict__ hi, uint32_t n) {
+                                                                 const uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                 const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
   bool whole;
   const uint32_t i = Sort64First(n, &whole);
   if (i >= n) return;
@@ -3345,7 +3351,9 @@ __global__ __launch_bounds__(kSort64Threads) void merge64_kernel(uint64_t* __res
 // hi[j] = high word of keys[index[j]]: the keys of the second sort, in the order the first one left
 __global__ __launch_bounds__(kSort64Threads) void gather_hi64_kernel(const uint64_t* __restrict__ keys,
                                                                      const uint32_t* __restrict__ index,
-                                                                     uint32_t* __restrict__ hi, uint32_t n) {
+                                                                     uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                     const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
   bool whole;
   const uint32_t i = Sort64First(n, &whole);
   if (i >= n) return;
@@ -3366,7 +3374,9 @@ __global__ __launch_bounds__(kSort64Threads) void permute64_kernel(const uint64_
                                                                    const uint32_t* __restrict__ values,
                                                                    const uint32_t* __restrict__ index,
                                                                    uint32_t* __restrict__ hiThenValues,
-                                                                   uint64_t* __restrict__ keysOut, uint32_t n) {
+                                                                   uint64_t* __restrict__ keysOut, uint32_t maxCount,
+                                                                   const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
   bool whole;
   const uint32_t i = Sort64First(n, &whole);
   if (i >= n) return;
@@ -3392,7 +3402,9 @@ __global__ __launch_bounds__(kSort64Threads) void permute64_kernel(const uint64_
 // keys[i] = keysIn[i], values[i] = valuesIn[i]: the permuted arrays back into the caller's
 __global__ __launch_bounds__(kSort64Threads) void copy_back64_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ values,
                                                                      const uint64_t* __restrict__ keysIn,
-                                                                     const uint32_t* __restrict__ valuesIn, uint32_t n) {
+                                                                     const uint32_t* __restrict__ valuesIn, uint32_t maxCount,
+                                                                     const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
   bool whole;
   const uint32_t i = Sort64First(n, &whole);
   if (i >= n) return;

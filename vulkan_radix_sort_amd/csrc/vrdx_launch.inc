@@ -192,17 +192,17 @@
     "_ZN4vrdx11spin_kernelEPyj") \
   /* 64-bit keys: split64_kernel [high words | iota], merge, gather of the high words, permute, copy back */ \
   X(kSplit64, (&split64_kernel<false>), kSort64Threads, 0, \
-    "_ZN4vrdx14split64_kernelILb0EEEvPKmPjS3_j") \
+    "_ZN4vrdx14split64_kernelILb0EEEvPKmPjS3_jPKj") \
   X(kSplit64Iota, (&split64_kernel<true>), kSort64Threads, 0, \
-    "_ZN4vrdx14split64_kernelILb1EEEvPKmPjS3_j") \
+    "_ZN4vrdx14split64_kernelILb1EEEvPKmPjS3_jPKj") \
   X(kMerge64, (&merge64_kernel), kSort64Threads, 0, \
-    "_ZN4vrdx14merge64_kernelEPmPKjS2_j") \
+    "_ZN4vrdx14merge64_kernelEPmPKjS2_jS2_") \
   X(kGatherHi64, (&gather_hi64_kernel), kSort64Threads, 0, \
-    "_ZN4vrdx18gather_hi64_kernelEPKmPKjPjj") \
+    "_ZN4vrdx18gather_hi64_kernelEPKmPKjPjjS3_") \
   X(kPermute64, (&permute64_kernel), kSort64Threads, 0, \
-    "_ZN4vrdx16permute64_kernelEPKmPKjS3_PjPmj") \
+    "_ZN4vrdx16permute64_kernelEPKmPKjS3_PjPmjS3_") \
   X(kCopyBack64, (&copy_back64_kernel), kSort64Threads, 0, \
-    "_ZN4vrdx18copy_back64_kernelEPmPjPKmPKjj")
+    "_ZN4vrdx18copy_back64_kernelEPmPjPKmPKjjS5_")
 
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
@@ -357,35 +357,39 @@ hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t 
 }
 
 // ---- 64-bit keys ------------------------------------------------------------------------------------
-// one thread per four elements; an empty launch is the recorder's business (it records none)
-static uint32_t Sort64Grid(uint32_t count) { return (count + 4u * kSort64Threads - 1u) / (4u * kSort64Threads); }
-static bool Sort64CountFits(uint32_t count) { return count != 0 && count <= VRDX_MAX_ELEMENTS; }
+// one thread per four elements of the bound (the kernels take the count from countPtr where there is one); an empty launch
+// is the recorder's business (it records none)
+static uint32_t Sort64Grid(uint32_t maxCount) { return (maxCount + 4u * kSort64Threads - 1u) / (4u * kSort64Threads); }
+static bool Sort64CountFits(uint32_t maxCount) { return maxCount != 0 && maxCount <= VRDX_MAX_ELEMENTS; }
 
-hipError_t LaunchSplit64(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other, uint32_t count) {
-  if (!Sort64CountFits(count)) return hipErrorInvalidValue;
-  return Launch(iota ? kSplit64Iota : kSplit64, Sort64Grid(count), stream, keys, lo, other, count);
+hipError_t LaunchSplit64(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other, uint32_t maxCount,
+                         const uint32_t* countPtr) {
+  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
+  return Launch(iota ? kSplit64Iota : kSplit64, Sort64Grid(maxCount), stream, keys, lo, other, maxCount, countPtr);
 }
 
-hipError_t LaunchMerge64(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t count) {
-  if (!Sort64CountFits(count)) return hipErrorInvalidValue;
-  return Launch(kMerge64, Sort64Grid(count), stream, keys, lo, hi, count);
+hipError_t LaunchMerge64(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
+                         const uint32_t* countPtr) {
+  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kMerge64, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr);
 }
 
-hipError_t LaunchGatherHi64(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi, uint32_t count) {
-  if (!Sort64CountFits(count)) return hipErrorInvalidValue;
-  return Launch(kGatherHi64, Sort64Grid(count), stream, keys, index, hi, count);
+hipError_t LaunchGatherHi64(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi, uint32_t maxCount,
+                            const uint32_t* countPtr) {
+  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kGatherHi64, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr);
 }
 
 hipError_t LaunchPermute64(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
-                           uint32_t* hiThenValues, uint64_t* keysOut, uint32_t count) {
-  if (!Sort64CountFits(count)) return hipErrorInvalidValue;
-  return Launch(kPermute64, Sort64Grid(count), stream, keys, values, index, hiThenValues, keysOut, count);
+                           uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr) {
+  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kPermute64, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues, keysOut, maxCount, countPtr);
 }
 
 hipError_t LaunchCopyBack64(hipStream_t stream, uint64_t* keys, uint32_t* values, const uint64_t* keysIn,
-                            const uint32_t* valuesIn, uint32_t count) {
-  if (!Sort64CountFits(count)) return hipErrorInvalidValue;
-  return Launch(kCopyBack64, Sort64Grid(count), stream, keys, values, keysIn, valuesIn, count);
+                            const uint32_t* valuesIn, uint32_t maxCount, const uint32_t* countPtr) {
+  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kCopyBack64, Sort64Grid(maxCount), stream, keys, values, keysIn, valuesIn, maxCount, countPtr);
 }
 
 // ---- the LDS order check and the calibration spin -----------------------------------------------------

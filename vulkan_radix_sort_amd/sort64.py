@@ -5,6 +5,11 @@ in place, on torch's current stream (``vrdxHipCmdSort64[KeyValue]``); ``values``
 with their keys.  An ``int64`` tensor with negative entries therefore ends with them behind the others: flip bit 63 before
 and after for the signed order.  Everything is checked on the host before anything is recorded, no data is read, so the
 call does not synchronise and can be captured into a ``torch.cuda.graph``.
+
+``sort64(sorter, keys, count=t)`` sorts only ``keys[:t]`` (and ``values[:t]``), ``t`` a one-element ``int32`` / ``uint32``
+tensor on the keys' device that is read on the GPU when the sort runs (``vrdxHipCmdSort64[KeyValue]Indirect``): a count
+that a kernel produced needs no read-back, and a captured call replays on whatever the tensor holds then.  ``keys.numel()``
+is the bound -- a count beyond it is clamped to it -- and sizes the storage; elements from the count on are left alone.
 """
 from __future__ import annotations
 
@@ -34,10 +39,12 @@ def _check_array(torch, name, t, dtypes, what, device=None):
         raise ValueError(f"{name} is on {t.device}, keys are on {device}")
 
 
-def sort64(sorter: Sorter, keys, values=None, storage=None):
+def sort64(sorter: Sorter, keys, values=None, storage=None, count=None):
     """Sorts ``keys`` in place as uint64 (``values``, if given, travel with their keys).  ``storage``: a uint8 tensor of at
     least ``sorter.storage_requirements64(keys.numel(), key_value=values is not None)`` bytes on the keys' device whose
-    address is a multiple of 16, allocated here when omitted.  Returns the storage used (one sort in flight per storage)."""
+    address is a multiple of 16, allocated here when omitted.  ``count``: a one-element int32 / uint32 tensor on the keys'
+    device; only the first min(count, keys.numel()) elements are sorted, the count is read on the device and must not be
+    part of ``storage``.  Returns the storage used (one sort in flight per storage)."""
     import torch
 
     _check_array(torch, "keys", keys, _eight_byte_integer_dtypes(torch), "8-byte integers (int64 or uint64, sorted as uint64)")
@@ -46,6 +53,17 @@ def sort64(sorter: Sorter, keys, values=None, storage=None):
                      keys.device)
         if values.numel() != keys.numel():
             raise ValueError(f"values hold {values.numel()} elements, keys {keys.numel()}")
+    if count is not None:
+        if not isinstance(count, torch.Tensor):
+            raise TypeError(f"count must be a torch.Tensor, got {type(count).__name__}")
+        if count.dtype not in _four_byte_integer_dtypes(torch):
+            raise TypeError(f"count must hold a 4-byte integer (int32 or uint32), got {count.dtype}")
+        if count.numel() != 1:
+            raise ValueError(f"count must hold one element, got shape {tuple(count.shape)}")
+        if count.device.type != "cuda":
+            raise ValueError(f"count must live on a GPU, got {count.device}")
+        if count.device != keys.device:
+            raise ValueError(f"count is on {count.device}, keys are on {keys.device}")
     n = keys.numel()
     if n > MAX_ELEMENTS:
         raise ValueError(f"{n} keys: at most {MAX_ELEMENTS} per call")
@@ -62,8 +80,14 @@ def sort64(sorter: Sorter, keys, values=None, storage=None):
     elif storage.numel() < required:
         raise ValueError(f"storage holds {storage.numel()} bytes, the sort needs {required}")
     stream = torch.cuda.current_stream(keys.device).cuda_stream
-    if values is None:
-        sorter.cmd_sort64(stream, n, keys.data_ptr(), 0, storage.data_ptr(), 0)
+    if count is None:
+        if values is None:
+            sorter.cmd_sort64(stream, n, keys.data_ptr(), 0, storage.data_ptr(), 0)
+        else:
+            sorter.cmd_sort64_key_value(stream, n, keys.data_ptr(), 0, values.data_ptr(), 0, storage.data_ptr(), 0)
+    elif values is None:
+        sorter.cmd_sort64_indirect(stream, n, count.data_ptr(), 0, keys.data_ptr(), 0, storage.data_ptr(), 0)
     else:
-        sorter.cmd_sort64_key_value(stream, n, keys.data_ptr(), 0, values.data_ptr(), 0, storage.data_ptr(), 0)
+        sorter.cmd_sort64_key_value_indirect(stream, n, count.data_ptr(), 0, keys.data_ptr(), 0, values.data_ptr(), 0,
+                                             storage.data_ptr(), 0)
     return storage
