@@ -254,9 +254,9 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
  *   [5,6] key+value: the copy back into the caller's arrays (keys-only: 6 == 5)
  *   slots 7 ... 14 coincide with slot 6
  *
- * Out of scope, each left to the caller: segmented 64-bit sorts; signed and floating-point orders (flip the sign bit, or the
- * IEEE bits, before and after); descending order (complement the keys); values wider than 32 bits (sort an index as the value
- * and gather by it).
+ * Out of scope, each left to the caller: signed and floating-point orders (flip the sign bit, or the IEEE bits, before and
+ * after); descending order (complement the keys); values wider than 32 bits (sort an index as the value and gather by it).
+ * Many independent arrays of 64-bit keys: vrdxHipCmdSortSegmented64 below.
  */
 void vrdxHipGetSorter64StorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
                                            VrdxSorterStorageRequirements* requirements);
@@ -300,6 +300,55 @@ void vrdxHipCmdSort64KeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter 
                                       VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                                       VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
                                       uint32_t query);
+
+/**
+ * Segmented sort of 64-bit keys (not part of the reference API): vrdxHipCmdSortSegmented[KeyValue] with uint64 keys,
+ * parameters in the same order.  Native kernels, not a chain of the 32-bit entry points: a segment that fits a workgroup's
+ * LDS is loaded once, ranked by up to eight bytes inside the workgroup and stored once.
+ *
+ * Data: keysBuffer + keysOffset holds uint64 keys and is a multiple of 8; valuesBuffer + valuesOffset holds one uint32 value
+ * per key and is a multiple of 4; offsetsBuffer + offsetsOffset holds segmentCount + 1 uint32 offsets o[] in CSR form, read on
+ * the device only; nothing writes them.
+ * Order: every segment [o[i], o[i+1]) is sorted ascending as unsigned 64-bit, stably; values travel with their keys.
+ * Untouched elements: elements before o[0], from o[segmentCount] on, and in segments of fewer than 2 elements are not written
+ * at all (not rewritten with their own value).
+ * Bad offsets: as for the 32-bit form -- a segment with o[i] > o[i+1] or o[i+1] > maxElementCount is left alone and raises
+ * VRDX_HIP_STATUS_SEGMENTS_INVALID in the storage's failure word and in the sorter's word; any offsets that are not monotone
+ * raise it (with the bit raised, valid segments that overlap each other are unspecified).  Nothing is ever written outside
+ * [0, maxElementCount) of the caller's arrays or outside the storage requirement.
+ * Storage: vrdxHipGetSorter64[KeyValue]StorageRequirements(maxElementCount); storageOffset is a multiple of 16, one sort in
+ * flight per storage.  Header words 0-3, the two list counters and the lists lie where the 32-bit segmented sort keeps them
+ * (inside the front part, vrdxGetSorterKeyValueStorageRequirements(maxElementCount) bytes); behind that, on 128-byte lines, one
+ * 8-byte scratch key per element where the 64-bit sorts keep A and B, and for key+value one 4-byte scratch value per element
+ * where they keep T.  Word 1 reads VRDX_HIP_VERDICT_NONE after the sort.
+ * Recording: the call never blocks and reads nothing on the host; grids depend on segmentCount, maxElementCount and the CU
+ * count only; with a NULL query pool it is legal inside a stream capture, and the captured graph may be replayed on other keys
+ * and another segmentation with the same segmentCount.  segmentCount == 0 or maxElementCount == 0 records nothing but the
+ * timestamps; maxElementCount > 2^30 - 4 is clamped (VRDX_HIP_STATUS_COUNT_CLAMPED).
+ * Sizes are classed on the device.  Up to 4096 keys one 256-thread workgroup sorts the segment in LDS; up to 16384 keys
+ * (keys-only) or 8192 elements (key+value: 12 bytes x 16384 do not fit the LDS) one 1024-thread workgroup does; beyond that one
+ * workgroup runs an LSD sort through memory in tiles of 8192 elements, between the segment and its index range of the
+ * scratch arrays.  In every class a byte that is the same in all keys of a segment costs no pass, so keys of fewer than 64
+ * significant bits (tile id << 32 | depth) take fewer than eight.  One workgroup sorts a large segment, so a few huge
+ * segments leave most of the device idle: 64 segments of 262144 keys take 1.4 ms on an MI355X, a third of one
+ * vrdxHipCmdSort64 per segment, and the loop wins once the segments are far larger.
+ *
+ * Timestamps (all 15 slots recorded; ts[14] - ts[0] is the sort):
+ *   [0,1] the fill of the storage header and list counters
+ *   [1,2] the 256-thread launch over every segment (sorts those of <= 4096 elements, lists the others)
+ *   [2,3] the 1024-thread in-LDS launch over the listed mid segments (3 == 2 when maxElementCount < 4097)
+ *   [3,4] the launch over the listed large segments (4 == 3 when maxElementCount < 16385 keys-only, < 8193 key+value)
+ *   slots 5 ... 14 coincide with slot 4
+ */
+void vrdxHipCmdSortSegmented64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                               uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                               VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
+                               VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                       uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                       VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                       VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                       VkQueryPool queryPool, uint32_t query);
 
 /* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves

@@ -10,8 +10,18 @@ Every step sorts fresh keys (seeded, generated on the device outside the timed r
 event interval around the enqueue of the whole job, so a host-bound loop of enqueues is charged what it costs.  Each shape
 prints ONE JSON line; the segmented result of the last step is compared with the torch_sort result (`"match"`).
 
+--keys64 times the same for uint64 keys (vrdxHipCmdSortSegmented64[KeyValue]), four ways, alternating in one process:
+
+  segmented64  one vrdxHipCmdSortSegmented64[KeyValue] call (vulkan_radix_sort_amd.sort_segments64)
+  composed     what the 32-bit entry points offer: split into words with torch ops, sort_segments(lo, values=hi), then
+               sort_segments(hi, values=lo), recombine; key+value: the words carry an index (sort_segments(lo, values=index),
+               gather the high words by it, sort_segments(hi, values=index)) and keys and values are gathered by it at the end
+  per_array    one vrdxHipCmdSort64[KeyValue] per segment on one stream and storage
+  torch_sort   two stable torch.sort: by key, then by segment id
+Every way's result on one extra, untimed input is compared with np.lexsort((keys, segment id)) on the host (`"match_*"`).
+
 usage: python tools/segmented_bench.py [--shapes 65536x256,8192x2048,...,mixed] [--steps 5] [--warmup 2] [--loop-steps 3]
-       [--modes keys,kv] [--only segmented] [--out FILE]
+       [--modes keys,kv] [--only segmented] [--out FILE] [--keys64 [--patterns uniform,tile_depth]]
 """
 import argparse
 import json
@@ -43,6 +53,146 @@ def segment_sizes(shape, rng):
     return np.full(count, length, dtype=np.int64)
 
 
+def make_keys64(torch, pattern, n, gen):
+    if pattern == "uniform":  # 63 random bits
+        return torch.randint(0, (1 << 63) - 1, (n,), dtype=torch.int64, device="cuda", generator=gen)
+    if pattern == "tile_depth":  # a 16-bit tile id over the bits of a positive float depth (tools/sort64_bench.py)
+        tile = torch.randint(0, 1 << 16, (n,), dtype=torch.int64, device="cuda", generator=gen)
+        depth = torch.rand(n, dtype=torch.float32, device="cuda", generator=gen) * 100.0 + 0.1
+        return (tile << 32) | depth.view(torch.int32).to(torch.int64)
+    raise ValueError(pattern)
+
+
+def main64(args):
+    import torch
+    import vulkan_radix_sort_amd as vrdx
+
+    torch.cuda.set_device(0)
+    sorter = vrdx.Sorter(0)
+    all_ways = ("segmented64", "composed", "per_array", "torch_sort")
+    ways = [w for w in all_ways if not args.only or w in args.only.split(",")]
+    out = open(args.out, "a") if args.out else None
+    verify_step = 1 << 20  # the seed offset of the one input every way is checked on
+
+    for shape in args.shapes.split(","):
+        rng = np.random.default_rng(args.seed)
+        sizes = segment_sizes(shape, rng)
+        offsets_h = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        n = int(offsets_h[-1])
+        offsets = torch.from_numpy(offsets_h.astype(np.uint32).view(np.int32)).cuda()
+        seg_h = np.repeat(np.arange(len(sizes), dtype=np.int64), sizes)
+        seg_ids = torch.from_numpy(seg_h).cuda()
+        starts = [int(x) for x in offsets_h[:-1]]
+        lengths = [int(x) for x in sizes]
+        big = max(lengths) if lengths else 0
+        for pattern in args.patterns.split(","):
+            order = None  # np.lexsort of the verification input: the same for both modes
+            for mode in args.modes.split(","):
+                kv = mode == "kv"
+                keys = torch.empty(n, dtype=torch.int64, device="cuda")
+                values = torch.empty(n, dtype=torch.int32, device="cuda") if kv else None
+                storage = torch.empty(sorter.storage_requirements64(n, key_value=kv).size, dtype=torch.uint8, device="cuda")
+                req32 = (sorter.key_value_storage_requirements(n)).size
+                storage32 = torch.empty(req32, dtype=torch.uint8, device="cuda")
+                loop_storage = torch.empty(max(16, sorter.storage_requirements64(big, key_value=kv).size), dtype=torch.uint8,
+                                           device="cuda")
+                gen = torch.Generator(device="cuda")
+                stream = torch.cuda.current_stream()
+                iota = torch.arange(n, dtype=torch.int32, device="cuda")
+
+                def fresh(step):
+                    gen.manual_seed(args.seed * 1000003 + step)
+                    keys.copy_(make_keys64(torch, pattern, n, gen))
+                    if kv:
+                        values.copy_(iota)
+
+                def run_segmented64():
+                    vrdx.sort_segments64(sorter, keys, offsets, values=values, storage=storage)
+
+                def run_composed():
+                    lo = (keys & 0xFFFFFFFF).to(torch.int32)
+                    hi = (keys >> 32).to(torch.int32)
+                    if not kv:
+                        vrdx.sort_segments(sorter, lo, offsets, values=hi, storage=storage32)
+                        vrdx.sort_segments(sorter, hi, offsets, values=lo, storage=storage32)
+                        keys.copy_((hi.to(torch.int64) << 32) | (lo.to(torch.int64) & 0xFFFFFFFF))
+                        return
+                    index = iota.clone()
+                    vrdx.sort_segments(sorter, lo, offsets, values=index, storage=storage32)
+                    hi = hi[index.to(torch.int64)]
+                    vrdx.sort_segments(sorter, hi, offsets, values=index, storage=storage32)
+                    gather = index.to(torch.int64)
+                    keys.copy_(keys[gather])
+                    values.copy_(values[gather])
+
+                def run_per_array():
+                    s = stream.cuda_stream
+                    kp, sp = keys.data_ptr(), loop_storage.data_ptr()
+                    for b, m in zip(starts, lengths):
+                        if kv:
+                            sorter.cmd_sort64_key_value(s, m, kp, 8 * b, values.data_ptr(), 4 * b, sp, 0)
+                        else:
+                            sorter.cmd_sort64(s, m, kp, 8 * b, sp, 0)
+
+                def run_torch_sort():
+                    by_key, first = torch.sort(keys, stable=True)  # (63-bit keys: the signed order is the unsigned one)
+                    _, second = torch.sort(seg_ids[first], stable=True)
+                    keys.copy_(by_key[second])
+                    if kv:
+                        values.copy_(values[first[second]])
+
+                fns = {"segmented64": run_segmented64, "composed": run_composed, "per_array": run_per_array,
+                       "torch_sort": run_torch_sort}
+                result = {"shape": shape, "keys64": True, "pattern": pattern, "segments": len(sizes), "keys": n,
+                          "key_value": kv, "max_segment": big}
+                times = {w: [] for w in ways}
+                # the ways take turns step by step, so that a drift of the clocks meets all of them alike
+                for step in range(args.warmup + args.steps):
+                    for way in ways:
+                        if way == "per_array" and step >= min(args.warmup, 1) + args.loop_steps:
+                            continue
+                        fresh(step)
+                        torch.cuda.synchronize()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        fns[way]()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        if step >= (min(args.warmup, 1) if way == "per_array" else args.warmup):
+                            times[way].append(e0.elapsed_time(e1))
+                fresh(verify_step)
+                torch.cuda.synchronize()
+                if order is None:
+                    order = np.lexsort((keys.cpu().numpy().view(np.uint64), seg_h))
+                want = keys.cpu().numpy()[order]
+                for way in ways:
+                    fresh(verify_step)
+                    fns[way]()
+                    torch.cuda.synchronize()
+                    ok = np.array_equal(keys.cpu().numpy(), want)
+                    if kv:
+                        ok = ok and np.array_equal(values.cpu().numpy().astype(np.int64), order)
+                    result["match_" + way] = bool(ok)
+                    result[way + "_ms"] = float(np.median(times[way]))
+                    result[way + "_ms_min"] = float(np.min(times[way]))
+                    result[way + "_steps"] = len(times[way])
+                if "segmented64" in ways:
+                    result["status"] = sorter.read_status(stream.cuda_stream, storage.data_ptr(), 0)
+                    for way in ways[1:]:
+                        result["speedup_vs_" + way] = result[way + "_ms"] / result["segmented64_ms"]
+                    result["segmented64_gkeys_s"] = n / (result["segmented64_ms"] * 1e6)
+                line = json.dumps(result)
+                print(line, flush=True)
+                if out:
+                    out.write(line + "\n")
+                    out.flush()
+                del keys, values, storage, storage32, loop_storage, iota
+                torch.cuda.empty_cache()
+    if out:
+        out.close()
+    sorter.destroy()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default=DEFAULT_SHAPES)
@@ -53,6 +203,8 @@ def main():
     ap.add_argument("--only", default="", help="comma list of the ways to run (default: all three)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default="")
+    ap.add_argument("--keys64", action="store_true", help="uint64 keys: segmented64, composed, per_array, torch_sort")
+    ap.add_argument("--patterns", default="uniform,tile_depth", help="--keys64: key patterns")
     args = ap.parse_args()
 
     import torch
@@ -60,6 +212,8 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("segmented_bench.py needs a GPU (there is no CPU fallback)")
+    if args.keys64:
+        return main64(args)
     torch.cuda.set_device(0)
     sorter = vrdx.Sorter(0)
     ways = [w for w in ("segmented", "per_array", "torch_sort") if not args.only or w in args.only.split(",")]

@@ -34,6 +34,7 @@ from .api import (  # noqa: F401
 )
 from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
+from .segmented64 import sort_segments64  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -60,4 +61,5 @@ __all__ = [
     "VERDICT_MSD_SORTED",
     "sort_segments",
     "sort64",
+    "sort_segments64",
 ]

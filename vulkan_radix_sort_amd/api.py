@@ -20,6 +20,8 @@ reference (C++ / Vulkan)                        here
 ``vrdxHipCmdSort64KeyValue`` (HIP only)         ``Sorter.cmd_sort64_key_value(...)``
 ``vrdxHipCmdSort64Indirect`` (HIP only)         ``Sorter.cmd_sort64_indirect(...)``
 ``vrdxHipCmdSort64KeyValueIndirect`` (HIP only) ``Sorter.cmd_sort64_key_value_indirect(...)``
+``vrdxHipCmdSortSegmented64`` (HIP only)        ``Sorter.cmd_sort_segmented64(...)``
+``vrdxHipCmdSortSegmented64KeyValue`` (HIP only) ``Sorter.cmd_sort_segmented64_key_value(...)``
 =============================================  ==============================================
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
@@ -73,6 +75,9 @@ EXPORTED_SYMBOLS = (
     "vrdxHipCmdSort64KeyValue",
     "vrdxHipCmdSort64Indirect",
     "vrdxHipCmdSort64KeyValueIndirect",
+    # many independent arrays of uint64 keys in one call
+    "vrdxHipCmdSortSegmented64",
+    "vrdxHipCmdSortSegmented64KeyValue",
 )
 
 # bits of vrdxHipReadSorterStatus (include/vk_radix_sort.h)
@@ -196,6 +201,10 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxHipCmdSort64Indirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
     lib.vrdxHipCmdSort64KeyValueIndirect.restype = None
     lib.vrdxHipCmdSort64KeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortSegmented64.restype = None
+    lib.vrdxHipCmdSortSegmented64.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortSegmented64KeyValue.restype = None
+    lib.vrdxHipCmdSortSegmented64KeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
     lib.vrdxHipCreateQueryPool.argtypes = [u32, ctypes.POINTER(vp)]
     lib.vrdxHipDestroyQueryPool.restype = None
@@ -369,6 +378,24 @@ class Sorter:
                                                   _handle(offsets), offsets_offset, _handle(keys), keys_offset,
                                                   _handle(values), values_offset, _handle(storage), storage_offset,
                                                   _pool(query_pool), query)
+
+    def cmd_sort_segmented64(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
+                             keys_offset, storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSortSegmented64``: ``cmd_sort_segmented`` of uint64 keys (``keys_offset`` a multiple of 8); storage of
+        ``storage_requirements64(max_element_count)`` bytes."""
+        self._lib.vrdxHipCmdSortSegmented64(_handle(command_buffer), self.handle, max_element_count, segment_count,
+                                            _handle(offsets), offsets_offset, _handle(keys), keys_offset, _handle(storage),
+                                            storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_segmented64_key_value(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset,
+                                       keys, keys_offset, values, values_offset, storage, storage_offset, query_pool=None,
+                                       query=0):
+        """``vrdxHipCmdSortSegmented64KeyValue``: the same with one uint32 value per key; storage of
+        ``storage_requirements64(max_element_count, key_value=True)`` bytes."""
+        self._lib.vrdxHipCmdSortSegmented64KeyValue(_handle(command_buffer), self.handle, max_element_count, segment_count,
+                                                    _handle(offsets), offsets_offset, _handle(keys), keys_offset,
+                                                    _handle(values), values_offset, _handle(storage), storage_offset,
+                                                    _pool(query_pool), query)
 
     def cmd_sort64(self, command_buffer, element_count, keys, keys_offset, storage, storage_offset, query_pool=None,
                    query=0):

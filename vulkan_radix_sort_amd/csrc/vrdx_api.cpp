@@ -793,6 +793,74 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   MaybeRecheckOrder(sorter, stream, atomicRank);
 }
 
+// The segmented sort of 64-bit keys (include/vk_radix_sort.h, vrdxHipCmdSortSegmented64): RecordSegmentedSort with the 64-bit
+// kernels and the 64-bit storage (vrdx_layout.h, MakeSegmented64Layout) -- the same fill, the same three launches, the same
+// slots.  Grids depend on segmentCount, maxElementCount and the CU count only.
+void RecordSegmentedSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
+                           VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
+                           VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                           VkQueryPool queryPool, uint32_t query) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
+  const bool keyValue = valuesBuffer != nullptr;
+  if (maxElementCount > VRDX_MAX_ELEMENTS) {
+    // as in RecordSegmentedSort: segments ending behind the clamped bound are left alone (and flagged on the device)
+    maxElementCount = VRDX_MAX_ELEMENTS;
+    sorter->countClamped.store(1u, std::memory_order_relaxed);
+  }
+  DeviceScope deviceScope(sorter->device);
+  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
+  StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
+  const vrdx::Segmented64Layout layout = vrdx::MakeSegmented64Layout(
+      maxElementCount, sorter->minStorageBufferOffsetAlignment, keyValue, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (segmentCount == 0 || maxElementCount == 0 || !layout.fits) {
+    stamps.Finish();
+    if (segmentCount != 0 && maxElementCount != 0)  // (cannot happen for N >= 1: MakeSegmented64Layout fits every count)
+      EnqueueCheck(sorter, "segmented 64-bit storage layout", hipErrorInvalidValue);
+    return;
+  }
+  const bool atomicRank = sorter->atomicRank.load(std::memory_order_relaxed);
+  vrdx::Segmented64Args a;
+  a.keys = reinterpret_cast<uint64_t*>(BufferAddress(keysBuffer, keysOffset));
+  a.values = keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
+  a.keysScratch = reinterpret_cast<uint64_t*>(storage + layout.keysScratchOffset);
+  a.valuesScratch = keyValue ? reinterpret_cast<uint32_t*>(storage + layout.valuesScratchOffset) : nullptr;
+  a.offsets = reinterpret_cast<const uint32_t*>(BufferAddress(offsetsBuffer, offsetsOffset));
+  a.segmentCount = segmentCount;
+  a.maxCount = maxElementCount;
+  a.midCount = reinterpret_cast<uint32_t*>(storage + layout.midCountOffset);
+  a.midList = reinterpret_cast<uint32_t*>(storage + layout.midListOffset);
+  a.midCap = layout.midCap;
+  a.largeCount = reinterpret_cast<uint32_t*>(storage + layout.largeCountOffset);
+  a.largeList = reinterpret_cast<uint32_t*>(storage + layout.largeListOffset);
+  a.largeCap = layout.largeCap;
+  a.failure = reinterpret_cast<uint32_t*>(storage + VRDX_OFF_FAILURE);
+  a.stickyFailure = sorter->stickyStatus;
+
+  EnqueueCheck(sorter, "segmented_clear_kernel", vrdx::LaunchSegmentedClear64(stream, a));
+  stamps.AdvanceTo(1);
+  const uint32_t cus = (uint32_t)sorter->computeUnits;
+  EnqueueCheck(sorter, "segmented_small64_kernel",
+               vrdx::LaunchSegmented64(stream, vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20), keyValue,
+                                       atomicRank, a));
+  stamps.AdvanceTo(2);
+  // the lists by grid stride, one workgroup per CU: the 1024-thread forms take 66 to 89 registers and 90 to 144 KiB of LDS,
+  // so one is resident per CU
+  const uint32_t midGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.midCap), cus);
+  if (midGrid != 0) {
+    EnqueueCheck(sorter, "segmented_mid64_kernel",
+                 vrdx::LaunchSegmented64(stream, vrdx::kSegmentMid, midGrid, keyValue, atomicRank, a));
+    stamps.AdvanceTo(3);
+  }
+  const uint32_t largeGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.largeCap), cus);
+  if (largeGrid != 0) {
+    EnqueueCheck(sorter, "segmented_large64_kernel",
+                 vrdx::LaunchSegmented64(stream, vrdx::kSegmentLarge, largeGrid, keyValue, atomicRank, a));
+    stamps.AdvanceTo(4);
+  }
+  stamps.Finish();
+  MaybeRecheckOrder(sorter, stream, atomicRank);
+}
+
 // The 64-bit sorts (include/vk_radix_sort.h, vrdxHipCmdSort64[KeyValue][Indirect]): two stable 32-bit key+value sorts, low words first
 // and high words second, each through RecordSort on word arrays inside the storage (vrdx_layout.h, MakeSort64Layout), with
 // the streaming kernels of vrdx_kernels.hip ("64-bit keys") around them:
@@ -1014,6 +1082,23 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
                                      VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
                       valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSortSegmented64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                               uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                               VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
+                               VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
+                        keysOffset, nullptr, 0, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                       uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                       VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                       VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                       VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
+                        keysOffset, valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipGetSorter64StorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,

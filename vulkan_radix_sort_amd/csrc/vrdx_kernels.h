@@ -268,6 +268,40 @@ hipError_t LaunchPermute64(hipStream_t stream, const uint64_t* keys, const uint3
 hipError_t LaunchCopyBack64(hipStream_t stream, uint64_t* keys, uint32_t* values, const uint64_t* keysIn,
                             const uint32_t* valuesIn, uint32_t maxCount, const uint32_t* countPtr);
 
+// ---- segmented sort of 64-bit keys (vrdxHipCmdSortSegmented64[KeyValue]; vrdx_kernels.hip, "segmented sort of 64-bit
+// keys"): the three size classes of the segmented sort, every segment moved through memory once in the in-LDS classes ----
+//   segmented_small64_kernel  256 threads, one workgroup per segment by grid stride: checks the offsets, sorts segments of
+//                             2 ... kSeg64SmallMax keys in LDS (SortInWorkgroup64<256, 16>), lists the bigger ones;
+//   segmented_mid64_kernel    1024 threads over the mid list: SortInWorkgroup64<1024, 16> keys-only (two word planes of
+//                             64 KiB), <1024, 8> key+value (three planes of 32 KiB: 12 bytes x 16384 do not fit the LDS,
+//                             so the key+value mid class ends at 8192);
+//   segmented_large64_kernel  1024 threads over the large list: SegmentLsd64, tiles of kSeg64LargeTile keys.
+constexpr uint32_t kSeg64SmallMax = 256u * 16u;
+constexpr uint32_t kSeg64MidMax = 1024u * 16u;         // keys-only
+constexpr uint32_t kSeg64MidMaxKeyValue = 1024u * 8u;  // key+value
+constexpr uint32_t kSeg64LargeTile = 1024u * 8u;       // keys per tile of the large kernel's passes, both forms
+struct Segmented64Args {
+  uint64_t* keys;
+  uint32_t* values;             // KV only
+  uint64_t* keysScratch;        // large segments: the same index range as in keys
+  uint32_t* valuesScratch;      // KV only
+  const uint32_t* offsets;      // segmentCount + 1 words, read on the device
+  uint32_t segmentCount;
+  uint32_t maxCount;            // no segment may end behind it
+  uint32_t* midCount;           // appended to by the small kernel (zeroed by the fill in front of it)
+  uint32_t* midList;            // [midCap] segment ids
+  uint32_t midCap;
+  uint32_t* largeCount;
+  uint32_t* largeList;          // [largeCap] segment ids
+  uint32_t largeCap;
+  uint32_t* failure;            // the storage's failure word (word 3 of the header): VRDX_HIP_STATUS_SEGMENTS_INVALID
+  uint32_t* stickyFailure;      // the sorter's word
+};
+// The fill in front of the first launch is segmented_clear_kernel as it is: the same header words and list counters.
+hipError_t LaunchSegmentedClear64(hipStream_t stream, const Segmented64Args& args);
+hipError_t LaunchSegmented64(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                             const Segmented64Args& args);
+
 // ---- the kernels' dynamic LDS and the MSD plan's grids: one definition for the kernels (vrdx_kernels.hip) and for both
 // launch backends (vrdx_launch.inc) ----
 // Key+value tiles replay the permutation for the values through the SAME staging buffer after the
@@ -303,6 +337,20 @@ constexpr size_t SmallSortLdsWords(int threads, int kpt, bool kv) {
 constexpr size_t SegmentLargeLdsWords(bool kv) {
   // staging (keys, values) | wave counters 16 x 256 | scan scratch 16 | bases 4 x 256 | tile starts 256 | tile counts 256 | 16
   return (size_t)kSegLargeTile * (kv ? 2 : 1) + 16 * 256 + 16 + 4 * 256 + 256 + 256 + 16;
+}
+
+// SortInWorkgroup64: one staging plane per key word (and one for the values) | wave counters | scan scratch and the two
+// masks of varying bytes.  256 x 16: 36 KiB keys-only, 52 KiB key+value; 1024 x 16 keys-only: 144 KiB; 1024 x 8 key+value:
+// 112 KiB.
+constexpr size_t SortInWorkgroup64LdsWords(int threads, int kpt, bool kv) {
+  return (size_t)threads * kpt * (kv ? 3 : 2) + (size_t)(threads / 64) * 256 + 16;
+}
+constexpr int Seg64MidKpt(bool kv) { return (int)((kv ? kSeg64MidMaxKeyValue : kSeg64MidMax) / 1024u); }
+
+constexpr size_t Segment64LargeLdsWords(bool kv) {
+  // staging (low words, high words, values) | wave counters 16 x 256 | scan scratch 32 | bases 8 x 256 | tile starts 256 |
+  // tile counts 256 | 16: 90 KiB keys-only, 122 KiB key+value
+  return (size_t)kSeg64LargeTile * (kv ? 3 : 2) + 16 * 256 + 32 + 8 * 256 + 256 + 256 + 16;
 }
 
 // histogram_msd_kernel

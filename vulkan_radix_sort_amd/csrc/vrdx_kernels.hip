@@ -3423,6 +3423,439 @@ __global__ __launch_bounds__(kSort64Threads) void copy_back64_kernel(uint64_t* _
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// segmented sort of 64-bit keys (vrdxHipCmdSortSegmented64[KeyValue]): the segmented sort's three size classes with the
+// key held as two words
+// ---------------------------------------------------------------------------------------------
+// A key is a pair of register arrays, lo[] and hi[]; a ranking pass ranks ONE of them by one of its bytes with the same
+// RankAtomic / RankBallot and wave-private counters as every other kernel, and moves both words (and the value) through
+// the staging buffer: one word plane per array, each with the StagingSlot swizzle of the 4-byte kernels, so every LDS
+// access is a 4-byte one with the bank pattern those kernels were tuned for.  Up to eight passes -- the low word's four
+// bytes, then the high word's -- between one load and one store of the segment.
+// A byte that is the same in every key of the segment is not ranked at all: before the passes the workgroup ORs
+// key ^ first key over the segment's real elements (pads do not take part: they stay behind the real keys in every pass
+// that runs, and a pass that does not run leaves everything where it is), and a pass whose byte of that mask is zero is
+// skipped.  tile id << 32 | depth keys, hashes of fewer than 64 bits and counters take five or six passes instead of eight.
+
+// The OR over the 64 lanes of a wave, in lane 63 (the DPP moves of WaveInclusiveScan: lanes that receive nothing get 0).
+__device__ __forceinline__ uint32_t WaveInclusiveOr(uint32_t v) {
+  int x = (int)v;
+  x |= __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true);   // row_shr:1
+  x |= __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, true);   // row_shr:2
+  x |= __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, true);   // row_shr:4
+  x |= __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, true);   // row_shr:8
+  x |= __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+  x |= __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+  return (uint32_t)x;
+}
+
+// Wave-striped load of KPT 8-byte keys per lane as two word arrays: lo[i], hi[i] = base[first + 64 * i] (all ones where
+// the index is >= n).  first + 64 * KPT stays far below 2^29 (a tile's positions), so the byte offset fits 32 bits.
+template <int KPT>
+__device__ __forceinline__ void LoadStriped64(const uint64_t* base, uint32_t first, uint32_t n, uint32_t (&lo)[KPT],
+                                              uint32_t (&hi)[KPT], uint32_t slots) {
+  const char* const bytes = reinterpret_cast<const char*>(base);
+  const uint32_t offset = first * 8u;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    uint64_t k = ~0ull;
+    if (first + i * 64 < n) k = *reinterpret_cast<const uint64_t*>(bytes + ((uint64_t)offset + (uint64_t)(i * 512)));
+    lo[i] = (uint32_t)k;
+    hi[i] = (uint32_t)(k >> 32);
+  }
+}
+
+// One ranking pass of SortInWorkgroup64 by byte `shift / 8` of word[] (lo or hi itself): rank, scan, both words (and the
+// value) to their sorted slots of the staging planes, and back in wave-striped order.
+template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK>
+__device__ __forceinline__ void RankPass64(const uint32_t (&word)[KPT], uint32_t (&lo)[KPT], uint32_t (&hi)[KPT],
+                                           uint32_t (&val)[KV ? KPT : 1], uint32_t shift, uint32_t first, uint32_t slots,
+                                           uint32_t* smem) {
+  constexpr int WAVES = THREADS / 64;
+  constexpr uint32_t TILE = THREADS * KPT;
+  uint32_t* const stagedLo = smem;
+  uint32_t* const stagedHi = smem + TILE;
+  uint32_t* const stagedValues = smem + 2 * TILE;             // key+value
+  uint32_t* const waveHist = smem + TILE * (KV ? 3 : 2);      // WAVES x 256
+  uint32_t* const scanScratch = waveHist + WAVES * 256;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t* const myHist = waveHist + wave * 256;
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;  // my own row: no barrier needed before ranking
+  uint32_t rank[KPT];
+  if constexpr (ATOMIC_RANK)
+    RankAtomic<KPT, false, true>(word, shift, myHist, lane, rank, slots);
+  else
+    RankBallot<KPT, false, true>(word, shift, myHist, lane, rank, slots);
+  LdsBarrier();
+  // (as in SortInWorkgroup: keeps the pass-independent read-back addresses out of the registers between the passes)
+  uint32_t firstNow = first;
+  asm volatile("" : "+v"(firstNow));
+
+  uint32_t count = 0;
+  if (tid < 256) {
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) count += waveHist[w * 256 + tid];
+  }
+  const uint32_t exclusive = BlockExclusiveScan256(tid < 256 ? count : 0u, scanScratch, tid);
+  if (tid < 256) {
+    uint32_t run = exclusive;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      const uint32_t c = waveHist[w * 256 + tid];
+      waveHist[w * 256 + tid] = run;
+      run += c;
+    }
+  }
+  LdsBarrier();
+
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[(word[i] >> shift) & 0xFFu]);
+    stagedLo[slot] = lo[i];
+    stagedHi[slot] = hi[i];
+    if constexpr (KV) stagedValues[slot] = val[i];
+  }
+  LdsBarrier();
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    const uint32_t slot = StagingSlot<TILE>(firstNow + 64 * i);
+    lo[i] = stagedLo[slot];
+    hi[i] = stagedHi[slot];
+    if constexpr (KV) val[i] = stagedValues[slot];
+  }
+  // the next pass writes the staging planes only after two more barriers
+}
+
+// The sort of n <= THREADS * KPT 64-bit keys inside one workgroup, in[0..n) -> out[0..n) (in == out: in place): the shape
+// of SortInWorkgroup.  Pads are the all-ones key with value 0: last in memory order and the largest key, so every stable
+// pass leaves them behind the real elements -- real all-ones keys included, which sit in front of them from the start.
+// LDS: SortInWorkgroup64LdsWords (vrdx_kernels.h).
+template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK>
+__device__ __forceinline__ void SortInWorkgroup64(const uint64_t* keysIn, uint64_t* keysOut, const uint32_t* valuesIn,
+                                                  uint32_t* valuesOut, uint32_t n, uint32_t* smem) {
+  constexpr int WAVES = THREADS / 64;
+  constexpr uint32_t TILE = THREADS * KPT;
+  static_assert(KPT % 4 == 0, "chunks of four slots");
+  uint32_t* const varying = smem + TILE * (KV ? 3 : 2) + WAVES * 256 + 8;  // [0]: low word, [1]: high word (behind the scan's scratch)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the ceil(n / 256) chunks of four 64-element slots dealt out evenly over the waves, as in SortInWorkgroup
+  const uint32_t chunks = (n + 255u) / 256u;
+  const uint32_t base = chunks / WAVES, extra = chunks % WAVES;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+  const uint32_t slots = 4u * (base + (w < extra ? 1u : 0u));
+  const uint32_t first = 256u * (w * base + (w < extra ? w : extra)) + lane;
+
+  uint32_t lo[KPT], hi[KPT];
+  uint32_t val[KV ? KPT : 1];
+  if (tid < 2) varying[tid] = 0;
+  const uint64_t key0 = keysIn[0];  // uniform (n >= 1)
+  LoadStriped64<KPT>(keysIn, first, n, lo, hi, slots);
+  if constexpr (KV) LoadStriped<KPT, false, true>(valuesIn, first, n, false, 0u, val, slots);
+
+  // which bytes differ between any two keys of the segment
+  uint32_t diffLo = 0, diffHi = 0;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    if (first + 64 * i < n) {
+      diffLo |= lo[i] ^ (uint32_t)key0;
+      diffHi |= hi[i] ^ (uint32_t)(key0 >> 32);
+    }
+  }
+  diffLo = WaveInclusiveOr(diffLo);
+  diffHi = WaveInclusiveOr(diffHi);
+  LdsBarrier();  // varying[] is zero
+  if (lane == 63) {
+    if (diffLo != 0) atomicOr(&varying[0], diffLo);
+    if (diffHi != 0) atomicOr(&varying[1], diffHi);
+  }
+  LdsBarrier();
+  const uint32_t varyingLo = (uint32_t)__builtin_amdgcn_readfirstlane((int)varying[0]);
+  const uint32_t varyingHi = (uint32_t)__builtin_amdgcn_readfirstlane((int)varying[1]);
+
+  // two loops, one per word: a run-time choice between the arrays inside one loop would copy registers
+#pragma unroll 1
+  for (uint32_t shift = 0; shift < 32; shift += 8) {
+    if (((varyingLo >> shift) & 0xFFu) == 0) continue;  // uniform: every key has the same byte here
+    RankPass64<THREADS, KPT, KV, ATOMIC_RANK>(lo, lo, hi, val, shift, first, slots, smem);
+  }
+#pragma unroll 1
+  for (uint32_t shift = 0; shift < 32; shift += 8) {
+    if (((varyingHi >> shift) & 0xFFu) == 0) continue;
+    RankPass64<THREADS, KPT, KV, ATOMIC_RANK>(hi, lo, hi, val, shift, first, slots, smem);
+  }
+
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    const uint32_t index = first + 64 * i;
+    if (index < n) {
+      keysOut[index] = (uint64_t)hi[i] << 32 | lo[i];
+      if constexpr (KV) valuesOut[index] = val[i];
+    }
+  }
+}
+
+// SegmentBounds for any args struct with offsets, maxCount, failure and stickyFailure: ONE statement of the offset rule for
+// the kernels added from here on.  (SegmentBounds itself stays as it is, a non-template on SegmentedArgs: the 32-bit kernels'
+// code is not to move.)
+template <typename Args>
+__device__ __forceinline__ bool SegmentBoundsOf(const Args& a, uint32_t segment, bool flag, uint32_t* begin, uint32_t* end) {
+  const uint32_t b = a.offsets[segment];
+  const uint32_t e = a.offsets[segment + 1];
+  if (b <= e && e <= a.maxCount) {
+    *begin = b;
+    *end = e;
+    return true;
+  }
+  if (flag && threadIdx.x == 0) {
+    atomicOr(a.failure, kSegmentsInvalid);
+    if (a.stickyFailure != nullptr) atomicOr(a.stickyFailure, kSegmentsInvalid);
+  }
+  return false;
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(256) void segmented_small64_kernel(Segmented64Args a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
+  for (uint32_t s = blockIdx.x; s < a.segmentCount; s += gridDim.x) {
+    uint32_t begin = 0, end = 0;
+    if (!SegmentBoundsOf(a, s, true, &begin, &end)) continue;  // uniform
+    const uint32_t n = end - begin;
+    if (n > kSeg64SmallMax) {
+      if (threadIdx.x == 0) {
+        const bool mid = n <= kMidMax;
+        const uint32_t slot = atomicAdd(mid ? a.midCount : a.largeCount, 1u);
+        if (slot < (mid ? a.midCap : a.largeCap)) (mid ? a.midList : a.largeList)[slot] = s;
+      }
+      continue;
+    }
+    if (n < 2) continue;
+    LdsBarrier();  // the previous segment's read-back of the staging planes is over
+    SortInWorkgroup64<256, 16, KV, ATOMIC_RANK>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
+                                                KV ? a.values + begin : nullptr, n, smem);
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_mid64_kernel(Segmented64Args a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
+  const uint32_t listed = min(*a.midCount, a.midCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = a.midList[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBoundsOf(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    const uint32_t n = end - begin;
+    if (n <= kSeg64SmallMax || n > kMidMax) continue;
+    LdsBarrier();
+    SortInWorkgroup64<1024, (int)(kMidMax / 1024u), KV, ATOMIC_RANK>(a.keys + begin, a.keys + begin,
+                                                                     KV ? a.values + begin : nullptr,
+                                                                     KV ? a.values + begin : nullptr, n, smem);
+  }
+}
+
+// One large segment of 64-bit keys in one workgroup: SegmentLsd with 8-byte keys.  One read of the segment builds all EIGHT
+// byte histograms; a pass whose byte is the same in every key is skipped (the upper bytes of the high word usually are,
+// inside one segment); the others walk the segment in tiles of kSeg64LargeTile keys, in order, ping-ponging between the
+// caller's range and the same index range of the 8-byte scratch; an odd number of passes ends with a copy back.
+// LDS: Segment64LargeLdsWords (vrdx_kernels.h).
+static_assert(8 * 256 * kSegHistCopies <= 2 * kSeg64LargeTile, "the histogram replicas alias the two staging planes");
+
+template <bool KV, bool ATOMIC_RANK>
+__device__ __forceinline__ void SegmentLsd64(uint64_t* keys, uint32_t* values, uint64_t* keysScratch, uint32_t* valuesScratch,
+                                             uint32_t n, uint32_t* smem) {
+  constexpr int THREADS = 1024, KPT = (int)(kSeg64LargeTile / 1024u), WAVES = THREADS / 64;
+  constexpr uint32_t TILE = kSeg64LargeTile;
+  uint32_t* const stagedLo = smem;
+  uint32_t* const stagedHi = smem + TILE;
+  uint32_t* const stagedValues = smem + 2 * TILE;  // KV only
+  uint32_t* const waveHist = smem + TILE * (KV ? 3 : 2);
+  uint32_t* const scanScratch = waveHist + WAVES * 256;  // 32: two rounds of the table scan
+  uint32_t* const bases = scanScratch + 32;      // [pass][digit]: where the next key of digit d goes, this pass
+  uint32_t* const tileStart = bases + 8 * 256;   // tile-local position of digit d's first key
+  uint32_t* const tileCount = tileStart + 256;
+  uint32_t* const misc = tileCount + 256;        // [0]: bit p = pass p is not trivial
+  uint32_t* const bins = smem;                   // [pass][digit][copy], before the passes (aliases the staging planes)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // 1. histograms
+  for (uint32_t i = tid; i < 8 * 256 * kSegHistCopies; i += THREADS) bins[i] = 0;
+  if (tid == 0) misc[0] = 0;
+  LdsBarrier();
+  const uint32_t copy = tid & (kSegHistCopies - 1);
+  auto count = [&](uint64_t key) {
+    const uint32_t l = (uint32_t)key, h = (uint32_t)(key >> 32);
+#pragma unroll
+    for (uint32_t p = 0; p < 4; ++p) {
+      atomicAdd(&bins[(p * 256 + ((l >> (8 * p)) & 0xFFu)) * kSegHistCopies + copy], 1u);
+      atomicAdd(&bins[((p + 4) * 256 + ((h >> (8 * p)) & 0xFFu)) * kSegHistCopies + copy], 1u);
+    }
+  };
+  {
+    constexpr uint32_t U = 4;  // loads in flight per lane
+    uint32_t i = tid;
+    for (; i + (U - 1) * THREADS < n; i += U * THREADS) {
+      uint64_t k[U];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) k[u] = keys[i + u * THREADS];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) count(k[u]);
+    }
+    for (; i < n; i += THREADS) count(keys[i]);
+  }
+  LdsBarrier();
+#pragma unroll 1
+  for (uint32_t round = 0; round < 2; ++round) {
+    // thread t: pass 4 * round + t / 256, digit t % 256 -- the exclusive scan over the 256 digits of each pass (four waves
+    // per pass)
+    const uint32_t p = 4u * round + ((uint32_t)tid >> 8), d = (uint32_t)tid & 255u;
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kSegHistCopies; ++r) c += bins[(p * 256 + d) * kSegHistCopies + ((r + tid) & (kSegHistCopies - 1))];
+    const uint32_t x = WaveInclusiveScan(c);
+    if (lane == 63) scanScratch[16 * round + wave] = x;
+    if (c != 0 && c != n) atomicOr(&misc[0], 1u << p);  // two digits at least: the pass moves keys
+    LdsBarrier();
+    uint32_t add = 0;
+    for (int v = wave & ~3; v < wave; ++v) add += scanScratch[16 * round + v];
+    bases[p * 256 + d] = x - c + add;
+  }
+  LdsBarrier();
+  const uint32_t active = (uint32_t)__builtin_amdgcn_readfirstlane((int)misc[0]);
+
+  // 2. the passes
+  uint64_t* src = keys;
+  uint64_t* dst = keysScratch;
+  uint32_t* srcV = values;
+  uint32_t* dstV = valuesScratch;
+  uint32_t* const myHist = waveHist + wave * 256;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+  // one pass by byte `shift / 8` of the low (HI = false_type) or the high word
+  auto runPass = [&](auto hiWord, uint32_t pass) {
+    constexpr bool HI = decltype(hiWord)::value;
+    const uint32_t shift = 8 * (pass & 3u);
+    uint32_t* const base = bases + pass * 256;
+#pragma unroll 1
+    for (uint32_t t0 = 0; t0 < n; t0 += TILE) {
+      const uint32_t m = min(TILE, n - t0);
+      // the chunks of four 64-key slots dealt out evenly over the waves, as in SortInWorkgroup: pads (the largest key) only
+      // in the last chunk, behind every real key of the tile
+      const uint32_t chunks = (m + 255u) / 256u;
+      const uint32_t per = chunks / WAVES, extra = chunks % WAVES;
+      const uint32_t slots = 4u * (per + (w < extra ? 1u : 0u));
+      const uint32_t first = 256u * (w * per + (w < extra ? w : extra)) + lane;
+      uint32_t lo[KPT], hi[KPT];
+      uint32_t val[KV ? KPT : 1];
+      LoadStriped64<KPT>(src + t0, first, m, lo, hi, slots);
+      if constexpr (KV) LoadStriped<KPT, false, true>(srcV + t0, first, m, false, 0u, val, slots);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;
+      uint32_t rank[KPT];
+      if constexpr (ATOMIC_RANK)
+        RankAtomic<KPT, false, true>(HI ? hi : lo, shift, myHist, lane, rank, slots);
+      else
+        RankBallot<KPT, false, true>(HI ? hi : lo, shift, myHist, lane, rank, slots);
+      LdsBarrier();
+      uint32_t c = 0;
+      if (tid < 256) {
+#pragma unroll
+        for (int v = 0; v < WAVES; ++v) c += waveHist[v * 256 + tid];
+      }
+      const uint32_t exclusive = BlockExclusiveScan256(tid < 256 ? c : 0u, scanScratch, tid);
+      if (tid < 256) {
+        uint32_t run = exclusive;
+#pragma unroll
+        for (int v = 0; v < WAVES; ++v) {
+          const uint32_t h = waveHist[v * 256 + tid];
+          waveHist[v * 256 + tid] = run;
+          run += h;
+        }
+        tileStart[tid] = exclusive;
+        tileCount[tid] = tid == 255 ? c - (256u * chunks - m) : c;  // (the pads are digit 255's last keys)
+      }
+      LdsBarrier();
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        if (i % 4 == 0 && (uint32_t)i >= slots) break;
+        const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[((HI ? hi[i] : lo[i]) >> shift) & 0xFFu]);
+        stagedLo[slot] = lo[i];
+        stagedHi[slot] = hi[i];
+        if constexpr (KV) stagedValues[slot] = val[i];
+      }
+      LdsBarrier();
+      // sorted position q of the tile -> base[d] + q - tileStart[d]: runs of one digit land contiguously
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        if (i % 4 == 0 && (uint32_t)i >= slots) break;
+        const uint32_t q = first + 64 * i;
+        if (q < m) {
+          const uint32_t slot = StagingSlot<TILE>(q);
+          const uint32_t kl = stagedLo[slot], kh = stagedHi[slot];
+          const uint32_t d = ((HI ? kh : kl) >> shift) & 0xFFu;
+          const uint32_t to = base[d] + q - tileStart[d];
+          // always < n while the segment is this workgroup's alone; segments that overlap (offsets that are not monotone,
+          // flagged by the small kernel) may change keys under the counts, and must still never write outside the range
+          if (to < n) {
+            dst[to] = (uint64_t)kh << 32 | kl;
+            if constexpr (KV) dstV[to] = stagedValues[slot];
+          }
+        }
+      }
+      LdsBarrier();  // every lane has read base[] and tileStart[] of this tile
+      if (tid < 256) base[tid] += tileCount[tid];
+      // (the next tile reads base[] two barriers later, and writes the staging planes and tileStart[] one barrier later)
+    }
+    __syncthreads();  // this pass's stores are complete before the next pass (or the copy back) reads them
+    uint64_t* const t = src;
+    src = dst;
+    dst = t;
+    uint32_t* const tv = srcV;
+    srcV = dstV;
+    dstV = tv;
+  };
+#pragma unroll 1
+  for (uint32_t pass = 0; pass < 4; ++pass) {
+    if (((active >> pass) & 1u) == 0) continue;  // uniform
+    runPass(std::false_type{}, pass);
+  }
+#pragma unroll 1
+  for (uint32_t pass = 4; pass < 8; ++pass) {
+    if (((active >> pass) & 1u) == 0) continue;
+    runPass(std::true_type{}, pass);
+  }
+
+  // 3. an odd number of passes left the result in the scratch range
+  if (src != keys) {
+    for (uint32_t i = tid; i < n; i += THREADS) {
+      keys[i] = src[i];
+      if constexpr (KV) values[i] = srcV[i];
+    }
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_large64_kernel(Segmented64Args a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
+  const uint32_t listed = min(*a.largeCount, a.largeCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = a.largeList[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBoundsOf(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    if (end - begin <= kMidMax) continue;
+    __syncthreads();  // the previous segment is done (its copy back included)
+    SegmentLsd64<KV, ATOMIC_RANK>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
+                                  KV ? a.valuesScratch + begin : nullptr, end - begin, smem);
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs

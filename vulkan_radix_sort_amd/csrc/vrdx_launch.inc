@@ -202,7 +202,32 @@
   X(kPermute64, (&permute64_kernel), kSort64Threads, 0, \
     "_ZN4vrdx16permute64_kernelEPKmPKjS3_PjPmjS3_") \
   X(kCopyBack64, (&copy_back64_kernel), kSort64Threads, 0, \
-    "_ZN4vrdx18copy_back64_kernelEPmPjPKmPKjjS5_")
+    "_ZN4vrdx18copy_back64_kernelEPmPjPKmPKjjS5_") \
+  /* the segmented sort of 64-bit keys [small | mid | large][key-value][atomic rank] */ \
+  X(kSegmented64Small, (&segmented_small64_kernel<false, false>), 256, SortInWorkgroup64LdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx24segmented_small64_kernelILb0ELb0EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64SmallA, (&segmented_small64_kernel<false, true>), 256, SortInWorkgroup64LdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx24segmented_small64_kernelILb0ELb1EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64SmallV, (&segmented_small64_kernel<true, false>), 256, SortInWorkgroup64LdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx24segmented_small64_kernelILb1ELb0EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64SmallVA, (&segmented_small64_kernel<true, true>), 256, SortInWorkgroup64LdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx24segmented_small64_kernelILb1ELb1EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64Mid, (&segmented_mid64_kernel<false, false>), 1024, SortInWorkgroup64LdsWords(1024, Seg64MidKpt(false), false) * 4, \
+    "_ZN4vrdx22segmented_mid64_kernelILb0ELb0EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64MidA, (&segmented_mid64_kernel<false, true>), 1024, SortInWorkgroup64LdsWords(1024, Seg64MidKpt(false), false) * 4, \
+    "_ZN4vrdx22segmented_mid64_kernelILb0ELb1EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64MidV, (&segmented_mid64_kernel<true, false>), 1024, SortInWorkgroup64LdsWords(1024, Seg64MidKpt(true), true) * 4, \
+    "_ZN4vrdx22segmented_mid64_kernelILb1ELb0EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64MidVA, (&segmented_mid64_kernel<true, true>), 1024, SortInWorkgroup64LdsWords(1024, Seg64MidKpt(true), true) * 4, \
+    "_ZN4vrdx22segmented_mid64_kernelILb1ELb1EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64Large, (&segmented_large64_kernel<false, false>), 1024, Segment64LargeLdsWords(false) * 4, \
+    "_ZN4vrdx24segmented_large64_kernelILb0ELb0EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64LargeA, (&segmented_large64_kernel<false, true>), 1024, Segment64LargeLdsWords(false) * 4, \
+    "_ZN4vrdx24segmented_large64_kernelILb0ELb1EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64LargeV, (&segmented_large64_kernel<true, false>), 1024, Segment64LargeLdsWords(true) * 4, \
+    "_ZN4vrdx24segmented_large64_kernelILb1ELb0EEEvNS_15Segmented64ArgsE") \
+  X(kSegmented64LargeVA, (&segmented_large64_kernel<true, true>), 1024, Segment64LargeLdsWords(true) * 4, \
+    "_ZN4vrdx24segmented_large64_kernelILb1ELb1EEEvNS_15Segmented64ArgsE")
 
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
@@ -354,6 +379,22 @@ hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t 
                            const SegmentedArgs& args) {
   if (grid == 0) return hipErrorInvalidValue;
   return Launch(KernelId(kSegmentedSmall - 3 * (2 * keyValue + atomicRank) + sizeClass), grid, stream, args);
+}
+
+// ---- segmented sort of 64-bit keys ------------------------------------------------------------------
+hipError_t LaunchSegmentedClear64(hipStream_t stream, const Segmented64Args& args) {
+  // segmented_clear_kernel reads the failure word and the two counters only
+  SegmentedArgs clear = {};
+  clear.midCount = args.midCount;
+  clear.largeCount = args.largeCount;
+  clear.failure = args.failure;
+  return Launch(kSegmentedClear, 1, stream, clear);
+}
+
+hipError_t LaunchSegmented64(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                             const Segmented64Args& args) {
+  if (grid == 0) return hipErrorInvalidValue;
+  return Launch(Form(KernelId(kSegmented64Small + 4 * sizeClass), keyValue, atomicRank), grid, stream, args);
 }
 
 // ---- 64-bit keys ------------------------------------------------------------------------------------

@@ -232,6 +232,44 @@ static inline Sort64Layout MakeSort64Layout(uint32_t maxElementCount, uint32_t a
   return s;
 }
 
+// The segmented 64-bit sorts' carving of the 64-bit storage (vrdxHipCmdSortSegmented64[KeyValue]; RecordSegmentedSort64 in
+// vrdx_api.cpp): header, list counters and lists where MakeSegmentedLayout keeps them -- inside the inner 32-bit storage --
+// and the scratch arrays where MakeSort64Layout keeps its word arrays, behind it:
+//   [0, 16)                        header words 0-3
+//   midCountOffset, largeCountOffset, midListOffset, largeListOffset   as in SegmentedLayout; the large list holds
+//                                  N / (midMax + 1) ids: a large segment has more than midMax elements (vrdx_kernels.h:
+//                                  16384 keys-only, 8192 key+value)
+//   keysScratchOffset = loOffset   uint64[N] on a 128-byte line: A and B of the 64-bit sorts, 2 x Align(4 N, 128) bytes
+//   valuesScratchOffset = keysTempOffset   key+value only: uint32[N] in the front half of T
+struct Segmented64Layout {
+  uint64_t midCountOffset, largeCountOffset;
+  uint64_t midListOffset, largeListOffset;
+  uint32_t midCap, largeCap;
+  uint64_t keysScratchOffset, valuesScratchOffset;
+  bool fits;  // every region lies inside the requirement of its form, the lists in front of the scratch arrays
+};
+
+static inline Segmented64Layout MakeSegmented64Layout(uint32_t maxElementCount, uint32_t align, bool keyValue,
+                                                      uint64_t storageAddress = 0) {
+  const StorageLayout l = MakeLayout(maxElementCount, align, 0, storageAddress);
+  const Sort64Layout w = MakeSort64Layout(maxElementCount, align, storageAddress);
+  Segmented64Layout s;
+  s.midCountOffset = l.histogramOffset;
+  s.largeCountOffset = l.histogramOffset + 256;
+  s.midCap = maxElementCount / (256u * 16u + 1u);
+  s.largeCap = maxElementCount / (keyValue ? 1024u * 8u + 1u : 1024u * 16u + 1u);
+  s.midListOffset = l.msdBucketOffset;
+  s.largeListOffset = s.midListOffset + 4ull * s.midCap;
+  const uint64_t listsEnd = s.largeListOffset + 4ull * s.largeCap;
+  s.keysScratchOffset = w.loOffset;
+  s.valuesScratchOffset = w.keysTempOffset;
+  const uint64_t keysEnd = s.keysScratchOffset + (uint64_t)maxElementCount * sizeof(uint64_t);
+  const uint64_t valuesEnd = s.valuesScratchOffset + (uint64_t)maxElementCount * sizeof(uint32_t);
+  s.fits = listsEnd <= w.innerSize && keysEnd <= s.valuesScratchOffset &&
+           (keyValue ? valuesEnd <= w.keyValueSize : keysEnd <= w.keysOnlySize);
+  return s;
+}
+
 // The MSD plan's scatter (msd_scatter_or_pass0_kernel, one workgroup per CU and tile) cuts the sort into EQUAL tiles that fill whole
 // rounds of `cus` tiles: keys per tile, a multiple of 4096 (four 64-key slots per wave of its 1024 threads), at most 32768.
 // 520 tiles of 32768 keys would cost three rounds, the third for eight tiles; 768 tiles of 24576 cost three rounds of three
