@@ -149,6 +149,14 @@ void vrdxGetSorterKeyValueStorageRequirements(VrdxSorter sorter, uint32_t maxEle
  *                 role).  Pass 0 is a second role of the scatter launch, and beyond 18.1 M pass 1 one of the bucket
  *                 launch -- when the device turns the plan down, [3,4] IS pass 0 and [4,5] pass 1
  *   ONE_WORKGROUP [13,14] the one kernel
+ *
+ * Alignment and bounds, for vrdxCmdSort, vrdxCmdSortIndirect, vrdxCmdSortKeyValue and vrdxCmdSortKeyValueIndirect alike:
+ *   keysBuffer + keysOffset, valuesBuffer + valuesOffset and indirectBuffer + indirectOffset are multiples of 4.  Nothing
+ *   more is required of them: an array may start at any uint32 of a larger allocation (keys + 1, a packed batch), and keys,
+ *   values and the count need not share a residue mod 16.
+ *   storageBuffer + storageOffset is a multiple of 16.
+ *   Nothing outside [0, elementCount) of the caller's arrays is written -- with a device-side count, nothing from
+ *   min(count, maxElementCount) on -- and nothing outside the storage requirement; the count word is only read.
  */
 void vrdxCmdSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount,
                  VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
@@ -191,6 +199,8 @@ void vrdxCmdSortKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorte
  * Order: every segment is sorted ascending as uint32, stably; values travel with their keys.  Elements before o[0] and from
  * o[segmentCount] on are not touched.
  * Storage: what vrdxGetSorter[KeyValue]StorageRequirements(maxElementCount) returns; one sort in flight per storage.
+ * Alignment: keysBuffer + keysOffset, valuesBuffer + valuesOffset and offsetsBuffer + offsetsOffset are multiples of 4, and
+ * nothing more is required of them; storageBuffer + storageOffset is a multiple of 16.
  * Bad offsets: a segment with o[i] > o[i+1] or o[i+1] > maxElementCount is left alone and the sort raises
  * VRDX_HIP_STATUS_SEGMENTS_INVALID in the storage's failure word (vrdxHipReadStatus) and in the sorter's word
  * (vrdxHipReadSorterStatus).  Any offsets that are not monotone raise it, so a clear bit means every segment was sorted (with

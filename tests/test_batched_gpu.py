@@ -62,6 +62,50 @@ def test_hip_shard_executor_sorts_mixed_arrays_through_one_storage(oracle):
     ex.close()
 
 
+def test_hip_shard_executor_sorts_views_into_one_packed_buffer(oracle):
+    """The arrays of a batch as views into ONE packed buffer at odd element offsets (4, 8 and 12 mod 16, as a caller that
+    packs its arrays back to back hands them over), a sentinel word between neighbours: every size regime of the executor's
+    sorts, keys-only and key+value with random values, each view bit-exact and every sentinel intact."""
+    import torch
+    from vulkan_radix_sort_amd.batched import HipShardExecutor
+    device = torch.cuda.current_device()
+    ex = HipShardExecutor(device)
+    sentinel = np.uint32(0x5EA15EA1)
+    sizes = [5001, 70_003, 1, 16385, 300_002, 4097, 1_000_003]
+    starts, cursor = [], 0
+    for i, n in enumerate(sizes):
+        cursor += 1                                   # at least one sentinel in front ...
+        cursor += (1 + i % 3 - cursor) % 4            # ... and the view at element 1, 2 or 3 mod 4
+        starts.append(cursor)
+        cursor += n
+    total = cursor + 1
+    host_keys, host_values = np.full(total, sentinel, np.uint32), np.full(total, sentinel, np.uint32)
+    expected = []
+    for i, (n, at) in enumerate(zip(sizes, starts)):
+        k, v = oracle.generate(500 + i, n, 32 if i % 2 else 16)
+        host_keys[at:at + n], host_values[at:at + n] = k, v
+        expected.append(oracle.sort(k, v if i % 2 == 0 else None))
+    packed_keys = torch.from_numpy(host_keys.view(np.int32).copy()).cuda(device)
+    packed_values = torch.from_numpy(host_values.view(np.int32).copy()).cuda(device)
+    assert packed_keys.data_ptr() % 16 == 0 and packed_values.data_ptr() % 16 == 0
+    arrays = [(packed_keys[at:at + n], packed_values[at:at + n] if i % 2 == 0 else None)
+              for i, (n, at) in enumerate(zip(sizes, starts))]
+    assert sorted({k.data_ptr() % 16 for k, _ in arrays}) == [4, 8, 12]
+    assert ex(arrays) == 0
+    got_keys = packed_keys.cpu().numpy().view(np.uint32)
+    got_values = packed_values.cpu().numpy().view(np.uint32)
+    inside = np.zeros(total, bool)
+    for i, (n, at, (ek, ev, _)) in enumerate(zip(sizes, starts, expected)):
+        inside[at:at + n] = True
+        assert np.array_equal(got_keys[at:at + n], ek), (i, n)
+        if i % 2 == 0:
+            assert np.array_equal(got_values[at:at + n], ev), (i, n)
+        else:
+            assert np.array_equal(got_values[at:at + n], host_values[at:at + n]), (i, n)   # keys-only: values untouched
+    assert bool((got_keys[~inside] == sentinel).all()) and bool((got_values[~inside] == sentinel).all())
+    ex.close()
+
+
 def test_hip_shard_executor_orders_sorts_enqueued_on_different_streams(oracle):
     """All sorts of an executor share ONE storage buffer (histogram, status rows, tickets, scratch arrays), so two
     of them must never be in flight at once.  A caller that switches torch's current stream between two enqueue()

@@ -10,7 +10,7 @@ import zlib
 import numpy as np
 import pytest
 
-from segmented_cases import (_dev, _host, ballot_sorter, check, expected, make_keys, mixed_offsets,  # noqa: F401
+from segmented_cases import (GUARD, _dev, _host, ballot_sorter, check, expected, make_keys, mixed_offsets,  # noqa: F401
                              run_segmented, sorter, torch_mod)
 
 pytestmark = pytest.mark.gpu
@@ -138,6 +138,38 @@ def test_sort_segments_python_front_end(torch_mod, sorter):
     torch.cuda.synchronize()
     check(_host(dk), _host(dv), keys, iota, offsets)
     assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
+
+
+def test_sort_segments_accepts_views_off_a_sixteen_byte_boundary(torch_mod, sorter):
+    """keys = big[1:1 + n] and values = other[3:3 + n]: contiguous views at 4 and 12 mod 16, which the front end hands on as
+    they are.  Every size class, random values; big[0], other[:3] and the words behind both views keep their sentinel."""
+    import vulkan_radix_sort_amd as vrdx
+    torch = torch_mod
+    rng = np.random.default_rng(14)
+    sizes = rng.integers(0, 3000, size=200)
+    sizes[::40] = [20001, 4097, 16384, 16385, 4096]
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
+    n = int(offsets[-1])
+    keys = make_keys("uniform", n, rng)
+    values = rng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
+    big = _dev(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
+    other = _dev(torch, np.concatenate([np.full(3, GUARD, np.uint32), values, np.full(64, GUARD, np.uint32)]))
+    dk, dv, do = big[1:1 + n], other[3:3 + n], _dev(torch, offsets)
+    assert big.data_ptr() % 16 == 0 and dk.data_ptr() % 16 == 4 and dv.data_ptr() % 16 == 12
+    assert dk.is_contiguous() and dv.is_contiguous()
+    storage = vrdx.sort_segments(sorter, dk, do, values=dv)
+    torch.cuda.synchronize()
+    check(_host(dk), _host(dv), keys, values, offsets)
+    whole, whole_values = _host(big), _host(other)
+    assert whole[0] == GUARD and bool((whole[1 + n:] == GUARD).all())
+    assert bool((whole_values[:3] == GUARD).all()) and bool((whole_values[3 + n:] == GUARD).all())
+    assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
+    keys_only = _dev(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
+    vrdx.sort_segments(sorter, keys_only[1:1 + n], do)
+    torch.cuda.synchronize()
+    whole = _host(keys_only)
+    check(whole[1:1 + n], None, keys, None, offsets)
+    assert whole[0] == GUARD and bool((whole[1 + n:] == GUARD).all())
 
 
 def test_captured_graph_replays_on_new_keys_and_a_new_segmentation(torch_mod, sorter):

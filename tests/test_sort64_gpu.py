@@ -225,6 +225,16 @@ def test_sort64_python_front_end(torch_mod, sorter):
     check64(dk.cpu().numpy().view(np.uint64), dv.cpu().numpy().view(np.uint32), keys, iota)
     with pytest.raises(ValueError):
         vrdx.sort64(sorter, dk, dv, storage=own[:1024])
+    # storage off a 16-byte boundary is refused (the front end passes storageOffset 0: the contract falls on the address),
+    # at every residue, and nothing is recorded: the keys stay as they are
+    assert own.data_ptr() % 16 == 0
+    before = dk.clone()
+    for shift in (4, 8, 12, 1):
+        with pytest.raises(ValueError, match="16-byte"):
+            vrdx.sort64(sorter, dk, dv, storage=own[shift:])
+    assert vrdx.sort64(sorter, dk, dv, storage=own[16:]) is not None   # (a multiple of 16 is fine: 4096 spare bytes)
+    torch.cuda.synchronize()
+    assert bool((dk == before).all())                                     # sorted input stays as it is
     assert sorter.read_sorter_status(stream) == 0
 
 

@@ -345,7 +345,7 @@ constexpr uint32_t kHistGroupVecs = kHistGroupKeys / 4;     // 16-byte vectors p
 static_assert(kHistGroupVecs == kHistThreads * 4, "four loads per lane and group");
 
 template <bool NT>
-__device__ __forceinline__ void HistFetch(const u32x4* keys4, uint32_t group, uint32_t tid, uint32_t nvec,
+__device__ __forceinline__ void HistFetch(const u32x4_a4* keys4, uint32_t group, uint32_t tid, uint32_t nvec,
                                           u32x4 (&k)[4]) {
 #pragma unroll
   for (uint32_t u = 0; u < 4; ++u) {
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(kHistThreads) void histogram_kernel(const uint32_t*
   };
 
   const uint32_t nvec = n >> 2;
-  const u32x4* keys4 = reinterpret_cast<const u32x4*>(keys);
+  const u32x4_a4* keys4 = reinterpret_cast<const u32x4_a4*>(keys);  // the caller's keys: 4-byte aligned, no more
   const uint32_t groups = (nvec + kHistGroupVecs - 1) / kHistGroupVecs;
   // Inputs of more than half the 256 MiB Infinity Cache are read with non-temporal loads (little of them
   // would still be there for pass 0): 51 instead of 55 us at N = 2^26, 90 instead of 104 us at 2^27, no
@@ -2314,7 +2314,8 @@ __global__ __launch_bounds__(kHistThreads) void histogram_msd_kernel(MsdArgs a) 
     for (uint32_t u = 0; u < 4; ++u) {
       uint32_t i = tile * tileVecs + (first + u) * kHistThreads + tid;
       i = i < nvec ? i : (nvec != 0 ? nvec - 1 : 0u);
-      k[u] = NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(keys) + i) : reinterpret_cast<const u32x4*>(keys)[i];
+      const u32x4_a4* const keys4 = reinterpret_cast<const u32x4_a4*>(keys);  // the caller's keys: 4-byte aligned, no more
+      k[u] = NT ? __builtin_nontemporal_load(keys4 + i) : keys4[i];
     }
   };
   auto tally = [&](auto form, uint32_t tile, uint32_t first, const u32x4 (&k)[4], uint32_t nvec) {
