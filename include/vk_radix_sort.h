@@ -378,7 +378,9 @@ VkResult vrdxHipGetQueryPoolResults(VkQueryPool queryPool, uint32_t firstQuery, 
 
 /* Device-side failure word of the LAST sort recorded with this storage (recording a sort clears the
  * word): 0 = ok.  A non-zero value means a bounded look-back spin expired (the GPU never hangs; the
- * output is then unspecified).  Synchronises the given stream.  Diagnostic only. */
+ * output is then unspecified).  Synchronises the given stream.  Diagnostic only.
+ * "The last sort" is the last one that had elements: a call with elementCount == 0 (segmented: segmentCount == 0 or
+ * maxElementCount == 0) records nothing but its timestamps and leaves the storage, this word included, as it was. */
 uint32_t vrdxHipReadStatus(VkCommandBuffer commandBuffer, VkBuffer storageBuffer,
                            VkDeviceSize storageOffset);
 
@@ -434,7 +436,10 @@ void vrdxHipDescribePlan(VrdxSorter sorter, uint32_t elementCount, int keyValue,
 
 /* What the DEVICE made of the plan of the last sort that used this storage (word 1 of the storage; synchronises the
  * stream): vrdxHipDescribePlan is the host's intention, this is the verdict.  Meaningful for the two plans that are
- * decided on the device; a sort that ran the four passes leaves one of the "turned down" values. */
+ * decided on the device; a sort that ran the four passes leaves one of the "turned down" values.  Every sort that has
+ * elements writes the word -- the one-workgroup sort zeroes it too -- so the verdict of an earlier sort on the same storage
+ * never survives one; a call with elementCount == 0 writes nothing, and the verdict stays that of the last sort that had
+ * elements (as with vrdxHipReadStatus). */
 #define VRDX_HIP_VERDICT_NONE 0u            /* no plan was taken: the four passes ran (also: FOUR_PASSES / ONE_WORKGROUP sorts) */
 #define VRDX_HIP_VERDICT_HYBRID8_RUNS 1u    /* HYBRID8: launch 0 scattered by the highest varying byte, the buckets were sorted in LDS */
 #define VRDX_HIP_VERDICT_HYBRID8_DECLINED 2u /* HYBRID8: a bucket did not fit, the four passes ran */

@@ -414,9 +414,11 @@ SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCou
   p.atomicRank = sorter->atomicRank.load(std::memory_order_relaxed);  // one answer for the whole sort
   const bool adaptive = EnvKnobs().forcedConfig < 0;
   if (elementCount == 0) return p;
-  // Small sorts: one workgroup, one launch, nothing but the caller's keys / values and the failure word touched (the
-  // general path costs six launches = 30-45 us however small N is).  Forcing a tile geometry (VRDX_TILE_CONFIG) also
-  // forces the general path, which is how the tests reach it at small sizes.
+  // Small sorts: one workgroup, one launch, nothing but the caller's keys / values and words 1-3 of the storage header
+  // touched -- the kernel zeroes the plan's verdict, the MSD plan's word and the failure word, so that the verdict an
+  // earlier sort left on this storage is not read as this one's (the general path costs six launches = 30-45 us however
+  // small N is).  Forcing a tile geometry (VRDX_TILE_CONFIG) also forces the general path, which is how the tests reach
+  // it at small sizes.
   if (elementCount <= vrdx::kSmallSortMaxElements && adaptive && EnvKnobs().smallSort) {
     p.oneWorkgroup = true;
     p.layout = vrdx::MakeLayout(elementCount, sorter->minStorageBufferOffsetAlignment, 0, storageAddress);  // (the failure word)

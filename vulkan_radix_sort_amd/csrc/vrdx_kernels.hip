@@ -1639,7 +1639,10 @@ __global__ __launch_bounds__(THREADS) void small_sort_kernel(uint32_t* keys, uin
   static_assert(THREADS >= 256 && THREADS % 256 == 0, "one thread per digit");
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const uint32_t n = ElementCount(maxCount, countPtr);
-  if (threadIdx.x == 0) *failure = 0;  // the one word of storage vrdxHipReadStatus looks at: nothing here can spin
+  // Words 1-3 of the storage header (failure is word 3): the failure word vrdxHipReadStatus looks at -- nothing here can
+  // spin -- and, in front of it, the plan's verdict and the MSD plan's word, which no plan of THIS sort writes: an earlier
+  // sort's verdict on the same storage must not be read as this one's (VRDX_HIP_VERDICT_NONE, include/vk_radix_sort.h).
+  if (threadIdx.x < 3) failure[(int)threadIdx.x - 2] = 0;
   SortInWorkgroup<THREADS, KPT, KV, ATOMIC_RANK>(keys, keys, values, values, n, VRDX_PASSES, smem);
 }
 
