@@ -1,0 +1,166 @@
+// CPU-only check of the host planner (vrdx_plan.h).  Two modes:
+//   plan_check                              sweeps element counts under several CU counts, both value modes, both ranking
+//                                           modes and every forced tile geometry: the invariants of plan_invariants.h hold of
+//                                           every plan, and the sizes at which the plan changes are those of kAtomicEdges /
+//                                           kBallotEdges, found again here from the functions themselves;
+//   plan_check describe <cus> <atomic> <n>...   one line per (n, key+value): n, 0 | 1, the plan's name (those of
+//                                           vulkan_radix_sort_amd/api.py, PLAN_NAMES), its bits, hybridCap, msdCap, launches and
+//                                           tile geometry -- what the Python tests hold their hand-kept numbers to.
+// Built by tests/native/Makefile; nothing of HIP is linked (vrdx_kernels.h needs one of its headers).
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <iterator>
+#include <string_view>
+#include <vector>
+
+#include "plan_invariants.h"
+
+namespace {
+
+// what kind of plan the host records: one workgroup | eight-bit hybrid with that capacity | MSD | four passes
+struct Kind {
+  bool oneWorkgroup;
+  uint32_t hybridCap, msdBits, msdCap;
+  bool operator==(const Kind& o) const {
+    return oneWorkgroup == o.oneWorkgroup && hybridCap == o.hybridCap && msdBits == o.msdBits && msdCap == o.msdCap;
+  }
+};
+
+Kind KindOf(const vrdx::SortPlan& p) { return Kind{p.oneWorkgroup, p.hybridCap, p.msdBits, p.msdBits != 0 ? p.msdCap : 0u}; }
+
+// the same from the rules alone (no layout, no tile plan): cheap enough for every n
+Kind KindByRule(const vrdx::PlanContext& c, bool keyValue, uint32_t n) {
+  if (n <= vrdx::kSmallSortMaxElements) return Kind{n != 0, 0, 0, 0};  // (the empty sort records nothing)
+  Kind k{false, vrdx::HybridCapacity(c, n), 0, 0};
+  k.msdBits = vrdx::MsdBits(c, keyValue, n, k.hybridCap, &k.msdCap);
+  if (k.msdBits == 0) k.msdCap = 0;
+  return k;
+}
+
+const char* PlanName(uint32_t plan) {
+  switch (plan) {
+    case VRDX_HIP_PLAN_ONE_WORKGROUP: return "one-workgroup";
+    case VRDX_HIP_PLAN_FOUR_PASSES: return "four-passes";
+    case VRDX_HIP_PLAN_HYBRID8: return "hybrid-8";
+    case VRDX_HIP_PLAN_MSD: return "msd";
+    default: return "none";
+  }
+}
+
+int Describe(int argc, char** argv) {
+  if (argc < 5) {
+    std::fprintf(stderr, "usage: plan_check describe <cus> <atomic: 0 | 1> <n>...\n");
+    return 2;
+  }
+  vrdx::PlanContext c;
+  c.computeUnits = std::atoi(argv[2]);
+  c.atomicRank = std::atoi(argv[3]) != 0;
+  for (int i = 4; i < argc; ++i) {
+    const uint32_t n = (uint32_t)std::strtoul(argv[i], nullptr, 10);
+    for (int keyValue = 0; keyValue < 2; ++keyValue) {
+      const vrdx::SortPlan p = vrdx::PlanSort(c, keyValue != 0, n, 0);  // (address 0, like vrdxHipDescribePlan)
+      VrdxHipPlanInfo info = {};
+      if (n != 0) vrdx::DescribePlan(p, &info);
+      char config[32] = "-";
+      if (p.stepCount > 1) vrdx::ConfigName(vrdx::kTileConfigs[p.configIndex], config, sizeof(config));
+      std::printf("%u %d %s %u %u %u %u %s\n", n, keyValue, PlanName(info.plan), info.bits, p.hybridCap, p.msdBits != 0 ? p.msdCap : 0u,
+                  info.launches, config);
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc >= 2 && std::string_view(argv[1]) == "describe") return Describe(argc, argv);
+  uint64_t cases = 0;
+  int failures = 0;
+  const auto fail = [&failures](const char* what, uint32_t n, uint32_t cus, int keyValue, int atomicRank, int forced) {
+    if (failures < 10) std::printf("FAIL %s: n=%u cus=%u key+value=%d atomic=%d forced=%d\n", what, n, cus, keyValue, atomicRank, forced);
+    ++failures;
+  };
+
+  // 1. the invariants, at every swept count and +-2 around every edge: adaptive plans at every CU count, every forced tile
+  // geometry at 256 CUs (a forced geometry changes nothing that depends on the CU count but the tile plan)
+  const auto check = [&](uint32_t n, bool dense) {
+    for (uint32_t cus : plan_test::kCuCounts)
+      for (int forced = -1; forced < vrdx::kNumTileConfigs; ++forced) {
+        if (forced >= 0 && cus != 256 && !dense) continue;
+        for (int keyValue = 0; keyValue < 2; ++keyValue)
+          for (int atomicRank = 0; atomicRank < 2; ++atomicRank) {
+            vrdx::PlanContext c;
+            c.computeUnits = (int)cus;
+            c.atomicRank = atomicRank != 0;
+            c.forcedConfig = forced;
+            const vrdx::SortPlan p = vrdx::PlanSort(c, keyValue != 0, n, 0);
+            ++cases;
+            if (!plan_test::PlanInvariantsHold(c, keyValue != 0, n, 0)) fail("invariants", n, cus, keyValue, atomicRank, forced);
+            // the planner and the rules it is made of agree on the kind of plan, whatever the CU count
+            if (forced < 0 && !(KindOf(p) == KindByRule(c, keyValue != 0, n))) fail("kind", n, cus, keyValue, atomicRank, forced);
+            if (forced >= 0 && n != 0 && (p.oneWorkgroup || p.hybridCap != 0 || p.msdBits != 0)) fail("forced", n, cus, keyValue, atomicRank, forced);
+          }
+      }
+  };
+  plan_test::ForEachSweptCount(check);
+  for (uint32_t edge : plan_test::kAtomicEdges)
+    for (int d = -2; d <= 2; ++d) check((uint32_t)((int64_t)edge + d), true);
+  for (uint32_t edge : plan_test::kBallotEdges)
+    for (int d = -2; d <= 2; ++d) check((uint32_t)((int64_t)edge + d), true);
+
+  // 2. a layout that cannot fit: one count past VRDX_MAX_ELEMENTS the reference's uint32 byte sizes wrap and the storage is
+  // smaller than the keys (the entry points clamp the count, so the recorder never plans it): refused, nothing recorded
+  for (int forced = -1; forced < vrdx::kNumTileConfigs; ++forced)
+    for (int keyValue = 0; keyValue < 2; ++keyValue) {
+      vrdx::PlanContext c{256, true};
+      c.forcedConfig = forced;
+      const uint32_t n = VRDX_MAX_ELEMENTS + 4u;
+      const vrdx::SortPlan p = vrdx::PlanSort(c, keyValue != 0, n, 0);
+      ++cases;
+      if (p.fits || p.stepCount != 0 || p.launches != 0 || p.msdBits != 0 || p.blockSums || !plan_test::PlanInvariantsHold(c, keyValue != 0, n, 0))
+        fail("unfittable", n, 256, keyValue, 1, forced);
+    }
+
+  // 3. the edges, found from the rules at EVERY n up to past the MSD plan's last size: the sizes behind which the kind of plan
+  // changes are exactly the listed ones, keys-only and key+value, and what lies between them is what the table says
+  const uint32_t scanUpTo = (1u << 26) + (1u << 20);
+  for (int atomicRank = 0; atomicRank < 2; ++atomicRank)
+    for (int keyValue = 0; keyValue < 2; ++keyValue) {
+      const vrdx::PlanContext c{256, atomicRank != 0};
+      std::vector<uint32_t> edges;
+      std::vector<Kind> kinds;
+      Kind last = KindByRule(c, keyValue != 0, 1);
+      for (uint32_t n = 2; n <= scanUpTo; ++n) {
+        const Kind k = KindByRule(c, keyValue != 0, n);
+        if (k == last) continue;
+        edges.push_back(n - 1);
+        kinds.push_back(last);
+        last = k;
+      }
+      kinds.push_back(last);
+      cases += scanUpTo;
+      const std::vector<uint32_t> wantEdges = atomicRank ? std::vector<uint32_t>(std::begin(plan_test::kAtomicEdges), std::end(plan_test::kAtomicEdges))
+                                                         : std::vector<uint32_t>(std::begin(plan_test::kBallotEdges), std::end(plan_test::kBallotEdges));
+      const std::vector<Kind> wantKinds =
+          atomicRank ? std::vector<Kind>{{true, 0, 0, 0},      {false, 4096, 0, 0},    {false, 8192, 0, 0},    {false, 16384, 0, 0}, {false, 32768, 0, 0},
+                                         {false, 0, 10, 18432}, {false, 0, 10, 36864}, {false, 0, 11, 36864}, {false, 0, 0, 0}}
+                     : std::vector<Kind>{{true, 0, 0, 0}, {false, 4096, 0, 0}, {false, 8192, 0, 0}, {false, 16384, 0, 0}, {false, 0, 0, 0}};
+      if (edges != wantEdges || !(kinds == wantKinds)) {
+        fail("edges", 0, 256, keyValue, atomicRank, -1);
+        for (size_t i = 0; i < edges.size() && i < 16; ++i)
+          std::printf("  up to %u: one-workgroup %d hybridCap %u msdBits %u msdCap %u\n", edges[i], (int)kinds[i].oneWorkgroup, kinds[i].hybridCap,
+                      kinds[i].msdBits, kinds[i].msdCap);
+      }
+      // ... and the planner says the same either side of every edge
+      for (size_t i = 0; i < edges.size(); ++i)
+        for (uint32_t n : {edges[i], edges[i] + 1}) {
+          if (!(KindOf(vrdx::PlanSort(c, keyValue != 0, n, 0)) == kinds[i + (n - edges[i])])) fail("plan at an edge", n, 256, keyValue, atomicRank, -1);
+        }
+    }
+  // kMsdStreamedOutputUpTo (vrdx_kernels.h) is the ten-bit plan's last size (also a static_assert of vrdx_plan.h)
+  if (vrdx::kMsdStreamedOutputUpTo != plan_test::kAtomicEdges[6]) fail("kMsdStreamedOutputUpTo", vrdx::kMsdStreamedOutputUpTo, 256, 0, 1, -1);
+
+  std::printf("plan: %llu cases, %d failures\n", (unsigned long long)cases, failures);
+  return failures != 0;
+}

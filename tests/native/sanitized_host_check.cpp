@@ -1,6 +1,6 @@
 // Host-only pieces under AddressSanitizer + UndefinedBehaviorSanitizer (CPU test run; GPU sanitizers are
-// not available on this pool): the storage-layout math shared by host and device (vrdx_layout.h), the
-// oracle's restatement of the reference's three shaders (vrdx_oracle.c) and our port of the reference's
+// not available on this pool): the storage-layout math shared by host and device (vrdx_layout.h), the host's
+// planning functions (vrdx_plan.h) either side of every size at which the plan changes, the oracle's restatement of the reference's three shaders (vrdx_oracle.c) and our port of the reference's
 // CPU backend / data generator (cpu_sort.cc), on ragged sizes, against std::stable_sort.
 #include <algorithm>
 #include <cstdint>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../vulkan_radix_sort_amd/csrc/vrdx_layout.h"
+#include "plan_invariants.h"
 
 extern "C" {
 int vrdx_oracle_sort(uint32_t* keys, uint32_t* values, uint32_t elementCount, uint32_t* globalHistogramOut);
@@ -53,6 +54,18 @@ int main() {
   }
   const vrdx::StorageLayout top = vrdx::MakeLayout(VRDX_MAX_ELEMENTS, VRDX_STORAGE_ALIGN, vrdx::RoundUp(VRDX_MAX_ELEMENTS, 8192));
   if (top.keyValueSize != vrdx_oracle_storage_size(VRDX_MAX_ELEMENTS, VRDX_STORAGE_ALIGN, 1)) ++failures;
+  // the planner: the invariants of every plan at the plan's edges, keys and pairs, both ranking modes, every alignment
+  const auto planAt = [&failures](uint32_t edge) {
+    for (const bool atomicRank : {true, false})
+      for (int d = -2; d <= 2; ++d)
+        for (const bool keyValue : {false, true})
+          for (uint32_t address = 0; address < 128; address += 16) {
+            const vrdx::PlanContext context{256, atomicRank};
+            if (!plan_test::PlanInvariantsHold(context, keyValue, (uint32_t)((int64_t)edge + d), 0x7f0000001000ull + address)) ++failures;
+          }
+  };
+  for (const uint32_t edge : plan_test::kAtomicEdges) planAt(edge);
+  for (const uint32_t edge : plan_test::kBallotEdges) planAt(edge);
   std::printf("sanitized host check: %d failures\n", failures);
   return failures != 0;
 }

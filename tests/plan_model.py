@@ -79,7 +79,7 @@ def msd_verdict(keys, n, bits, cap):
 
 
 def hybrid_capacity(n):
-    """HybridCapacity (vrdx_api.cpp) for the one-atomic ranking: the smallest of 4096 ... 32768 that leaves twice the
+    """HybridCapacity (vrdx_plan.h; pinned by tests/test_plan_check.py) for the one-atomic ranking: the smallest of 4096 ... 32768 that leaves twice the
     mean bucket of the host's element count, the largest also with 3 % room; 0 = no hybrid plan."""
     mean = -(-n // 256)
     need, need_last = mean * 200 // 100, mean * 103 // 100

@@ -26,7 +26,7 @@ from test_sort_gpu import ROUND, decline_msd, msd_capacity
 
 M = 8_200_003     # the MSD plan: ten bits, half-size buckets (18432); M % 4 == 3
 H = 300_001       # the hybrid plan, buckets of 4096
-MSD_BITS = 10     # what MsdBits (vrdx_api.cpp) records at M, at ROUND and at 2 ROUND + 1
+MSD_BITS = 10     # what MsdBits (vrdx_plan.h) records at M, at ROUND and at 2 ROUND + 1
 TAIL_SPLIT_N = 2 * ROUND + 1   # the smallest size of test_tail_split_tiles_at_their_boundaries (keys-only)
 BLOCK_SUMS_N = ROUND           # the smallest size of test_block_sums_in_sorts_of_one_round
 SEGMENTED_N = 400_000
@@ -217,7 +217,7 @@ def padded(a):
 # ---- what the device must decide ---------------------------------------------------------------------------------------------
 
 def ballot_hybrid_capacity(n):
-    """HybridCapacity (vrdx_api.cpp) for the ballot ranking: as plan_model.hybrid_capacity, but the largest bucket is 16384
+    """HybridCapacity (vrdx_plan.h; pinned by tests/test_plan_check.py) for the ballot ranking: as plan_model.hybrid_capacity, but the largest bucket is 16384
     (the ballot forms of the 32768-element bucket kernel would spill); 0 = no hybrid plan.  That sorter never records the
     MSD plan (MsdBits), so beyond the hybrid plan its sorts are the four passes alone."""
     mean = -(-n // 256)

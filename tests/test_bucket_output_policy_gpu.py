@@ -25,7 +25,7 @@ from test_plan_choice_gpu import plan_storage_word
 from test_sort_gpu import torch_mod, sorter, gpu_sort, MSD_HALF_UP_TO  # noqa: F401 (fixtures)
 
 STREAMING_ABOVE = 1 << 24     # vrdx_kernels.h kStreamingLoadsAbove
-TEN_BITS_UP_TO = 36_649_984   # vrdx_api.cpp MsdBits: ceil(n / 1024) * 103 // 100 <= 36864
+TEN_BITS_UP_TO = 36_649_984   # vrdx_plan.h MsdBits (pinned by tests/test_plan_check.py): ceil(n / 1024) * 103 // 100 <= 36864
 FULL_CAP = 36864
 BUCKETS = 1024                # of the ten-bit plan
 

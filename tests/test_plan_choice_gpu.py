@@ -13,8 +13,9 @@ import functools
 import numpy as np
 import pytest
 
+import plan_check_tool
 import plan_model as model
-from test_sort_gpu import torch_mod, sorter, gpu_sort, msd_capacity, MSD_FROM, MSD_HALF_UP_TO  # noqa: F401 (fixtures)
+from test_sort_gpu import torch_mod, sorter, ballot_sorter, gpu_sort, msd_capacity, MSD_FROM, MSD_HALF_UP_TO  # noqa: F401 (fixtures)
 
 HALF = 8_600_003      # the half-size bucket kernel (10 bits, buckets of 18432); n % 4 == 3
 FULL10 = 19_000_001   # the full-size bucket kernel, 10 bits (36864)
@@ -95,6 +96,30 @@ PLAN_TABLE = [(1, "one-workgroup", 1), (4096, "one-workgroup", 1), (16384, "one-
 def test_recorded_plan_and_launch_count_by_size(sorter, n, plan, launches, key_value):
     info = sorter.describe_plan(n, key_value)
     assert (info.name, int(info.launches)) == (plan, launches), (n, key_value)
+
+
+def _described(sorter, sizes):
+    """{(n, key_value): (name, bits, launches)} by vrdxHipDescribePlan"""
+    infos = {(n, kv): sorter.describe_plan(n, kv) for n in sizes for kv in (False, True)}
+    return {at: (info.name, int(info.bits), int(info.launches)) for at, info in infos.items()}
+
+
+@pytest.mark.gpu
+def test_described_plans_are_the_planners_either_side_of_every_edge(torch_mod, sorter, ballot_sorter):
+    """vrdxHipDescribePlan against tests/native/plan_check (the same vrdx_plan.h, compiled for the CPU) for this device's CU
+    count, either side of every size at which the plan changes under either ranking: nothing is launched.  A sorter's whole
+    set is one table or the other -- the one-atomic ranking's for the sorter every other test here presumes it of (an
+    MI355X serves LDS atomics in lane order), the ballot ranking's for the sorter created under VRDX_RANK=ballot."""
+    cus = torch_mod.cuda.get_device_properties(0).multi_processor_count
+    sizes = sorted(set(plan_check_tool.edge_sizes(plan_check_tool.ATOMIC_TABLE) + plan_check_tool.edge_sizes(plan_check_tool.BALLOT_TABLE) + [1 << 25]))
+    tables = {atomic: {at: (row.name, row.bits, row.launches) for at, row in plan_check_tool.describe(cus, atomic, sizes).items()}
+              for atomic in (True, False)}
+    assert tables[True] != tables[False]
+    for which, atomic in ((sorter, True), (ballot_sorter, False)):
+        got = _described(which, sizes)
+        came_up_atomic = got[1 << 25, False][0] == "msd"   # (only the one-atomic ranking records the MSD plan)
+        assert got == tables[came_up_atomic], sorted(at for at in got if got[at] != tables[came_up_atomic][at])
+        assert came_up_atomic == atomic
 
 
 # ---- 2. the window at every position -----------------------------------------------------------------------------------

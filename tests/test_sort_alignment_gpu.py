@@ -299,7 +299,7 @@ def test_non_temporal_bucket_output(torch_mod, sorter, oracle, n, kind, a):
 
 def test_eleven_bit_window(torch_mod, sorter, oracle):
     """The first sizes of the eleven-bit plan, keys at 8 mod 16.  Ten bits end where ceil(n / 1024) * 103 // 100 exceeds
-    36864 (MsdBits in vrdx_api.cpp), which is n = 36 649 985: this is the third size past it, n mod 4 == 3."""
+    36864 (MsdBits in vrdx_plan.h), which is n = 36 649 985: this is the third size past it, n mod 4 == 3."""
     n = 36_649_987
     info = sorter.describe_plan(n, False)
     assert info.name == "msd" and info.bits == 11 and n % 4 == 3

@@ -87,7 +87,7 @@ def check_against_oracle(torch, sorter, oracle, keys, values=None, **kw):
         assert np.array_equal(gv, ev)
 
 
-MSD_FROM = 8_150_000        # vrdx_api.cpp MsdBits: sorts past the end of the eight-bit plan (8.1 M) record the MSD plan in front of the passes
+MSD_FROM = 8_150_000        # vrdx_plan.h MsdBits (pinned by tests/test_plan_check.py): sorts past the end of the eight-bit plan (8.1 M) record the MSD plan in front of the passes
 MSD_FROM_KEYS = MSD_FROM    # (keys-only and key+value alike since the half-size bucket kernel)
 MSD_HALF_UP_TO = 18_149_376  # ... with buckets of at most 18432 (512-thread bucket kernel) while ceil(n / 1024) * 104 // 100 <= 18432
 
@@ -813,7 +813,7 @@ def test_two_valued_bytes_take_the_ballot_ranking(torch_mod, sorter, oracle, n):
         assert np.array_equal(gk, ek) and np.array_equal(gp, ep)
 
 
-# one size inside every regime of the size-adaptive tile selection (ConfigIndex in vrdx_api.cpp; f =
+# one size inside every regime of the size-adaptive tile selection (ConfigIndex in vrdx_plan.h; f =
 # N / (256 CUs * 32768)): 1024x8 | 1024x16 | 1024x32 | two-sub-tile 1024x32x2 | 1024x16 between
 # rounds | ... -- all ragged (odd) sizes
 BREAK_POINT_SIZES = [int(f * (1 << 23)) + 12345 for f in (0.10, 0.20, 0.40, 0.58, 0.80, 1.2, 1.6, 1.99, 2.3, 2.8, 3.3)] + \
@@ -1070,7 +1070,7 @@ def test_small_sort_boundary_sizes(torch_mod, sorter, oracle, n):
     check_against_oracle(torch_mod, sorter, oracle, k, iota, count=max(n - 3, 0), indirect=True, max_count=n)
 
 
-ALL_TILE_CONFIGS = ["1024x8", "1024x16", "1024x32", "1024x32x2"]  # == kTileConfigs in vrdx_launch.inc
+ALL_TILE_CONFIGS = ["1024x8", "1024x16", "1024x32", "1024x32x2"]  # == kTileConfigs in vrdx_kernels.h
 
 
 def _selftest(args, **env):

@@ -1,6 +1,6 @@
 """Without a GPU: the inputs of tests/storage_reuse_cases.py are what their names say.  Every call of CALLS is put through
 tests/plan_model.py with the constants the host uses at its bound -- ten bits and msd_capacity() where the MSD plan is
-recorded, hybrid_capacity() for the hybrid plan, the ballot sorter's capacity rule (HybridCapacity in vrdx_api.cpp: no
+recorded, hybrid_capacity() for the hybrid plan, the ballot sorter's capacity rule (HybridCapacity in vrdx_plan.h: no
 bucket beyond 16384, and never the MSD plan) -- and the verdict must be the one the table of CALLS states.  A generator that
 changes cannot turn a "declined" call into an "accepted" one, or the other way round, without this file noticing."""
 import numpy as np

@@ -22,11 +22,12 @@
 #include "../../include/vk_radix_sort.h"
 #include "vrdx_kernels.h"
 #include "vrdx_layout.h"
+#include "vrdx_plan.h"
 
 struct VrdxSorter_T {
   int device = 0;
   int computeUnits = 0;
-  // (tile geometry is chosen per sort from the element count, see ConfigIndex)
+  // (tile geometry is chosen per sort from the element count, see ConfigIndex in vrdx_plan.h)
   // LDS returning atomics proven lane-ordered on this device (at creation; vrdxHipRecheck may revise it)
   std::atomic<bool> atomicRank{false};
   // sorts recorded on the general path: behind every 65536th one a small, stream-ordered repeat of the lane-order check
@@ -72,14 +73,6 @@ int DeviceOrdinalFromHandle(const void* handle, int* ordinal) {
   return 0;
 }
 
-// "1024x32", or "1024x32x2" for the two-sub-tile kernel
-void ConfigName(const vrdx::TileConfig& c, char* out, size_t size) {
-  if (c.subTiles == 1)
-    std::snprintf(out, size, "%dx%d", c.threads, c.keysPerThread);
-  else
-    std::snprintf(out, size, "%dx%dx%d", c.threads, c.keysPerThread, c.subTiles);
-}
-
 // The environment knobs (tuning / testing only), read once.  VRDX_RANK is not among them: it is read
 // whenever a sorter is created or re-checked (RankModeIs).
 struct Knobs {
@@ -109,7 +102,7 @@ const Knobs& EnvKnobs() {
     if (const char* env = std::getenv("VRDX_TILE_CONFIG")) {
       for (int i = 0; i < vrdx::kNumTileConfigs && k.forcedConfig < 0; ++i) {
         char name[32];
-        ConfigName(vrdx::kTileConfigs[i], name, sizeof(name));
+        vrdx::ConfigName(vrdx::kTileConfigs[i], name, sizeof(name));
         if (std::strcmp(env, name) == 0) k.forcedConfig = i;
       }
       if (k.forcedConfig < 0) std::fprintf(stderr, "vrdx-hip: unknown VRDX_TILE_CONFIG '%s', using the defaults\n", env);
@@ -126,51 +119,6 @@ const Knobs& EnvKnobs() {
     return k;
   }();
   return knobs;
-}
-
-// Tile geometry by problem size, measured on MI355X (tools: `vrdx_selftest sweep`, tables in
-// profiles/r01_sweep_*.txt).  Three regimes:
-//  * small sorts want many small tiles (parallelism across the CUs; six launches cost ~45 us);
-//  * beyond that throughput grows with the tile (fewer look-backs per key, longer digit runs) up to
-//    the 32768 keys whose staging buffer fits the CU's LDS ONCE -- so these tiles run one workgroup
-//    per CU in lock-step ROUNDS of computeUnits tiles, and a sort whose tile count is just above a
-//    multiple of the CU count pays for a whole extra round.  f below is the size in such rounds.
-//    (16384-key tiles, two workgroups per CU, degrade gracefully in a partial round and used to win
-//    just past the round boundaries; on the final kernels they no longer do);
-//  * the two-sub-tile kernel (65536 keys, keys-only) halves the rounds again: best when f is in
-//    (1, 2], just below 4 or 6.
-enum : int { kCfg1024x8 = 0, kCfg1024x16 = 1, kCfg1024x32 = 2, kCfg1024x32x2 = 3 };
-
-// msd: the MSD plan is recorded in front of the passes, which are then only the fallback for skewed keys; its per-tile counts
-// take a quarter to a half of the reference's partition-histogram area, so the passes must not take tiles of 16384.
-int ConfigIndex(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCount, bool atomicRank, bool msd = false) {
-  const int forced = EnvKnobs().forcedConfig;
-  // (the two-sub-tile kernel is keys-only: a key+value sort under a forced 1024x32x2 takes 1024x32)
-  if (forced >= 0) return forced == kCfg1024x32x2 && (keyValue || !atomicRank) ? kCfg1024x32 : forced;
-  const double f = (double)elementCount / ((double)sorter->computeUnits * 32768.0);
-  // Behind the MSD plan the passes are the fallback only, and the plan's own launches double as its first two (one kernel, two
-  // roles): those kernels exist for 1024x32 key+value and the two-sub-tile geometry keys-only (the plan is recorded with the
-  // one-atomic ranking only), which are then taken at every size -- keys-only at one round of tiles and below as even-split
-  // tiles of two half-size sub-tiles.
-  if (msd) return keyValue ? kCfg1024x32 : kCfg1024x32x2;
-  if (keyValue) {
-    if (f <= 0.26) return kCfg1024x8;
-    if (f <= 0.53) return kCfg1024x16;
-    // just past one round of 32768-element tiles, two workgroups of 16384 per CU fill the second round's gap
-    // (1.2-2.6 % at 1.07 <= f <= 1.32, profiles/r03_sweep_by_geometry.txt; still so with the tail split of round 4,
-    // profiles/r04_tail_split_kv.txt)
-    if (f > 1.0 && f <= 1.35) return kCfg1024x16;
-    return kCfg1024x32;
-  }
-  if (f <= 0.125) return kCfg1024x8;
-  if (f <= 0.5) return kCfg1024x16;   // beyond: even-split 1024x32 tiles (PlanTiles), 7 % faster at f = 0.536
-  if (f <= 1.0) return kCfg1024x32;
-  // Beyond one round the two-sub-tile kernel (65536 keys per workgroup: half the look-backs per key), whose last,
-  // partial round is cut into small equal tiles (tail split, PlanTiles): with that it is the fastest geometry at every
-  // size from one round up (profiles/r04_tail_split_keys.txt; without it, it lost a whole 65536-key round to the
-  // 1024x32 tiles whenever the tile count passed a multiple of the CU count -- f in (2, 3.3] and beyond 4 in round 3).
-  // It holds two sub-tiles' keys in registers: only with the one-atomic ranking.
-  return atomicRank ? kCfg1024x32x2 : kCfg1024x32;
 }
 
 #ifdef VRDX_TRACE
@@ -207,62 +155,25 @@ void DumpTrace() {
 }
 #endif
 
-// Mid-size sorts record the hybrid plan (vrdx_kernels.hip, PassPlan) next to the four passes: launch 0 scatters by the
-// keys' highest byte that varies and bucket_sort_kernel finishes every bucket inside one workgroup -- if the DEVICE finds that no bucket
-// exceeds the capacity returned here; otherwise the four passes run as usual and the bucket launch is empty.  The
-// capacity is the smallest of 4096 / 8192 / 16384 / 32768 (the last one with the one-atomic ranking only) that leaves a
-// bucket twice the room of its mean N / 256; the largest one is recorded as long as it leaves 3 % (a bucket sort
-// costs what the bucket's elements cost, whatever the capacity; uniform keys spread by half a percent at these sizes --
-// mean 31800, sigma 178 at 8.1 M: the capacity is 5 sigma away -- and a plan that does not apply costs one empty
-// launch, 3 us, where one that does saves 17-25 %): N <= 8.1 M elements (4.0 M with the ballot ranking).
-// 0 = the plan is not recorded (larger N, a forced tile geometry, VRDX_HYBRID=0).
-uint32_t HybridCapacity(bool atomicRank, uint32_t elementCount) {
-  if (!EnvKnobs().hybrid || elementCount <= vrdx::kSmallSortMaxElements) return 0;
-  // a bucket may hold twice the mean bucket; the LARGEST capacity is tried with less room than the others (3 %): failing
-  // costs one empty launch, the plan is worth a fifth to a third of the sort (profiles/r03_hybrid_headroom.txt)
-  const uint64_t mean = (elementCount + VRDX_RADIX - 1) / VRDX_RADIX;
-  const uint32_t need = (uint32_t)(mean * 200u / 100u);
-  const uint32_t needLast = (uint32_t)(mean * 103u / 100u);
-  // 32768-element buckets: the one-atomic ranking only (the ballot forms of that kernel would spill); key+value stages
-  // keys and values through one buffer there (SharedStage in vrdx_kernels.hip)
-  const uint32_t largest = atomicRank ? 32768u : 16384u;
-  if (need <= 4096u) return 4096u;
-  if (need <= 8192u) return 8192u;
-  if (need <= 16384u) return 16384u;
-  if (need <= largest) return largest;
-  return needLast <= largest ? largest : 0u;
+// What the planner (vrdx_plan.h) is told about this sorter and the environment; built once per recorded sort, with ONE load
+// of the ranking mode: one answer for the whole sort.
+vrdx::PlanContext PlanContextOf(const VrdxSorter_T* sorter) {
+  const Knobs& k = EnvKnobs();
+  vrdx::PlanContext c;
+  c.computeUnits = sorter->computeUnits;
+  c.atomicRank = sorter->atomicRank.load(std::memory_order_relaxed);
+  c.minStorageBufferOffsetAlignment = sorter->minStorageBufferOffsetAlignment;
+  c.forcedConfig = k.forcedConfig;
+  c.hybrid = k.hybrid;
+  c.msd = k.msd;
+  c.smallSort = k.smallSort;
+  c.blockSums = k.blockSums;
+  return c;
 }
 
-// The MSD plan (vrdx_kernels.hip, "MSD plan"): one stable scatter by the keys' top 10 or 11 bits, then every bucket by its
-// remaining bits in two passes inside one workgroup -- three ranking steps and two trips through memory instead of four
-// and four.  Recorded, in front of the four passes (which return on its verdict), for sorts beyond the eight-bit
-// plan's reach whose mean bucket leaves 3 % of room in the bucket kernel's capacity (uniform keys spread by half a percent
-// at these sizes): ten bits up to 36.6 M keys / 32.5 M pairs, eleven bits up to twice that.  Returns the bits or 0.
-// One-atomic ranking only.  VRDX_MSD=0 switches it off (VRDX_HYBRID=0 and a forced tile geometry as well).
-uint32_t MsdBits(bool atomicRank, bool keyValue, uint32_t elementCount, uint32_t hybridCap, uint32_t* capacity) {
-  if (!EnvKnobs().msd || !atomicRank) return 0;
-  // From where the EIGHT-bit plan ends (8.1 M: hybridCap == 0), keys-only and key+value.  Up to 18.1 M elements the buckets
-  // hold at most 18432 and the half-size bucket kernel sorts them, two workgroups to a CU: with it the plan is 8-15 % faster
-  // than round 4's nine-bit hybrid plan and the four passes at one round of tiles, which key+value sorts of these sizes
-  // took before (profiles/r05_msd_half_buckets.txt); that plan's kernels are gone since.
-  if (hybridCap != 0 || elementCount <= vrdx::kSmallSortMaxElements ||
-      vrdx::RoundUp(elementCount, vrdx::kMsdTileKeys) > vrdx::kMsdMaxTiles)
-    return 0;
-  const uint32_t cap = keyValue ? vrdx::kMsdCapKeyValue : vrdx::kMsdCapKeys;
-  *capacity = cap;
-  for (uint32_t bits = 10; bits <= 11; ++bits) {
-    const uint64_t mean = ((uint64_t)elementCount + (1u << bits) - 1u) >> bits;
-    if (mean * 103u / 100u <= cap) {
-      // buckets of half the size: the bucket kernel of 512 threads, two workgroups per CU (bucket_sort2_half_kernel)
-      // (4 % of headroom here: 5.3 sigma of a uniform bucket of 17700; the 3 % of the full size would be 4 sigma at this
-      // capacity, and with 1024 buckets one sort in thirty at the top of the range would be turned down)
-      if (bits == 10 && mean * 104u / 100u <= vrdx::kMsdHalfCap)
-        *capacity = vrdx::kMsdHalfCap;
-      return bits;
-    }
-  }
-  return 0;
-}
+using vrdx::SortPlan;
+using vrdx::SortStep;
+using vrdx::Step;
 
 inline uint8_t* BufferAddress(VkBuffer buffer, VkDeviceSize offset) {
   return reinterpret_cast<uint8_t*>(buffer) + offset;
@@ -315,153 +226,6 @@ class StampCursor {
   hipStream_t stream_;
   uint32_t slot_ = 0;
 };
-
-// The tile plan of a sort (vrdx_layout.h, PlanTiles): even-split tiles for sorts of one round, tail-split tiles behind
-// the whole rounds of a longer one -- where the kernels' forms with run-time slot counts exist and where they were
-// measured to pay (profiles/r04_tail_split_keys.txt, r04_tail_split_kv.txt; f = size in rounds of CUs x 32768):
-//   keys-only 1024x32x2   even split (-9.5 % at f = 1.07) and tail split at every size (f = 2.06: 0.191 instead of
-//                         0.230 ms; 3.06: 0.261 / 0.272; 4.06: 0.340 / 0.388)
-//   keys-only 1024x32     even split (-3.5 % at f = 0.5); NO tail split (+0 ... +4 %: these tiles are short enough that
-//                         a few of them in a last round cost what 256 small ones cost)
-//   key+value 1024x32     NO even split (its split form fetches the values late, vrdx_kernels.hip: +2 ... +7 % at
-//                         0.55 < f < 1); tail split while the rest is at most half a round (f = 1.06: 0.184 / 0.193 ms,
-//                         2.06: 0.294 / 0.303, 3.06: 0.399 / 0.408, 4.06: 0.524 / 0.532; beyond half a round -1 ... +4 %)
-vrdx::TilePlan PlanTiles(const VrdxSorter_T* sorter, int configIndex, bool keyValue, uint32_t elementCount, bool atomicRank) {
-  const vrdx::TileConfig& c = vrdx::kTileConfigs[configIndex];
-  const bool pair = configIndex == kCfg1024x32x2;
-  const bool splitForms = pair ? (!keyValue && atomicRank) : configIndex == kCfg1024x32;
-  const bool evenSplit = !keyValue;
-  const uint32_t tailPercent = pair ? 100u : (keyValue ? 50u : 0u);
-  return vrdx::PlanTiles(elementCount, (uint32_t)sorter->computeUnits, (uint32_t)c.threads, (uint32_t)c.keysPerThread,
-                         (uint32_t)c.subTiles, splitForms, evenSplit, tailPercent);
-}
-
-// The steps of a sort in the order they are enqueued, each with the timestamp slot it ends.  The slots carry the
-// reference's names (include/vk_radix_sort.h): 0 start, 1 "transfer", 2 + 3 p "upsweep" / 3 + 3 p "spine" / 4 + 3 p
-// "downsweep" of pass p, 14 end; a slot no step ends coincides with the one before it (StampCursor).
-enum class Step : uint8_t {
-  kFill,               // slot 1: state fill, and the copy of an indirect count (not counted as a launch)
-  kHistogram,          // slot 2, pass 0's "upsweep": the fused histogram of all four passes
-  kHistogramMsd,       // slot 2: the MSD plan's form of it
-  kSpineMsd,           // slot 3: a real "spine"
-  kMsdScatterOrPass0,  // slot 4, pass 0's "downsweep": the MSD plan's scatter, whose second role is pass 0
-  kMsdBucketsOrPass1,  // slot 5, pass 1's "upsweep": the MSD plan's full-size buckets, whose second role is pass 1
-  kBucketSortHalf,     // slot 5: its half-size buckets
-  kBucketSort,         // slot 5: the eight-bit plan's buckets
-  kPass,               // slot 4 + 3 p, "downsweep": pass p, look-back fused into it ("spine" = "upsweep" = the slot before)
-  kSmallSort,          // slot 14: the one-workgroup sort
-};
-struct SortStep { Step what; uint8_t pass, slot; const char* name; };  // (pass: kPass only; name: what EnqueueCheck reports)
-constexpr uint32_t kMaxSortSteps = 8;  // fill, histogram, spine, scatter, half-size buckets, passes 1-3
-
-// Everything the host decides about a sort, in ONE place: RecordSort records it and vrdxHipDescribePlan reports it.
-// storageAddress: the absolute address the storage is handed over at -- only its low seven bits matter (the pads in front
-// of the 128-byte aligned regions); 0 is the worst case for what fits, which is what vrdxHipDescribePlan assumes.
-struct SortPlan {
-  bool keyValue = false;
-  uint32_t elementCount = 0;
-  bool atomicRank = false;
-  bool oneWorkgroup = false;    // small_sort_kernel: one launch, no storage layout
-  uint32_t hybridCap = 0;       // the eight-bit hybrid plan is recorded with this bucket capacity
-  uint32_t msdBits = 0;         // the MSD plan is recorded in front of the passes (10 | 11)
-  uint32_t msdCap = 0;          // kMsdHalfCap: bucket_sort2_half_kernel, and pass 1 a launch of its own
-  uint32_t msdTileKeys = 0;
-  uint32_t msdTiles = 0;
-  int configIndex = 0;
-  vrdx::TilePlan tilePlan{};
-  bool blockSums = false;
-  bool fits = true;             // false: not even tiles of full capacity fit the caller's storage (refused)
-  vrdx::StorageLayout layout{};
-  SortStep steps[kMaxSortSteps];  // none: the empty sort and the refused one
-  uint32_t stepCount = 0;
-  uint32_t launches = 0;        // kernels among the steps
-};
-
-// The MSD plan's scatter launch is ALSO pass 0 of the fallback and its bucket launch pass 1 (one branch on the verdict, on
-// the device; vrdx_kernels.hip, msd_scatter_or_pass0_kernel): only passes 2 and 3 remain as launches that return when the
-// plan runs.  With buckets of the half-size kernel (512 threads; the passes' bodies need 1024) only the scatter launch has
-// a second role.  The eight-bit plan's bucket sort sits between launch 0 and launch 1 (which is empty when the plan applies).
-void ListSteps(SortPlan& p) {
-  const auto add = [&p](Step what, const char* name, uint32_t slot, uint32_t pass = 0) {
-    p.steps[p.stepCount++] = SortStep{what, (uint8_t)pass, (uint8_t)slot, name};
-    if (what != Step::kFill) ++p.launches;
-  };
-  const bool msd = p.msdBits != 0, halfBuckets = msd && p.msdCap == vrdx::kMsdHalfCap;
-  if (p.oneWorkgroup) return add(Step::kSmallSort, "small_sort_kernel", 14);
-  add(Step::kFill, "hipMemcpyAsync(count)", 1);
-  if (msd)
-    add(Step::kHistogramMsd, "histogram_msd_kernel", 2);
-  else
-    add(Step::kHistogram, "histogram_kernel", 2);
-  if (msd) {
-    add(Step::kSpineMsd, "spine_msd_kernel", 3);
-    add(Step::kMsdScatterOrPass0, "msd_scatter_or_pass0_kernel", 4);
-    if (halfBuckets)
-      add(Step::kBucketSortHalf, "bucket_sort2_half_kernel", 5);
-    else
-      add(Step::kMsdBucketsOrPass1, "msd_buckets_or_pass1_kernel", 5);
-  }
-  for (uint32_t pass = !msd ? 0u : halfBuckets ? 1u : 2u; pass < VRDX_PASSES; ++pass) {
-    if (pass == 1 && p.hybridCap != 0) add(Step::kBucketSort, "bucket_sort_kernel", 5);
-    add(Step::kPass, "onesweep_kernel", 4 + 3 * pass, pass);
-  }
-}
-
-SortPlan PlanSort(const VrdxSorter_T* sorter, bool keyValue, uint32_t elementCount, uint64_t storageAddress) {
-  SortPlan p;
-  p.keyValue = keyValue;
-  p.elementCount = elementCount;
-  p.atomicRank = sorter->atomicRank.load(std::memory_order_relaxed);  // one answer for the whole sort
-  const bool adaptive = EnvKnobs().forcedConfig < 0;
-  if (elementCount == 0) return p;
-  // Small sorts: one workgroup, one launch, nothing but the caller's keys / values and words 1-3 of the storage header
-  // touched -- the kernel zeroes the plan's verdict, the MSD plan's word and the failure word, so that the verdict an
-  // earlier sort left on this storage is not read as this one's (the general path costs six launches = 30-45 us however
-  // small N is).  Forcing a tile geometry (VRDX_TILE_CONFIG) also forces the general path, which is how the tests reach
-  // it at small sizes.
-  if (elementCount <= vrdx::kSmallSortMaxElements && adaptive && EnvKnobs().smallSort) {
-    p.oneWorkgroup = true;
-    p.layout = vrdx::MakeLayout(elementCount, sorter->minStorageBufferOffsetAlignment, 0, storageAddress);  // (the failure word)
-    ListSteps(p);
-    return p;
-  }
-  p.hybridCap = adaptive ? HybridCapacity(p.atomicRank, elementCount) : 0u;
-  p.msdBits = adaptive ? MsdBits(p.atomicRank, keyValue, elementCount, p.hybridCap, &p.msdCap) : 0u;
-  p.configIndex = ConfigIndex(sorter, keyValue, elementCount, p.atomicRank, p.msdBits != 0);
-  p.tilePlan = PlanTiles(sorter, p.configIndex, keyValue, elementCount, p.atomicRank);
-  // Block sums instead of the look-back chain: sorts of one round (PlanTiles) on the four-pass plan -- with a hybrid
-  // plan recorded, launch 0 may rank by another byte than its pass index, which the block-sum form does not look up.
-  p.blockSums = p.tilePlan.blockSums && p.hybridCap == 0 && EnvKnobs().blockSums;
-  // keys per tile of the MSD plan's histogram and scatter: equal tiles that fill whole rounds of one workgroup per CU
-  // (vrdx_layout.h); keys-only sorts by ten bits take two consecutive tiles per scatter workgroup (vrdx_kernels.hip)
-  p.msdTileKeys = vrdx::MsdTileKeysFor(elementCount, (uint32_t)sorter->computeUnits, vrdx::kMsdMaxTiles,
-                                       !keyValue && p.msdBits == 10);
-  p.msdTiles = vrdx::RoundUp(elementCount, p.msdTileKeys);
-  const uint32_t align = sorter->minStorageBufferOffsetAlignment;
-  p.layout = vrdx::MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, p.blockSums, p.msdBits, p.msdTiles);
-  if (p.msdBits != 0 && !vrdx::LayoutFits(p.layout, elementCount)) {
-    // (cannot happen for the sizes MsdBits admits -- tests/native/layout_check.cpp sweeps them -- but the storage is the
-    // caller's: without the plan's rows in front of the status regions the layout fits for every N)
-    p.msdBits = 0;
-    p.layout = vrdx::MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, p.blockSums);
-  }
-  if (!vrdx::LayoutFits(p.layout, elementCount)) {
-    // EVERY sort of the general path is checked, not only those with a plan in front: the layout depends on the tile plan,
-    // and a forced tile geometry (VRDX_TILE_CONFIG) can select plans the offline sweep of tests/native/layout_check.cpp
-    // never saw.  Tiles of the kernel's full capacity without block rows fit for every N (2 (tiles - 1) KiB <= (P - 1) KiB
-    // from 8192 keys per tile up); smaller tiles cannot be helped: the scratch arrays must not leave the caller's
-    // allocation, so that sort is refused and says so (VRDX_HIP_STATUS_ENQUEUE_REFUSED).
-    const vrdx::TileConfig& c = vrdx::kTileConfigs[p.configIndex];
-    p.tilePlan = vrdx::PlanTiles(elementCount, (uint32_t)sorter->computeUnits, (uint32_t)c.threads, (uint32_t)c.keysPerThread,
-                                 (uint32_t)c.subTiles, false, false, 0);
-    p.blockSums = false;
-    p.msdBits = 0;
-    p.layout = vrdx::MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, false, 0);
-    p.fits = vrdx::LayoutFits(p.layout, elementCount);
-  }
-  if (p.fits) ListSteps(p);
-  return p;
-}
 
 // Launches go to the sorter's device (a Vulkan command buffer belongs to one device too); the
 // calling thread's current device is put back afterwards.
@@ -631,21 +395,8 @@ vrdx::BucketSortArgs BucketSortArgsOf(const SortPlan& plan, const SortBuffers& b
   return a;
 }
 
-// Grid of the fused histogram.  Every workgroup ends with up to 1024 global atomics on the same 1024 words, so few, long-lived
-// workgroups win for large inputs: one per CU and at least two groups of 16384 keys each (tools/hist_grid.sh, removed, last at
-// commit 3645810: 17.4 us with 256 workgroups against 21.1 us with 512 at N = 2^23; equal at 2^25).  Small inputs want the
-// opposite -- the kernel is one memory latency long, so up to 128 workgroups of at least 4096 keys share it: 6.9 instead of 9.7 us
-// at 2^18, 7.9 instead of 9.8 us at 2^20, same at 2^22.  The MSD plan's form takes whole tiles of up to 32768 keys per workgroup.
-uint32_t HistogramGrid(const VrdxSorter_T* sorter, const SortPlan& plan) {
-  const uint32_t cap = (uint32_t)sorter->computeUnits * vrdx::kHistWorkgroupsPerCu;
-  if (plan.msdBits != 0) return std::min<uint32_t>(plan.msdTiles, cap);
-  const uint32_t wide = std::min<uint32_t>(128u, vrdx::RoundUp(plan.elementCount, 4096u));
-  const uint32_t grid = std::max(vrdx::RoundUp(plan.elementCount, 2 * vrdx::kHistGroupKeys), wide);
-  return std::max(std::min(grid, cap), 1u);
-}
-
 // Enqueues one step of the list; the value the runtime returned for it goes to EnqueueCheck.
-hipError_t EnqueueStep(const VrdxSorter_T* sorter, hipStream_t stream, const SortPlan& plan, const SortBuffers& b,
+hipError_t EnqueueStep(const VrdxSorter_T* sorter, const vrdx::PlanContext& context, hipStream_t stream, const SortPlan& plan, const SortBuffers& b,
                        const vrdx::MsdArgs& msd, const SortStep& step) {
   const bool keyValue = plan.keyValue, atomicRank = plan.atomicRank;
   const uint32_t tiles = plan.tilePlan.tiles;
@@ -661,9 +412,9 @@ hipError_t EnqueueStep(const VrdxSorter_T* sorter, hipStream_t stream, const Sor
       if (b.countPtr == nullptr) return hipSuccess;
       return hipMemcpyAsync(b.storage + plan.layout.countOffset, b.countPtr, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
     case Step::kHistogram:
-      return vrdx::LaunchHistogram(stream, HistogramGrid(sorter, plan), b.keys, plan.elementCount, b.countPtr, b.histogram, b.tickets,
+      return vrdx::LaunchHistogram(stream, vrdx::HistogramGrid(context, plan), b.keys, plan.elementCount, b.countPtr, b.histogram, b.tickets,
                                    b.storage + plan.layout.statusClearOffset, (uint32_t)plan.layout.statusClearBytes);
-    case Step::kHistogramMsd: return vrdx::LaunchHistogramMsd(stream, HistogramGrid(sorter, plan), msd);
+    case Step::kHistogramMsd: return vrdx::LaunchHistogramMsd(stream, vrdx::HistogramGrid(context, plan), msd);
     case Step::kSpineMsd: return vrdx::LaunchSpineMsd(stream, msd);
     case Step::kMsdScatterOrPass0: return vrdx::LaunchMsdFused(stream, false, keyValue, msd, PassArgs(plan, b, 0), tiles);
     case Step::kMsdBucketsOrPass1: return vrdx::LaunchMsdFused(stream, true, keyValue, msd, PassArgs(plan, b, 1), tiles);
@@ -695,7 +446,8 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
   DeviceScope deviceScope(sorter->device);
 
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
-  const SortPlan plan = PlanSort(sorter, keyValue, elementCount, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  const vrdx::PlanContext context = PlanContextOf(sorter);
+  const SortPlan plan = vrdx::PlanSort(context, keyValue, elementCount, (uint64_t)reinterpret_cast<uintptr_t>(storage));
   const SortBuffers b = ResolveBuffers(
       sorter, plan.layout, storage, reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset)),
       keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr,
@@ -713,7 +465,7 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
   if (!plan.fits)
     EnqueueCheck(sorter, "storage layout (status rows do not fit the reference's partition-histogram area)", hipErrorInvalidValue);
   for (uint32_t i = 0; i < plan.stepCount; ++i) {
-    EnqueueCheck(sorter, plan.steps[i].name, EnqueueStep(sorter, stream, plan, b, msd, plan.steps[i]));
+    EnqueueCheck(sorter, plan.steps[i].name, EnqueueStep(sorter, context, stream, plan, b, msd, plan.steps[i]));
     stamps.AdvanceTo(plan.steps[i].slot);
   }
   stamps.Finish();
@@ -1267,28 +1019,8 @@ void vrdxHipDescribePlan(VrdxSorter sorter, uint32_t elementCount, int keyValue,
   std::memset(info, 0, sizeof(*info));
   if (sorter == nullptr || elementCount == 0) return;
   if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
-  const bool kv = keyValue != 0;
-  const uint32_t fourPasses = kv ? 68u : 36u;  // 4 (histogram) + 4 x (read + write)
-  const uint32_t twoTrips = kv ? 36u : 20u;    // 4 (histogram) + scatter (read + write) + buckets (read + write)
   // the recorder's own planning function (storage address 0: the alignment at which the least fits)
-  const SortPlan plan = PlanSort(sorter, kv, elementCount, 0);
-  info->fallbackBytesPerElement = fourPasses;
-  info->launches = plan.launches;
-  if (plan.oneWorkgroup) {
-    info->plan = VRDX_HIP_PLAN_ONE_WORKGROUP;
-    info->bytesPerElement = info->fallbackBytesPerElement = kv ? 16u : 8u;
-  } else if (plan.msdBits != 0) {
-    info->plan = VRDX_HIP_PLAN_MSD;
-    info->bits = plan.msdBits;
-    info->bytesPerElement = twoTrips;
-  } else if (plan.hybridCap != 0) {
-    info->plan = VRDX_HIP_PLAN_HYBRID8;
-    info->bits = 8;
-    info->bytesPerElement = twoTrips;
-  } else {
-    info->plan = VRDX_HIP_PLAN_FOUR_PASSES;
-    info->bytesPerElement = fourPasses;
-  }
+  vrdx::DescribePlan(vrdx::PlanSort(PlanContextOf(sorter), keyValue != 0, elementCount, 0), info);
 }
 
 uint32_t vrdxHipReadPlanVerdict(VkCommandBuffer commandBuffer, VkBuffer storageBuffer, VkDeviceSize storageOffset) {
@@ -1313,13 +1045,11 @@ const char* vrdxHipVersionString(void) {
   struct Text {
     char text[160];
     Text() {
-      VrdxSorter_T nominal;  // an MI355X: 256 CUs, lane-ordered LDS atomics
-      nominal.computeUnits = 256;
-      const vrdx::TileConfig& k = vrdx::kTileConfigs[ConfigIndex(&nominal, false, 1u << 25, true, false)];
-      const vrdx::TileConfig& kv = vrdx::kTileConfigs[ConfigIndex(&nominal, true, 1u << 25, true, false)];
+      vrdx::PlanContext nominal{256, true};  // an MI355X: 256 CUs, lane-ordered LDS atomics
+      nominal.forcedConfig = EnvKnobs().forcedConfig;
       char kName[32], kvName[32];
-      ConfigName(k, kName, sizeof(kName));
-      ConfigName(kv, kvName, sizeof(kvName));
+      vrdx::ConfigName(vrdx::kTileConfigs[vrdx::ConfigIndex(nominal, false, 1u << 25)], kName, sizeof(kName));
+      vrdx::ConfigName(vrdx::kTileConfigs[vrdx::ConfigIndex(nominal, true, 1u << 25)], kvName, sizeof(kvName));
       std::snprintf(text, sizeof(text), "vrdx-hip %d.%d.%d gfx950 tiles at 2^25: keys=%s key-value=%s%s",
                     VRDX_VERSION_MAJOR, VRDX_VERSION_MINOR, VRDX_VERSION_PATCH, kName, kvName,
                     EnvKnobs().forcedConfig >= 0 ? " (forced)" : " (size-adaptive)");

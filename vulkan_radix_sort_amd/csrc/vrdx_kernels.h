@@ -32,7 +32,10 @@ struct TileConfig {
   uint32_t tileKeys() const { return (uint32_t)threads * (uint32_t)keysPerThread * (uint32_t)subTiles; }
 };
 constexpr int kNumTileConfigs = 4;
-extern const TileConfig kTileConfigs[kNumTileConfigs];  // vrdx_launch.inc
+// Every geometry here is selected by ConfigIndex (vrdx_plan.h) for some size range; nothing else is built.
+constexpr TileConfig kTileConfigs[kNumTileConfigs] = {
+    {1024, 8, 1}, {1024, 16, 1}, {1024, 32, 1}, {1024, 32, 2},
+};
 
 // Every spin is bounded: a look-back that makes no progress for this many trips sets the failure word and goes on
 // (result unspecified) instead of hanging the GPU.
@@ -396,7 +399,7 @@ constexpr uint32_t MsdBucketGrid(uint32_t bits, bool halfSizeKernel) { return ha
 // 18 K keys, half the LDS work to hide a write-back behind) nothing was measured and every bucket keeps plain stores
 // (DESIGN.md 5.B).
 constexpr uint32_t kMsdStreamedOutputFrom = 1u << 25;
-constexpr uint32_t kMsdStreamedOutputUpTo = 36649984u;  // the ten-bit plan's last size (vrdx_api.cpp, MsdBits)
+constexpr uint32_t kMsdStreamedOutputUpTo = 36649984u;  // the ten-bit plan's last size (MsdBits; asserted in vrdx_plan.h)
 constexpr uint32_t MsdPlainTail(uint32_t computeUnits, uint32_t elementCount, uint32_t bits) {
   return elementCount >= kMsdStreamedOutputFrom && elementCount <= kMsdStreamedOutputUpTo ? computeUnits : 1u << bits;
 }

@@ -262,11 +262,6 @@ static hipError_t Launch(KernelId id, uint32_t grid, hipStream_t stream, Args...
 // a form of a family of four, listed as [key-value][atomic rank]
 static KernelId Form(KernelId first, bool keyValue, bool atomicRank) { return KernelId(first + 2 * keyValue + atomicRank); }
 
-// Every geometry here is selected by ConfigIndex (vrdx_api.cpp) for some size range; nothing else is built.
-const TileConfig kTileConfigs[kNumTileConfigs] = {
-    {1024, 8, 1}, {1024, 16, 1}, {1024, 32, 1}, {1024, 32, 2},
-};
-
 hipError_t PrepareKernels() {
   for (int id = 0; id < kNumKernels; ++id) {
     const hipError_t e = PrepareKernel(KernelId(id));
@@ -275,7 +270,7 @@ hipError_t PrepareKernels() {
   return hipSuccess;
 }
 
-// run-time slot counts (even-split and tail-split tiles, PlanTiles in vrdx_api.cpp): multiples of 4, at most the geometry's
+// run-time slot counts (even-split and tail-split tiles, PlanTiles in vrdx_plan.h): multiples of 4, at most the geometry's
 static bool SlotsFit(const OnesweepArgs& a, uint32_t keysPerThread) {
   return a.slots % 4 == 0 && a.slots <= keysPerThread && a.tailSlots % 4 == 0 && a.tailSlots != 0 &&
          a.tailSlots <= keysPerThread;

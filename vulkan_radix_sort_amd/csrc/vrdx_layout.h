@@ -33,7 +33,7 @@
 // tile is never looked at, so rows = tiles - 1, and two regions (pass p uses region p & 1 and zeroes its own
 // row of the other one for pass p + 1) need 2 * (tiles - 1) KiB <= (P - 1) KiB, P = ceil(N / 4096): true for
 // every N when no tile is smaller than 8192 keys, and for the tail tiles of 4096 keys and more that a sort of
-// one round and more may end with (PlanTiles in vrdx_api.cpp; checked by tests/native/layout_check.cpp).
+// one round and more may end with (PlanTiles in vrdx_plan.h; checked by tests/native/layout_check.cpp).
 // N <= 2^30 - 4 (the reference's uint32 byte-size math wraps above that, :105-115) keeps every
 // prefix inside 30 bits.
 //
@@ -84,8 +84,8 @@
 namespace vrdx {
 
 // reference: src/vk_radix_sort.h.in:105-106 (uint32 arithmetic on purpose)
-static inline uint32_t RoundUp(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
-static inline uint32_t Align(uint32_t a, uint32_t b) { return (a + b - 1) / b * b; }
+static constexpr uint32_t RoundUp(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+static constexpr uint32_t Align(uint32_t a, uint32_t b) { return (a + b - 1) / b * b; }
 
 // reference: src/vk_radix_sort.h.in:108-111
 static inline uint64_t HistogramSize(uint32_t elementCount, uint32_t align) {

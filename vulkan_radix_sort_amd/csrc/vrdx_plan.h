@@ -1,0 +1,339 @@
+// Everything the HOST decides about a sort, as plain functions of the element count, key+value or not, and a PlanContext
+// (CU count, ranking mode, storage alignment, the planning knobs): the plan (one workgroup, eight-bit hybrid, MSD by 10 or
+// 11 bits, four passes), the bucket capacity, the tile geometry and tile plan, block sums, the storage layout, the step
+// list with its timestamp slots, the histogram grid and the fallback taken when a layout does not fit.  No HIP call, no
+// environment, no static state: the recorder (vrdx_api.cpp) builds one PlanContext per recorded sort and calls PlanSort;
+// tests/native/plan_check.cpp and layout_check.cpp call the same functions at every size on a CPU.
+#ifndef VRDX_PLAN_H
+#define VRDX_PLAN_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <algorithm>
+
+#include "../../include/vk_radix_sort.h"
+#include "vrdx_kernels.h"
+#include "vrdx_layout.h"
+
+namespace vrdx {
+
+// What planning depends on besides the sort itself.  The knobs are those of the environment (vrdx_api.cpp, EnvKnobs;
+// INTEGRATION.md) at their defaults.
+struct PlanContext {
+  int computeUnits = 0;
+  bool atomicRank = false;  // the one-atomic ranking (LDS returning atomics proven lane-ordered), else the ballot ranking
+  uint32_t minStorageBufferOffsetAlignment = VRDX_STORAGE_ALIGN;
+  int forcedConfig = -1;    // VRDX_TILE_CONFIG: one geometry for everything, and the general path at every size
+  bool hybrid = true;       // VRDX_HYBRID=0: always the four-pass plan
+  bool msd = true;          // VRDX_MSD=0 (or VRDX_HYBRID=0): no MSD plan
+  bool smallSort = true;    // VRDX_SMALL_SORT=0: always the general path
+  bool blockSums = true;    // VRDX_BLOCK_SUMS=0: sorts of one round keep the classic look-back (measurements)
+};
+
+// "1024x32", or "1024x32x2" for the two-sub-tile kernel
+static inline void ConfigName(const TileConfig& c, char* out, size_t size) {
+  if (c.subTiles == 1)
+    snprintf(out, size, "%dx%d", c.threads, c.keysPerThread);
+  else
+    snprintf(out, size, "%dx%dx%d", c.threads, c.keysPerThread, c.subTiles);
+}
+
+// Tile geometry by problem size, measured on MI355X (tools: `vrdx_selftest sweep`, tables in
+// profiles/r01_sweep_*.txt).  Three regimes:
+//  * small sorts want many small tiles (parallelism across the CUs; six launches cost ~45 us);
+//  * beyond that throughput grows with the tile (fewer look-backs per key, longer digit runs) up to
+//    the 32768 keys whose staging buffer fits the CU's LDS ONCE -- so these tiles run one workgroup
+//    per CU in lock-step ROUNDS of computeUnits tiles, and a sort whose tile count is just above a
+//    multiple of the CU count pays for a whole extra round.  f below is the size in such rounds.
+//    (16384-key tiles, two workgroups per CU, degrade gracefully in a partial round and used to win
+//    just past the round boundaries; on the final kernels they no longer do);
+//  * the two-sub-tile kernel (65536 keys, keys-only) halves the rounds again: best when f is in
+//    (1, 2], just below 4 or 6.
+enum : int { kCfg1024x8 = 0, kCfg1024x16 = 1, kCfg1024x32 = 2, kCfg1024x32x2 = 3 };  // indices of kTileConfigs
+
+// msd: the MSD plan is recorded in front of the passes, which are then only the fallback for skewed keys; its per-tile counts
+// take a quarter to a half of the reference's partition-histogram area, so the passes must not take tiles of 16384.
+constexpr int ConfigIndex(const PlanContext& c, bool keyValue, uint32_t elementCount, bool msd = false) {
+  const int forced = c.forcedConfig;
+  // (the two-sub-tile kernel is keys-only: a key+value sort under a forced 1024x32x2 takes 1024x32)
+  if (forced >= 0) return forced == kCfg1024x32x2 && (keyValue || !c.atomicRank) ? kCfg1024x32 : forced;
+  const double f = (double)elementCount / ((double)c.computeUnits * 32768.0);
+  // Behind the MSD plan the passes are the fallback only, and the plan's own launches double as its first two (one kernel, two
+  // roles): those kernels exist for 1024x32 key+value and the two-sub-tile geometry keys-only (the plan is recorded with the
+  // one-atomic ranking only), which are then taken at every size -- keys-only at one round of tiles and below as even-split
+  // tiles of two half-size sub-tiles.
+  if (msd) return keyValue ? kCfg1024x32 : kCfg1024x32x2;
+  if (keyValue) {
+    if (f <= 0.26) return kCfg1024x8;
+    if (f <= 0.53) return kCfg1024x16;
+    // just past one round of 32768-element tiles, two workgroups of 16384 per CU fill the second round's gap
+    // (1.2-2.6 % at 1.07 <= f <= 1.32, profiles/r03_sweep_by_geometry.txt; still so with the tail split of round 4,
+    // profiles/r04_tail_split_kv.txt)
+    if (f > 1.0 && f <= 1.35) return kCfg1024x16;
+    return kCfg1024x32;
+  }
+  if (f <= 0.125) return kCfg1024x8;
+  if (f <= 0.5) return kCfg1024x16;   // beyond: even-split 1024x32 tiles (PlanTiles), 7 % faster at f = 0.536
+  if (f <= 1.0) return kCfg1024x32;
+  // Beyond one round the two-sub-tile kernel (65536 keys per workgroup: half the look-backs per key), whose last,
+  // partial round is cut into small equal tiles (tail split, PlanTiles): with that it is the fastest geometry at every
+  // size from one round up (profiles/r04_tail_split_keys.txt; without it, it lost a whole 65536-key round to the
+  // 1024x32 tiles whenever the tile count passed a multiple of the CU count -- f in (2, 3.3] and beyond 4 in round 3).
+  // It holds two sub-tiles' keys in registers: only with the one-atomic ranking.
+  return c.atomicRank ? kCfg1024x32x2 : kCfg1024x32;
+}
+
+// Mid-size sorts record the hybrid plan (vrdx_kernels.hip, PassPlan) next to the four passes: launch 0 scatters by the
+// keys' highest byte that varies and bucket_sort_kernel finishes every bucket inside one workgroup -- if the DEVICE finds that no bucket
+// exceeds the capacity returned here; otherwise the four passes run as usual and the bucket launch is empty.  The
+// capacity is the smallest of 4096 / 8192 / 16384 / 32768 (the last one with the one-atomic ranking only) that leaves a
+// bucket twice the room of its mean N / 256; the largest one is recorded as long as it leaves 3 % (a bucket sort
+// costs what the bucket's elements cost, whatever the capacity; uniform keys spread by half a percent at these sizes --
+// mean 31800, sigma 178 at 8.1 M: the capacity is 5 sigma away -- and a plan that does not apply costs one empty
+// launch, 3 us, where one that does saves 17-25 %): N <= 8.1 M elements (4.0 M with the ballot ranking).
+// 0 = the plan is not recorded (larger N, a forced tile geometry, VRDX_HYBRID=0).
+constexpr uint32_t HybridCapacity(const PlanContext& c, uint32_t elementCount) {
+  if (!c.hybrid || elementCount <= kSmallSortMaxElements) return 0;
+  // a bucket may hold twice the mean bucket; the LARGEST capacity is tried with less room than the others (3 %): failing
+  // costs one empty launch, the plan is worth a fifth to a third of the sort (profiles/r03_hybrid_headroom.txt)
+  const uint64_t mean = (elementCount + VRDX_RADIX - 1) / VRDX_RADIX;
+  const uint32_t need = (uint32_t)(mean * 200u / 100u);
+  const uint32_t needLast = (uint32_t)(mean * 103u / 100u);
+  // 32768-element buckets: the one-atomic ranking only (the ballot forms of that kernel would spill); key+value stages
+  // keys and values through one buffer there (SharedStage in vrdx_kernels.hip)
+  const uint32_t largest = c.atomicRank ? 32768u : 16384u;
+  if (need <= 4096u) return 4096u;
+  if (need <= 8192u) return 8192u;
+  if (need <= 16384u) return 16384u;
+  if (need <= largest) return largest;
+  return needLast <= largest ? largest : 0u;
+}
+
+// The MSD plan (vrdx_kernels.hip, "MSD plan"): one stable scatter by the keys' top 10 or 11 bits, then every bucket by its
+// remaining bits in two passes inside one workgroup -- three ranking steps and two trips through memory instead of four
+// and four.  Recorded, in front of the four passes (which return on its verdict), for sorts beyond the eight-bit
+// plan's reach whose mean bucket leaves 3 % of room in the bucket kernel's capacity (uniform keys spread by half a percent
+// at these sizes): ten bits up to 36.6 M keys / 32.5 M pairs, eleven bits up to twice that.  Returns the bits or 0.
+// One-atomic ranking only.  VRDX_MSD=0 switches it off (VRDX_HYBRID=0 and a forced tile geometry as well).
+constexpr uint32_t MsdBits(const PlanContext& c, bool keyValue, uint32_t elementCount, uint32_t hybridCap, uint32_t* capacity) {
+  if (!c.msd || !c.atomicRank) return 0;
+  // From where the EIGHT-bit plan ends (8.1 M: hybridCap == 0), keys-only and key+value.  Up to 18.1 M elements the buckets
+  // hold at most 18432 and the half-size bucket kernel sorts them, two workgroups to a CU: with it the plan is 8-15 % faster
+  // than round 4's nine-bit hybrid plan and the four passes at one round of tiles, which key+value sorts of these sizes
+  // took before (profiles/r05_msd_half_buckets.txt); that plan's kernels are gone since.
+  if (hybridCap != 0 || elementCount <= kSmallSortMaxElements || RoundUp(elementCount, kMsdTileKeys) > kMsdMaxTiles) return 0;
+  const uint32_t cap = keyValue ? kMsdCapKeyValue : kMsdCapKeys;
+  *capacity = cap;
+  for (uint32_t bits = 10; bits <= 11; ++bits) {
+    const uint64_t mean = ((uint64_t)elementCount + (1u << bits) - 1u) >> bits;
+    if (mean * 103u / 100u <= cap) {
+      // buckets of half the size: the bucket kernel of 512 threads, two workgroups per CU (bucket_sort2_half_kernel)
+      // (4 % of headroom here: 5.3 sigma of a uniform bucket of 17700; the 3 % of the full size would be 4 sigma at this
+      // capacity, and with 1024 buckets one sort in thirty at the top of the range would be turned down)
+      if (bits == 10 && mean * 104u / 100u <= kMsdHalfCap)
+        *capacity = kMsdHalfCap;
+      return bits;
+    }
+  }
+  return 0;
+}
+
+// kMsdStreamedOutputUpTo (vrdx_kernels.h) quotes the rule above: the ten-bit plan's last size, keys-only and key+value.
+constexpr uint32_t AdaptiveMsdBits(bool keyValue, uint32_t elementCount) {
+  const PlanContext mi355x{256, true};
+  uint32_t capacity = 0;
+  return MsdBits(mi355x, keyValue, elementCount, HybridCapacity(mi355x, elementCount), &capacity);
+}
+static_assert(AdaptiveMsdBits(false, kMsdStreamedOutputUpTo) == 10 && AdaptiveMsdBits(false, kMsdStreamedOutputUpTo + 1) == 11 &&
+                  AdaptiveMsdBits(true, kMsdStreamedOutputUpTo) == 10 && AdaptiveMsdBits(true, kMsdStreamedOutputUpTo + 1) == 11,
+              "kMsdStreamedOutputUpTo is not the ten-bit MSD plan's last size");
+
+// The tile plan of a sort (vrdx_layout.h, PlanTiles): even-split tiles for sorts of one round, tail-split tiles behind
+// the whole rounds of a longer one -- where the kernels' forms with run-time slot counts exist and where they were
+// measured to pay (profiles/r04_tail_split_keys.txt, r04_tail_split_kv.txt; f = size in rounds of CUs x 32768):
+//   keys-only 1024x32x2   even split (-9.5 % at f = 1.07) and tail split at every size (f = 2.06: 0.191 instead of
+//                         0.230 ms; 3.06: 0.261 / 0.272; 4.06: 0.340 / 0.388)
+//   keys-only 1024x32     even split (-3.5 % at f = 0.5); NO tail split (+0 ... +4 %: these tiles are short enough that
+//                         a few of them in a last round cost what 256 small ones cost)
+//   key+value 1024x32     NO even split (its split form fetches the values late, vrdx_kernels.hip: +2 ... +7 % at
+//                         0.55 < f < 1); tail split while the rest is at most half a round (f = 1.06: 0.184 / 0.193 ms,
+//                         2.06: 0.294 / 0.303, 3.06: 0.399 / 0.408, 4.06: 0.524 / 0.532; beyond half a round -1 ... +4 %)
+static inline TilePlan PlanTiles(const PlanContext& c, int configIndex, bool keyValue, uint32_t elementCount) {
+  const TileConfig& t = kTileConfigs[configIndex];
+  const bool pair = configIndex == kCfg1024x32x2;
+  const bool splitForms = pair ? (!keyValue && c.atomicRank) : configIndex == kCfg1024x32;
+  const bool evenSplit = !keyValue;
+  const uint32_t tailPercent = pair ? 100u : (keyValue ? 50u : 0u);
+  return PlanTiles(elementCount, (uint32_t)c.computeUnits, (uint32_t)t.threads, (uint32_t)t.keysPerThread, (uint32_t)t.subTiles,
+                   splitForms, evenSplit, tailPercent);
+}
+
+// The steps of a sort in the order they are enqueued, each with the timestamp slot it ends.  The slots carry the
+// reference's names (include/vk_radix_sort.h): 0 start, 1 "transfer", 2 + 3 p "upsweep" / 3 + 3 p "spine" / 4 + 3 p
+// "downsweep" of pass p, 14 end; a slot no step ends coincides with the one before it (StampCursor in vrdx_api.cpp).
+enum class Step : uint8_t {
+  kFill,               // slot 1: state fill, and the copy of an indirect count (not counted as a launch)
+  kHistogram,          // slot 2, pass 0's "upsweep": the fused histogram of all four passes
+  kHistogramMsd,       // slot 2: the MSD plan's form of it
+  kSpineMsd,           // slot 3: a real "spine"
+  kMsdScatterOrPass0,  // slot 4, pass 0's "downsweep": the MSD plan's scatter, whose second role is pass 0
+  kMsdBucketsOrPass1,  // slot 5, pass 1's "upsweep": the MSD plan's full-size buckets, whose second role is pass 1
+  kBucketSortHalf,     // slot 5: its half-size buckets
+  kBucketSort,         // slot 5: the eight-bit plan's buckets
+  kPass,               // slot 4 + 3 p, "downsweep": pass p, look-back fused into it ("spine" = "upsweep" = the slot before)
+  kSmallSort,          // slot 14: the one-workgroup sort
+};
+struct SortStep { Step what; uint8_t pass, slot; const char* name; };  // (pass: kPass only; name: what EnqueueCheck reports)
+constexpr uint32_t kMaxSortSteps = 8;  // fill, histogram, spine, scatter, half-size buckets, passes 1-3
+
+// Everything the host decides about a sort, in ONE place: RecordSort records it and vrdxHipDescribePlan reports it.
+// storageAddress: the absolute address the storage is handed over at -- only its low seven bits matter (the pads in front
+// of the 128-byte aligned regions); 0 is the worst case for what fits, which is what vrdxHipDescribePlan assumes.
+struct SortPlan {
+  bool keyValue = false;
+  uint32_t elementCount = 0;
+  bool atomicRank = false;
+  bool oneWorkgroup = false;    // small_sort_kernel: one launch, no storage layout
+  uint32_t hybridCap = 0;       // the eight-bit hybrid plan is recorded with this bucket capacity
+  uint32_t msdBits = 0;         // the MSD plan is recorded in front of the passes (10 | 11)
+  uint32_t msdCap = 0;          // kMsdHalfCap: bucket_sort2_half_kernel, and pass 1 a launch of its own
+  uint32_t msdTileKeys = 0;
+  uint32_t msdTiles = 0;
+  int configIndex = 0;
+  TilePlan tilePlan{};
+  bool blockSums = false;
+  bool fits = true;             // false: not even tiles of full capacity fit the caller's storage (refused)
+  StorageLayout layout{};
+  SortStep steps[kMaxSortSteps];  // none: the empty sort and the refused one
+  uint32_t stepCount = 0;
+  uint32_t launches = 0;        // kernels among the steps
+};
+
+// The MSD plan's scatter launch is ALSO pass 0 of the fallback and its bucket launch pass 1 (one branch on the verdict, on
+// the device; vrdx_kernels.hip, msd_scatter_or_pass0_kernel): only passes 2 and 3 remain as launches that return when the
+// plan runs.  With buckets of the half-size kernel (512 threads; the passes' bodies need 1024) only the scatter launch has
+// a second role.  The eight-bit plan's bucket sort sits between launch 0 and launch 1 (which is empty when the plan applies).
+static inline void ListSteps(SortPlan& p) {
+  const auto add = [&p](Step what, const char* name, uint32_t slot, uint32_t pass = 0) {
+    p.steps[p.stepCount++] = SortStep{what, (uint8_t)pass, (uint8_t)slot, name};
+    if (what != Step::kFill) ++p.launches;
+  };
+  const bool msd = p.msdBits != 0, halfBuckets = msd && p.msdCap == kMsdHalfCap;
+  if (p.oneWorkgroup) return add(Step::kSmallSort, "small_sort_kernel", 14);
+  add(Step::kFill, "hipMemcpyAsync(count)", 1);
+  if (msd)
+    add(Step::kHistogramMsd, "histogram_msd_kernel", 2);
+  else
+    add(Step::kHistogram, "histogram_kernel", 2);
+  if (msd) {
+    add(Step::kSpineMsd, "spine_msd_kernel", 3);
+    add(Step::kMsdScatterOrPass0, "msd_scatter_or_pass0_kernel", 4);
+    if (halfBuckets)
+      add(Step::kBucketSortHalf, "bucket_sort2_half_kernel", 5);
+    else
+      add(Step::kMsdBucketsOrPass1, "msd_buckets_or_pass1_kernel", 5);
+  }
+  for (uint32_t pass = !msd ? 0u : halfBuckets ? 1u : 2u; pass < VRDX_PASSES; ++pass) {
+    if (pass == 1 && p.hybridCap != 0) add(Step::kBucketSort, "bucket_sort_kernel", 5);
+    add(Step::kPass, "onesweep_kernel", 4 + 3 * pass, pass);
+  }
+}
+
+static inline SortPlan PlanSort(const PlanContext& c, bool keyValue, uint32_t elementCount, uint64_t storageAddress) {
+  SortPlan p;
+  p.keyValue = keyValue;
+  p.elementCount = elementCount;
+  p.atomicRank = c.atomicRank;  // one answer for the whole sort
+  const bool adaptive = c.forcedConfig < 0;
+  if (elementCount == 0) return p;
+  // Small sorts: one workgroup, one launch, nothing but the caller's keys / values and words 1-3 of the storage header
+  // touched -- the kernel zeroes the plan's verdict, the MSD plan's word and the failure word, so that the verdict an
+  // earlier sort left on this storage is not read as this one's (the general path costs six launches = 30-45 us however
+  // small N is).  Forcing a tile geometry (VRDX_TILE_CONFIG) also forces the general path, which is how the tests reach
+  // it at small sizes.
+  if (elementCount <= kSmallSortMaxElements && adaptive && c.smallSort) {
+    p.oneWorkgroup = true;
+    p.layout = MakeLayout(elementCount, c.minStorageBufferOffsetAlignment, 0, storageAddress);  // (the failure word)
+    ListSteps(p);
+    return p;
+  }
+  p.hybridCap = adaptive ? HybridCapacity(c, elementCount) : 0u;
+  p.msdBits = adaptive ? MsdBits(c, keyValue, elementCount, p.hybridCap, &p.msdCap) : 0u;
+  p.configIndex = ConfigIndex(c, keyValue, elementCount, p.msdBits != 0);
+  p.tilePlan = PlanTiles(c, p.configIndex, keyValue, elementCount);
+  // Block sums instead of the look-back chain: sorts of one round (PlanTiles) on the four-pass plan -- with a hybrid
+  // plan recorded, launch 0 may rank by another byte than its pass index, which the block-sum form does not look up.
+  p.blockSums = p.tilePlan.blockSums && p.hybridCap == 0 && c.blockSums;
+  // keys per tile of the MSD plan's histogram and scatter: equal tiles that fill whole rounds of one workgroup per CU
+  // (vrdx_layout.h); keys-only sorts by ten bits take two consecutive tiles per scatter workgroup (vrdx_kernels.hip)
+  p.msdTileKeys = MsdTileKeysFor(elementCount, (uint32_t)c.computeUnits, kMsdMaxTiles, !keyValue && p.msdBits == 10);
+  p.msdTiles = RoundUp(elementCount, p.msdTileKeys);
+  const uint32_t align = c.minStorageBufferOffsetAlignment;
+  p.layout = MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, p.blockSums, p.msdBits, p.msdTiles);
+  if (p.msdBits != 0 && !LayoutFits(p.layout, elementCount)) {
+    // (never taken for the sizes MsdBits admits -- tests/native/layout_check.cpp asserts it on this very function, at every
+    // size it sweeps -- but the storage is the caller's: without the plan's rows in front of the status regions the layout
+    // fits for every N)
+    p.msdBits = 0;
+    p.layout = MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, p.blockSums);
+  }
+  if (!LayoutFits(p.layout, elementCount)) {
+    // EVERY sort of the general path is checked, not only those with a plan in front: the layout depends on the tile plan,
+    // and a forced tile geometry (VRDX_TILE_CONFIG) can select plans the sweep of tests/native/layout_check.cpp (adaptive
+    // plans only) never saw.  Tiles of the kernel's full capacity without block rows fit for every N (2 (tiles - 1) KiB <=
+    // (P - 1) KiB from 8192 keys per tile up); smaller tiles cannot be helped: the scratch arrays must not leave the caller's
+    // allocation, so that sort is refused and says so (VRDX_HIP_STATUS_ENQUEUE_REFUSED).
+    const TileConfig& t = kTileConfigs[p.configIndex];
+    p.tilePlan = PlanTiles(elementCount, (uint32_t)c.computeUnits, (uint32_t)t.threads, (uint32_t)t.keysPerThread,
+                           (uint32_t)t.subTiles, false, false, 0);
+    p.blockSums = false;
+    p.msdBits = 0;
+    p.layout = MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, false, 0);
+    p.fits = LayoutFits(p.layout, elementCount);
+  }
+  if (p.fits) ListSteps(p);
+  return p;
+}
+
+// Grid of the fused histogram.  Every workgroup ends with up to 1024 global atomics on the same 1024 words, so few, long-lived
+// workgroups win for large inputs: one per CU and at least two groups of 16384 keys each (tools/hist_grid.sh, removed, last at
+// commit 3645810: 17.4 us with 256 workgroups against 21.1 us with 512 at N = 2^23; equal at 2^25).  Small inputs want the
+// opposite -- the kernel is one memory latency long, so up to 128 workgroups of at least 4096 keys share it: 6.9 instead of 9.7 us
+// at 2^18, 7.9 instead of 9.8 us at 2^20, same at 2^22.  The MSD plan's form takes whole tiles of up to 32768 keys per workgroup.
+static inline uint32_t HistogramGrid(const PlanContext& c, const SortPlan& plan) {
+  const uint32_t cap = (uint32_t)c.computeUnits * kHistWorkgroupsPerCu;
+  if (plan.msdBits != 0) return std::min<uint32_t>(plan.msdTiles, cap);
+  const uint32_t wide = std::min<uint32_t>(128u, RoundUp(plan.elementCount, 4096u));
+  const uint32_t grid = std::max(RoundUp(plan.elementCount, 2 * kHistGroupKeys), wide);
+  return std::max(std::min(grid, cap), 1u);
+}
+
+// What vrdxHipDescribePlan reports of a plan (include/vk_radix_sort.h); *info zeroed by the caller.
+static inline void DescribePlan(const SortPlan& plan, VrdxHipPlanInfo* info) {
+  const bool kv = plan.keyValue;
+  const uint32_t fourPasses = kv ? 68u : 36u;  // 4 (histogram) + 4 x (read + write)
+  const uint32_t twoTrips = kv ? 36u : 20u;    // 4 (histogram) + scatter (read + write) + buckets (read + write)
+  info->fallbackBytesPerElement = fourPasses;
+  info->launches = plan.launches;
+  if (plan.oneWorkgroup) {
+    info->plan = VRDX_HIP_PLAN_ONE_WORKGROUP;
+    info->bytesPerElement = info->fallbackBytesPerElement = kv ? 16u : 8u;
+  } else if (plan.msdBits != 0) {
+    info->plan = VRDX_HIP_PLAN_MSD;
+    info->bits = plan.msdBits;
+    info->bytesPerElement = twoTrips;
+  } else if (plan.hybridCap != 0) {
+    info->plan = VRDX_HIP_PLAN_HYBRID8;
+    info->bits = 8;
+    info->bytesPerElement = twoTrips;
+  } else {
+    info->plan = VRDX_HIP_PLAN_FOUR_PASSES;
+    info->bytesPerElement = fourPasses;
+  }
+}
+
+}  // namespace vrdx
+
+#endif  // VRDX_PLAN_H
