@@ -360,6 +360,61 @@ void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter
                                        VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                                        VkQueryPool queryPool, uint32_t query);
 
+/**
+ * Sort by a bit range of the key (not part of the reference API; the begin_bit / end_bit of CUB, hipCUB and rocPRIM): the
+ * four whole-key calls with beginBit and endBit right behind the keys (and values) arguments, everything else in the
+ * order of the matching whole-key call.
+ *
+ * Order: let f(k) = (k >> beginBit) & (2^(endBit - beginBit) - 1).  After the call, elements [0, n) are the input elements in
+ * ascending order of f(key); elements with equal f keep their input order; keys are moved WHOLE -- the bits outside the
+ * range are carried along untouched and never compared -- and values travel with their keys.  The keys-only calls are
+ * stable in the same sense, which is observable: the bits outside the range tell keys of equal field apart.  (Sorting
+ * masked keys is not the same thing: a key that packs its sort field next to a payload or a second field -- cell id |
+ * flags, depth | id, a class bit above an index -- has to come back whole, and equal fields in input order are what makes
+ * multi-field LSD compositions and stable partitions by a flag work.)
+ * Valid ranges: 0 <= beginBit <= endBit <= 32.
+ *   beginBit == endBit is the empty range: like elementCount == 0 it records nothing but the timestamps and touches neither
+ *   the arrays nor the storage.
+ *   beginBit == 0 and endBit == 32 IS the matching whole-key call: every plan applies, behaviour is the same bit for bit.
+ *   beginBit > endBit or endBit > 32 is refused like a storage layout that does not fit: the timestamps are recorded, nothing
+ *   else is touched, and the sorter's word raises VRDX_HIP_STATUS_ENQUEUE_REFUSED.
+ * Storage, alignment and bounds: exactly as for the whole-key calls -- vrdxGetSorter[KeyValue]StorageRequirements(
+ * maxElementCount), the same alignment rules, nothing written outside [0, n) of the caller's arrays or outside the
+ * storage requirement.
+ * Count: the indirect forms read the count on the device and clamp it to the bound; the count word is only read.
+ * maxElementCount > 2^30 - 4 is clamped (VRDX_HIP_STATUS_COUNT_CLAMPED).
+ * Capture: with a NULL query pool the calls are legal inside a stream capture; the graph may be replayed on other data and,
+ * for the indirect forms, on other counts up to the bound.
+ * Status: vrdxHipReadStatus works on the storage.  Word 1 reads VRDX_HIP_VERDICT_NONE after any range sort that had
+ * elements, also on storage where an MSD sort left its verdict.
+ * Size: range sorts run in ONE workgroup and one launch, which ranks the P = ceil((endBit - beginBit) / 8) digits of the
+ * range (the last one of the bits that are left) -- up to 16384 elements (maxElementCount for the indirect forms).  A call
+ * with more elements and a range other than [0, 32) is REFUSED like an invalid range: the timestamps are recorded, nothing
+ * else is touched, VRDX_HIP_STATUS_ENQUEUE_REFUSED is raised.  vrdxHipDescribeSortBitsPlan reports ONE_WORKGROUP (8 / 16 bytes
+ * per element) for what is sorted and VRDX_HIP_PLAN_NONE for what is refused.
+ * Timestamps: the 15-slot contract as for ONE_WORKGROUP above.
+ *
+ * Out of scope: range sorts of more than 16384 elements (the range forms of the histogram and pass kernels are not part of
+ * this library yet: DESIGN.md section 4.13); ranges for the 64-bit and the segmented sorts; descending, signed and
+ * floating-point orders.
+ */
+void vrdxHipCmdSortBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                        VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                        VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSortBitsKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                                VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset, uint32_t beginBit,
+                                uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                                uint32_t query);
+void vrdxHipCmdSortBitsIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                                VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSortBitsKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                        VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                        VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                        uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                        VkQueryPool queryPool, uint32_t query);
+
 /* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves
  * (vkCreateQueryPool / vkGetQueryPoolResults, bench/vulkan_benchmark.cc:195-198,318-321).
@@ -433,6 +488,11 @@ typedef struct VrdxHipPlanInfo {
   uint32_t launches;                /* kernel launches recorded (fills and copies not counted) */
 } VrdxHipPlanInfo;
 void vrdxHipDescribePlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, VrdxHipPlanInfo* info);
+/* The same for vrdxHipCmdSortBits[KeyValue][Indirect] with the range [beginBit, endBit): ONE_WORKGROUP up to 16384 elements;
+ * the range of all 32 bits reports what vrdxHipDescribePlan reports; an empty or invalid range, and a range sort of more
+ * elements (which is refused), report VRDX_HIP_PLAN_NONE. */
+void vrdxHipDescribeSortBitsPlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, uint32_t beginBit, uint32_t endBit,
+                                 VrdxHipPlanInfo* info);
 
 /* What the DEVICE made of the plan of the last sort that used this storage (word 1 of the storage; synchronises the
  * stream): vrdxHipDescribePlan is the host's intention, this is the verdict.  Meaningful for the two plans that are

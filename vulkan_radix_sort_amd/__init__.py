@@ -35,6 +35,7 @@ from .api import (  # noqa: F401
 from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
 from .segmented64 import sort_segments64  # noqa: F401
+from .sort_bits import sort_bits  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -62,4 +63,5 @@ __all__ = [
     "sort_segments",
     "sort64",
     "sort_segments64",
+    "sort_bits",
 ]

@@ -1,4 +1,4 @@
-"""ctypes binding of libvrdx_hip.so -- the eight vrdx* entry points of include/vk_radix_sort.h.
+"""ctypes binding of libvrdx_hip.so -- the vrdx* entry points of include/vk_radix_sort.h.
 
 Mirrors the reference interface (src/vk_radix_sort.h.in:11-81 under /root/reference):
 
@@ -22,6 +22,8 @@ reference (C++ / Vulkan)                        here
 ``vrdxHipCmdSort64KeyValueIndirect`` (HIP only) ``Sorter.cmd_sort64_key_value_indirect(...)``
 ``vrdxHipCmdSortSegmented64`` (HIP only)        ``Sorter.cmd_sort_segmented64(...)``
 ``vrdxHipCmdSortSegmented64KeyValue`` (HIP only) ``Sorter.cmd_sort_segmented64_key_value(...)``
+``vrdxHipCmdSortBits[KeyValue][Indirect]``      ``Sorter.cmd_sort_bits[_key_value][_indirect](...)``
+``vrdxHipDescribeSortBitsPlan`` (HIP only)      ``Sorter.describe_sort_bits_plan(n, key_value, begin_bit, end_bit)``
 =============================================  ==============================================
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
@@ -78,6 +80,12 @@ EXPORTED_SYMBOLS = (
     # many independent arrays of uint64 keys in one call
     "vrdxHipCmdSortSegmented64",
     "vrdxHipCmdSortSegmented64KeyValue",
+    # by a bit range of the key
+    "vrdxHipCmdSortBits",
+    "vrdxHipCmdSortBitsKeyValue",
+    "vrdxHipCmdSortBitsIndirect",
+    "vrdxHipCmdSortBitsKeyValueIndirect",
+    "vrdxHipDescribeSortBitsPlan",
 )
 
 # bits of vrdxHipReadSorterStatus (include/vk_radix_sort.h)
@@ -205,6 +213,17 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxHipCmdSortSegmented64.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u32]
     lib.vrdxHipCmdSortSegmented64KeyValue.restype = None
     lib.vrdxHipCmdSortSegmented64KeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
+    # the range sits right behind the keys (and values): (..., keys, keysOffset[, values, valuesOffset], beginBit, endBit, ...)
+    lib.vrdxHipCmdSortBits.restype = None
+    lib.vrdxHipCmdSortBits.argtypes = [vp, vp, u32, vp, u64, u32, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortBitsKeyValue.restype = None
+    lib.vrdxHipCmdSortBitsKeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortBitsIndirect.restype = None
+    lib.vrdxHipCmdSortBitsIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortBitsKeyValueIndirect.restype = None
+    lib.vrdxHipCmdSortBitsKeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
+    lib.vrdxHipDescribeSortBitsPlan.restype = None
+    lib.vrdxHipDescribeSortBitsPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
     lib.vrdxHipCreateQueryPool.argtypes = [u32, ctypes.POINTER(vp)]
     lib.vrdxHipDestroyQueryPool.restype = None
@@ -430,6 +449,38 @@ class Sorter:
                                                    _handle(values), values_offset, _handle(storage), storage_offset,
                                                    _pool(query_pool), query)
 
+    def cmd_sort_bits(self, command_buffer, element_count, keys, keys_offset, begin_bit, end_bit, storage, storage_offset,
+                      query_pool=None, query=0):
+        """``vrdxHipCmdSortBits``: stable sort by the bits [begin_bit, end_bit) of the uint32 keys, which move whole;
+        storage of ``storage_requirements(n)`` bytes.  Up to 16384 elements (more are refused, except with [0, 32))."""
+        self._lib.vrdxHipCmdSortBits(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
+                                     begin_bit, end_bit, _handle(storage), storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_bits_key_value(self, command_buffer, element_count, keys, keys_offset, values, values_offset, begin_bit,
+                                end_bit, storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSortBitsKeyValue``: the same with values that travel with their keys; storage of
+        ``key_value_storage_requirements(n)`` bytes."""
+        self._lib.vrdxHipCmdSortBitsKeyValue(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
+                                             _handle(values), values_offset, begin_bit, end_bit, _handle(storage),
+                                             storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_bits_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys, keys_offset,
+                               begin_bit, end_bit, storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSortBitsIndirect``: ``cmd_sort_bits`` of the first min(count, ``max_element_count``) keys, the count
+        one uint32 at ``indirect + indirect_offset`` that is read on the device."""
+        self._lib.vrdxHipCmdSortBitsIndirect(_handle(command_buffer), self.handle, max_element_count, _handle(indirect),
+                                             indirect_offset, _handle(keys), keys_offset, begin_bit, end_bit,
+                                             _handle(storage), storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_bits_key_value_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys,
+                                         keys_offset, values, values_offset, begin_bit, end_bit, storage, storage_offset,
+                                         query_pool=None, query=0):
+        """``vrdxHipCmdSortBitsKeyValueIndirect``: the same with values that travel with their keys."""
+        self._lib.vrdxHipCmdSortBitsKeyValueIndirect(_handle(command_buffer), self.handle, max_element_count,
+                                                     _handle(indirect), indirect_offset, _handle(keys), keys_offset,
+                                                     _handle(values), values_offset, begin_bit, end_bit, _handle(storage),
+                                                     storage_offset, _pool(query_pool), query)
+
     # -- diagnostics ------------------------------------------------------------------------
     def read_status(self, command_buffer, storage, storage_offset=0) -> int:
         return int(self._lib.vrdxHipReadStatus(_handle(command_buffer), _handle(storage), storage_offset))
@@ -445,6 +496,13 @@ class Sorter:
         moves (what a whole-sort roofline figure is priced with)."""
         info = VrdxHipPlanInfo()
         self._lib.vrdxHipDescribePlan(self.handle, element_count, 1 if key_value else 0, ctypes.byref(info))
+        return info
+
+    def describe_sort_bits_plan(self, element_count: int, key_value: bool, begin_bit: int, end_bit: int) -> VrdxHipPlanInfo:
+        """``vrdxHipDescribeSortBitsPlan``: the plan ``cmd_sort_bits*`` records for that many elements and that range."""
+        info = VrdxHipPlanInfo()
+        self._lib.vrdxHipDescribeSortBitsPlan(self.handle, element_count, 1 if key_value else 0, begin_bit, end_bit,
+                                              ctypes.byref(info))
         return info
 
     def read_plan_verdict(self, command_buffer, storage, storage_offset=0) -> int:

@@ -1,4 +1,4 @@
-// Host recorder of the HIP backend: the eight vrdx* entry points of include/vk_radix_sort.h.
+// Host recorder of the HIP backend: the vrdx* entry points of include/vk_radix_sort.h.
 //
 // Mirrors the reference's host side (src/vk_radix_sort.h.in:141-507) in behaviour:
 //   * vrdxCreateSorter builds an immutable sorter and is the only call that can fail;
@@ -423,16 +423,23 @@ hipError_t EnqueueStep(const VrdxSorter_T* sorter, const vrdx::PlanContext& cont
     case Step::kPass: return vrdx::LaunchOnesweep(stream, plan.configIndex, tiles, keyValue, atomicRank, PassArgs(plan, b, step.pass));
     case Step::kSmallSort:
       return vrdx::LaunchSmallSort(stream, atomicRank, b.keys, b.values, plan.elementCount, b.countPtr, b.failure);
+    // a bit-range sort: the range behind the arguments of the whole-key kernel
+    case Step::kSmallSortBits:
+      return vrdx::LaunchSmallSortBits(stream, atomicRank, b.keys, b.values, plan.elementCount, b.countPtr, b.failure,
+                                       plan.rangeBegin, plan.rangeWidth);
   }
   return hipErrorInvalidValue;
 }
 
 // reference: gpuSort, src/vk_radix_sort.h.in:344-507
+// beginBit, endBit: the whole key for vrdxCmdSort*; vrdxHipCmdSortBits* hand their range on (include/vk_radix_sort.h) -- the
+// full range takes the whole-key plan (PlanSortBits forwards it), an empty one has no step, an invalid one and one beyond one
+// workgroup's reach are refused.
 void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount,
                 VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
                 VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                 VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
-                uint32_t query) {
+                uint32_t query, uint32_t beginBit = 0, uint32_t endBit = 32) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
   const bool keyValue = valuesBuffer != nullptr;
   if (elementCount > VRDX_MAX_ELEMENTS) {
@@ -447,7 +454,8 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
 
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
   const vrdx::PlanContext context = PlanContextOf(sorter);
-  const SortPlan plan = vrdx::PlanSort(context, keyValue, elementCount, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  const SortPlan plan =
+      vrdx::PlanSortBits(context, keyValue, elementCount, beginBit, endBit, (uint64_t)reinterpret_cast<uintptr_t>(storage));
   const SortBuffers b = ResolveBuffers(
       sorter, plan.layout, storage, reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset)),
       keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr,
@@ -463,7 +471,11 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
   // the scratch arrays: a caller that reads the pool afterwards must not wait on events that never were.
   StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
   if (!plan.fits)
-    EnqueueCheck(sorter, "storage layout (status rows do not fit the reference's partition-histogram area)", hipErrorInvalidValue);
+    EnqueueCheck(sorter,
+                 beginBit > endBit || endBit > 32 ? "bit range (0 <= beginBit <= endBit <= 32)"
+                 : endBit - beginBit < 32        ? "bit range over more than 16384 elements (not built)"
+                                                 : "storage layout (status rows do not fit the reference's partition-histogram area)",
+                 hipErrorInvalidValue);
   for (uint32_t i = 0; i < plan.stepCount; ++i) {
     EnqueueCheck(sorter, plan.steps[i].name, EnqueueStep(sorter, context, stream, plan, b, msd, plan.steps[i]));
     stamps.AdvanceTo(plan.steps[i].slot);
@@ -855,6 +867,38 @@ void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter
                         keysOffset, valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
 }
 
+void vrdxHipCmdSortBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                        VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                        VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSort(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, nullptr, 0, storageBuffer, storageOffset,
+             queryPool, query, beginBit, endBit);
+}
+
+void vrdxHipCmdSortBitsKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                                VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset, uint32_t beginBit,
+                                uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                                uint32_t query) {
+  RecordSort(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, valuesBuffer, valuesOffset, storageBuffer,
+             storageOffset, queryPool, query, beginBit, endBit);
+}
+
+void vrdxHipCmdSortBitsIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                                VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSort(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, nullptr, 0,
+             storageBuffer, storageOffset, queryPool, query, beginBit, endBit);
+}
+
+void vrdxHipCmdSortBitsKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                        VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                        VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                        uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                        VkQueryPool queryPool, uint32_t query) {
+  RecordSort(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, valuesBuffer,
+             valuesOffset, storageBuffer, storageOffset, queryPool, query, beginBit, endBit);
+}
+
 void vrdxHipGetSorter64StorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
                                            VrdxSorterStorageRequirements* requirements) {
   requirements->size = vrdx::MakeSort64Layout(maxElementCount, sorter->minStorageBufferOffsetAlignment).keysOnlySize;
@@ -1021,6 +1065,16 @@ void vrdxHipDescribePlan(VrdxSorter sorter, uint32_t elementCount, int keyValue,
   if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
   // the recorder's own planning function (storage address 0: the alignment at which the least fits)
   vrdx::DescribePlan(vrdx::PlanSort(PlanContextOf(sorter), keyValue != 0, elementCount, 0), info);
+}
+
+void vrdxHipDescribeSortBitsPlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, uint32_t beginBit, uint32_t endBit,
+                                 VrdxHipPlanInfo* info) {
+  if (info == nullptr) return;
+  std::memset(info, 0, sizeof(*info));
+  if (sorter == nullptr || elementCount == 0 || beginBit >= endBit || endBit > 32) return;
+  if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
+  const SortPlan plan = vrdx::PlanSortBits(PlanContextOf(sorter), keyValue != 0, elementCount, beginBit, endBit, 0);
+  if (plan.stepCount != 0) vrdx::DescribePlan(plan, info);  // (no step: a range sort beyond one workgroup, which is refused)
 }
 
 uint32_t vrdxHipReadPlanVerdict(VkCommandBuffer commandBuffer, VkBuffer storageBuffer, VkDeviceSize storageOffset) {

@@ -102,6 +102,13 @@ constexpr uint32_t kSmallSortMaxElements = 16384;
 hipError_t LaunchSmallSort(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
                            const uint32_t* countPtr, uint32_t* failure);
 
+// The bit-range sorts (vrdxHipCmdSortBits[KeyValue][Indirect]): small_sort_bits_kernel, the range form of the launch above.
+// The order is by the field f(key) = the `width` bits of the key from bit beginBit, 1 <= width <= 31 (the range of all 32
+// bits IS the whole-key sort); keys move whole.  The kernel ranks ceil(width / 8) digits, digit p the min(8, width - 8 p) bits
+// of the key from bit beginBit + 8 p.  The range travels as two kernel arguments behind those of small_sort_kernel.
+hipError_t LaunchSmallSortBits(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
+                               const uint32_t* countPtr, uint32_t* failure, uint32_t beginBit, uint32_t width);
+
 // Mid-size sorts, hybrid plan (PassPlan in vrdx_kernels.hip): launch 0 scatters by the keys' highest byte that varies,
 // bucket_sort_kernel sorts each of the 256 buckets by the bytes below it inside one workgroup.  hybridCap = 4096, 8192, 16384
 // or 32768 elements per bucket (1024 threads x 4 / 8 / 16 / 32); the device decides whether the plan applies.

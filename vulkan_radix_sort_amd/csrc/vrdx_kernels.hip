@@ -683,8 +683,35 @@ __device__ __forceinline__ void TestDelayFirstTile(uint32_t tile, uint32_t spinL
 //
 // Counters are wave-private and LDS serves one wave's operations in program order, so the add of
 // slot i is visible to slot i + 1 without any barrier.
+// The digit a pass ranks by.  Whole-key sorts: (key >> shift) & MASK, shift = 8 x the byte.  RANGE (the bit-range sorts,
+// vrdxHipCmdSortBits): `shift` is a RangeDigit word -- the digit's first bit in bits 0-7, its width (1 ... 8) in bits 8-15,
+// both wave-uniform -- and the digit is one v_bfe_u32, like DigitWord of the MSD plan (a run-time `& mask` cost the bucket
+// kernel 10 %, see there).  v_bfe_u32 takes offset and width modulo 32; neither reaches 32 here.
+// A macro over a compile-time RANGE, not a function: the whole-key kernels then see the very expression they were written
+// with, and compile to the instructions they compiled to before the range forms existed (a helper function in its place
+// changed one or two instructions in every one of them: interprocedural passes run in front of the inliner).
+__device__ __forceinline__ uint32_t RangeDigit(uint32_t beginBit, uint32_t width, uint32_t pass) {
+  const uint32_t left = width > 8u * pass ? width - 8u * pass : 0u;  // (0: never ranked)
+  return (beginBit + 8u * pass) | ((left < 8u ? left : 8u) << 8);
+}
+#define VRDX_DIGIT(RANGE, MASK, key, shift) \
+  ((RANGE) ? __builtin_amdgcn_ubfe((key), (shift) & 0xFFu, (shift) >> 8) : ((key) >> (shift)) & (MASK))
+
+// MatchDigit for the range forms: the same function under another name.  Every caller of MatchDigit passes a digit masked
+// with 0xFF, which the compiler knows and uses inside it; a caller with a v_bfe_u32 digit would take that knowledge away
+// from all of them (the ballot forms of every kernel grew by 40-90 instructions).
+__device__ __forceinline__ uint64_t MatchRangeDigit(uint32_t digit) {
+  uint64_t same = ~0ull;
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const uint64_t vote = __ballot((digit >> b) & 1u);
+    same &= ((digit >> b) & 1u) ? vote : ~vote;
+  }
+  return same;
+}
+
 // PACKED: ranks (< 64 * KPT <= 65536) are written two to a register, out[i / 2] bits 16*(i % 2).
-template <int KPT, bool PACKED = false, bool DYN = false>
+template <int KPT, bool PACKED = false, bool DYN = false, bool RANGE = false>
 __device__ __forceinline__ void RankBallot(const uint32_t (&key)[KPT], uint32_t shift, uint32_t* myHist,
                                            int lane, uint32_t (&out)[PACKED ? KPT / 2 : KPT], uint32_t slots = KPT) {
   static_assert(!PACKED || KPT % 2 == 0, "whole pairs");
@@ -692,8 +719,8 @@ __device__ __forceinline__ void RankBallot(const uint32_t (&key)[KPT], uint32_t 
 #pragma unroll
   for (int i = 0; i < KPT; ++i) {
     if (DYN && i % 4 == 0 && (uint32_t)i >= slots) break;
-    const uint32_t d = (key[i] >> shift) & 0xFFu;
-    const uint64_t same = MatchDigit(d);
+    const uint32_t d = VRDX_DIGIT(RANGE, 0xFFu, key[i], shift);
+    const uint64_t same = RANGE ? MatchRangeDigit(d) : MatchDigit(d);
     const uint32_t below = LanesBelow(same);
     const uint32_t prior = __hip_atomic_load(&myHist[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (below == 0)
@@ -713,8 +740,8 @@ __device__ __forceinline__ void RankBallot(const uint32_t (&key)[KPT], uint32_t 
 }
 
 // PACKED: ranks (< 64 * KPT <= 65536) are written two to a register, out[i / 2] bits 16*(i % 2).
-// MASK: the digit is (key >> shift) & MASK -- 0xFF in every kernel built today.
-template <int KPT, bool PACKED, bool DYN = false, uint32_t MASK = 0xFFu>
+// MASK: the digit is (key >> shift) & MASK -- 0xFF in every kernel built today.  RANGE: VRDX_DIGIT above.
+template <int KPT, bool PACKED, bool DYN = false, uint32_t MASK = 0xFFu, bool RANGE = false>
 __device__ __forceinline__ void RankAtomic(const uint32_t (&key)[KPT], uint32_t shift, uint32_t* myHist,
                                            int lane, uint32_t (&out)[PACKED ? KPT / 2 : KPT], uint32_t slots = KPT) {
   // eight slots at a time: eight atomics in flight, eight wave-uniform flags live (more would
@@ -733,14 +760,14 @@ __device__ __forceinline__ void RankAtomic(const uint32_t (&key)[KPT], uint32_t 
   for (int base = 0; base < KPT; base += CHUNK) {
     if (DYN && (uint32_t)base >= slots) break;
     uint32_t r[CHUNK];
-    const uint32_t probe = (key[base] >> shift) & MASK;
+    const uint32_t probe = VRDX_DIGIT(RANGE, MASK, key[base], shift);
     const bool watch = __popcll(__ballot(probe != (uint32_t)__builtin_amdgcn_readfirstlane(probe))) <= 48;  // wave-uniform
     if (watch) {
       bool uniform[CHUNK];
 #pragma unroll
       for (int c = 0; c < CHUNK; ++c) {
         const int i = base + c;
-        const uint32_t d = (key[i] >> shift) & MASK;
+        const uint32_t d = VRDX_DIGIT(RANGE, MASK, key[i], shift);
         const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
         const uint64_t others = __ballot(d != d0);
         uniform[c] = others == 0ull;  // wave-uniform
@@ -782,7 +809,7 @@ __device__ __forceinline__ void RankAtomic(const uint32_t (&key)[KPT], uint32_t 
     } else {
 #pragma unroll
       for (int c = 0; c < CHUNK; ++c)
-        r[c] = __hip_atomic_fetch_add(&myHist[(key[base + c] >> shift) & MASK], 1u, __ATOMIC_RELAXED,
+        r[c] = __hip_atomic_fetch_add(&myHist[VRDX_DIGIT(RANGE, MASK, key[base + c], shift)], 1u, __ATOMIC_RELAXED,
                                       __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 #pragma unroll
@@ -1488,9 +1515,12 @@ __global__ __launch_bounds__(THREADS, (PairMinWavesPerSimd<THREADS, KPT>())) voi
 // bucket of the hybrid plan, bytes = 3).
 // A wave takes only as many slots of 64 elements as n needs (a multiple of four, like the even-split tiles of
 // onesweep_kernel), so a bucket or small sort costs what its elements cost, not what the kernel could hold.
-template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK>
+// RANGE (small_sort_bits_kernel): by the `bytes` BITS of the key from bit beginBit instead -- ceil(bytes / 8) digits, the
+// last one of the bits that are left (RangeDigit); pads have all ones in every digit of every range and stay last.
+template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK, bool RANGE = false>
 __device__ __forceinline__ void SortInWorkgroup(const uint32_t* keysIn, uint32_t* keysOut, const uint32_t* valuesIn,
-                                                uint32_t* valuesOut, uint32_t n, uint32_t bytes, uint32_t* smem) {
+                                                uint32_t* valuesOut, uint32_t n, uint32_t bytes, uint32_t* smem,
+                                                const uint32_t beginBit = 0) {
   constexpr int WAVES = THREADS / 64;
   constexpr uint32_t TILE = THREADS * KPT;
   constexpr bool SHARED = SharedStage(THREADS, KPT, KV);
@@ -1532,14 +1562,15 @@ __device__ __forceinline__ void SortInWorkgroup(const uint32_t* keysIn, uint32_t
   constexpr bool PACKED = SHARED;
   static_assert(!PACKED || TILE <= 65536, "packed 16-bit positions");
 #pragma unroll 1
-  for (uint32_t shift = 0; shift < 8 * bytes; shift += 8) {
+  for (uint32_t bit = 0; bit < (RANGE ? bytes : 8 * bytes); bit += 8) {
+    const uint32_t shift = RANGE ? RangeDigit(beginBit, bytes, bit / 8u) : bit;
 #pragma unroll
     for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;  // my own row: no barrier needed before ranking
     uint32_t rank[PACKED ? KPT / 2 : KPT];
     if constexpr (ATOMIC_RANK)
-      RankAtomic<KPT, PACKED, DYN>(key, shift, myHist, lane, rank, slots);
+      RankAtomic<KPT, PACKED, DYN, 0xFFu, RANGE>(key, shift, myHist, lane, rank, slots);
     else
-      RankBallot<KPT, PACKED, DYN>(key, shift, myHist, lane, rank, slots);
+      RankBallot<KPT, PACKED, DYN, RANGE>(key, shift, myHist, lane, rank, slots);
     LdsBarrier();
     // The read-back addresses below do not depend on the pass: left alone the compiler computes all KPT of them once,
     // in front of the loop, and keeps them in registers through every pass (the 32768-element key+value form then spills).
@@ -1570,7 +1601,7 @@ __device__ __forceinline__ void SortInWorkgroup(const uint32_t* keysIn, uint32_t
         if (DYN && (uint32_t)base >= slots) break;
         uint32_t p[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) p[c] = myHist[(key[base + c] >> shift) & 0xFFu];  // four reads in flight, then four stores
+        for (int c = 0; c < 4; ++c) p[c] = myHist[VRDX_DIGIT(RANGE, 0xFFu, key[base + c], shift)];  // four reads in flight, then four stores
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const int i = base + c;
@@ -1606,7 +1637,7 @@ __device__ __forceinline__ void SortInWorkgroup(const uint32_t* keysIn, uint32_t
 #pragma unroll
       for (int i = 0; i < KPT; ++i) {
         if (DYN && i % 4 == 0 && (uint32_t)i >= slots) break;
-        const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[(key[i] >> shift) & 0xFFu]);
+        const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[VRDX_DIGIT(RANGE, 0xFFu, key[i], shift)]);
         stagedKeys[slot] = key[i];
         if constexpr (KV) stagedValues[slot] = val[i];
       }
@@ -1644,6 +1675,18 @@ __global__ __launch_bounds__(THREADS) void small_sort_kernel(uint32_t* keys, uin
   // sort's verdict on the same storage must not be read as this one's (VRDX_HIP_VERDICT_NONE, include/vk_radix_sort.h).
   if (threadIdx.x < 3) failure[(int)threadIdx.x - 2] = 0;
   SortInWorkgroup<THREADS, KPT, KV, ATOMIC_RANK>(keys, keys, values, values, n, VRDX_PASSES, smem);
+}
+
+// The one-workgroup form of a bit-range sort (vrdxHipCmdSortBits): ceil(width / 8) digits of the range instead of four bytes.
+template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(THREADS) void small_sort_bits_kernel(uint32_t* keys, uint32_t* values, uint32_t maxCount,
+                                                                   const uint32_t* countPtr, uint32_t* failure, uint32_t beginBit,
+                                                                   uint32_t width) {
+  static_assert(THREADS >= 256 && THREADS % 256 == 0, "one thread per digit");
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  if (threadIdx.x < 3) failure[(int)threadIdx.x - 2] = 0;  // header words 1-3, see small_sort_kernel
+  SortInWorkgroup<THREADS, KPT, KV, ATOMIC_RANK, true>(keys, keys, values, values, n, width, smem, beginBit);
 }
 
 // ---------------------------------------------------------------------------------------------

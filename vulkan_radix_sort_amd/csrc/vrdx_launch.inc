@@ -227,7 +227,25 @@
   X(kSegmented64LargeV, (&segmented_large64_kernel<true, false>), 1024, Segment64LargeLdsWords(true) * 4, \
     "_ZN4vrdx24segmented_large64_kernelILb1ELb0EEEvNS_15Segmented64ArgsE") \
   X(kSegmented64LargeVA, (&segmented_large64_kernel<true, true>), 1024, Segment64LargeLdsWords(true) * 4, \
-    "_ZN4vrdx24segmented_large64_kernelILb1ELb1EEEvNS_15Segmented64ArgsE")
+    "_ZN4vrdx24segmented_large64_kernelILb1ELb1EEEvNS_15Segmented64ArgsE") \
+  /* ---- the bit-range sorts (vrdxHipCmdSortBits): the range form of small_sort_kernel, in the same order ---- */ \
+  /* small_sort_bits_kernel [256 | 1024 threads][key-value][atomic rank] */ \
+  X(kSmallBits256, (&small_sort_bits_kernel<256, 16, false, false>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx22small_sort_bits_kernelILi256ELi16ELb0ELb0EEEvPjS1_jPKjS1_jj") \
+  X(kSmallBits256A, (&small_sort_bits_kernel<256, 16, false, true>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx22small_sort_bits_kernelILi256ELi16ELb0ELb1EEEvPjS1_jPKjS1_jj") \
+  X(kSmallBits256V, (&small_sort_bits_kernel<256, 16, true, false>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx22small_sort_bits_kernelILi256ELi16ELb1ELb0EEEvPjS1_jPKjS1_jj") \
+  X(kSmallBits256VA, (&small_sort_bits_kernel<256, 16, true, true>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx22small_sort_bits_kernelILi256ELi16ELb1ELb1EEEvPjS1_jPKjS1_jj") \
+  X(kSmallBits1024, (&small_sort_bits_kernel<1024, 16, false, false>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx22small_sort_bits_kernelILi1024ELi16ELb0ELb0EEEvPjS1_jPKjS1_jj") \
+  X(kSmallBits1024A, (&small_sort_bits_kernel<1024, 16, false, true>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx22small_sort_bits_kernelILi1024ELi16ELb0ELb1EEEvPjS1_jPKjS1_jj") \
+  X(kSmallBits1024V, (&small_sort_bits_kernel<1024, 16, true, false>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx22small_sort_bits_kernelILi1024ELi16ELb1ELb0EEEvPjS1_jPKjS1_jj") \
+  X(kSmallBits1024VA, (&small_sort_bits_kernel<1024, 16, true, true>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx22small_sort_bits_kernelILi1024ELi16ELb1ELb1EEEvPjS1_jPKjS1_jj")
 
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
@@ -313,6 +331,15 @@ hipError_t LaunchSmallSort(hipStream_t stream, bool atomicRank, uint32_t* keys, 
                            const uint32_t* countPtr, uint32_t* failure) {
   const KernelId first = maxCount <= 256u * 16u ? kSmall256 : kSmall1024;
   return Launch(Form(first, values != nullptr, atomicRank), 1, stream, keys, values, maxCount, countPtr, failure);
+}
+
+// The bit-range sorts: the range travels behind the arguments of the whole-key kernel.  Widths 1 ... 31 only (v_bfe_u32 takes a
+// width modulo 32; the recorder forwards the one range of 32 bits to the whole-key sort).
+hipError_t LaunchSmallSortBits(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
+                               const uint32_t* countPtr, uint32_t* failure, uint32_t beginBit, uint32_t width) {
+  if (width < 1u || width > 31u || beginBit + width > 32u || maxCount > kSmallSortMaxElements) return hipErrorInvalidValue;
+  const KernelId first = maxCount <= 256u * 16u ? kSmallBits256 : kSmallBits1024;
+  return Launch(Form(first, values != nullptr, atomicRank), 1, stream, keys, values, maxCount, countPtr, failure, beginBit, width);
 }
 
 hipError_t LaunchBucketSort(hipStream_t stream, bool keyValue, bool atomicRank, const BucketSortArgs& args) {

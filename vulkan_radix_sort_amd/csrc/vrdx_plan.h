@@ -184,6 +184,7 @@ enum class Step : uint8_t {
   kBucketSort,         // slot 5: the eight-bit plan's buckets
   kPass,               // slot 4 + 3 p, "downsweep": pass p, look-back fused into it ("spine" = "upsweep" = the slot before)
   kSmallSort,          // slot 14: the one-workgroup sort
+  kSmallSortBits,      // slot 14: the one-workgroup sort by the digits of a bit range (PlanSortBits)
 };
 struct SortStep { Step what; uint8_t pass, slot; const char* name; };  // (pass: kPass only; name: what EnqueueCheck reports)
 constexpr uint32_t kMaxSortSteps = 8;  // fill, histogram, spine, scatter, half-size buckets, passes 1-3
@@ -209,6 +210,8 @@ struct SortPlan {
   SortStep steps[kMaxSortSteps];  // none: the empty sort and the refused one
   uint32_t stepCount = 0;
   uint32_t launches = 0;        // kernels among the steps
+  // a bit-range sort (PlanSortBits): by the rangeWidth bits (1 ... 31) of the key from bit rangeBegin; 0: the whole key
+  uint32_t rangeBegin = 0, rangeWidth = 0;
 };
 
 // The MSD plan's scatter launch is ALSO pass 0 of the fallback and its bucket launch pass 1 (one branch on the verdict, on
@@ -221,6 +224,7 @@ static inline void ListSteps(SortPlan& p) {
     if (what != Step::kFill) ++p.launches;
   };
   const bool msd = p.msdBits != 0, halfBuckets = msd && p.msdCap == kMsdHalfCap;
+  if (p.oneWorkgroup && p.rangeWidth != 0) return add(Step::kSmallSortBits, "small_sort_bits_kernel", 14);
   if (p.oneWorkgroup) return add(Step::kSmallSort, "small_sort_kernel", 14);
   add(Step::kFill, "hipMemcpyAsync(count)", 1);
   if (msd)
@@ -294,6 +298,34 @@ static inline SortPlan PlanSort(const PlanContext& c, bool keyValue, uint32_t el
     p.fits = LayoutFits(p.layout, elementCount);
   }
   if (p.fits) ListSteps(p);
+  return p;
+}
+
+// The plan of a bit-range sort (vrdxHipCmdSortBits; include/vk_radix_sort.h) by the bits [beginBit, endBit) of the key: one
+// workgroup ranking ceil((endBit - beginBit) / 8) digits in one launch -- wherever PlanSort takes one workgroup, i.e. up to
+// kSmallSortMaxElements elements.  Larger range sorts are NOT built: the plan then has no step and
+// fits == false, and the recorder refuses the call like a layout that does not fit.
+// The range of all 32 bits is PlanSort itself; an empty range has no step, like an empty sort; an invalid one (beginBit >
+// endBit, endBit > 32) has none either and is refused.
+static inline SortPlan PlanSortBits(const PlanContext& c, bool keyValue, uint32_t elementCount, uint32_t beginBit, uint32_t endBit,
+                                    uint64_t storageAddress) {
+  if (beginBit == 0 && endBit == 32) return PlanSort(c, keyValue, elementCount, storageAddress);
+  SortPlan p;
+  p.keyValue = keyValue;
+  p.elementCount = elementCount;
+  p.atomicRank = c.atomicRank;
+  p.fits = beginBit <= endBit && endBit <= 32;
+  if (!p.fits || beginBit == endBit || elementCount == 0) return p;
+  const SortPlan whole = PlanSort(c, keyValue, elementCount, storageAddress);
+  if (!whole.oneWorkgroup) {
+    p.fits = false;  // beyond one workgroup: not built
+    return p;
+  }
+  p = whole;
+  p.rangeBegin = beginBit;
+  p.rangeWidth = endBit - beginBit;  // 1 ... 31: the kernel extracts with v_bfe_u32, which takes a width modulo 32
+  p.stepCount = p.launches = 0;
+  ListSteps(p);
   return p;
 }
 
