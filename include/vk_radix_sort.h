@@ -395,8 +395,8 @@ void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter
  * Timestamps: the 15-slot contract as for ONE_WORKGROUP above.
  *
  * Out of scope: range sorts of more than 16384 elements (the range forms of the histogram and pass kernels are not part of
- * this library yet: DESIGN.md section 4.13); ranges for the 64-bit and the segmented sorts; descending, signed and
- * floating-point orders.
+ * this library yet: DESIGN.md section 4.13); ranges for the 64-bit sorts; descending, signed and floating-point orders.
+ * Ranges for the segmented sort: vrdxHipCmdSortSegmentedBits below.
  */
 void vrdxHipCmdSortBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
                         VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
@@ -414,6 +414,40 @@ void vrdxHipCmdSortBitsKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorte
                                         VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                                         uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                                         VkQueryPool queryPool, uint32_t query);
+
+/**
+ * Segmented sort by a bit range of the key (not part of the reference API; CUB's DeviceSegmentedRadixSort with begin_bit /
+ * end_bit): vrdxHipCmdSortSegmented[KeyValue] with beginBit and endBit in front of storageBuffer, the position they have in
+ * vrdxHipCmdSortBits*.
+ *
+ * Order: with f(k) = (k >> beginBit) & (2^(endBit - beginBit) - 1), every segment [o[i], o[i+1]) ends up in ascending order
+ * of f(key); elements of equal f keep their input order; keys are moved WHOLE and values travel with their keys, as
+ * vrdxHipCmdSortBits defines it.  A whole-key segmented sort of masked keys gives a different result.
+ * Everything else is vrdxHipCmdSortSegmented[KeyValue]'s, word for word: the storage
+ * (vrdxGetSorter[KeyValue]StorageRequirements(maxElementCount)), the alignment rules, offsets read on the device only, bad
+ * offsets (VRDX_HIP_STATUS_SEGMENTS_INVALID, the segment left alone, nothing written outside [0, maxElementCount) or outside
+ * the storage requirement), the clamp at 2^30 - 4, word 1 reading VRDX_HIP_VERDICT_NONE afterwards, the timestamp slots
+ * (fill, small, mid, large, the rest coincide), and capture and replay on another segmentation with the same segmentCount.
+ * Ranges, as for vrdxHipCmdSortBits: 0 <= beginBit <= endBit <= 32.
+ *   [0, 32) records exactly what vrdxHipCmdSortSegmented[KeyValue] records: the same kernels, bit for bit the same work.
+ *   beginBit == endBit records the timestamps and nothing else.
+ *   beginBit > endBit or endBit > 32 records the timestamps, touches nothing and raises VRDX_HIP_STATUS_ENQUEUE_REFUSED in
+ *   the sorter's word.
+ * Sizes: there is none at which a range is refused.  Segments of up to 4096 and up to 16384 elements are sorted in LDS by the
+ * P = ceil((endBit - beginBit) / 8) digits of the range; a larger segment is sorted by one workgroup through memory, one walk
+ * of the segment per digit of the range that differs between its keys (at most P, where the whole-key form takes up to four).
+ * So a single array of more than 16384 elements CAN be range-sorted as one segment, but then by one workgroup: correct, and
+ * slow.  vrdxHipCmdSortBits beyond 16384 elements stays refused.
+ */
+void vrdxHipCmdSortSegmentedBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                 uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                 VkBuffer keysBuffer, VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit,
+                                 VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSortSegmentedBitsKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                         uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                         VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                         VkDeviceSize valuesOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                                         VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
 
 /* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves

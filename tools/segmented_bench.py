@@ -20,8 +20,20 @@ prints ONE JSON line; the segmented result of the last step is compared with the
   torch_sort   two stable torch.sort: by key, then by segment id
 Every way's result on one extra, untimed input is compared with np.lexsort((keys, segment id)) on the host (`"match_*"`).
 
+--bits BEGIN END (repeatable) times the segmented sort by the bit range [BEGIN, END) of uint32 keys
+(vrdxHipCmdSortSegmentedBits[KeyValue]), three ways taking turns in one process, each between one pair of events:
+
+  range        one vrdxHipCmdSortSegmentedBits[KeyValue] call (vulkan_radix_sort_amd.sort_segments_bits)
+  workaround   what the whole-key entry points offer: the field and an iota with torch ops, sort_segments(field, values=iota),
+               then the keys (and values) gathered by the sorted iota
+  whole_key    sort_segments of the same keys: ANOTHER result (the whole key orders it), timed as the price of four digits
+The timed steps come in --rounds rounds (default 5); a way's time is the median over all of them, and `whole_key_spread_ms` is
+the range of the whole-key sort's five per-round medians -- the run-to-run spread the range sort at [0, 8) is held against.
+On one extra, untimed input `range` must equal `workaround` bit for bit (`"match"`) and differ from `whole_key`.
+
 usage: python tools/segmented_bench.py [--shapes 65536x256,8192x2048,...,mixed] [--steps 5] [--warmup 2] [--loop-steps 3]
        [--modes keys,kv] [--only segmented] [--out FILE] [--keys64 [--patterns uniform,tile_depth]]
+       [--bits BEGIN END [--bits BEGIN END ...] [--rounds 5]]
 """
 import argparse
 import json
@@ -36,6 +48,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 DEFAULT_SHAPES = "65536x256,8192x2048,1024x16384,64x262144,4x4194304,mixed"
+BITS_SHAPES = "65536x256,8192x2048,1024x16384,64x262144"
 
 
 def segment_sizes(shape, rng):
@@ -193,9 +206,112 @@ def main64(args):
     sorter.destroy()
 
 
+def main_bits(args):
+    import torch
+    import vulkan_radix_sort_amd as vrdx
+
+    torch.cuda.set_device(0)
+    sorter = vrdx.Sorter(0)
+    ways = ("range", "workaround", "whole_key")
+    out = open(args.out, "a") if args.out else None
+    verify_step = 1 << 20  # the seed offset of the one input the ways are compared on
+
+    for shape in (args.shapes or BITS_SHAPES).split(","):
+        rng = np.random.default_rng(args.seed)
+        sizes = segment_sizes(shape, rng)
+        offsets_h = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        n = int(offsets_h[-1])
+        offsets = torch.from_numpy(offsets_h.astype(np.uint32).view(np.int32)).cuda()
+        for begin, end in args.bits:
+            if not 0 <= begin < end <= 32:
+                sys.exit(f"--bits {begin} {end}: not a range with 0 <= BEGIN < END <= 32")
+            mask = (1 << (end - begin)) - 1
+            for mode in args.modes.split(","):
+                kv = mode == "kv"
+                keys = torch.empty(n, dtype=torch.int32, device="cuda")
+                values = torch.empty(n, dtype=torch.int32, device="cuda") if kv else None
+                req = (sorter.key_value_storage_requirements(n) if kv else sorter.storage_requirements(n)).size
+                storage = torch.empty(req, dtype=torch.uint8, device="cuda")
+                storage_kv = torch.empty(sorter.key_value_storage_requirements(n).size, dtype=torch.uint8, device="cuda")
+                gen = torch.Generator(device="cuda")
+                payload = torch.arange(n, dtype=torch.int32, device="cuda") * 3 + 1
+
+                def fresh(step):
+                    gen.manual_seed(args.seed * 1000003 + step)
+                    keys.copy_(torch.randint(-(1 << 31), 1 << 31, (n,), dtype=torch.int64, device="cuda", generator=gen).to(torch.int32))
+                    if kv:
+                        values.copy_(payload)
+
+                def run_range():
+                    vrdx.sort_segments_bits(sorter, keys, offsets, begin, end, values=values, storage=storage)
+
+                def run_workaround():
+                    field = (((keys.to(torch.int64) & 0xFFFFFFFF) >> begin) & mask).to(torch.int32)
+                    index = torch.arange(n, dtype=torch.int32, device="cuda")
+                    vrdx.sort_segments(sorter, field, offsets, values=index, storage=storage_kv)
+                    gather = index.to(torch.int64)
+                    keys.copy_(keys[gather])
+                    if kv:
+                        values.copy_(values[gather])
+
+                def run_whole_key():
+                    vrdx.sort_segments(sorter, keys, offsets, values=values, storage=storage)
+
+                fns = {"range": run_range, "workaround": run_workaround, "whole_key": run_whole_key}
+                result = {"shape": shape, "bits": [begin, end], "segments": len(sizes), "keys": n, "key_value": kv,
+                          "rounds": args.rounds, "steps_per_round": args.steps}
+                rounds = {w: [] for w in ways}
+                step = 0
+                for r in range(args.rounds):
+                    times = {w: [] for w in ways}
+                    # the ways take turns step by step, so that a drift of the clocks meets all of them alike
+                    for i in range((args.warmup if r == 0 else 0) + args.steps):
+                        for way in ways:
+                            fresh(step)
+                            torch.cuda.synchronize()
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record()
+                            fns[way]()
+                            e1.record()
+                            torch.cuda.synchronize()
+                            if r > 0 or i >= args.warmup:
+                                times[way].append(e0.elapsed_time(e1))
+                        step += 1
+                    for way in ways:
+                        rounds[way].append(times[way])
+                outputs = {}
+                for way in ways:
+                    fresh(verify_step)
+                    fns[way]()
+                    torch.cuda.synchronize()
+                    outputs[way] = (keys.clone(), values.clone() if kv else None)
+                    medians = [float(np.median(t)) for t in rounds[way]]
+                    result[way + "_ms"] = float(np.median(np.concatenate(rounds[way])))
+                    result[way + "_ms_min"] = float(np.min(np.concatenate(rounds[way])))
+                    result[way + "_round_medians_ms"] = medians
+                result["whole_key_spread_ms"] = max(result["whole_key_round_medians_ms"]) - min(result["whole_key_round_medians_ms"])
+                (a, av), (b, bv), (c, _) = outputs["range"], outputs["workaround"], outputs["whole_key"]
+                result["match"] = bool(torch.equal(a, b) and (not kv or torch.equal(av, bv)))
+                result["whole_key_differs"] = not bool(torch.equal(a, c))
+                result["status"] = sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0)
+                result["range_vs_workaround"] = result["workaround_ms"] / result["range_ms"]
+                result["range_vs_whole_key"] = result["whole_key_ms"] / result["range_ms"]
+                result["range_gkeys_s"] = n / (result["range_ms"] * 1e6)
+                line = json.dumps(result)
+                print(line, flush=True)
+                if out:
+                    out.write(line + "\n")
+                    out.flush()
+                del keys, values, storage, storage_kv, payload, outputs
+                torch.cuda.empty_cache()
+    if out:
+        out.close()
+    sorter.destroy()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default=DEFAULT_SHAPES)
+    ap.add_argument("--shapes", default="")
     ap.add_argument("--modes", default="keys,kv")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -205,6 +321,9 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--keys64", action="store_true", help="uint64 keys: segmented64, composed, per_array, torch_sort")
     ap.add_argument("--patterns", default="uniform,tile_depth", help="--keys64: key patterns")
+    ap.add_argument("--bits", type=int, nargs=2, action="append", metavar=("BEGIN", "END"),
+                    help="sort by the key bits [BEGIN, END): range, workaround, whole_key (repeatable)")
+    ap.add_argument("--rounds", type=int, default=5, help="--bits: rounds of --steps timed steps")
     args = ap.parse_args()
 
     import torch
@@ -212,6 +331,9 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("segmented_bench.py needs a GPU (there is no CPU fallback)")
+    if args.bits:
+        return main_bits(args)
+    args.shapes = args.shapes or DEFAULT_SHAPES
     if args.keys64:
         return main64(args)
     torch.cuda.set_device(0)

@@ -36,6 +36,7 @@ from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
 from .segmented64 import sort_segments64  # noqa: F401
 from .sort_bits import sort_bits  # noqa: F401
+from .segmented_bits import sort_segments_bits  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -64,4 +65,5 @@ __all__ = [
     "sort64",
     "sort_segments64",
     "sort_bits",
+    "sort_segments_bits",
 ]

@@ -24,6 +24,7 @@ reference (C++ / Vulkan)                        here
 ``vrdxHipCmdSortSegmented64KeyValue`` (HIP only) ``Sorter.cmd_sort_segmented64_key_value(...)``
 ``vrdxHipCmdSortBits[KeyValue][Indirect]``      ``Sorter.cmd_sort_bits[_key_value][_indirect](...)``
 ``vrdxHipDescribeSortBitsPlan`` (HIP only)      ``Sorter.describe_sort_bits_plan(n, key_value, begin_bit, end_bit)``
+``vrdxHipCmdSortSegmentedBits[KeyValue]``       ``Sorter.cmd_sort_segmented_bits[_key_value](...)``
 =============================================  ==============================================
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
@@ -86,6 +87,8 @@ EXPORTED_SYMBOLS = (
     "vrdxHipCmdSortBitsIndirect",
     "vrdxHipCmdSortBitsKeyValueIndirect",
     "vrdxHipDescribeSortBitsPlan",
+    "vrdxHipCmdSortSegmentedBits",
+    "vrdxHipCmdSortSegmentedBitsKeyValue",
 )
 
 # bits of vrdxHipReadSorterStatus (include/vk_radix_sort.h)
@@ -222,6 +225,11 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxHipCmdSortBitsIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
     lib.vrdxHipCmdSortBitsKeyValueIndirect.restype = None
     lib.vrdxHipCmdSortBitsKeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
+    # the segmented sort by a bit range: vrdxHipCmdSortSegmented[KeyValue] with beginBit, endBit in front of the storage
+    lib.vrdxHipCmdSortSegmentedBits.restype = None
+    lib.vrdxHipCmdSortSegmentedBits.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortSegmentedBitsKeyValue.restype = None
+    lib.vrdxHipCmdSortSegmentedBitsKeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
     lib.vrdxHipDescribeSortBitsPlan.restype = None
     lib.vrdxHipDescribeSortBitsPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
@@ -397,6 +405,23 @@ class Sorter:
                                                   _handle(offsets), offsets_offset, _handle(keys), keys_offset,
                                                   _handle(values), values_offset, _handle(storage), storage_offset,
                                                   _pool(query_pool), query)
+
+    def cmd_sort_segmented_bits(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
+                                keys_offset, begin_bit, end_bit, storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSortSegmentedBits``: ``cmd_sort_segmented`` by the bits [begin_bit, end_bit) of the keys -- every
+        segment stable by that field, keys moved whole; segments of any size."""
+        self._lib.vrdxHipCmdSortSegmentedBits(_handle(command_buffer), self.handle, max_element_count, segment_count,
+                                              _handle(offsets), offsets_offset, _handle(keys), keys_offset, begin_bit,
+                                              end_bit, _handle(storage), storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_segmented_bits_key_value(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset,
+                                          keys, keys_offset, values, values_offset, begin_bit, end_bit, storage,
+                                          storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSortSegmentedBitsKeyValue``: the same with values that travel with their keys."""
+        self._lib.vrdxHipCmdSortSegmentedBitsKeyValue(_handle(command_buffer), self.handle, max_element_count,
+                                                      segment_count, _handle(offsets), offsets_offset, _handle(keys),
+                                                      keys_offset, _handle(values), values_offset, begin_bit, end_bit,
+                                                      _handle(storage), storage_offset, _pool(query_pool), query)
 
     def cmd_sort_segmented64(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
                              keys_offset, storage, storage_offset, query_pool=None, query=0):

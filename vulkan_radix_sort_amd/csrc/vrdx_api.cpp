@@ -489,10 +489,13 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
 // also lists the bigger ones), the 1024-thread in-LDS form over the mid list, one workgroup per large segment.
 // Grids depend on segmentCount, maxElementCount and the CU count only, so a captured call can be replayed on any segmentation
 // with the same segmentCount.
+// beginBit, endBit: the whole key for vrdxHipCmdSortSegmented*; vrdxHipCmdSortSegmentedBits* hand their range on.  The full
+// range records the whole-key kernels, an empty one nothing but the timestamps, an invalid one is refused; every other range
+// records the same fill and the range forms of the three launches, with the same grids.
 void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
                          VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
                          VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
-                         VkQueryPool queryPool, uint32_t query) {
+                         VkQueryPool queryPool, uint32_t query, uint32_t beginBit = 0, uint32_t endBit = 32) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
   const bool keyValue = valuesBuffer != nullptr;
   if (maxElementCount > VRDX_MAX_ELEMENTS) {
@@ -504,6 +507,13 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   DeviceScope deviceScope(sorter->device);
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
   StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
+  if (beginBit >= endBit || endBit > 32) {
+    stamps.Finish();
+    if (beginBit != endBit) EnqueueCheck(sorter, "bit range (0 <= beginBit <= endBit <= 32)", hipErrorInvalidValue);
+    return;  // (the empty range: nothing to order by)
+  }
+  const bool wholeKey = endBit - beginBit == 32;  // the range kernels take widths 1 ... 31
+  const uint32_t width = endBit - beginBit;
   const vrdx::SegmentedLayout layout =
       vrdx::MakeSegmentedLayout(maxElementCount, sorter->minStorageBufferOffsetAlignment, (uint64_t)reinterpret_cast<uintptr_t>(storage));
   if (segmentCount == 0 || maxElementCount == 0 || !(keyValue ? layout.fitsKeyValue : layout.fitsKeys)) {
@@ -538,21 +548,23 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   // grid stride with at most as many workgroups as can be resident (the in-LDS form of 16384 keys and the large kernel
   // hold one or two workgroups per CU)
   const uint32_t cus = (uint32_t)sorter->computeUnits;
-  EnqueueCheck(sorter, "segmented_small_kernel",
-               vrdx::LaunchSegmented(stream, vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20), keyValue,
-                                     atomicRank, a));
+  const auto launch = [&](vrdx::SegmentClass sizeClass, uint32_t grid) {
+    return wholeKey ? vrdx::LaunchSegmented(stream, sizeClass, grid, keyValue, atomicRank, a)
+                    : vrdx::LaunchSegmentedBits(stream, sizeClass, grid, keyValue, atomicRank, a, beginBit, width);
+  };
+  EnqueueCheck(sorter, wholeKey ? "segmented_small_kernel" : "segmented_small_bits_kernel",
+               launch(vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20)));
   stamps.AdvanceTo(2);
   // (a launch that is not recorded leaves its slot to coincide with the one before)
   const uint32_t midGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.midCap), 2u * cus);
   if (midGrid != 0) {
-    EnqueueCheck(sorter, "segmented_mid_kernel",
-                 vrdx::LaunchSegmented(stream, vrdx::kSegmentMid, midGrid, keyValue, atomicRank, a));
+    EnqueueCheck(sorter, wholeKey ? "segmented_mid_kernel" : "segmented_mid_bits_kernel", launch(vrdx::kSegmentMid, midGrid));
     stamps.AdvanceTo(3);
   }
   const uint32_t largeGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.largeCap), 2u * cus);
   if (largeGrid != 0) {
-    EnqueueCheck(sorter, "segmented_large_kernel",
-                 vrdx::LaunchSegmented(stream, vrdx::kSegmentLarge, largeGrid, keyValue, atomicRank, a));
+    EnqueueCheck(sorter, wholeKey ? "segmented_large_kernel" : "segmented_large_bits_kernel",
+                 launch(vrdx::kSegmentLarge, largeGrid));
     stamps.AdvanceTo(4);
   }
   stamps.Finish();
@@ -848,6 +860,23 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
                                      VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
                       valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSortSegmentedBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                 uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                 VkBuffer keysBuffer, VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit,
+                                 VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                      nullptr, 0, storageBuffer, storageOffset, queryPool, query, beginBit, endBit);
+}
+
+void vrdxHipCmdSortSegmentedBitsKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                         uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                         VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                         VkDeviceSize valuesOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                                         VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                      valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query, beginBit, endBit);
 }
 
 void vrdxHipCmdSortSegmented64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,

@@ -255,6 +255,14 @@ hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args);
 enum SegmentClass { kSegmentSmall = 0, kSegmentMid = 1, kSegmentLarge = 2 };  // segmented_small / mid / large_kernel
 hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
                            const SegmentedArgs& args);
+// The segmented sort by a bit range (vrdxHipCmdSortSegmentedBits[KeyValue]): segmented_small_bits / mid_bits / large_bits_kernel,
+// the range forms of the three launches above.  Every segment is ordered by f(key) = the `width` bits of the key from bit
+// beginBit, 1 <= width <= 31 (the range of all 32 bits IS the whole-key segmented sort); keys move whole.  The in-LDS kernels
+// rank ceil(width / 8) digits (SortInWorkgroup's RANGE form); the large kernel counts those digits of the field in its one
+// histogram read and walks the segment once per digit that varies.  The range travels as two kernel arguments behind
+// SegmentedArgs, which does not change.
+hipError_t LaunchSegmentedBits(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                               const SegmentedArgs& args, uint32_t beginBit, uint32_t width);
 
 // ---- 64-bit keys (vrdxHipCmdSort64[KeyValue][Indirect]): the steps around the two 32-bit sorts (vrdx_kernels.hip, "64-bit
 // keys") ----

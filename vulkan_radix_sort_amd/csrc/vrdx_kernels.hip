@@ -1823,12 +1823,16 @@ __global__ __launch_bounds__(1024) void segmented_mid_kernel(SegmentedArgs a) {
 // Global data written by one wave and read by another inside this workgroup only ever crosses a __syncthreads() (same CU:
 // the L1 is shared, the barrier's release waits for the stores).
 // LDS: SegmentLargeLdsWords (vrdx_kernels.h).
+// RANGE (segmented_large_bits_kernel): by the `width` (1 ... 31) bits of the key from bit beginBit instead -- P = ceil(width / 8)
+// digits, digit p the min(8, width - 8 p) bits from bit beginBit + 8 p (RangeDigit).  Step 1 counts the P digits of the FIELD,
+// tables P ... 3 stay empty and their passes are never active; a pad's digit is all ones in the digit's own width; the copy
+// back follows the number of ACTIVE passes, as it does for whole keys.
 constexpr uint32_t kSegHistCopies = 8;
 static_assert(4 * 256 * kSegHistCopies <= kSegLargeTile, "the histogram replicas alias the staging buffer");
 
-template <bool KV, bool ATOMIC_RANK>
+template <bool KV, bool ATOMIC_RANK, bool RANGE = false>
 __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uint32_t* keysScratch, uint32_t* valuesScratch,
-                                           uint32_t n, uint32_t* smem) {
+                                           uint32_t n, uint32_t* smem, const uint32_t beginBit = 0, const uint32_t width = 0) {
   constexpr int THREADS = 1024, KPT = 16, WAVES = THREADS / 64;
   constexpr uint32_t TILE = kSegLargeTile;
   uint32_t* const stagedKeys = smem;
@@ -1849,7 +1853,14 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
   const uint32_t copy = tid & (kSegHistCopies - 1);
   auto count = [&](uint32_t key) {
 #pragma unroll
-    for (uint32_t p = 0; p < 4; ++p) atomicAdd(&bins[(p * 256 + ((key >> (8 * p)) & 0xFFu)) * kSegHistCopies + copy], 1u);
+    for (uint32_t p = 0; p < 4; ++p) {
+      if constexpr (RANGE) {
+        if (8u * p >= width) break;  // uniform: the range has no digit p
+        atomicAdd(&bins[(p * 256 + VRDX_DIGIT(true, 0xFFu, key, RangeDigit(beginBit, width, p))) * kSegHistCopies + copy], 1u);
+      } else {
+        atomicAdd(&bins[(p * 256 + ((key >> (8 * p)) & 0xFFu)) * kSegHistCopies + copy], 1u);
+      }
+    }
   };
   {
     constexpr uint32_t U = 8;  // loads in flight per lane
@@ -1891,7 +1902,7 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
 #pragma unroll 1
   for (uint32_t pass = 0; pass < 4; ++pass) {
     if (((active >> pass) & 1u) == 0) continue;  // uniform
-    const uint32_t shift = 8 * pass;
+    const uint32_t shift = RANGE ? RangeDigit(beginBit, width, pass) : 8 * pass;
     uint32_t* const base = bases + pass * 256;
 #pragma unroll 1
     for (uint32_t t0 = 0; t0 < n; t0 += TILE) {
@@ -1910,9 +1921,9 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
       for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;
       uint32_t rank[KPT];
       if constexpr (ATOMIC_RANK)
-        RankAtomic<KPT, false, true>(key, shift, myHist, lane, rank, slots);
+        RankAtomic<KPT, false, true, 0xFFu, RANGE>(key, shift, myHist, lane, rank, slots);
       else
-        RankBallot<KPT, false, true>(key, shift, myHist, lane, rank, slots);
+        RankBallot<KPT, false, true, RANGE>(key, shift, myHist, lane, rank, slots);
       LdsBarrier();
       uint32_t c = 0;
       if (tid < 256) {
@@ -1929,13 +1940,16 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
           run += h;
         }
         tileStart[tid] = exclusive;
-        tileCount[tid] = tid == 255 ? c - (256u * chunks - m) : c;  // (the pads are digit 255's last keys)
+        if constexpr (RANGE)  // (the pads are the last keys of the digit of all ones, 2^w - 1 in a digit of w bits)
+          tileCount[tid] = (uint32_t)tid == (1u << (shift >> 8)) - 1u ? c - (256u * chunks - m) : c;
+        else
+          tileCount[tid] = tid == 255 ? c - (256u * chunks - m) : c;  // (the pads are digit 255's last keys)
       }
       LdsBarrier();
 #pragma unroll
       for (int i = 0; i < KPT; ++i) {
         if (i % 4 == 0 && (uint32_t)i >= slots) break;
-        const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[(key[i] >> shift) & 0xFFu]);
+        const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[VRDX_DIGIT(RANGE, 0xFFu, key[i], shift)]);
         stagedKeys[slot] = key[i];
         if constexpr (KV) stagedValues[slot] = val[i];
       }
@@ -1948,7 +1962,7 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
         if (q < m) {
           const uint32_t slot = StagingSlot<TILE>(q);
           const uint32_t k = stagedKeys[slot];
-          const uint32_t d = (k >> shift) & 0xFFu;
+          const uint32_t d = VRDX_DIGIT(RANGE, 0xFFu, k, shift);
           const uint32_t to = base[d] + q - tileStart[d];
           // always < n while the segment is this workgroup's alone; segments that overlap (offsets that are not monotone,
           // flagged by the small kernel) may change keys under the counts, and must still never write outside the range
@@ -1992,6 +2006,63 @@ __global__ __launch_bounds__(1024) void segmented_large_kernel(SegmentedArgs a) 
     __syncthreads();  // the previous segment is done (its copy back included)
     SegmentLsd<KV, ATOMIC_RANK>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
                                 KV ? a.valuesScratch + begin : nullptr, end - begin, smem);
+  }
+}
+
+// The segmented sort by a bit range of the key (vrdxHipCmdSortSegmentedBits[KeyValue]): the three kernels above with the range
+// forms of SortInWorkgroup and SegmentLsd.  The range -- beginBit and width = endBit - beginBit, 1 ... 31 -- travels as two
+// scalar arguments BEHIND SegmentedArgs, which segmented_clear_kernel and the whole-key kernels share unchanged.  Offsets are
+// checked, segments classified and listed exactly as above: the size classes do not depend on the range.
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(256) void segmented_small_bits_kernel(SegmentedArgs a, uint32_t beginBit, uint32_t width) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  for (uint32_t s = blockIdx.x; s < a.segmentCount; s += gridDim.x) {
+    uint32_t begin = 0, end = 0;
+    if (!SegmentBounds(a, s, true, &begin, &end)) continue;  // uniform
+    const uint32_t n = end - begin;
+    if (n > kSegSmallMax) {
+      if (threadIdx.x == 0) {
+        const bool mid = n <= kSegMidMax;
+        const uint32_t slot = atomicAdd(mid ? a.midCount : a.largeCount, 1u);
+        if (slot < (mid ? a.midCap : a.largeCap)) (mid ? a.midList : a.largeList)[slot] = s;
+      }
+      continue;
+    }
+    if (n < 2) continue;
+    LdsBarrier();  // the previous segment's read-back of the staging buffer is over
+    SortInWorkgroup<256, 16, KV, ATOMIC_RANK, true>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
+                                                    KV ? a.values + begin : nullptr, n, width, smem, beginBit);
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_mid_bits_kernel(SegmentedArgs a, uint32_t beginBit, uint32_t width) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t listed = min(*a.midCount, a.midCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = a.midList[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    const uint32_t n = end - begin;
+    if (n <= kSegSmallMax || n > kSegMidMax) continue;
+    LdsBarrier();
+    SortInWorkgroup<1024, 16, KV, ATOMIC_RANK, true>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
+                                                     KV ? a.values + begin : nullptr, n, width, smem, beginBit);
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_large_bits_kernel(SegmentedArgs a, uint32_t beginBit, uint32_t width) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t listed = min(*a.largeCount, a.largeCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = a.largeList[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    if (end - begin <= kSegMidMax) continue;
+    __syncthreads();  // the previous segment is done (its copy back included)
+    SegmentLsd<KV, ATOMIC_RANK, true>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
+                                      KV ? a.valuesScratch + begin : nullptr, end - begin, smem, beginBit, width);
   }
 }
 

@@ -245,7 +245,33 @@
   X(kSmallBits1024V, (&small_sort_bits_kernel<1024, 16, true, false>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
     "_ZN4vrdx22small_sort_bits_kernelILi1024ELi16ELb1ELb0EEEvPjS1_jPKjS1_jj") \
   X(kSmallBits1024VA, (&small_sort_bits_kernel<1024, 16, true, true>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
-    "_ZN4vrdx22small_sort_bits_kernelILi1024ELi16ELb1ELb1EEEvPjS1_jPKjS1_jj")
+    "_ZN4vrdx22small_sort_bits_kernelILi1024ELi16ELb1ELb1EEEvPjS1_jPKjS1_jj") \
+  /* ---- the segmented sort by a bit range (vrdxHipCmdSortSegmentedBits): the range forms of the three segmented kernels \
+     [small | mid | large][key-value][atomic rank] ---- */ \
+  X(kSegmentedBitsSmall, (&segmented_small_bits_kernel<false, false>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx27segmented_small_bits_kernelILb0ELb0EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsSmallA, (&segmented_small_bits_kernel<false, true>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx27segmented_small_bits_kernelILb0ELb1EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsSmallV, (&segmented_small_bits_kernel<true, false>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx27segmented_small_bits_kernelILb1ELb0EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsSmallVA, (&segmented_small_bits_kernel<true, true>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx27segmented_small_bits_kernelILb1ELb1EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsMid, (&segmented_mid_bits_kernel<false, false>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx25segmented_mid_bits_kernelILb0ELb0EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsMidA, (&segmented_mid_bits_kernel<false, true>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx25segmented_mid_bits_kernelILb0ELb1EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsMidV, (&segmented_mid_bits_kernel<true, false>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx25segmented_mid_bits_kernelILb1ELb0EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsMidVA, (&segmented_mid_bits_kernel<true, true>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx25segmented_mid_bits_kernelILb1ELb1EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsLarge, (&segmented_large_bits_kernel<false, false>), 1024, SegmentLargeLdsWords(false) * 4, \
+    "_ZN4vrdx27segmented_large_bits_kernelILb0ELb0EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsLargeA, (&segmented_large_bits_kernel<false, true>), 1024, SegmentLargeLdsWords(false) * 4, \
+    "_ZN4vrdx27segmented_large_bits_kernelILb0ELb1EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsLargeV, (&segmented_large_bits_kernel<true, false>), 1024, SegmentLargeLdsWords(true) * 4, \
+    "_ZN4vrdx27segmented_large_bits_kernelILb1ELb0EEEvNS_13SegmentedArgsEjj") \
+  X(kSegmentedBitsLargeVA, (&segmented_large_bits_kernel<true, true>), 1024, SegmentLargeLdsWords(true) * 4, \
+    "_ZN4vrdx27segmented_large_bits_kernelILb1ELb1EEEvNS_13SegmentedArgsEjj")
 
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
@@ -401,6 +427,14 @@ hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t 
                            const SegmentedArgs& args) {
   if (grid == 0) return hipErrorInvalidValue;
   return Launch(KernelId(kSegmentedSmall - 3 * (2 * keyValue + atomicRank) + sizeClass), grid, stream, args);
+}
+
+// The range forms: the range travels behind SegmentedArgs.  Widths 1 ... 31 only (v_bfe_u32 takes a width modulo 32; the
+// recorder forwards the one range of 32 bits to the whole-key kernels).
+hipError_t LaunchSegmentedBits(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                               const SegmentedArgs& args, uint32_t beginBit, uint32_t width) {
+  if (grid == 0 || width < 1u || width > 31u || beginBit + width > 32u) return hipErrorInvalidValue;
+  return Launch(Form(KernelId(kSegmentedBitsSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args, beginBit, width);
 }
 
 // ---- segmented sort of 64-bit keys ------------------------------------------------------------------
