@@ -264,8 +264,10 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
  *   [5,6] key+value: the copy back into the caller's arrays (keys-only: 6 == 5)
  *   slots 7 ... 14 coincide with slot 6
  *
- * Out of scope, each left to the caller: signed and floating-point orders (flip the sign bit, or the IEEE bits, before and
- * after); descending order (complement the keys); values wider than 32 bits (sort an index as the value and gather by it).
+ * Signed, float64 and descending orders: vrdxHipCmdSort64Ordered* below, in the same kernels and at no extra trip over the
+ * keys.
+ * Out of scope, each left to the caller: values wider than 32 bits (sort an index as the value and gather by it); keys wider
+ * than 64 bits (sort by the low 64 bits, then by the high ones: every sort here is stable).
  * Many independent arrays of 64-bit keys: vrdxHipCmdSortSegmented64 below.
  */
 void vrdxHipGetSorter64StorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
@@ -361,6 +363,66 @@ void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter
                                        VkQueryPool queryPool, uint32_t query);
 
 /**
+ * Key orders of the 64-bit sorts (not part of the reference API): the six 64-bit calls above with one order word, `order`,
+ * right behind the keys (and values) arguments -- the position beginBit / endBit have in vrdxHipCmdSortBits* -- and
+ * everything else in the order of the matching call.  int64 and float64 keys, ascending or descending, at no extra trip
+ * over the keys: the kernels that take the keys apart and put them together, and the segmented kernels between their load
+ * and their store, apply the order where the key is in registers anyway.
+ *
+ * The order word: one key type, VRDX_HIP_KEY_UINT64, VRDX_HIP_KEY_INT64 or VRDX_HIP_KEY_FLOAT64, with
+ * VRDX_HIP_ORDER_DESCENDING or-ed in or not.
+ * Order: let T(k) = k ^ flip ^ (FLOAT64 and bit 63 of k set ? 0x7FFFFFFFFFFFFFFF : 0) on the key's 64 bits, with flip = 0 for
+ * UINT64, 1 << 63 for INT64 and FLOAT64, and the complement of that for descending.  After the call the elements (of every
+ * segment) are in ascending unsigned order of T(key).  T is a bijection, so:
+ *   UINT64, INT64   ascending (descending) as unsigned, as two's-complement signed integers;
+ *   FLOAT64         IEEE-754 totalOrder on the bits: NaNs with the sign bit set first, then -inf ... -0.0, then +0.0 ... +inf,
+ *                   NaNs with the sign bit clear last, NaNs among themselves by their payload bits; descending is the reverse;
+ *   stability       elements of EQUAL key keep their input order, for descending too (not the reverse of the ascending
+ *                   result): what CUB's SortKeysDescending / SortPairsDescending and a stable torch.sort(descending=True) give;
+ *   keys come back bit for bit as they went in, values travel with their keys.
+ * FLOAT64 differs from torch.sort (and numpy.sort) in two ways: torch.sort puts ALL NaNs last (first when descending),
+ * whatever their sign bit, and treats -0.0 and +0.0 as equal, leaving them in input order; here -0.0 sorts in front of +0.0.
+ * On keys without NaNs and without zeros of both signs the two agree.
+ * Everything else is the twin's, word for word: the storage (vrdxHipGetSorter64[KeyValue]StorageRequirements), the alignment
+ * rules, the device-side count of the indirect forms and its clamp, untouched elements, bad offsets
+ * (VRDX_HIP_STATUS_SEGMENTS_INVALID), the clamp at 2^30 - 4, the timestamp slots, the status and verdict words, capture and
+ * replay.
+ *   order == VRDX_HIP_KEY_UINT64 records exactly what the twin records: the same kernels, bit for bit the same work.
+ *   An order word with any other bit set, or a key type above VRDX_HIP_KEY_FLOAT64, is refused like an invalid bit range: the
+ *   timestamps are recorded, nothing else is touched, and the sorter's word raises VRDX_HIP_STATUS_ENQUEUE_REFUSED.
+ * Out of scope: orders for the 32-bit sorts and the bit-range sorts; float32; ranges for the 64-bit sorts.
+ */
+#define VRDX_HIP_KEY_UINT64 0u
+#define VRDX_HIP_KEY_INT64 1u
+#define VRDX_HIP_KEY_FLOAT64 2u
+#define VRDX_HIP_ORDER_DESCENDING 0x100u
+void vrdxHipCmdSort64Ordered(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                             VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                             VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSort64OrderedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount,
+                                     VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                     VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
+                                     VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSort64OrderedIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                     VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                     VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer,
+                                     VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSort64OrderedKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                             VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                             VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                             uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                             VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSortSegmented64Ordered(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                      uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                      VkBuffer keysBuffer, VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer,
+                                      VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdSortSegmented64OrderedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                              uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                              VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                              VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
+                                              VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+
+/**
  * Sort by a bit range of the key (not part of the reference API; the begin_bit / end_bit of CUB, hipCUB and rocPRIM): the
  * four whole-key calls with beginBit and endBit right behind the keys (and values) arguments, everything else in the
  * order of the matching whole-key call.
@@ -395,7 +457,8 @@ void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter
  * Timestamps: the 15-slot contract as for ONE_WORKGROUP above.
  *
  * Out of scope: range sorts of more than 16384 elements (the range forms of the histogram and pass kernels are not part of
- * this library yet: DESIGN.md section 4.13); ranges for the 64-bit sorts; descending, signed and floating-point orders.
+ * this library yet: DESIGN.md section 4.13); ranges for the 64-bit sorts; descending, signed and floating-point orders of
+ * 32-bit keys (the 64-bit sorts have them: vrdxHipCmdSort64Ordered* above).
  * Ranges for the segmented sort: vrdxHipCmdSortSegmentedBits below.
  */
 void vrdxHipCmdSortBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,

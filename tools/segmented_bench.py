@@ -31,9 +31,15 @@ The timed steps come in --rounds rounds (default 5); a way's time is the median 
 the range of the whole-key sort's five per-round medians -- the run-to-run spread the range sort at [0, 8) is held against.
 On one extra, untimed input `range` must equal `workaround` bit for bit (`"match"`) and differ from `whole_key`.
 
+--order ORDER [--descending] (ORDER: uint64, int64, float64) times the key orders of the segmented sort of uint64 keys
+(vrdxHipCmdSortSegmented64Ordered[KeyValue]), three ways taking turns in one process on keys of 64 random bits
+(tools/key_order_ways.py): `ordered`, the `workaround` in torch around sort_segments64, and the `unordered` sort_segments64 on
+keys that are T(keys) already.  --rounds rounds of --steps steps; `ordered` must equal `workaround` bit for bit (`"match"`).
+
 usage: python tools/segmented_bench.py [--shapes 65536x256,8192x2048,...,mixed] [--steps 5] [--warmup 2] [--loop-steps 3]
        [--modes keys,kv] [--only segmented] [--out FILE] [--keys64 [--patterns uniform,tile_depth]]
        [--bits BEGIN END [--bits BEGIN END ...] [--rounds 5]]
+       [--order ORDER [--descending] [--rounds 5]]
 """
 import argparse
 import json
@@ -309,6 +315,73 @@ def main_bits(args):
     sorter.destroy()
 
 
+def main_order(args):
+    import torch
+    import vulkan_radix_sort_amd as vrdx
+    from key_order_ways import inverse_, make_keys as random_keys, summarise, take_turns, transform_
+
+    torch.cuda.set_device(0)
+    sorter = vrdx.Sorter(0)
+    ways = ("ordered", "workaround", "unordered")
+    out = open(args.out, "a") if args.out else None
+    order, descending = args.order, args.descending
+    for shape in (args.shapes or BITS_SHAPES).split(","):
+        sizes = segment_sizes(shape, np.random.default_rng(args.seed))
+        offsets_h = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        n = int(offsets_h[-1])
+        offsets = torch.from_numpy(offsets_h.astype(np.uint32).view(np.int32)).cuda()
+        for mode in args.modes.split(","):
+            kv = mode == "kv"
+            keys = torch.empty(n, dtype=torch.int64, device="cuda")
+            values = torch.empty(n, dtype=torch.int32, device="cuda") if kv else None
+            payload = torch.arange(n, dtype=torch.int32, device="cuda") * 3 + 1
+            storage = torch.empty(sorter.storage_requirements64(n, key_value=kv).size, dtype=torch.uint8, device="cuda")
+            gen = torch.Generator(device="cuda")
+
+            def fresh(step):
+                gen.manual_seed(args.seed * 1000003 + step)
+                keys.copy_(random_keys(torch, n, gen))
+                if kv:
+                    values.copy_(payload)
+
+            def run_ordered():
+                vrdx.sort_segments64(sorter, keys, offsets, values=values, storage=storage, order=order, descending=descending)
+
+            def run_workaround():
+                transform_(keys, order, descending)
+                vrdx.sort_segments64(sorter, keys, offsets, values=values, storage=storage)
+                inverse_(keys, order, descending)
+
+            def run_unordered():
+                vrdx.sort_segments64(sorter, keys, offsets, values=values, storage=storage)
+
+            fns = {"ordered": run_ordered, "workaround": run_workaround, "unordered": run_unordered}
+            prepare = {"ordered": lambda: None, "workaround": lambda: None,
+                       "unordered": lambda: transform_(keys, order, descending)}
+            times = take_turns(torch, ways, fns, fresh, prepare, args.rounds, args.steps, args.warmup)
+            outputs = {}
+            for way in ("ordered", "workaround"):
+                fresh(1 << 20)
+                fns[way]()
+                torch.cuda.synchronize()
+                outputs[way] = (keys.clone(), values.clone() if kv else None)
+            (a, av), (b, bv) = outputs["ordered"], outputs["workaround"]
+            result = {"shape": shape, "segments": len(sizes), "keys": n, "order": order, "descending": descending,
+                      "key_value": kv, "rounds": args.rounds, "steps_per_round": args.steps,
+                      "match": bool(torch.equal(a, b) and (not kv or torch.equal(av, bv))),
+                      "status": sorter.read_sorter_status(torch.cuda.current_stream().cuda_stream)}
+            line = summarise(result, ways, times)
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+            del keys, values, storage, payload, outputs
+            torch.cuda.empty_cache()
+    if out:
+        out.close()
+    sorter.destroy()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="")
@@ -323,7 +396,10 @@ def main():
     ap.add_argument("--patterns", default="uniform,tile_depth", help="--keys64: key patterns")
     ap.add_argument("--bits", type=int, nargs=2, action="append", metavar=("BEGIN", "END"),
                     help="sort by the key bits [BEGIN, END): range, workaround, whole_key (repeatable)")
-    ap.add_argument("--rounds", type=int, default=5, help="--bits: rounds of --steps timed steps")
+    ap.add_argument("--rounds", type=int, default=5, help="--bits, --order: rounds of --steps timed steps")
+    ap.add_argument("--order", default="", choices=["", "uint64", "int64", "float64"],
+                    help="uint64 keys in a key order: ordered, workaround, unordered")
+    ap.add_argument("--descending", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -333,6 +409,8 @@ def main():
         sys.exit("segmented_bench.py needs a GPU (there is no CPU fallback)")
     if args.bits:
         return main_bits(args)
+    if args.order:
+        return main_order(args)
     args.shapes = args.shapes or DEFAULT_SHAPES
     if args.keys64:
         return main64(args)

@@ -17,8 +17,14 @@ value out), copy back 24.  Each shape prints ONE JSON line; the sort64 result of
 a device word, and adds "indirect": true to every line: the same work by the same kernels and grids, so its sort64_ms over
 that of a run without the flag is the price of reading the count on the device.
 
+--order ORDER [--descending] (ORDER: uint64, int64, float64) times the key orders instead (vrdxHipCmdSort64Ordered[KeyValue]),
+three ways taking turns in one process, each between one pair of events, on keys of 64 random bits (tools/key_order_ways.py):
+`ordered`, the `workaround` in torch around the unordered call, and the `unordered` call on keys that are T(keys) already.
+The timed steps come in --rounds rounds; on one extra, untimed input `ordered` must equal `workaround` bit for bit (`"match"`).
+
 usage: python tools/sort64_bench.py [--sizes 1048576,4194304,33554432] [--patterns uniform,bits32,tile_depth]
        [--modes keys,kv] [--steps 7] [--warmup 2] [--indirect] [--out FILE]
+       [--order ORDER [--descending] [--rounds 3]]
 """
 import argparse
 import json
@@ -48,6 +54,68 @@ def make_keys(torch, pattern, n, seed):
     raise ValueError(pattern)
 
 
+def main_order(args):
+    import torch
+    import vulkan_radix_sort_amd as vrdx
+    from key_order_ways import inverse_, make_keys as random_keys, summarise, take_turns, transform_
+
+    torch.cuda.set_device(0)
+    sorter = vrdx.Sorter(0)
+    ways = ("ordered", "workaround", "unordered")
+    out = open(args.out, "a") if args.out else None
+    order, descending = args.order, args.descending
+    for n in (int(x) for x in args.sizes.split(",")):
+        for mode in args.modes.split(","):
+            kv = mode == "kv"
+            keys = torch.empty(n, dtype=torch.int64, device="cuda")
+            values = torch.empty(n, dtype=torch.int32, device="cuda") if kv else None
+            iota = torch.arange(n, dtype=torch.int32, device="cuda")
+            storage = torch.empty(sorter.storage_requirements64(n, kv).size, dtype=torch.uint8, device="cuda")
+            gen = torch.Generator(device="cuda")
+
+            def fresh(step):
+                gen.manual_seed(args.seed * 1000003 + step)
+                keys.copy_(random_keys(torch, n, gen))
+                if kv:
+                    values.copy_(iota)
+
+            def run_ordered():
+                vrdx.sort64(sorter, keys, values, storage=storage, order=order, descending=descending)
+
+            def run_workaround():
+                transform_(keys, order, descending)
+                vrdx.sort64(sorter, keys, values, storage=storage)
+                inverse_(keys, order, descending)
+
+            def run_unordered():
+                vrdx.sort64(sorter, keys, values, storage=storage)
+
+            fns = {"ordered": run_ordered, "workaround": run_workaround, "unordered": run_unordered}
+            prepare = {"ordered": lambda: None, "workaround": lambda: None,
+                       "unordered": lambda: transform_(keys, order, descending)}
+            times = take_turns(torch, ways, fns, fresh, prepare, args.rounds, args.steps, args.warmup)
+            outputs = {}
+            for way in ("ordered", "workaround"):
+                fresh(1 << 20)
+                fns[way]()
+                torch.cuda.synchronize()
+                outputs[way] = (keys.clone(), values.clone() if kv else None)
+            (a, av), (b, bv) = outputs["ordered"], outputs["workaround"]
+            result = {"n": n, "order": order, "descending": descending, "key_value": kv, "rounds": args.rounds,
+                      "steps_per_round": args.steps, "match": bool(torch.equal(a, b) and (not kv or torch.equal(av, bv))),
+                      "status": sorter.read_sorter_status(torch.cuda.current_stream().cuda_stream)}
+            line = summarise(result, ways, times)
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+            del keys, values, storage, iota, outputs
+            torch.cuda.empty_cache()
+    if out:
+        out.close()
+    sorter.destroy()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1048576,4194304,33554432")
@@ -58,6 +126,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--indirect", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--order", default="", choices=["", "uint64", "int64", "float64"],
+                    help="time the key orders: ordered, workaround, unordered")
+    ap.add_argument("--descending", action="store_true")
+    ap.add_argument("--rounds", type=int, default=3, help="--order: rounds of --steps timed steps")
     args = ap.parse_args()
 
     import torch
@@ -65,6 +137,8 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("sort64_bench.py needs a GPU (there is no CPU fallback)")
+    if args.order:
+        return main_order(args)
     torch.cuda.set_device(0)
     sorter = vrdx.Sorter(0)
     stream = torch.cuda.current_stream().cuda_stream

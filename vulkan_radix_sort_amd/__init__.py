@@ -31,6 +31,12 @@ from .api import (  # noqa: F401
     VERDICT_HYBRID8_DECLINED,
     VERDICT_MSD_RUNS,
     VERDICT_MSD_SORTED,
+    KEY_UINT64,
+    KEY_INT64,
+    KEY_FLOAT64,
+    ORDER_DESCENDING,
+    KEY_ORDERS,
+    order_word,
 )
 from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
@@ -61,6 +67,12 @@ __all__ = [
     "VERDICT_HYBRID8_DECLINED",
     "VERDICT_MSD_RUNS",
     "VERDICT_MSD_SORTED",
+    "KEY_UINT64",
+    "KEY_INT64",
+    "KEY_FLOAT64",
+    "ORDER_DESCENDING",
+    "KEY_ORDERS",
+    "order_word",
     "sort_segments",
     "sort64",
     "sort_segments64",

@@ -25,6 +25,8 @@ reference (C++ / Vulkan)                        here
 ``vrdxHipCmdSortBits[KeyValue][Indirect]``      ``Sorter.cmd_sort_bits[_key_value][_indirect](...)``
 ``vrdxHipDescribeSortBitsPlan`` (HIP only)      ``Sorter.describe_sort_bits_plan(n, key_value, begin_bit, end_bit)``
 ``vrdxHipCmdSortSegmentedBits[KeyValue]``       ``Sorter.cmd_sort_segmented_bits[_key_value](...)``
+``vrdxHipCmdSort64Ordered[KeyValue][Indirect]`` ``Sorter.cmd_sort64_ordered[_key_value][_indirect](...)``
+``vrdxHipCmdSortSegmented64Ordered[KeyValue]``  ``Sorter.cmd_sort_segmented64_ordered[_key_value](...)``
 =============================================  ==============================================
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
@@ -89,7 +91,31 @@ EXPORTED_SYMBOLS = (
     "vrdxHipDescribeSortBitsPlan",
     "vrdxHipCmdSortSegmentedBits",
     "vrdxHipCmdSortSegmentedBitsKeyValue",
+    # int64, float64 and descending orders of the uint64 sorts
+    "vrdxHipCmdSort64Ordered",
+    "vrdxHipCmdSort64OrderedKeyValue",
+    "vrdxHipCmdSort64OrderedIndirect",
+    "vrdxHipCmdSort64OrderedKeyValueIndirect",
+    "vrdxHipCmdSortSegmented64Ordered",
+    "vrdxHipCmdSortSegmented64OrderedKeyValue",
 )
+
+# the order word of vrdxHipCmdSort64Ordered* and vrdxHipCmdSortSegmented64Ordered* (include/vk_radix_sort.h): one key type,
+# ORDER_DESCENDING or-ed in or not
+KEY_UINT64 = 0
+KEY_INT64 = 1
+KEY_FLOAT64 = 2
+ORDER_DESCENDING = 0x100
+KEY_ORDERS = {"uint64": KEY_UINT64, "int64": KEY_INT64, "float64": KEY_FLOAT64}
+
+
+def order_word(order: str, descending: bool = False) -> int:
+    """The order word for ``order`` in ``KEY_ORDERS`` (``"uint64"``, ``"int64"``, ``"float64"``) and a direction."""
+    if not isinstance(order, str):
+        raise TypeError(f"order must be one of {', '.join(map(repr, KEY_ORDERS))}, got {type(order).__name__}")
+    if order not in KEY_ORDERS:
+        raise ValueError(f"order must be one of {', '.join(map(repr, KEY_ORDERS))}, got {order!r}")
+    return KEY_ORDERS[order] | (ORDER_DESCENDING if descending else 0)
 
 # bits of vrdxHipReadSorterStatus (include/vk_radix_sort.h)
 STATUS_LOOKBACK_GAVE_UP = 0x00000001
@@ -230,6 +256,19 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxHipCmdSortSegmentedBits.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
     lib.vrdxHipCmdSortSegmentedBitsKeyValue.restype = None
     lib.vrdxHipCmdSortSegmentedBitsKeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
+    # the order word sits right behind the keys (and values), where the bit-range sorts have their range
+    lib.vrdxHipCmdSort64Ordered.restype = None
+    lib.vrdxHipCmdSort64Ordered.argtypes = [vp, vp, u32, vp, u64, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSort64OrderedKeyValue.restype = None
+    lib.vrdxHipCmdSort64OrderedKeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSort64OrderedIndirect.restype = None
+    lib.vrdxHipCmdSort64OrderedIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSort64OrderedKeyValueIndirect.restype = None
+    lib.vrdxHipCmdSort64OrderedKeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortSegmented64Ordered.restype = None
+    lib.vrdxHipCmdSortSegmented64Ordered.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, u32, vp, u64, vp, u32]
+    lib.vrdxHipCmdSortSegmented64OrderedKeyValue.restype = None
+    lib.vrdxHipCmdSortSegmented64OrderedKeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, u32, vp, u64, vp, u32]
     lib.vrdxHipDescribeSortBitsPlan.restype = None
     lib.vrdxHipDescribeSortBitsPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
@@ -473,6 +512,53 @@ class Sorter:
                                                    _handle(indirect), indirect_offset, _handle(keys), keys_offset,
                                                    _handle(values), values_offset, _handle(storage), storage_offset,
                                                    _pool(query_pool), query)
+
+    def cmd_sort64_ordered(self, command_buffer, element_count, keys, keys_offset, order, storage, storage_offset,
+                           query_pool=None, query=0):
+        """``vrdxHipCmdSort64Ordered``: ``cmd_sort64`` in the order of the word ``order`` (``KEY_UINT64``, ``KEY_INT64`` or
+        ``KEY_FLOAT64``, ``| ORDER_DESCENDING``): stable in both directions, keys come back bit for bit."""
+        self._lib.vrdxHipCmdSort64Ordered(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
+                                          order, _handle(storage), storage_offset, _pool(query_pool), query)
+
+    def cmd_sort64_ordered_key_value(self, command_buffer, element_count, keys, keys_offset, values, values_offset, order,
+                                     storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSort64OrderedKeyValue``: the same with one uint32 value per key."""
+        self._lib.vrdxHipCmdSort64OrderedKeyValue(_handle(command_buffer), self.handle, element_count, _handle(keys),
+                                                  keys_offset, _handle(values), values_offset, order, _handle(storage),
+                                                  storage_offset, _pool(query_pool), query)
+
+    def cmd_sort64_ordered_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys, keys_offset,
+                                    order, storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSort64OrderedIndirect``: ``cmd_sort64_indirect`` in the order of the word ``order``."""
+        self._lib.vrdxHipCmdSort64OrderedIndirect(_handle(command_buffer), self.handle, max_element_count,
+                                                  _handle(indirect), indirect_offset, _handle(keys), keys_offset, order,
+                                                  _handle(storage), storage_offset, _pool(query_pool), query)
+
+    def cmd_sort64_ordered_key_value_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys,
+                                              keys_offset, values, values_offset, order, storage, storage_offset,
+                                              query_pool=None, query=0):
+        """``vrdxHipCmdSort64OrderedKeyValueIndirect``: the same with one uint32 value per key."""
+        self._lib.vrdxHipCmdSort64OrderedKeyValueIndirect(_handle(command_buffer), self.handle, max_element_count,
+                                                          _handle(indirect), indirect_offset, _handle(keys), keys_offset,
+                                                          _handle(values), values_offset, order, _handle(storage),
+                                                          storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_segmented64_ordered(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
+                                     keys_offset, order, storage, storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSortSegmented64Ordered``: ``cmd_sort_segmented64`` with every segment in the order of the word
+        ``order``."""
+        self._lib.vrdxHipCmdSortSegmented64Ordered(_handle(command_buffer), self.handle, max_element_count, segment_count,
+                                                   _handle(offsets), offsets_offset, _handle(keys), keys_offset, order,
+                                                   _handle(storage), storage_offset, _pool(query_pool), query)
+
+    def cmd_sort_segmented64_ordered_key_value(self, command_buffer, max_element_count, segment_count, offsets,
+                                               offsets_offset, keys, keys_offset, values, values_offset, order, storage,
+                                               storage_offset, query_pool=None, query=0):
+        """``vrdxHipCmdSortSegmented64OrderedKeyValue``: the same with one uint32 value per key."""
+        self._lib.vrdxHipCmdSortSegmented64OrderedKeyValue(_handle(command_buffer), self.handle, max_element_count,
+                                                           segment_count, _handle(offsets), offsets_offset, _handle(keys),
+                                                           keys_offset, _handle(values), values_offset, order,
+                                                           _handle(storage), storage_offset, _pool(query_pool), query)
 
     def cmd_sort_bits(self, command_buffer, element_count, keys, keys_offset, begin_bit, end_bit, storage, storage_offset,
                       query_pool=None, query=0):

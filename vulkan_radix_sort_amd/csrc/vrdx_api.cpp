@@ -571,13 +571,21 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   MaybeRecheckOrder(sorter, stream, atomicRank);
 }
 
+static_assert(VRDX_HIP_KEY_UINT64 == vrdx::kKeyOrderUint64 && VRDX_HIP_KEY_INT64 == vrdx::kKeyOrderInt64 &&
+                  VRDX_HIP_KEY_FLOAT64 == vrdx::kKeyOrderFloat64 && VRDX_HIP_ORDER_DESCENDING == vrdx::kKeyOrderDescending,
+              "the order word of the header is the kernels'");
+constexpr const char* kKeyOrderRefused = "key order (a key type 0 ... 2, VRDX_HIP_ORDER_DESCENDING or not)";
+
 // The segmented sort of 64-bit keys (include/vk_radix_sort.h, vrdxHipCmdSortSegmented64): RecordSegmentedSort with the 64-bit
 // kernels and the 64-bit storage (vrdx_layout.h, MakeSegmented64Layout) -- the same fill, the same three launches, the same
 // slots.  Grids depend on segmentCount, maxElementCount and the CU count only.
+// order: VRDX_HIP_KEY_UINT64 for vrdxHipCmdSortSegmented64*; vrdxHipCmdSortSegmented64Ordered* hand their order word on.
+// VRDX_HIP_KEY_UINT64 records the kernels it always did, an invalid word is refused before anything is enqueued, every other
+// order records the same fill and the ordered forms of the three launches, with the same grids.
 void RecordSegmentedSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
                            VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
-                           VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
-                           VkQueryPool queryPool, uint32_t query) {
+                           VkBuffer valuesBuffer, VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
+                           VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
   const bool keyValue = valuesBuffer != nullptr;
   if (maxElementCount > VRDX_MAX_ELEMENTS) {
@@ -588,6 +596,12 @@ void RecordSegmentedSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uin
   DeviceScope deviceScope(sorter->device);
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
   StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
+  if (!vrdx::KeyOrderValid(order)) {
+    stamps.Finish();
+    EnqueueCheck(sorter, kKeyOrderRefused, hipErrorInvalidValue);
+    return;
+  }
+  const bool ordered = order != VRDX_HIP_KEY_UINT64;
   const vrdx::Segmented64Layout layout = vrdx::MakeSegmented64Layout(
       maxElementCount, sorter->minStorageBufferOffsetAlignment, keyValue, (uint64_t)reinterpret_cast<uintptr_t>(storage));
   if (segmentCount == 0 || maxElementCount == 0 || !layout.fits) {
@@ -617,22 +631,25 @@ void RecordSegmentedSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uin
   EnqueueCheck(sorter, "segmented_clear_kernel", vrdx::LaunchSegmentedClear64(stream, a));
   stamps.AdvanceTo(1);
   const uint32_t cus = (uint32_t)sorter->computeUnits;
-  EnqueueCheck(sorter, "segmented_small64_kernel",
-               vrdx::LaunchSegmented64(stream, vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20), keyValue,
-                                       atomicRank, a));
+  const auto launch = [&](vrdx::SegmentClass sizeClass, uint32_t grid) {
+    return ordered ? vrdx::LaunchSegmented64Ordered(stream, sizeClass, grid, keyValue, atomicRank, a, order)
+                   : vrdx::LaunchSegmented64(stream, sizeClass, grid, keyValue, atomicRank, a);
+  };
+  EnqueueCheck(sorter, ordered ? "segmented_small64_ordered_kernel" : "segmented_small64_kernel",
+               launch(vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20)));
   stamps.AdvanceTo(2);
   // the lists by grid stride, one workgroup per CU: the 1024-thread forms take 66 to 89 registers and 90 to 144 KiB of LDS,
   // so one is resident per CU
   const uint32_t midGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.midCap), cus);
   if (midGrid != 0) {
-    EnqueueCheck(sorter, "segmented_mid64_kernel",
-                 vrdx::LaunchSegmented64(stream, vrdx::kSegmentMid, midGrid, keyValue, atomicRank, a));
+    EnqueueCheck(sorter, ordered ? "segmented_mid64_ordered_kernel" : "segmented_mid64_kernel",
+                 launch(vrdx::kSegmentMid, midGrid));
     stamps.AdvanceTo(3);
   }
   const uint32_t largeGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.largeCap), cus);
   if (largeGrid != 0) {
-    EnqueueCheck(sorter, "segmented_large64_kernel",
-                 vrdx::LaunchSegmented64(stream, vrdx::kSegmentLarge, largeGrid, keyValue, atomicRank, a));
+    EnqueueCheck(sorter, ordered ? "segmented_large64_ordered_kernel" : "segmented_large64_kernel",
+                 launch(vrdx::kSegmentLarge, largeGrid));
     stamps.AdvanceTo(4);
   }
   stamps.Finish();
@@ -650,10 +667,14 @@ void RecordSegmentedSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uin
 // Indirect (indirectBuffer != nullptr): elementCount is the bound; layout, plans and grids come from it alone, and every
 // step -- the streaming kernels and, through RecordSort, the inner sorts -- reads the count from the caller's word when it
 // runs, so a captured call can be replayed on any count up to the bound.
+// order: VRDX_HIP_KEY_UINT64 for vrdxHipCmdSort64*; vrdxHipCmdSort64Ordered* hand their order word on.  VRDX_HIP_KEY_UINT64
+// records the kernels it always did; an invalid word is refused before anything is enqueued; every other order records the
+// ordered forms of the split, the gather, the permutation and the merge -- A, B hold the words of T(key) (vrdx_kernels.h), so
+// the inner sorts and the copy back are the same calls.
 void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer indirectBuffer,
                   VkDeviceSize indirectOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
-                  VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
-                  uint32_t query) {
+                  VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                  VkQueryPool queryPool, uint32_t query) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
   const bool keyValue = valuesBuffer != nullptr;
   if (elementCount > VRDX_MAX_ELEMENTS) {
@@ -663,6 +684,12 @@ void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t ele
   }
   DeviceScope deviceScope(sorter->device);
   StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
+  if (!vrdx::KeyOrderValid(order)) {
+    stamps.Finish();
+    EnqueueCheck(sorter, kKeyOrderRefused, hipErrorInvalidValue);
+    return;
+  }
+  const bool ordered = order != VRDX_HIP_KEY_UINT64;
   if (elementCount == 0) {
     stamps.Finish();
     return;
@@ -683,17 +710,22 @@ void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t ele
                storageBuffer, storageOffset + payload, storageBuffer, storageOffset, nullptr, 0);
   };
 
-  EnqueueCheck(sorter, "split64_kernel", vrdx::LaunchSplit64(stream, keyValue, keys, lo, other, elementCount, countPtr));
+  EnqueueCheck(sorter, ordered ? "split64_ordered_kernel" : "split64_kernel",
+               ordered ? vrdx::LaunchSplit64Ordered(stream, keyValue, keys, lo, other, elementCount, countPtr, order)
+                       : vrdx::LaunchSplit64(stream, keyValue, keys, lo, other, elementCount, countPtr));
   stamps.AdvanceTo(1);
   sortWords(layout.loOffset, layout.otherOffset);
   stamps.AdvanceTo(2);
   if (keyValue) {
-    EnqueueCheck(sorter, "gather_hi64_kernel", vrdx::LaunchGatherHi64(stream, keys, other, lo, elementCount, countPtr));
+    EnqueueCheck(sorter, ordered ? "gather_hi64_ordered_kernel" : "gather_hi64_kernel",
+                 ordered ? vrdx::LaunchGatherHi64Ordered(stream, keys, other, lo, elementCount, countPtr, order)
+                         : vrdx::LaunchGatherHi64(stream, keys, other, lo, elementCount, countPtr));
     stamps.AdvanceTo(3);
     sortWords(layout.loOffset, layout.otherOffset);
     stamps.AdvanceTo(4);
-    EnqueueCheck(sorter, "permute64_kernel",
-                 vrdx::LaunchPermute64(stream, keys, values, other, lo, keysTemp, elementCount, countPtr));
+    EnqueueCheck(sorter, ordered ? "permute64_ordered_kernel" : "permute64_kernel",
+                 ordered ? vrdx::LaunchPermute64Ordered(stream, keys, values, other, lo, keysTemp, elementCount, countPtr, order)
+                         : vrdx::LaunchPermute64(stream, keys, values, other, lo, keysTemp, elementCount, countPtr));
     stamps.AdvanceTo(5);
     EnqueueCheck(sorter, "copy_back64_kernel",
                  vrdx::LaunchCopyBack64(stream, keys, values, keysTemp, lo, elementCount, countPtr));
@@ -701,7 +733,9 @@ void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t ele
   } else {
     sortWords(layout.otherOffset, layout.loOffset);  // (slot 3 coincides with slot 2: no step between the sorts)
     stamps.AdvanceTo(4);
-    EnqueueCheck(sorter, "merge64_kernel", vrdx::LaunchMerge64(stream, keys, lo, other, elementCount, countPtr));
+    EnqueueCheck(sorter, ordered ? "merge64_ordered_kernel" : "merge64_kernel",
+                 ordered ? vrdx::LaunchMerge64Ordered(stream, keys, lo, other, elementCount, countPtr, order)
+                         : vrdx::LaunchMerge64(stream, keys, lo, other, elementCount, countPtr));
     stamps.AdvanceTo(5);
   }
   stamps.Finish();
@@ -884,7 +918,7 @@ void vrdxHipCmdSortSegmented64(VkCommandBuffer commandBuffer, VrdxSorter sorter,
                                VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
                                VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
-                        keysOffset, nullptr, 0, storageBuffer, storageOffset, queryPool, query);
+                        keysOffset, nullptr, 0, VRDX_HIP_KEY_UINT64, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -893,7 +927,25 @@ void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter
                                        VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                                        VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
-                        keysOffset, valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
+                        keysOffset, valuesBuffer, valuesOffset, VRDX_HIP_KEY_UINT64, storageBuffer, storageOffset, queryPool,
+                        query);
+}
+
+void vrdxHipCmdSortSegmented64Ordered(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                      uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                      VkBuffer keysBuffer, VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer,
+                                      VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
+                        keysOffset, nullptr, 0, order, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSortSegmented64OrderedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                              uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                              VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                              VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
+                                              VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
+                        keysOffset, valuesBuffer, valuesOffset, order, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
@@ -943,15 +995,15 @@ void vrdxHipGetSorter64KeyValueStorageRequirements(VrdxSorter sorter, uint32_t m
 void vrdxHipCmdSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
                       VkDeviceSize keysOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
                       uint32_t query) {
-  RecordSort64(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, nullptr, 0, storageBuffer,
-               storageOffset, queryPool, query);
+  RecordSort64(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, nullptr, 0, VRDX_HIP_KEY_UINT64,
+               storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSort64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
                               VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                               VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
   RecordSort64(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, valuesBuffer, valuesOffset,
-               storageBuffer, storageOffset, queryPool, query);
+               VRDX_HIP_KEY_UINT64, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSort64Indirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -959,7 +1011,7 @@ void vrdxHipCmdSort64Indirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, 
                               VkDeviceSize keysOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                               VkQueryPool queryPool, uint32_t query) {
   RecordSort64(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, nullptr, 0,
-               storageBuffer, storageOffset, queryPool, query);
+               VRDX_HIP_KEY_UINT64, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSort64KeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -968,7 +1020,39 @@ void vrdxHipCmdSort64KeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter 
                                       VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
                                       uint32_t query) {
   RecordSort64(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, valuesBuffer,
-               valuesOffset, storageBuffer, storageOffset, queryPool, query);
+               valuesOffset, VRDX_HIP_KEY_UINT64, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSort64Ordered(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                             VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                             VkQueryPool queryPool, uint32_t query) {
+  RecordSort64(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, nullptr, 0, order, storageBuffer,
+               storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSort64OrderedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount,
+                                     VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                     VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
+                                     VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSort64(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, valuesBuffer, valuesOffset, order,
+               storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSort64OrderedIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                     VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                     VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer,
+                                     VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSort64(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, nullptr, 0,
+               order, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdSort64OrderedKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                             VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                             VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                             uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                             VkQueryPool queryPool, uint32_t query) {
+  RecordSort64(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, valuesBuffer,
+               valuesOffset, order, storageBuffer, storageOffset, queryPool, query);
 }
 
 VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {

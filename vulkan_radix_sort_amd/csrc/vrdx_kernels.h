@@ -320,6 +320,38 @@ hipError_t LaunchSegmentedClear64(hipStream_t stream, const Segmented64Args& arg
 hipError_t LaunchSegmented64(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
                              const Segmented64Args& args);
 
+// ---- key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered*, vrdxHipCmdSortSegmented64Ordered*; vrdx_kernels.hip, "key
+// orders of the 64-bit sorts") ----
+// The order word of include/vk_radix_sort.h: a key type, VRDX_HIP_ORDER_DESCENDING or-ed in or not.  The kernels sort
+// T(key) ascending as unsigned 64-bit, T(k) = k ^ flip ^ (float64 and bit 63 of k set ? 0x7FFFFFFFFFFFFFFF : 0) with flip = 0
+// (uint64) or 1 << 63 (int64, float64), complemented for descending; T is a bijection, so equal keys and only they have equal
+// T, and they keep their input order in both directions.
+constexpr uint32_t kKeyOrderUint64 = 0, kKeyOrderInt64 = 1, kKeyOrderFloat64 = 2;
+constexpr uint32_t kKeyOrderTypeMask = 0xFFu;
+constexpr uint32_t kKeyOrderDescending = 0x100u;
+constexpr bool KeyOrderValid(uint32_t order) {
+  return (order & ~(kKeyOrderTypeMask | kKeyOrderDescending)) == 0 && (order & kKeyOrderTypeMask) <= kKeyOrderFloat64;
+}
+// The ordered forms of the launches above: the same arguments with the order word behind them.  order == kKeyOrderUint64 is
+// the recorder's business (it records the launches above); these refuse an invalid word with hipErrorInvalidValue.
+// lo[i] = low word of T(keys[i]); other[i] = its high word, or i (iota)
+hipError_t LaunchSplit64Ordered(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other,
+                                uint32_t maxCount, const uint32_t* countPtr, uint32_t order);
+// keys[i] = the inverse of T on hi[i] << 32 | lo[i]
+hipError_t LaunchMerge64Ordered(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
+                                const uint32_t* countPtr, uint32_t order);
+// hi[j] = high word of T(keys[index[j]]) (read: the high word of the key alone)
+hipError_t LaunchGatherHi64Ordered(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi,
+                                   uint32_t maxCount, const uint32_t* countPtr, uint32_t order);
+// keysOut[j] = (the key's high word, from T's high word hiThenValues[j]) << 32 | low word of keys[index[j]]; then
+// hiThenValues[j] = values[index[j]]
+hipError_t LaunchPermute64Ordered(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
+                                  uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr,
+                                  uint32_t order);
+// segmented_small64 / mid64 / large64_ordered_kernel: every segment in ascending order of T(key)
+hipError_t LaunchSegmented64Ordered(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                                    const Segmented64Args& args, uint32_t order);
+
 // ---- the kernels' dynamic LDS and the MSD plan's grids: one definition for the kernels (vrdx_kernels.hip) and for both
 // launch backends (vrdx_launch.inc) ----
 // Key+value tiles replay the permutation for the values through the SAME staging buffer after the

@@ -3555,6 +3555,50 @@ __global__ __launch_bounds__(kSort64Threads) void copy_back64_kernel(uint64_t* _
 // that runs, and a pass that does not run leaves everything where it is), and a pass whose byte of that mask is zero is
 // skipped.  tile id << 32 | depth keys, hashes of fewer than 64 bits and counters take five or six passes instead of eight.
 
+// Key orders (the ORDERED forms, vrdxHipCmdSort64Ordered* and vrdxHipCmdSortSegmented64Ordered*): the kernels sort T(key)
+// ascending as unsigned, T(k) = k ^ flip ^ (float64 and bit 63 of k set ? 0x7FFFFFFFFFFFFFFF : 0), flip = 0 (unsigned) or
+// 1 << 63 (signed, float64), complemented for descending.  As words: the high word's mask depends on the high word alone,
+// the low word's on the key's sign, which is bit 31 of the key's high word and bit 31 of T's high word ^ flipHi.
+struct KeyOrder64 {
+  uint32_t flipHi, flipLo;
+  uint32_t floatMask;  // all ones for float64
+};
+__device__ __forceinline__ KeyOrder64 MakeKeyOrder64(uint32_t order) {
+  const uint32_t type = order & kKeyOrderTypeMask;
+  const uint32_t descending = (order & kKeyOrderDescending) != 0 ? ~0u : 0u;
+  return KeyOrder64{(type != kKeyOrderUint64 ? 0x80000000u : 0u) ^ descending, descending, type == kKeyOrderFloat64 ? ~0u : 0u};
+}
+// all ones where the key is a float64 with its sign bit set: from the key's high word | from T(key)'s high word
+__device__ __forceinline__ uint32_t OrderNegOfKey(const KeyOrder64& o, uint32_t hi) {
+  return (uint32_t)((int32_t)hi >> 31) & o.floatMask;
+}
+__device__ __forceinline__ uint32_t OrderNegOfT(const KeyOrder64& o, uint32_t tHi) {
+  return (uint32_t)((int32_t)(tHi ^ o.flipHi) >> 31) & o.floatMask;
+}
+// a word of T(key) from the key's, and back (an involution once `neg` is known)
+__device__ __forceinline__ uint32_t OrderLow(const KeyOrder64& o, uint32_t lo, uint32_t neg) { return lo ^ o.flipLo ^ neg; }
+__device__ __forceinline__ uint32_t OrderHigh(const KeyOrder64& o, uint32_t hi, uint32_t neg) {
+  return hi ^ o.flipHi ^ (neg & 0x7FFFFFFFu);
+}
+// the high word alone: T(key)'s from the key's | the key's from T(key)'s
+__device__ __forceinline__ uint32_t OrderHighOfKey(const KeyOrder64& o, uint32_t hi) {
+  return OrderHigh(o, hi, OrderNegOfKey(o, hi));
+}
+__device__ __forceinline__ uint32_t OrderHighOfT(const KeyOrder64& o, uint32_t tHi) {
+  return OrderHigh(o, tHi, OrderNegOfT(o, tHi));
+}
+// key -> T(key) and T(key) -> key, on a key held as two words
+__device__ __forceinline__ void OrderForward(const KeyOrder64& o, uint32_t& lo, uint32_t& hi) {
+  const uint32_t neg = OrderNegOfKey(o, hi);
+  lo = OrderLow(o, lo, neg);
+  hi = OrderHigh(o, hi, neg);
+}
+__device__ __forceinline__ void OrderInverse(const KeyOrder64& o, uint32_t& lo, uint32_t& hi) {
+  const uint32_t neg = OrderNegOfT(o, hi);
+  lo = OrderLow(o, lo, neg);
+  hi = OrderHigh(o, hi, neg);
+}
+
 // The OR over the 64 lanes of a wave, in lane 63 (the DPP moves of WaveInclusiveScan: lanes that receive nothing get 0).
 __device__ __forceinline__ uint32_t WaveInclusiveOr(uint32_t v) {
   int x = (int)v;
@@ -3653,9 +3697,13 @@ __device__ __forceinline__ void RankPass64(const uint32_t (&word)[KPT], uint32_t
 // of SortInWorkgroup.  Pads are the all-ones key with value 0: last in memory order and the largest key, so every stable
 // pass leaves them behind the real elements -- real all-ones keys included, which sit in front of them from the start.
 // LDS: SortInWorkgroup64LdsWords (vrdx_kernels.h).
-template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK>
+// ORDERED (the segmented *_ordered_kernel forms): the order is that of T(key) (KeyOrder64).  The real elements, and key0,
+// become T(key) right behind the load and keys again in front of the store, so the masks of varying bytes are those of
+// T(key); the pads stay all ones -- last in memory order and the largest word in T-space too, so the argument above holds
+// with "the keys that T maps to all ones" for "real all-ones keys".
+template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK, bool ORDERED = false>
 __device__ __forceinline__ void SortInWorkgroup64(const uint64_t* keysIn, uint64_t* keysOut, const uint32_t* valuesIn,
-                                                  uint32_t* valuesOut, uint32_t n, uint32_t* smem) {
+                                                  uint32_t* valuesOut, uint32_t n, uint32_t* smem, uint32_t order = 0) {
   constexpr int WAVES = THREADS / 64;
   constexpr uint32_t TILE = THREADS * KPT;
   static_assert(KPT % 4 == 0, "chunks of four slots");
@@ -3671,9 +3719,20 @@ __device__ __forceinline__ void SortInWorkgroup64(const uint64_t* keysIn, uint64
   uint32_t lo[KPT], hi[KPT];
   uint32_t val[KV ? KPT : 1];
   if (tid < 2) varying[tid] = 0;
-  const uint64_t key0 = keysIn[0];  // uniform (n >= 1)
+  uint64_t key0 = keysIn[0];  // uniform (n >= 1)
   LoadStriped64<KPT>(keysIn, first, n, lo, hi, slots);
   if constexpr (KV) LoadStriped<KPT, false, true>(valuesIn, first, n, false, 0u, val, slots);
+  if constexpr (ORDERED) {
+    const KeyOrder64 o = MakeKeyOrder64(order);
+    uint32_t lo0 = (uint32_t)key0, hi0 = (uint32_t)(key0 >> 32);
+    OrderForward(o, lo0, hi0);
+    key0 = (uint64_t)hi0 << 32 | lo0;
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      if (i % 4 == 0 && (uint32_t)i >= slots) break;
+      if (first + 64 * i < n) OrderForward(o, lo[i], hi[i]);
+    }
+  }
 
   // which bytes differ between any two keys of the segment
   uint32_t diffLo = 0, diffHi = 0;
@@ -3713,6 +3772,7 @@ __device__ __forceinline__ void SortInWorkgroup64(const uint64_t* keysIn, uint64
     if (i % 4 == 0 && (uint32_t)i >= slots) break;
     const uint32_t index = first + 64 * i;
     if (index < n) {
+      if constexpr (ORDERED) OrderInverse(MakeKeyOrder64(order), lo[i], hi[i]);
       keysOut[index] = (uint64_t)hi[i] << 32 | lo[i];
       if constexpr (KV) valuesOut[index] = val[i];
     }
@@ -3784,11 +3844,17 @@ __global__ __launch_bounds__(1024) void segmented_mid64_kernel(Segmented64Args a
 // inside one segment); the others walk the segment in tiles of kSeg64LargeTile keys, in order, ping-ponging between the
 // caller's range and the same index range of the 8-byte scratch; an odd number of passes ends with a copy back.
 // LDS: Segment64LargeLdsWords (vrdx_kernels.h).
+// ORDERED (segmented_large64_ordered_kernel): by T(key) (KeyOrder64).  The histogram read counts the bytes of T(key); the
+// FIRST pass that runs turns its tiles into T(key) behind the load, the LAST one turns them back in front of the store, and
+// between the two the segment's two ranges hold T(key) -- they are this workgroup's alone until the kernel ends, and one
+// workgroup walks a whole segment, so every instruction per key and pass is on its critical path (transforming in every pass
+// measured +4-6 % at 64 x 262144 keys against the unordered sort of T(keys), this form +0-2 %: DESIGN.md 4.15).  With no pass to run nothing is transformed.  The ranking
+// code, shared with every other kernel, sees plain words, and a tile's pads stay all ones, digit 255's last keys.
 static_assert(8 * 256 * kSegHistCopies <= 2 * kSeg64LargeTile, "the histogram replicas alias the two staging planes");
 
-template <bool KV, bool ATOMIC_RANK>
+template <bool KV, bool ATOMIC_RANK, bool ORDERED = false>
 __device__ __forceinline__ void SegmentLsd64(uint64_t* keys, uint32_t* values, uint64_t* keysScratch, uint32_t* valuesScratch,
-                                             uint32_t n, uint32_t* smem) {
+                                             uint32_t n, uint32_t* smem, uint32_t order = 0) {
   constexpr int THREADS = 1024, KPT = (int)(kSeg64LargeTile / 1024u), WAVES = THREADS / 64;
   constexpr uint32_t TILE = kSeg64LargeTile;
   uint32_t* const stagedLo = smem;
@@ -3808,8 +3874,10 @@ __device__ __forceinline__ void SegmentLsd64(uint64_t* keys, uint32_t* values, u
   if (tid == 0) misc[0] = 0;
   LdsBarrier();
   const uint32_t copy = tid & (kSegHistCopies - 1);
+  const KeyOrder64 keyOrder = MakeKeyOrder64(ORDERED ? order : 0u);  // (ORDERED only)
   auto count = [&](uint64_t key) {
-    const uint32_t l = (uint32_t)key, h = (uint32_t)(key >> 32);
+    uint32_t l = (uint32_t)key, h = (uint32_t)(key >> 32);
+    if constexpr (ORDERED) OrderForward(keyOrder, l, h);
 #pragma unroll
     for (uint32_t p = 0; p < 4; ++p) {
       atomicAdd(&bins[(p * 256 + ((l >> (8 * p)) & 0xFFu)) * kSegHistCopies + copy], 1u);
@@ -3847,6 +3915,9 @@ __device__ __forceinline__ void SegmentLsd64(uint64_t* keys, uint32_t* values, u
   }
   LdsBarrier();
   const uint32_t active = (uint32_t)__builtin_amdgcn_readfirstlane((int)misc[0]);
+  // (ORDERED) the passes that take the keys into T-space and back: the lowest and the highest set bit of `active`
+  const uint32_t firstPass = ORDERED && active != 0 ? (uint32_t)__builtin_ctz(active) : 0u;
+  const uint32_t lastPass = ORDERED && active != 0 ? 31u - (uint32_t)__builtin_clz(active) : 0u;
 
   // 2. the passes
   uint64_t* src = keys;
@@ -3873,6 +3944,15 @@ __device__ __forceinline__ void SegmentLsd64(uint64_t* keys, uint32_t* values, u
       uint32_t val[KV ? KPT : 1];
       LoadStriped64<KPT>(src + t0, first, m, lo, hi, slots);
       if constexpr (KV) LoadStriped<KPT, false, true>(srcV + t0, first, m, false, 0u, val, slots);
+      if constexpr (ORDERED) {
+        if (pass == firstPass) {  // uniform
+#pragma unroll
+          for (int i = 0; i < KPT; ++i) {
+            if (i % 4 == 0 && (uint32_t)i >= slots) break;
+            if (first + 64 * i < m) OrderForward(keyOrder, lo[i], hi[i]);
+          }
+        }
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;
       uint32_t rank[KPT];
@@ -3915,8 +3995,11 @@ __device__ __forceinline__ void SegmentLsd64(uint64_t* keys, uint32_t* values, u
         const uint32_t q = first + 64 * i;
         if (q < m) {
           const uint32_t slot = StagingSlot<TILE>(q);
-          const uint32_t kl = stagedLo[slot], kh = stagedHi[slot];
+          uint32_t kl = stagedLo[slot], kh = stagedHi[slot];
           const uint32_t d = ((HI ? kh : kl) >> shift) & 0xFFu;
+          if constexpr (ORDERED) {
+            if (pass == lastPass) OrderInverse(keyOrder, kl, kh);  // uniform
+          }
           const uint32_t to = base[d] + q - tileStart[d];
           // always < n while the segment is this workgroup's alone; segments that overlap (offsets that are not monotone,
           // flagged by the small kernel) may change keys under the counts, and must still never write outside the range
@@ -3971,6 +4054,188 @@ __global__ __launch_bounds__(1024) void segmented_large64_kernel(Segmented64Args
     __syncthreads();  // the previous segment is done (its copy back included)
     SegmentLsd64<KV, ATOMIC_RANK>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
                                   KV ? a.valuesScratch + begin : nullptr, end - begin, smem);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered*, vrdxHipCmdSortSegmented64Ordered*): signed, float64, descending
+// ---------------------------------------------------------------------------------------------
+// The ordered forms of the kernels above, as kernels of their own: the order word travels as one more argument behind the
+// twin's, and none of the twins' code moves.  The composition's word arrays hold the words of T(key) (KeyOrder64 above), so
+// the two inner 32-bit sorts are the calls they were; the segmented kernels hold T(key) in their registers between the one
+// load and the one store (SortInWorkgroup64) or from the first pass's loads to the last pass's stores (SegmentLsd64).  Access patterns are the
+// twins': four elements per thread, a gather still loads ONE word of a key -- the high word's mask depends on the high word
+// alone, and the merge and the permutation find the sign the low word's mask needs in the transformed high word.
+
+// lo[i] = low word of T(keys[i]); other[i] = its high word, or i itself (IOTA)
+template <bool IOTA>
+__global__ __launch_bounds__(kSort64Threads) void split64_ordered_kernel(const uint64_t* __restrict__ keys,
+                                                                         uint32_t* __restrict__ lo,
+                                                                         uint32_t* __restrict__ other, uint32_t maxCount,
+                                                                         const uint32_t* countPtr, uint32_t order) {
+  const KeyOrder64 o = MakeKeyOrder64(order);
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4_a8* const pairs = reinterpret_cast<const u32x4_a8*>(keys + i);
+    const u32x4 a = pairs[0], b = pairs[1];
+    const u32x4 neg = u32x4{OrderNegOfKey(o, a.y), OrderNegOfKey(o, a.w), OrderNegOfKey(o, b.y), OrderNegOfKey(o, b.w)};
+    *reinterpret_cast<u32x4*>(lo + i) =
+        u32x4{OrderLow(o, a.x, neg.x), OrderLow(o, a.z, neg.y), OrderLow(o, b.x, neg.z), OrderLow(o, b.z, neg.w)};
+    *reinterpret_cast<u32x4*>(other + i) =
+        IOTA ? u32x4{i, i + 1u, i + 2u, i + 3u}
+             : u32x4{OrderHigh(o, a.y, neg.x), OrderHigh(o, a.w, neg.y), OrderHigh(o, b.y, neg.z), OrderHigh(o, b.w, neg.w)};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    const uint64_t k = keys[j];
+    uint32_t l = (uint32_t)k, h = (uint32_t)(k >> 32);
+    OrderForward(o, l, h);
+    lo[j] = l;
+    other[j] = IOTA ? j : h;
+  }
+}
+
+// keys[i] = the key whose T has the words hi[i], lo[i]
+__global__ __launch_bounds__(kSort64Threads) void merge64_ordered_kernel(uint64_t* __restrict__ keys,
+                                                                         const uint32_t* __restrict__ lo,
+                                                                         const uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                         const uint32_t* countPtr, uint32_t order) {
+  const KeyOrder64 o = MakeKeyOrder64(order);
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4 tl = *reinterpret_cast<const u32x4*>(lo + i), th = *reinterpret_cast<const u32x4*>(hi + i);
+    const u32x4 neg = u32x4{OrderNegOfT(o, th.x), OrderNegOfT(o, th.y), OrderNegOfT(o, th.z), OrderNegOfT(o, th.w)};
+    const u32x4 l = u32x4{OrderLow(o, tl.x, neg.x), OrderLow(o, tl.y, neg.y), OrderLow(o, tl.z, neg.z), OrderLow(o, tl.w, neg.w)};
+    const u32x4 h =
+        u32x4{OrderHigh(o, th.x, neg.x), OrderHigh(o, th.y, neg.y), OrderHigh(o, th.z, neg.z), OrderHigh(o, th.w, neg.w)};
+    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(keys + i);
+    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
+    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    uint32_t l = lo[j], h = hi[j];
+    OrderInverse(o, l, h);
+    keys[j] = (uint64_t)h << 32 | l;
+  }
+}
+
+// hi[j] = high word of T(keys[index[j]]), from the key's high word alone
+__global__ __launch_bounds__(kSort64Threads) void gather_hi64_ordered_kernel(const uint64_t* __restrict__ keys,
+                                                                             const uint32_t* __restrict__ index,
+                                                                             uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                             const uint32_t* countPtr, uint32_t order) {
+  const KeyOrder64 o = MakeKeyOrder64(order);
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
+  if (whole) {
+    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
+    *reinterpret_cast<u32x4*>(hi + i) =
+        u32x4{OrderHighOfKey(o, words[2ull * at.x + 1u]), OrderHighOfKey(o, words[2ull * at.y + 1u]),
+              OrderHighOfKey(o, words[2ull * at.z + 1u]), OrderHighOfKey(o, words[2ull * at.w + 1u])};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) hi[j] = OrderHighOfKey(o, words[2ull * index[j] + 1u]);
+}
+
+// keysOut[j] = (the high word that hiThenValues[j] is the transformed form of) << 32 | low word of keys[index[j]], raw as it
+// lies in the caller's keys; then hiThenValues[j] = values[index[j]]
+__global__ __launch_bounds__(kSort64Threads) void permute64_ordered_kernel(const uint64_t* __restrict__ keys,
+                                                                           const uint32_t* __restrict__ values,
+                                                                           const uint32_t* __restrict__ index,
+                                                                           uint32_t* __restrict__ hiThenValues,
+                                                                           uint64_t* __restrict__ keysOut, uint32_t maxCount,
+                                                                           const uint32_t* countPtr, uint32_t order) {
+  const KeyOrder64 o = MakeKeyOrder64(order);
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
+  if (whole) {
+    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
+    const u32x4 th = *reinterpret_cast<const u32x4*>(hiThenValues + i);
+    const u32x4 h = u32x4{OrderHighOfT(o, th.x), OrderHighOfT(o, th.y), OrderHighOfT(o, th.z), OrderHighOfT(o, th.w)};
+    const u32x4 l = u32x4{words[2ull * at.x], words[2ull * at.y], words[2ull * at.z], words[2ull * at.w]};
+    const u32x4 v = u32x4{values[at.x], values[at.y], values[at.z], values[at.w]};
+    u32x4* const pairs = reinterpret_cast<u32x4*>(keysOut + i);
+    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
+    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
+    *reinterpret_cast<u32x4*>(hiThenValues + i) = v;
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    const uint32_t at = index[j];
+    keysOut[j] = (uint64_t)OrderHighOfT(o, hiThenValues[j]) << 32 | words[2ull * at];
+    hiThenValues[j] = values[at];
+  }
+}
+
+// the three size classes of the segmented sort of 64-bit keys: the twins' loops around the ORDERED forms of
+// SortInWorkgroup64 and SegmentLsd64
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(256) void segmented_small64_ordered_kernel(Segmented64Args a, uint32_t order) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
+  for (uint32_t s = blockIdx.x; s < a.segmentCount; s += gridDim.x) {
+    uint32_t begin = 0, end = 0;
+    if (!SegmentBoundsOf(a, s, true, &begin, &end)) continue;  // uniform
+    const uint32_t n = end - begin;
+    if (n > kSeg64SmallMax) {
+      if (threadIdx.x == 0) {
+        const bool mid = n <= kMidMax;
+        const uint32_t slot = atomicAdd(mid ? a.midCount : a.largeCount, 1u);
+        if (slot < (mid ? a.midCap : a.largeCap)) (mid ? a.midList : a.largeList)[slot] = s;
+      }
+      continue;
+    }
+    if (n < 2) continue;
+    LdsBarrier();  // the previous segment's read-back of the staging planes is over
+    SortInWorkgroup64<256, 16, KV, ATOMIC_RANK, true>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
+                                                      KV ? a.values + begin : nullptr, n, smem, order);
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_mid64_ordered_kernel(Segmented64Args a, uint32_t order) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
+  const uint32_t listed = min(*a.midCount, a.midCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = a.midList[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBoundsOf(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    const uint32_t n = end - begin;
+    if (n <= kSeg64SmallMax || n > kMidMax) continue;
+    LdsBarrier();
+    SortInWorkgroup64<1024, (int)(kMidMax / 1024u), KV, ATOMIC_RANK, true>(a.keys + begin, a.keys + begin,
+                                                                           KV ? a.values + begin : nullptr,
+                                                                           KV ? a.values + begin : nullptr, n, smem, order);
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_large64_ordered_kernel(Segmented64Args a, uint32_t order) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
+  const uint32_t listed = min(*a.largeCount, a.largeCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = a.largeList[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBoundsOf(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    if (end - begin <= kMidMax) continue;
+    __syncthreads();  // the previous segment is done (its copy back included)
+    SegmentLsd64<KV, ATOMIC_RANK, true>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
+                                        KV ? a.valuesScratch + begin : nullptr, end - begin, smem, order);
   }
 }
 

@@ -271,7 +271,45 @@
   X(kSegmentedBitsLargeV, (&segmented_large_bits_kernel<true, false>), 1024, SegmentLargeLdsWords(true) * 4, \
     "_ZN4vrdx27segmented_large_bits_kernelILb1ELb0EEEvNS_13SegmentedArgsEjj") \
   X(kSegmentedBitsLargeVA, (&segmented_large_bits_kernel<true, true>), 1024, SegmentLargeLdsWords(true) * 4, \
-    "_ZN4vrdx27segmented_large_bits_kernelILb1ELb1EEEvNS_13SegmentedArgsEjj")
+    "_ZN4vrdx27segmented_large_bits_kernelILb1ELb1EEEvNS_13SegmentedArgsEjj") \
+  /* ---- key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered*): the ordered forms of the split [high words | iota], \
+     the merge, the gather and the permutation ---- */ \
+  X(kSplit64Ordered, (&split64_ordered_kernel<false>), kSort64Threads, 0, \
+    "_ZN4vrdx22split64_ordered_kernelILb0EEEvPKmPjS3_jPKjj") \
+  X(kSplit64OrderedIota, (&split64_ordered_kernel<true>), kSort64Threads, 0, \
+    "_ZN4vrdx22split64_ordered_kernelILb1EEEvPKmPjS3_jPKjj") \
+  X(kMerge64Ordered, (&merge64_ordered_kernel), kSort64Threads, 0, \
+    "_ZN4vrdx22merge64_ordered_kernelEPmPKjS2_jS2_j") \
+  X(kGatherHi64Ordered, (&gather_hi64_ordered_kernel), kSort64Threads, 0, \
+    "_ZN4vrdx26gather_hi64_ordered_kernelEPKmPKjPjjS3_j") \
+  X(kPermute64Ordered, (&permute64_ordered_kernel), kSort64Threads, 0, \
+    "_ZN4vrdx24permute64_ordered_kernelEPKmPKjS3_PjPmjS3_j") \
+  /* ---- vrdxHipCmdSortSegmented64Ordered*: the ordered forms of the three segmented 64-bit kernels \
+     [small | mid | large][key-value][atomic rank] ---- */ \
+  X(kSegmented64OrderedSmall, (&segmented_small64_ordered_kernel<false, false>), 256, SortInWorkgroup64LdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx32segmented_small64_ordered_kernelILb0ELb0EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedSmallA, (&segmented_small64_ordered_kernel<false, true>), 256, SortInWorkgroup64LdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx32segmented_small64_ordered_kernelILb0ELb1EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedSmallV, (&segmented_small64_ordered_kernel<true, false>), 256, SortInWorkgroup64LdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx32segmented_small64_ordered_kernelILb1ELb0EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedSmallVA, (&segmented_small64_ordered_kernel<true, true>), 256, SortInWorkgroup64LdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx32segmented_small64_ordered_kernelILb1ELb1EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedMid, (&segmented_mid64_ordered_kernel<false, false>), 1024, SortInWorkgroup64LdsWords(1024, Seg64MidKpt(false), false) * 4, \
+    "_ZN4vrdx30segmented_mid64_ordered_kernelILb0ELb0EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedMidA, (&segmented_mid64_ordered_kernel<false, true>), 1024, SortInWorkgroup64LdsWords(1024, Seg64MidKpt(false), false) * 4, \
+    "_ZN4vrdx30segmented_mid64_ordered_kernelILb0ELb1EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedMidV, (&segmented_mid64_ordered_kernel<true, false>), 1024, SortInWorkgroup64LdsWords(1024, Seg64MidKpt(true), true) * 4, \
+    "_ZN4vrdx30segmented_mid64_ordered_kernelILb1ELb0EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedMidVA, (&segmented_mid64_ordered_kernel<true, true>), 1024, SortInWorkgroup64LdsWords(1024, Seg64MidKpt(true), true) * 4, \
+    "_ZN4vrdx30segmented_mid64_ordered_kernelILb1ELb1EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedLarge, (&segmented_large64_ordered_kernel<false, false>), 1024, Segment64LargeLdsWords(false) * 4, \
+    "_ZN4vrdx32segmented_large64_ordered_kernelILb0ELb0EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedLargeA, (&segmented_large64_ordered_kernel<false, true>), 1024, Segment64LargeLdsWords(false) * 4, \
+    "_ZN4vrdx32segmented_large64_ordered_kernelILb0ELb1EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedLargeV, (&segmented_large64_ordered_kernel<true, false>), 1024, Segment64LargeLdsWords(true) * 4, \
+    "_ZN4vrdx32segmented_large64_ordered_kernelILb1ELb0EEEvNS_15Segmented64ArgsEj") \
+  X(kSegmented64OrderedLargeVA, (&segmented_large64_ordered_kernel<true, true>), 1024, Segment64LargeLdsWords(true) * 4, \
+    "_ZN4vrdx32segmented_large64_ordered_kernelILb1ELb1EEEvNS_15Segmented64ArgsEj")
 
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
@@ -487,6 +525,40 @@ hipError_t LaunchCopyBack64(hipStream_t stream, uint64_t* keys, uint32_t* values
                             const uint32_t* valuesIn, uint32_t maxCount, const uint32_t* countPtr) {
   if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
   return Launch(kCopyBack64, Sort64Grid(maxCount), stream, keys, values, keysIn, valuesIn, maxCount, countPtr);
+}
+
+// ---- key orders of the 64-bit sorts ------------------------------------------------------------------
+hipError_t LaunchSplit64Ordered(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other,
+                                uint32_t maxCount, const uint32_t* countPtr, uint32_t order) {
+  if (!Sort64CountFits(maxCount) || !KeyOrderValid(order)) return hipErrorInvalidValue;
+  return Launch(iota ? kSplit64OrderedIota : kSplit64Ordered, Sort64Grid(maxCount), stream, keys, lo, other, maxCount, countPtr,
+                order);
+}
+
+hipError_t LaunchMerge64Ordered(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
+                                const uint32_t* countPtr, uint32_t order) {
+  if (!Sort64CountFits(maxCount) || !KeyOrderValid(order)) return hipErrorInvalidValue;
+  return Launch(kMerge64Ordered, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr, order);
+}
+
+hipError_t LaunchGatherHi64Ordered(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi,
+                                   uint32_t maxCount, const uint32_t* countPtr, uint32_t order) {
+  if (!Sort64CountFits(maxCount) || !KeyOrderValid(order)) return hipErrorInvalidValue;
+  return Launch(kGatherHi64Ordered, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr, order);
+}
+
+hipError_t LaunchPermute64Ordered(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
+                                  uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr,
+                                  uint32_t order) {
+  if (!Sort64CountFits(maxCount) || !KeyOrderValid(order)) return hipErrorInvalidValue;
+  return Launch(kPermute64Ordered, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues, keysOut, maxCount, countPtr,
+                order);
+}
+
+hipError_t LaunchSegmented64Ordered(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                                    const Segmented64Args& args, uint32_t order) {
+  if (grid == 0 || !KeyOrderValid(order)) return hipErrorInvalidValue;
+  return Launch(Form(KernelId(kSegmented64OrderedSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args, order);
 }
 
 // ---- the LDS order check and the calibration spin -----------------------------------------------------
