@@ -3,10 +3,14 @@
 //                                           modes and every forced tile geometry: the invariants of plan_invariants.h hold of
 //                                           every plan, and the sizes at which the plan changes are those of kAtomicEdges /
 //                                           kBallotEdges, found again here from the functions themselves;
+//                                           the segmented and the 64-bit planners (PlanSegmentedSort, PlanSort64) over the matrix of
+//                                           record_trace.cpp: grids against the formulas restated here, no step of grid 0,
+//                                           slots that increase, no step in a refused or empty plan;
 //   plan_check describe <cus> <atomic> <n>...   one line per (n, key+value): n, 0 | 1, the plan's name (those of
 //                                           vulkan_radix_sort_amd/api.py, PLAN_NAMES), its bits, hybridCap, msdCap, launches and
 //                                           tile geometry -- what the Python tests hold their hand-kept numbers to.
 // Built by tests/native/Makefile; nothing of HIP is linked (vrdx_kernels.h needs one of its headers).
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -160,6 +164,65 @@ int main(int argc, char** argv) {
     }
   // kMsdStreamedOutputUpTo (vrdx_kernels.h) is the ten-bit plan's last size (also a static_assert of vrdx_plan.h)
   if (vrdx::kMsdStreamedOutputUpTo != plan_test::kAtomicEdges[6]) fail("kMsdStreamedOutputUpTo", vrdx::kMsdStreamedOutputUpTo, 256, 0, 1, -1);
+
+  // 4. the segmented and the 64-bit planners over the matrix of record_trace.cpp (counts, segment counts, bit ranges, order
+  // words) at every CU count, both key widths and value modes, against the rules restated here
+  const uint32_t counts[] = {0u, 1u, 4096u, 4097u, 8192u, 8193u, 16384u, 16385u, (1u << 20) + 3u, VRDX_MAX_ELEMENTS};
+  const uint32_t ranges[][2] = {{0, 32}, {5, 5}, {3, 20}, {9, 4}, {0, 33}};
+  const uint32_t orders[] = {0u, 1u, 2u, 0x100u, 0x102u, 3u, 0x200u};
+  for (uint32_t cus : plan_test::kCuCounts)
+    for (uint32_t n : counts)
+      for (int keyValue = 0; keyValue < 2; ++keyValue) {
+        vrdx::PlanContext c;
+        c.computeUnits = (int)cus;
+        c.atomicRank = true;
+        for (uint32_t segments : {0u, 1u, 2u * cus - 1u, 2u * cus + 1u, (1u << 20) + 1u})
+          for (uint32_t keyBytes : {4u, 8u})
+            for (uint32_t form = 0; form < (keyBytes == 4 ? 5u : 7u); ++form) {
+              vrdx::SegmentedKey key;
+              if (keyBytes == 4) key.beginBit = ranges[form][0], key.endBit = ranges[form][1];
+              if (keyBytes == 8) key.order = orders[form];
+              const vrdx::SegmentedPlan p = vrdx::PlanSegmentedSort(c, keyBytes, keyValue != 0, n, segments, key, 0);
+              ++cases;
+              const bool invalid = keyBytes == 4 ? key.beginBit > key.endBit || key.endBit > 32 : (key.order & ~0x100u) > 2;
+              const bool empty = n == 0 || segments == 0 || (keyBytes == 4 && key.beginBit == key.endBit);
+              bool ok = (p.refusal != nullptr) == invalid && p.stepCount <= 4;
+              if (invalid || empty) ok = ok && p.stepCount == 0;
+              // the caps: a mid segment holds 4097 elements and more, a large one more than the mid class takes
+              const uint32_t midCap = n / 4097u, largeCap = n / (keyBytes == 8 && keyValue ? 8193u : 16385u);
+              const uint32_t k = keyBytes == 4 ? 2u : 1u;
+              const uint32_t want[4] = {1u, std::min(segments, 1u << 20), std::min(std::min(segments, midCap), k * cus),
+                                        std::min(std::min(segments, largeCap), k * cus)};
+              uint32_t seen = 0;
+              for (uint32_t i = 0; i < p.stepCount && ok; ++i) {
+                const vrdx::SegmentedSortStep& step = p.steps[i];
+                const uint32_t what = (uint32_t)step.what;
+                ok = what < 4 && step.grid != 0 && step.grid == want[what] && step.slot == what + 1 && step.name != nullptr &&
+                     (i == 0 || step.slot > p.steps[i - 1].slot);
+                seen |= 1u << what;
+              }
+              if (!invalid && !empty)  // every launch whose grid is not 0 is there, the fill and the small launch always
+                for (uint32_t what = 0; what < 4; ++what) ok = ok && ((seen >> what & 1u) != 0) == (want[what] != 0);
+              // the form of a plan with steps: the whole key (width 0), the range, or the order word
+              if (p.stepCount != 0 && keyBytes == 4)
+                ok = ok && p.rangeWidth == (form == 0 ? 0u : key.endBit - key.beginBit) && p.rangeBegin == (form == 0 ? 0u : key.beginBit);
+              if (p.stepCount != 0 && keyBytes == 8) ok = ok && p.order == key.order && p.rangeWidth == 0;
+              if (!ok) fail(keyBytes == 4 ? "segmented plan" : "segmented 64-bit plan", n, cus, keyValue, (int)segments, (int)form);
+            }
+        for (uint32_t order : orders) {
+          const vrdx::Sort64Plan p = vrdx::PlanSort64(c, keyValue != 0, n, order, 0);
+          ++cases;
+          const bool invalid = (order & ~0x100u) > 2;
+          bool ok = (p.refusal != nullptr) == invalid && p.stepCount == (invalid || n == 0 ? 0u : keyValue ? 6u : 4u);
+          uint32_t sorts = 0;
+          for (uint32_t i = 0; i < p.stepCount && ok; ++i) {
+            ok = p.steps[i].name != nullptr && p.steps[i].slot <= 14 && (i == 0 || p.steps[i].slot > p.steps[i - 1].slot);
+            sorts += p.steps[i].what == vrdx::Step64::kSortLoOther || p.steps[i].what == vrdx::Step64::kSortOtherLo;
+          }
+          if (p.stepCount != 0) ok = ok && sorts == 2 && p.steps[0].what == vrdx::Step64::kSplit && p.steps[0].slot == 1;
+          if (!ok) fail("64-bit plan", n, cus, keyValue, 1, (int)order);
+        }
+      }
 
   std::printf("plan: %llu cases, %d failures\n", (unsigned long long)cases, failures);
   return failures != 0;

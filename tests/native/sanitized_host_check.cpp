@@ -66,6 +66,27 @@ int main() {
   };
   for (const uint32_t edge : plan_test::kAtomicEdges) planAt(edge);
   for (const uint32_t edge : plan_test::kBallotEdges) planAt(edge);
+  // the segmented and the 64-bit planners: every form, either side of the size classes, every alignment
+  for (const uint32_t n : {0u, 1u, 4097u, 16385u, (1u << 20) + 3u, (uint32_t)VRDX_MAX_ELEMENTS})
+    for (const bool keyValue : {false, true})
+      for (uint32_t address = 0; address < 128; address += 16) {
+        const vrdx::PlanContext context{256, true};
+        const uint64_t storage = 0x7f0000001000ull + address;
+        for (const uint32_t segments : {0u, 1u, 513u, (1u << 20) + 1u}) {
+          for (const vrdx::SegmentedKey key : {vrdx::SegmentedKey{}, vrdx::SegmentedKey{3, 20}, vrdx::SegmentedKey{5, 5}, vrdx::SegmentedKey{9, 4}}) {
+            const vrdx::SegmentedPlan p = vrdx::PlanSegmentedSort(context, 4, keyValue, n, segments, key, storage);
+            if (p.stepCount > 4 || (p.refusal != nullptr) != (key.beginBit > key.endBit) || (p.refusal != nullptr && p.stepCount != 0)) ++failures;
+          }
+          for (const uint32_t order : {0u, 0x102u, 3u}) {
+            const vrdx::SegmentedPlan p = vrdx::PlanSegmentedSort(context, 8, keyValue, n, segments, vrdx::SegmentedKey{0, 32, order}, storage);
+            if (p.stepCount > 4 || (p.refusal != nullptr) != (order == 3u) || (p.refusal != nullptr && p.stepCount != 0)) ++failures;
+          }
+        }
+        for (const uint32_t order : {0u, 0x102u, 3u}) {
+          const vrdx::Sort64Plan p = vrdx::PlanSort64(context, keyValue, n, order, storage);
+          if (p.stepCount != (order == 3u || n == 0 ? 0u : keyValue ? 6u : 4u) || (p.refusal != nullptr) != (order == 3u)) ++failures;
+        }
+      }
   std::printf("sanitized host check: %d failures\n", failures);
   return failures != 0;
 }

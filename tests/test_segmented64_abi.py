@@ -115,7 +115,7 @@ int main() {
   for (uint32_t n : counts)
     for (int kv = 0; kv < 2; ++kv)
       for (uint64_t a = 0; a < 128; a += 16) {
-        const vrdx::Segmented64Layout s = vrdx::MakeSegmented64Layout(n, 16, kv != 0, a);
+        const vrdx::SegmentedLayout s = vrdx::MakeSegmented64Layout(n, 16, kv != 0, a);
         const vrdx::Sort64Layout w = vrdx::MakeSort64Layout(n, 16, a);
         const uint64_t size = kv ? w.keyValueSize : w.keysOnlySize;  // vrdxHipGetSorter64[KeyValue]StorageRequirements
         ++seen;

@@ -99,11 +99,12 @@ def test_segmented_storage_carving_fits_every_count(tmp_path):
         "  unsigned long bad = 0, seen = 0;\n"
         "  auto check = [&](uint32_t n) {\n"
         "    for (uint64_t a = 0; a < 128; a += 16) {\n"
-        "      const vrdx::SegmentedLayout s = vrdx::MakeSegmentedLayout(n, 16, a);\n"
+        "      const vrdx::SegmentedLayout s = vrdx::MakeSegmentedLayout(n, 16, false, a);\n"
+        "      const bool fitsKeyValue = vrdx::MakeSegmentedLayout(n, 16, true, a).fits;\n"
         "      ++seen;\n"
         "      const bool listsOk = s.midCap == n / 4097 && s.largeCap == n / 16385 && s.midListOffset >= 16 + 4096 &&\n"
         "                           s.keysScratchOffset >= s.largeListOffset + 4ull * s.largeCap && (a + s.keysScratchOffset) % 128 == 0;\n"
-        "      if (!s.fitsKeys || !s.fitsKeyValue || !listsOk) { if (bad++ < 5) std::printf(\"n=%u a=%u\\n\", n, (unsigned)a); }\n"
+        "      if (!s.fits || !fitsKeyValue || !listsOk) { if (bad++ < 5) std::printf(\"n=%u a=%u\\n\", n, (unsigned)a); }\n"
         "    }\n"
         "  };\n"
         "  for (uint32_t n = 1; n <= (1u << 21); ++n) check(n);\n"

@@ -431,6 +431,34 @@ hipError_t EnqueueStep(const VrdxSorter_T* sorter, const vrdx::PlanContext& cont
   return hipErrorInvalidValue;
 }
 
+// What every recorder starts with: the stream, the count clamped to VRDX_MAX_ELEMENTS, the sorter's device and slot 0.
+struct Recording {
+  hipStream_t stream;
+  uint32_t count;  // elementCount / maxElementCount, clamped
+  DeviceScope deviceScope;
+  StampCursor stamps;
+  Recording(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t requested, VkQueryPool queryPool, uint32_t query)
+      : stream(reinterpret_cast<hipStream_t>(commandBuffer)),
+        count(std::min<uint32_t>(requested, VRDX_MAX_ELEMENTS)),
+        deviceScope(sorter->device),
+        stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream) {
+    // The reference's uint32 byte math wraps above 2^30 - 4 elements (src/vk_radix_sort.h.in:105-115): no storage
+    // requirement exists for such a count.  The first 2^30 - 4 elements are sorted, the tail is left alone (segments ending
+    // behind the clamped bound are left alone and flagged on the device), and the sorter's status word says so
+    // (VRDX_HIP_STATUS_COUNT_CLAMPED) -- like every other failure mode, never silently.
+    if (requested > VRDX_MAX_ELEMENTS) sorter->countClamped.store(1u, std::memory_order_relaxed);
+  }
+  // A refused plan (refusal != nullptr) and an empty one have no step and touch nothing, but every slot of the timestamp
+  // contract is recorded whatever the plan (reference: zero partitions -> every dispatch is empty, :353,448,465,487): a
+  // caller that reads the pool afterwards must not wait on events that never were.  true: the recorder returns.
+  bool NothingToRecord(const VrdxSorter_T* sorter, const char* refusal, uint32_t stepCount) {
+    if (refusal == nullptr && stepCount != 0) return false;
+    stamps.Finish();
+    if (refusal != nullptr) EnqueueCheck(sorter, refusal, hipErrorInvalidValue);
+    return true;
+  }
+};
+
 // reference: gpuSort, src/vk_radix_sort.h.in:344-507
 // beginBit, endBit: the whole key for vrdxCmdSort*; vrdxHipCmdSortBits* hand their range on (include/vk_radix_sort.h) -- the
 // full range takes the whole-key plan (PlanSortBits forwards it), an empty one has no step, an invalid one and one beyond one
@@ -440,22 +468,13 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
                 VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                 VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
                 uint32_t query, uint32_t beginBit = 0, uint32_t endBit = 32) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
+  Recording r(commandBuffer, sorter, elementCount, queryPool, query);
   const bool keyValue = valuesBuffer != nullptr;
-  if (elementCount > VRDX_MAX_ELEMENTS) {
-    // The reference's uint32 byte math wraps above 2^30 - 4 elements (src/vk_radix_sort.h.in:105-115): no storage
-    // requirement exists for such a count.  The first 2^30 - 4 elements are sorted, the tail is left alone, and the
-    // sorter's status word says so (VRDX_HIP_STATUS_COUNT_CLAMPED) -- like every other failure mode, never silently.
-    elementCount = VRDX_MAX_ELEMENTS;
-    sorter->countClamped.store(1u, std::memory_order_relaxed);
-  }
-
-  DeviceScope deviceScope(sorter->device);
-
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
   const vrdx::PlanContext context = PlanContextOf(sorter);
   const SortPlan plan =
-      vrdx::PlanSortBits(context, keyValue, elementCount, beginBit, endBit, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+      vrdx::PlanSortBits(context, keyValue, r.count, beginBit, endBit, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (r.NothingToRecord(sorter, plan.refusal, plan.stepCount)) return;
   const SortBuffers b = ResolveBuffers(
       sorter, plan.layout, storage, reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset)),
       keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr,
@@ -465,238 +484,88 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
     msd = MsdArgsOf(sorter, plan, b);
     sorter->plansRecorded.fetch_add(1u, std::memory_order_relaxed);
   }
-
-  // Every slot of the timestamp contract is recorded whatever the plan -- also by the empty sort (reference: zero
-  // partitions -> every dispatch is empty, :353,448,465,487) and the refused one, neither of which has a step or touches
-  // the scratch arrays: a caller that reads the pool afterwards must not wait on events that never were.
-  StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
-  if (!plan.fits)
-    EnqueueCheck(sorter,
-                 beginBit > endBit || endBit > 32 ? "bit range (0 <= beginBit <= endBit <= 32)"
-                 : endBit - beginBit < 32        ? "bit range over more than 16384 elements (not built)"
-                                                 : "storage layout (status rows do not fit the reference's partition-histogram area)",
-                 hipErrorInvalidValue);
   for (uint32_t i = 0; i < plan.stepCount; ++i) {
-    EnqueueCheck(sorter, plan.steps[i].name, EnqueueStep(sorter, context, stream, plan, b, msd, plan.steps[i]));
-    stamps.AdvanceTo(plan.steps[i].slot);
+    EnqueueCheck(sorter, plan.steps[i].name, EnqueueStep(sorter, context, r.stream, plan, b, msd, plan.steps[i]));
+    r.stamps.AdvanceTo(plan.steps[i].slot);
   }
-  stamps.Finish();
-  if (plan.stepCount > 1) MaybeRecheckOrder(sorter, stream, plan.atomicRank);  // (the general path)
-}
-
-// The segmented sort (include/vk_radix_sort.h, vrdxHipCmdSortSegmented): a fill of the header and the two list counters, then
-// three launches whose work is decided on the device from the offsets -- the 256-thread in-LDS form over every segment (it
-// also lists the bigger ones), the 1024-thread in-LDS form over the mid list, one workgroup per large segment.
-// Grids depend on segmentCount, maxElementCount and the CU count only, so a captured call can be replayed on any segmentation
-// with the same segmentCount.
-// beginBit, endBit: the whole key for vrdxHipCmdSortSegmented*; vrdxHipCmdSortSegmentedBits* hand their range on.  The full
-// range records the whole-key kernels, an empty one nothing but the timestamps, an invalid one is refused; every other range
-// records the same fill and the range forms of the three launches, with the same grids.
-void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
-                         VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
-                         VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
-                         VkQueryPool queryPool, uint32_t query, uint32_t beginBit = 0, uint32_t endBit = 32) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
-  const bool keyValue = valuesBuffer != nullptr;
-  if (maxElementCount > VRDX_MAX_ELEMENTS) {
-    // as in RecordSort: no storage requirement exists beyond it; segments ending behind the clamped bound are left alone
-    // (and flagged on the device)
-    maxElementCount = VRDX_MAX_ELEMENTS;
-    sorter->countClamped.store(1u, std::memory_order_relaxed);
-  }
-  DeviceScope deviceScope(sorter->device);
-  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
-  StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
-  if (beginBit >= endBit || endBit > 32) {
-    stamps.Finish();
-    if (beginBit != endBit) EnqueueCheck(sorter, "bit range (0 <= beginBit <= endBit <= 32)", hipErrorInvalidValue);
-    return;  // (the empty range: nothing to order by)
-  }
-  const bool wholeKey = endBit - beginBit == 32;  // the range kernels take widths 1 ... 31
-  const uint32_t width = endBit - beginBit;
-  const vrdx::SegmentedLayout layout =
-      vrdx::MakeSegmentedLayout(maxElementCount, sorter->minStorageBufferOffsetAlignment, (uint64_t)reinterpret_cast<uintptr_t>(storage));
-  if (segmentCount == 0 || maxElementCount == 0 || !(keyValue ? layout.fitsKeyValue : layout.fitsKeys)) {
-    stamps.Finish();
-    if (segmentCount != 0 && maxElementCount != 0)  // (cannot happen for N >= 1: MakeSegmentedLayout fits every count)
-      EnqueueCheck(sorter, "segmented storage layout", hipErrorInvalidValue);
-    return;
-  }
-  const bool atomicRank = sorter->atomicRank.load(std::memory_order_relaxed);
-  vrdx::SegmentedArgs a;
-  a.keys = reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset));
-  a.values = keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
-  a.keysScratch = reinterpret_cast<uint32_t*>(storage + layout.keysScratchOffset);
-  a.valuesScratch = keyValue ? reinterpret_cast<uint32_t*>(storage + layout.valuesScratchOffset) : nullptr;
-  a.offsets = reinterpret_cast<const uint32_t*>(BufferAddress(offsetsBuffer, offsetsOffset));
-  a.segmentCount = segmentCount;
-  a.maxCount = maxElementCount;
-  a.midCount = reinterpret_cast<uint32_t*>(storage + layout.midCountOffset);
-  a.midList = reinterpret_cast<uint32_t*>(storage + layout.midListOffset);
-  a.midCap = layout.midCap;
-  a.largeCount = reinterpret_cast<uint32_t*>(storage + layout.largeCountOffset);
-  a.largeList = reinterpret_cast<uint32_t*>(storage + layout.largeListOffset);
-  a.largeCap = layout.largeCap;
-  a.failure = reinterpret_cast<uint32_t*>(storage + VRDX_OFF_FAILURE);
-  a.stickyFailure = sorter->stickyStatus;
-
-  // header (plan verdict = VRDX_HIP_VERDICT_NONE, failure word) and the two list counters, in front of the first launch: a
-  // one-wave kernel, not a memset (vrdx_kernels.hip, segmented_clear_kernel)
-  EnqueueCheck(sorter, "segmented_clear_kernel", vrdx::LaunchSegmentedClear(stream, a));
-  stamps.AdvanceTo(1);
-  // one workgroup per segment up to 2^20 of them (a grid-stride loop beyond); the other two launches take their lists by
-  // grid stride with at most as many workgroups as can be resident (the in-LDS form of 16384 keys and the large kernel
-  // hold one or two workgroups per CU)
-  const uint32_t cus = (uint32_t)sorter->computeUnits;
-  const auto launch = [&](vrdx::SegmentClass sizeClass, uint32_t grid) {
-    return wholeKey ? vrdx::LaunchSegmented(stream, sizeClass, grid, keyValue, atomicRank, a)
-                    : vrdx::LaunchSegmentedBits(stream, sizeClass, grid, keyValue, atomicRank, a, beginBit, width);
-  };
-  EnqueueCheck(sorter, wholeKey ? "segmented_small_kernel" : "segmented_small_bits_kernel",
-               launch(vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20)));
-  stamps.AdvanceTo(2);
-  // (a launch that is not recorded leaves its slot to coincide with the one before)
-  const uint32_t midGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.midCap), 2u * cus);
-  if (midGrid != 0) {
-    EnqueueCheck(sorter, wholeKey ? "segmented_mid_kernel" : "segmented_mid_bits_kernel", launch(vrdx::kSegmentMid, midGrid));
-    stamps.AdvanceTo(3);
-  }
-  const uint32_t largeGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.largeCap), 2u * cus);
-  if (largeGrid != 0) {
-    EnqueueCheck(sorter, wholeKey ? "segmented_large_kernel" : "segmented_large_bits_kernel",
-                 launch(vrdx::kSegmentLarge, largeGrid));
-    stamps.AdvanceTo(4);
-  }
-  stamps.Finish();
-  MaybeRecheckOrder(sorter, stream, atomicRank);
+  r.stamps.Finish();
+  if (plan.stepCount > 1) MaybeRecheckOrder(sorter, r.stream, plan.atomicRank);  // (the general path)
 }
 
 static_assert(VRDX_HIP_KEY_UINT64 == vrdx::kKeyOrderUint64 && VRDX_HIP_KEY_INT64 == vrdx::kKeyOrderInt64 &&
                   VRDX_HIP_KEY_FLOAT64 == vrdx::kKeyOrderFloat64 && VRDX_HIP_ORDER_DESCENDING == vrdx::kKeyOrderDescending,
               "the order word of the header is the kernels'");
-constexpr const char* kKeyOrderRefused = "key order (a key type 0 ... 2, VRDX_HIP_ORDER_DESCENDING or not)";
 
-// The segmented sort of 64-bit keys (include/vk_radix_sort.h, vrdxHipCmdSortSegmented64): RecordSegmentedSort with the 64-bit
-// kernels and the 64-bit storage (vrdx_layout.h, MakeSegmented64Layout) -- the same fill, the same three launches, the same
-// slots.  Grids depend on segmentCount, maxElementCount and the CU count only.
-// order: VRDX_HIP_KEY_UINT64 for vrdxHipCmdSortSegmented64*; vrdxHipCmdSortSegmented64Ordered* hand their order word on.
-// VRDX_HIP_KEY_UINT64 records the kernels it always did, an invalid word is refused before anything is enqueued, every other
-// order records the same fill and the ordered forms of the three launches, with the same grids.
-void RecordSegmentedSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
-                           VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
-                           VkBuffer valuesBuffer, VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
-                           VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
+// The segmented sorts (include/vk_radix_sort.h, vrdxHipCmdSortSegmented*), all eight entry points: the steps of
+// PlanSegmentedSort (vrdx_plan.h) -- a fill and up to three launches -- on the 32-bit storage (Args = SegmentedArgs, Key =
+// uint32_t; key: the whole key or the bit range of vrdxHipCmdSortSegmentedBits*) or on the 64-bit storage (Segmented64Args,
+// uint64_t; key: the order word, VRDX_HIP_KEY_UINT64 or that of vrdxHipCmdSortSegmented64Ordered*).
+template <typename Args, typename Key>
+void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
+                         VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
+                         VkBuffer valuesBuffer, VkDeviceSize valuesOffset, const vrdx::SegmentedKey& key, VkBuffer storageBuffer,
+                         VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  Recording r(commandBuffer, sorter, maxElementCount, queryPool, query);
   const bool keyValue = valuesBuffer != nullptr;
-  if (maxElementCount > VRDX_MAX_ELEMENTS) {
-    // as in RecordSegmentedSort: segments ending behind the clamped bound are left alone (and flagged on the device)
-    maxElementCount = VRDX_MAX_ELEMENTS;
-    sorter->countClamped.store(1u, std::memory_order_relaxed);
-  }
-  DeviceScope deviceScope(sorter->device);
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
-  StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
-  if (!vrdx::KeyOrderValid(order)) {
-    stamps.Finish();
-    EnqueueCheck(sorter, kKeyOrderRefused, hipErrorInvalidValue);
-    return;
-  }
-  const bool ordered = order != VRDX_HIP_KEY_UINT64;
-  const vrdx::Segmented64Layout layout = vrdx::MakeSegmented64Layout(
-      maxElementCount, sorter->minStorageBufferOffsetAlignment, keyValue, (uint64_t)reinterpret_cast<uintptr_t>(storage));
-  if (segmentCount == 0 || maxElementCount == 0 || !layout.fits) {
-    stamps.Finish();
-    if (segmentCount != 0 && maxElementCount != 0)  // (cannot happen for N >= 1: MakeSegmented64Layout fits every count)
-      EnqueueCheck(sorter, "segmented 64-bit storage layout", hipErrorInvalidValue);
-    return;
-  }
-  const bool atomicRank = sorter->atomicRank.load(std::memory_order_relaxed);
-  vrdx::Segmented64Args a;
-  a.keys = reinterpret_cast<uint64_t*>(BufferAddress(keysBuffer, keysOffset));
+  const vrdx::SegmentedPlan plan = vrdx::PlanSegmentedSort(PlanContextOf(sorter), sizeof(Key), keyValue, r.count, segmentCount, key,
+                                                           (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (r.NothingToRecord(sorter, plan.refusal, plan.stepCount)) return;
+  const auto words = [storage](uint64_t offset) { return reinterpret_cast<uint32_t*>(storage + offset); };
+  Args a;
+  a.keys = reinterpret_cast<Key*>(BufferAddress(keysBuffer, keysOffset));
   a.values = keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
-  a.keysScratch = reinterpret_cast<uint64_t*>(storage + layout.keysScratchOffset);
-  a.valuesScratch = keyValue ? reinterpret_cast<uint32_t*>(storage + layout.valuesScratchOffset) : nullptr;
+  a.keysScratch = reinterpret_cast<Key*>(storage + plan.layout.keysScratchOffset);
+  a.valuesScratch = keyValue ? words(plan.layout.valuesScratchOffset) : nullptr;
   a.offsets = reinterpret_cast<const uint32_t*>(BufferAddress(offsetsBuffer, offsetsOffset));
   a.segmentCount = segmentCount;
-  a.maxCount = maxElementCount;
-  a.midCount = reinterpret_cast<uint32_t*>(storage + layout.midCountOffset);
-  a.midList = reinterpret_cast<uint32_t*>(storage + layout.midListOffset);
-  a.midCap = layout.midCap;
-  a.largeCount = reinterpret_cast<uint32_t*>(storage + layout.largeCountOffset);
-  a.largeList = reinterpret_cast<uint32_t*>(storage + layout.largeListOffset);
-  a.largeCap = layout.largeCap;
-  a.failure = reinterpret_cast<uint32_t*>(storage + VRDX_OFF_FAILURE);
+  a.maxCount = r.count;
+  a.midCount = words(plan.layout.midCountOffset);
+  a.midList = words(plan.layout.midListOffset);
+  a.midCap = plan.layout.midCap;
+  a.largeCount = words(plan.layout.largeCountOffset);
+  a.largeList = words(plan.layout.largeListOffset);
+  a.largeCap = plan.layout.largeCap;
+  a.failure = words(VRDX_OFF_FAILURE);
   a.stickyFailure = sorter->stickyStatus;
-
-  EnqueueCheck(sorter, "segmented_clear_kernel", vrdx::LaunchSegmentedClear64(stream, a));
-  stamps.AdvanceTo(1);
-  const uint32_t cus = (uint32_t)sorter->computeUnits;
-  const auto launch = [&](vrdx::SegmentClass sizeClass, uint32_t grid) {
-    return ordered ? vrdx::LaunchSegmented64Ordered(stream, sizeClass, grid, keyValue, atomicRank, a, order)
-                   : vrdx::LaunchSegmented64(stream, sizeClass, grid, keyValue, atomicRank, a);
-  };
-  EnqueueCheck(sorter, ordered ? "segmented_small64_ordered_kernel" : "segmented_small64_kernel",
-               launch(vrdx::kSegmentSmall, std::min<uint32_t>(segmentCount, 1u << 20)));
-  stamps.AdvanceTo(2);
-  // the lists by grid stride, one workgroup per CU: the 1024-thread forms take 66 to 89 registers and 90 to 144 KiB of LDS,
-  // so one is resident per CU
-  const uint32_t midGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.midCap), cus);
-  if (midGrid != 0) {
-    EnqueueCheck(sorter, ordered ? "segmented_mid64_ordered_kernel" : "segmented_mid64_kernel",
-                 launch(vrdx::kSegmentMid, midGrid));
-    stamps.AdvanceTo(3);
+  for (uint32_t i = 0; i < plan.stepCount; ++i) {
+    const vrdx::SegmentedSortStep& step = plan.steps[i];
+    const vrdx::SegmentClass sizeClass = vrdx::SegmentClass((int)step.what - (int)vrdx::SegmentedStep::kSmall);
+    hipError_t e;
+    // header (plan verdict = VRDX_HIP_VERDICT_NONE, failure word) and the two list counters, in front of the first launch
+    if (step.what == vrdx::SegmentedStep::kClear)
+      e = vrdx::LaunchSegmentedClear(r.stream, a);
+    else if constexpr (sizeof(Key) == 8)
+      e = vrdx::LaunchSegmented64(r.stream, sizeClass, step.grid, keyValue, plan.atomicRank, a, plan.order);
+    else
+      e = vrdx::LaunchSegmented(r.stream, sizeClass, step.grid, keyValue, plan.atomicRank, a, plan.rangeBegin, plan.rangeWidth);
+    EnqueueCheck(sorter, step.name, e);
+    r.stamps.AdvanceTo(step.slot);
   }
-  const uint32_t largeGrid = std::min<uint32_t>(std::min<uint32_t>(segmentCount, layout.largeCap), cus);
-  if (largeGrid != 0) {
-    EnqueueCheck(sorter, ordered ? "segmented_large64_ordered_kernel" : "segmented_large64_kernel",
-                 launch(vrdx::kSegmentLarge, largeGrid));
-    stamps.AdvanceTo(4);
-  }
-  stamps.Finish();
-  MaybeRecheckOrder(sorter, stream, atomicRank);
+  r.stamps.Finish();
+  MaybeRecheckOrder(sorter, r.stream, plan.atomicRank);
 }
+constexpr auto RecordSegmentedSort32 = RecordSegmentedSort<vrdx::SegmentedArgs, uint32_t>;
+constexpr auto RecordSegmentedSort64 = RecordSegmentedSort<vrdx::Segmented64Args, uint64_t>;
 
-// The 64-bit sorts (include/vk_radix_sort.h, vrdxHipCmdSort64[KeyValue][Indirect]): two stable 32-bit key+value sorts, low words first
-// and high words second, each through RecordSort on word arrays inside the storage (vrdx_layout.h, MakeSort64Layout), with
-// the streaming kernels of vrdx_kernels.hip ("64-bit keys") around them:
-//   keys-only   split (A = lo, B = hi) | sort (A, B) | sort (B, A) | merge (keys = B << 32 | A)
-//   key+value   split (A = lo, I = iota) | sort (A, I) | gather (A = hi of keys[I]) | sort (A, I) |
-//               permute (T = A << 32 | lo of keys[I], A = values[I]) | copy back (keys = T, values = A)
-// The inner sorts are recorded without a query pool; each step of this list ends one slot.  Nothing is decided from the
-// data on the host, so a captured call can be replayed on other data of the same count.
+// The 64-bit sorts (include/vk_radix_sort.h, vrdxHipCmdSort64[Ordered][KeyValue][Indirect]): the steps of PlanSort64
+// (vrdx_plan.h).  The inner sorts go through RecordSort, without a query pool, on word arrays inside the storage.
 // Indirect (indirectBuffer != nullptr): elementCount is the bound; layout, plans and grids come from it alone, and every
 // step -- the streaming kernels and, through RecordSort, the inner sorts -- reads the count from the caller's word when it
 // runs, so a captured call can be replayed on any count up to the bound.
-// order: VRDX_HIP_KEY_UINT64 for vrdxHipCmdSort64*; vrdxHipCmdSort64Ordered* hand their order word on.  VRDX_HIP_KEY_UINT64
-// records the kernels it always did; an invalid word is refused before anything is enqueued; every other order records the
-// ordered forms of the split, the gather, the permutation and the merge -- A, B hold the words of T(key) (vrdx_kernels.h), so
-// the inner sorts and the copy back are the same calls.
+// order: VRDX_HIP_KEY_UINT64 for vrdxHipCmdSort64*; vrdxHipCmdSort64Ordered* hand their order word on.
 void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer indirectBuffer,
                   VkDeviceSize indirectOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
                   VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                   VkQueryPool queryPool, uint32_t query) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
+  Recording r(commandBuffer, sorter, elementCount, queryPool, query);
   const bool keyValue = valuesBuffer != nullptr;
-  if (elementCount > VRDX_MAX_ELEMENTS) {
-    // as in RecordSort: no storage requirement exists beyond it, the tail is left alone
-    elementCount = VRDX_MAX_ELEMENTS;
-    sorter->countClamped.store(1u, std::memory_order_relaxed);
-  }
-  DeviceScope deviceScope(sorter->device);
-  StampCursor stamps(reinterpret_cast<VrdxHipQueryPool*>(queryPool), query, stream);
-  if (!vrdx::KeyOrderValid(order)) {
-    stamps.Finish();
-    EnqueueCheck(sorter, kKeyOrderRefused, hipErrorInvalidValue);
-    return;
-  }
-  const bool ordered = order != VRDX_HIP_KEY_UINT64;
-  if (elementCount == 0) {
-    stamps.Finish();
-    return;
-  }
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
-  const vrdx::Sort64Layout layout = vrdx::MakeSort64Layout(elementCount, sorter->minStorageBufferOffsetAlignment,
-                                                           (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  const vrdx::Sort64Plan plan =
+      vrdx::PlanSort64(PlanContextOf(sorter), keyValue, r.count, order, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (r.NothingToRecord(sorter, plan.refusal, plan.stepCount)) return;
+  const vrdx::Sort64Layout& layout = plan.layout;
+  const uint32_t n = r.count;
   uint64_t* const keys = reinterpret_cast<uint64_t*>(BufferAddress(keysBuffer, keysOffset));
   uint32_t* const values = keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
   uint32_t* const lo = reinterpret_cast<uint32_t*>(storage + layout.loOffset);
@@ -705,40 +574,26 @@ void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t ele
   const uint32_t* const countPtr =
       indirectBuffer != nullptr ? reinterpret_cast<const uint32_t*>(BufferAddress(indirectBuffer, indirectOffset)) : nullptr;
   // an inner sort: the words at `sortKeys` with those at `payload` as their values, in the storage's front part
-  auto sortWords = [&](uint64_t sortKeys, uint64_t payload) {
-    RecordSort(commandBuffer, sorter, elementCount, indirectBuffer, indirectOffset, storageBuffer, storageOffset + sortKeys,
-               storageBuffer, storageOffset + payload, storageBuffer, storageOffset, nullptr, 0);
+  const auto sortWords = [&](uint64_t sortKeys, uint64_t payload) {
+    RecordSort(commandBuffer, sorter, n, indirectBuffer, indirectOffset, storageBuffer, storageOffset + sortKeys, storageBuffer,
+               storageOffset + payload, storageBuffer, storageOffset, nullptr, 0);
+    return hipSuccess;  // (the inner sort has reported its own enqueues)
   };
-
-  EnqueueCheck(sorter, ordered ? "split64_ordered_kernel" : "split64_kernel",
-               ordered ? vrdx::LaunchSplit64Ordered(stream, keyValue, keys, lo, other, elementCount, countPtr, order)
-                       : vrdx::LaunchSplit64(stream, keyValue, keys, lo, other, elementCount, countPtr));
-  stamps.AdvanceTo(1);
-  sortWords(layout.loOffset, layout.otherOffset);
-  stamps.AdvanceTo(2);
-  if (keyValue) {
-    EnqueueCheck(sorter, ordered ? "gather_hi64_ordered_kernel" : "gather_hi64_kernel",
-                 ordered ? vrdx::LaunchGatherHi64Ordered(stream, keys, other, lo, elementCount, countPtr, order)
-                         : vrdx::LaunchGatherHi64(stream, keys, other, lo, elementCount, countPtr));
-    stamps.AdvanceTo(3);
-    sortWords(layout.loOffset, layout.otherOffset);
-    stamps.AdvanceTo(4);
-    EnqueueCheck(sorter, ordered ? "permute64_ordered_kernel" : "permute64_kernel",
-                 ordered ? vrdx::LaunchPermute64Ordered(stream, keys, values, other, lo, keysTemp, elementCount, countPtr, order)
-                         : vrdx::LaunchPermute64(stream, keys, values, other, lo, keysTemp, elementCount, countPtr));
-    stamps.AdvanceTo(5);
-    EnqueueCheck(sorter, "copy_back64_kernel",
-                 vrdx::LaunchCopyBack64(stream, keys, values, keysTemp, lo, elementCount, countPtr));
-    stamps.AdvanceTo(6);
-  } else {
-    sortWords(layout.otherOffset, layout.loOffset);  // (slot 3 coincides with slot 2: no step between the sorts)
-    stamps.AdvanceTo(4);
-    EnqueueCheck(sorter, ordered ? "merge64_ordered_kernel" : "merge64_kernel",
-                 ordered ? vrdx::LaunchMerge64Ordered(stream, keys, lo, other, elementCount, countPtr, order)
-                         : vrdx::LaunchMerge64(stream, keys, lo, other, elementCount, countPtr));
-    stamps.AdvanceTo(5);
+  for (uint32_t i = 0; i < plan.stepCount; ++i) {
+    hipError_t e = hipErrorInvalidValue;
+    switch (plan.steps[i].what) {
+      case vrdx::Step64::kSplit: e = vrdx::LaunchSplit64(r.stream, keyValue, keys, lo, other, n, countPtr, order); break;
+      case vrdx::Step64::kSortLoOther: e = sortWords(layout.loOffset, layout.otherOffset); break;
+      case vrdx::Step64::kSortOtherLo: e = sortWords(layout.otherOffset, layout.loOffset); break;
+      case vrdx::Step64::kGatherHi: e = vrdx::LaunchGatherHi64(r.stream, keys, other, lo, n, countPtr, order); break;
+      case vrdx::Step64::kPermute: e = vrdx::LaunchPermute64(r.stream, keys, values, other, lo, keysTemp, n, countPtr, order); break;
+      case vrdx::Step64::kCopyBack: e = vrdx::LaunchCopyBack64(r.stream, keys, values, keysTemp, lo, n, countPtr); break;
+      case vrdx::Step64::kMerge: e = vrdx::LaunchMerge64(r.stream, keys, lo, other, n, countPtr, order); break;
+    }
+    EnqueueCheck(sorter, plan.steps[i].name, e);
+    r.stamps.AdvanceTo(plan.steps[i].slot);
   }
-  stamps.Finish();
+  r.stamps.Finish();
 }
 
 }  // namespace
@@ -883,8 +738,8 @@ void vrdxHipCmdSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, u
                              uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
                              VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
                              VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
-  RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
-                      nullptr, 0, storageBuffer, storageOffset, queryPool, query);
+  RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                        nullptr, 0, {}, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -892,16 +747,16 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
                                      VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
                                      VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                                      VkQueryPool queryPool, uint32_t query) {
-  RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
-                      valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
+  RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                        valuesBuffer, valuesOffset, {}, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortSegmentedBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
                                  uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
                                  VkBuffer keysBuffer, VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit,
                                  VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
-  RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
-                      nullptr, 0, storageBuffer, storageOffset, queryPool, query, beginBit, endBit);
+  RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                        nullptr, 0, {beginBit, endBit}, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortSegmentedBitsKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -909,8 +764,8 @@ void vrdxHipCmdSortSegmentedBitsKeyValue(VkCommandBuffer commandBuffer, VrdxSort
                                          VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
                                          VkDeviceSize valuesOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
                                          VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
-  RecordSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
-                      valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query, beginBit, endBit);
+  RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                        valuesBuffer, valuesOffset, {beginBit, endBit}, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortSegmented64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -918,7 +773,7 @@ void vrdxHipCmdSortSegmented64(VkCommandBuffer commandBuffer, VrdxSorter sorter,
                                VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
                                VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
-                        keysOffset, nullptr, 0, VRDX_HIP_KEY_UINT64, storageBuffer, storageOffset, queryPool, query);
+                        keysOffset, nullptr, 0, {}, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -927,8 +782,7 @@ void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter
                                        VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                                        VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
-                        keysOffset, valuesBuffer, valuesOffset, VRDX_HIP_KEY_UINT64, storageBuffer, storageOffset, queryPool,
-                        query);
+                        keysOffset, valuesBuffer, valuesOffset, {}, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortSegmented64Ordered(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -936,7 +790,7 @@ void vrdxHipCmdSortSegmented64Ordered(VkCommandBuffer commandBuffer, VrdxSorter 
                                       VkBuffer keysBuffer, VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer,
                                       VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
-                        keysOffset, nullptr, 0, order, storageBuffer, storageOffset, queryPool, query);
+                        keysOffset, nullptr, 0, {0, 32, order}, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortSegmented64OrderedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
@@ -945,7 +799,7 @@ void vrdxHipCmdSortSegmented64OrderedKeyValue(VkCommandBuffer commandBuffer, Vrd
                                               VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
                                               VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort64(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
-                        keysOffset, valuesBuffer, valuesOffset, order, storageBuffer, storageOffset, queryPool, query);
+                        keysOffset, valuesBuffer, valuesOffset, {0, 32, order}, storageBuffer, storageOffset, queryPool, query);
 }
 
 void vrdxHipCmdSortBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
@@ -1184,10 +1038,10 @@ void vrdxHipDescribeSortBitsPlan(VrdxSorter sorter, uint32_t elementCount, int k
                                  VrdxHipPlanInfo* info) {
   if (info == nullptr) return;
   std::memset(info, 0, sizeof(*info));
-  if (sorter == nullptr || elementCount == 0 || beginBit >= endBit || endBit > 32) return;
+  if (sorter == nullptr) return;
   if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
   const SortPlan plan = vrdx::PlanSortBits(PlanContextOf(sorter), keyValue != 0, elementCount, beginBit, endBit, 0);
-  if (plan.stepCount != 0) vrdx::DescribePlan(plan, info);  // (no step: a range sort beyond one workgroup, which is refused)
+  if (plan.stepCount != 0) vrdx::DescribePlan(plan, info);  // (no step: refused -- an invalid range, one beyond one workgroup -- or empty)
 }
 
 uint32_t vrdxHipReadPlanVerdict(VkCommandBuffer commandBuffer, VkBuffer storageBuffer, VkDeviceSize storageOffset) {

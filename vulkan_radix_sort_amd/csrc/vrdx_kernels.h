@@ -253,16 +253,27 @@ struct SegmentedArgs {
 // The fill in front of the first launch (one wave): header words 0-3 (failure = word 3) and both list counters.
 hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args);
 enum SegmentClass { kSegmentSmall = 0, kSegmentMid = 1, kSegmentLarge = 2 };  // segmented_small / mid / large_kernel
+// width == 0: the whole key.  Otherwise the segmented sort by a bit range (vrdxHipCmdSortSegmentedBits[KeyValue]):
+// segmented_small_bits / mid_bits / large_bits_kernel, the range forms of the three kernels.  Every segment is ordered by f(key) =
+// the `width` bits of the key from bit beginBit, 1 <= width <= 31 (the range of all 32 bits IS the whole-key segmented sort);
+// keys move whole.  The in-LDS kernels rank ceil(width / 8) digits (SortInWorkgroup's RANGE form); the large kernel counts those
+// digits of the field in its one histogram read and walks the segment once per digit that varies.  The range travels as two
+// kernel arguments behind SegmentedArgs, which does not change.
 hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
-                           const SegmentedArgs& args);
-// The segmented sort by a bit range (vrdxHipCmdSortSegmentedBits[KeyValue]): segmented_small_bits / mid_bits / large_bits_kernel,
-// the range forms of the three launches above.  Every segment is ordered by f(key) = the `width` bits of the key from bit
-// beginBit, 1 <= width <= 31 (the range of all 32 bits IS the whole-key segmented sort); keys move whole.  The in-LDS kernels
-// rank ceil(width / 8) digits (SortInWorkgroup's RANGE form); the large kernel counts those digits of the field in its one
-// histogram read and walks the segment once per digit that varies.  The range travels as two kernel arguments behind
-// SegmentedArgs, which does not change.
-hipError_t LaunchSegmentedBits(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
-                               const SegmentedArgs& args, uint32_t beginBit, uint32_t width);
+                           const SegmentedArgs& args, uint32_t beginBit, uint32_t width);
+
+// ---- key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered*, vrdxHipCmdSortSegmented64Ordered*; vrdx_kernels.hip, "key
+// orders of the 64-bit sorts") ----
+// The order word of include/vk_radix_sort.h: a key type, VRDX_HIP_ORDER_DESCENDING or-ed in or not.  The kernels sort
+// T(key) ascending as unsigned 64-bit, T(k) = k ^ flip ^ (float64 and bit 63 of k set ? 0x7FFFFFFFFFFFFFFF : 0) with flip = 0
+// (uint64) or 1 << 63 (int64, float64), complemented for descending; T is a bijection, so equal keys and only they have equal
+// T, and they keep their input order in both directions.
+constexpr uint32_t kKeyOrderUint64 = 0, kKeyOrderInt64 = 1, kKeyOrderFloat64 = 2;
+constexpr uint32_t kKeyOrderTypeMask = 0xFFu;
+constexpr uint32_t kKeyOrderDescending = 0x100u;
+constexpr bool KeyOrderValid(uint32_t order) {
+  return (order & ~(kKeyOrderTypeMask | kKeyOrderDescending)) == 0 && (order & kKeyOrderTypeMask) <= kKeyOrderFloat64;
+}
 
 // ---- 64-bit keys (vrdxHipCmdSort64[KeyValue][Indirect]): the steps around the two 32-bit sorts (vrdx_kernels.hip, "64-bit
 // keys") ----
@@ -270,18 +281,22 @@ hipError_t LaunchSegmentedBits(hipStream_t stream, SegmentClass sizeClass, uint3
 // min(*countPtr, maxCount) elements (countPtr == nullptr: on maxCount).  keys: the caller's, 8-byte aligned; values: the
 // caller's, 4-byte aligned; every other array lies inside the storage on a 16-byte boundary (MakeSort64Layout).
 constexpr uint32_t kSort64Threads = 256;
-// lo[i] = low word of keys[i]; other[i] = its high word, or i (iota)
+// order: the order word above; kKeyOrderUint64 starts the kernels without one (split64_kernel ...), every other valid word the
+// ordered forms (split64_ordered_kernel ...) with the word behind the same arguments; an invalid word is refused with
+// hipErrorInvalidValue.  T = the identity for kKeyOrderUint64.
+// lo[i] = low word of T(keys[i]); other[i] = its high word, or i (iota)
 hipError_t LaunchSplit64(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other, uint32_t maxCount,
-                         const uint32_t* countPtr);
-// keys[i] = hi[i] << 32 | lo[i]
+                         const uint32_t* countPtr, uint32_t order);
+// keys[i] = the inverse of T on hi[i] << 32 | lo[i]
 hipError_t LaunchMerge64(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
-                         const uint32_t* countPtr);
-// hi[j] = high word of keys[index[j]]
+                         const uint32_t* countPtr, uint32_t order);
+// hi[j] = high word of T(keys[index[j]]) (read: the high word of the key alone)
 hipError_t LaunchGatherHi64(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi, uint32_t maxCount,
-                            const uint32_t* countPtr);
-// keysOut[j] = hiThenValues[j] << 32 | low word of keys[index[j]]; then hiThenValues[j] = values[index[j]]
+                            const uint32_t* countPtr, uint32_t order);
+// keysOut[j] = (the key's high word, from T's high word hiThenValues[j]) << 32 | low word of keys[index[j]]; then
+// hiThenValues[j] = values[index[j]]
 hipError_t LaunchPermute64(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
-                           uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr);
+                           uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr, uint32_t order);
 // keys[i] = keysIn[i]; values[i] = valuesIn[i]
 hipError_t LaunchCopyBack64(hipStream_t stream, uint64_t* keys, uint32_t* values, const uint64_t* keysIn,
                             const uint32_t* valuesIn, uint32_t maxCount, const uint32_t* countPtr);
@@ -316,41 +331,11 @@ struct Segmented64Args {
   uint32_t* stickyFailure;      // the sorter's word
 };
 // The fill in front of the first launch is segmented_clear_kernel as it is: the same header words and list counters.
-hipError_t LaunchSegmentedClear64(hipStream_t stream, const Segmented64Args& args);
+hipError_t LaunchSegmentedClear(hipStream_t stream, const Segmented64Args& args);
+// order as above: kKeyOrderUint64 starts segmented_small64 / mid64 / large64_kernel, every other valid word their ordered forms
+// (every segment in ascending order of T(key))
 hipError_t LaunchSegmented64(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
-                             const Segmented64Args& args);
-
-// ---- key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered*, vrdxHipCmdSortSegmented64Ordered*; vrdx_kernels.hip, "key
-// orders of the 64-bit sorts") ----
-// The order word of include/vk_radix_sort.h: a key type, VRDX_HIP_ORDER_DESCENDING or-ed in or not.  The kernels sort
-// T(key) ascending as unsigned 64-bit, T(k) = k ^ flip ^ (float64 and bit 63 of k set ? 0x7FFFFFFFFFFFFFFF : 0) with flip = 0
-// (uint64) or 1 << 63 (int64, float64), complemented for descending; T is a bijection, so equal keys and only they have equal
-// T, and they keep their input order in both directions.
-constexpr uint32_t kKeyOrderUint64 = 0, kKeyOrderInt64 = 1, kKeyOrderFloat64 = 2;
-constexpr uint32_t kKeyOrderTypeMask = 0xFFu;
-constexpr uint32_t kKeyOrderDescending = 0x100u;
-constexpr bool KeyOrderValid(uint32_t order) {
-  return (order & ~(kKeyOrderTypeMask | kKeyOrderDescending)) == 0 && (order & kKeyOrderTypeMask) <= kKeyOrderFloat64;
-}
-// The ordered forms of the launches above: the same arguments with the order word behind them.  order == kKeyOrderUint64 is
-// the recorder's business (it records the launches above); these refuse an invalid word with hipErrorInvalidValue.
-// lo[i] = low word of T(keys[i]); other[i] = its high word, or i (iota)
-hipError_t LaunchSplit64Ordered(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other,
-                                uint32_t maxCount, const uint32_t* countPtr, uint32_t order);
-// keys[i] = the inverse of T on hi[i] << 32 | lo[i]
-hipError_t LaunchMerge64Ordered(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
-                                const uint32_t* countPtr, uint32_t order);
-// hi[j] = high word of T(keys[index[j]]) (read: the high word of the key alone)
-hipError_t LaunchGatherHi64Ordered(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi,
-                                   uint32_t maxCount, const uint32_t* countPtr, uint32_t order);
-// keysOut[j] = (the key's high word, from T's high word hiThenValues[j]) << 32 | low word of keys[index[j]]; then
-// hiThenValues[j] = values[index[j]]
-hipError_t LaunchPermute64Ordered(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
-                                  uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr,
-                                  uint32_t order);
-// segmented_small64 / mid64 / large64_ordered_kernel: every segment in ascending order of T(key)
-hipError_t LaunchSegmented64Ordered(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
-                                    const Segmented64Args& args, uint32_t order);
+                             const Segmented64Args& args, uint32_t order);
 
 // ---- the kernels' dynamic LDS and the MSD plan's grids: one definition for the kernels (vrdx_kernels.hip) and for both
 // launch backends (vrdx_launch.inc) ----

@@ -461,22 +461,17 @@ hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedArgs& args) {
   return Launch(kSegmentedClear, 1, stream, args);
 }
 
+// width == 0: the whole key.  The range forms: the range travels behind SegmentedArgs, widths 1 ... 31 only (v_bfe_u32 takes a
+// width modulo 32; the planner forwards the one range of 32 bits to the whole-key kernels).
 hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
-                           const SegmentedArgs& args) {
-  if (grid == 0) return hipErrorInvalidValue;
-  return Launch(KernelId(kSegmentedSmall - 3 * (2 * keyValue + atomicRank) + sizeClass), grid, stream, args);
-}
-
-// The range forms: the range travels behind SegmentedArgs.  Widths 1 ... 31 only (v_bfe_u32 takes a width modulo 32; the
-// recorder forwards the one range of 32 bits to the whole-key kernels).
-hipError_t LaunchSegmentedBits(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
-                               const SegmentedArgs& args, uint32_t beginBit, uint32_t width) {
-  if (grid == 0 || width < 1u || width > 31u || beginBit + width > 32u) return hipErrorInvalidValue;
+                           const SegmentedArgs& args, uint32_t beginBit, uint32_t width) {
+  if (grid == 0 || width > 31u || beginBit + width > 32u) return hipErrorInvalidValue;
+  if (width == 0) return Launch(KernelId(kSegmentedSmall - 3 * (2 * keyValue + atomicRank) + sizeClass), grid, stream, args);
   return Launch(Form(KernelId(kSegmentedBitsSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args, beginBit, width);
 }
 
 // ---- segmented sort of 64-bit keys ------------------------------------------------------------------
-hipError_t LaunchSegmentedClear64(hipStream_t stream, const Segmented64Args& args) {
+hipError_t LaunchSegmentedClear(hipStream_t stream, const Segmented64Args& args) {
   // segmented_clear_kernel reads the failure word and the two counters only
   SegmentedArgs clear = {};
   clear.midCount = args.midCount;
@@ -486,79 +481,55 @@ hipError_t LaunchSegmentedClear64(hipStream_t stream, const Segmented64Args& arg
 }
 
 hipError_t LaunchSegmented64(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
-                             const Segmented64Args& args) {
-  if (grid == 0) return hipErrorInvalidValue;
-  return Launch(Form(KernelId(kSegmented64Small + 4 * sizeClass), keyValue, atomicRank), grid, stream, args);
+                             const Segmented64Args& args, uint32_t order) {
+  if (grid == 0 || !KeyOrderValid(order)) return hipErrorInvalidValue;
+  if (order == kKeyOrderUint64)
+    return Launch(Form(KernelId(kSegmented64Small + 4 * sizeClass), keyValue, atomicRank), grid, stream, args);
+  return Launch(Form(KernelId(kSegmented64OrderedSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args, order);
 }
 
 // ---- 64-bit keys ------------------------------------------------------------------------------------
 // one thread per four elements of the bound (the kernels take the count from countPtr where there is one); an empty launch
-// is the recorder's business (it records none)
+// is the planner's business (it lists none).  order == kKeyOrderUint64: the kernels without an order word.
 static uint32_t Sort64Grid(uint32_t maxCount) { return (maxCount + 4u * kSort64Threads - 1u) / (4u * kSort64Threads); }
-static bool Sort64CountFits(uint32_t maxCount) { return maxCount != 0 && maxCount <= VRDX_MAX_ELEMENTS; }
+static bool Sort64Fits(uint32_t maxCount, uint32_t order = kKeyOrderUint64) {
+  return maxCount != 0 && maxCount <= VRDX_MAX_ELEMENTS && KeyOrderValid(order);
+}
 
 hipError_t LaunchSplit64(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other, uint32_t maxCount,
-                         const uint32_t* countPtr) {
-  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
-  return Launch(iota ? kSplit64Iota : kSplit64, Sort64Grid(maxCount), stream, keys, lo, other, maxCount, countPtr);
+                         const uint32_t* countPtr, uint32_t order) {
+  if (!Sort64Fits(maxCount, order)) return hipErrorInvalidValue;
+  const uint32_t grid = Sort64Grid(maxCount);
+  if (order == kKeyOrderUint64) return Launch(iota ? kSplit64Iota : kSplit64, grid, stream, keys, lo, other, maxCount, countPtr);
+  return Launch(iota ? kSplit64OrderedIota : kSplit64Ordered, grid, stream, keys, lo, other, maxCount, countPtr, order);
 }
 
 hipError_t LaunchMerge64(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
-                         const uint32_t* countPtr) {
-  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
-  return Launch(kMerge64, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr);
+                         const uint32_t* countPtr, uint32_t order) {
+  if (!Sort64Fits(maxCount, order)) return hipErrorInvalidValue;
+  if (order == kKeyOrderUint64) return Launch(kMerge64, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr);
+  return Launch(kMerge64Ordered, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr, order);
 }
 
 hipError_t LaunchGatherHi64(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi, uint32_t maxCount,
-                            const uint32_t* countPtr) {
-  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
-  return Launch(kGatherHi64, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr);
+                            const uint32_t* countPtr, uint32_t order) {
+  if (!Sort64Fits(maxCount, order)) return hipErrorInvalidValue;
+  if (order == kKeyOrderUint64) return Launch(kGatherHi64, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr);
+  return Launch(kGatherHi64Ordered, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr, order);
 }
 
 hipError_t LaunchPermute64(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
-                           uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr) {
-  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
-  return Launch(kPermute64, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues, keysOut, maxCount, countPtr);
+                           uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr, uint32_t order) {
+  if (!Sort64Fits(maxCount, order)) return hipErrorInvalidValue;
+  if (order == kKeyOrderUint64)
+    return Launch(kPermute64, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues, keysOut, maxCount, countPtr);
+  return Launch(kPermute64Ordered, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues, keysOut, maxCount, countPtr, order);
 }
 
 hipError_t LaunchCopyBack64(hipStream_t stream, uint64_t* keys, uint32_t* values, const uint64_t* keysIn,
                             const uint32_t* valuesIn, uint32_t maxCount, const uint32_t* countPtr) {
-  if (!Sort64CountFits(maxCount)) return hipErrorInvalidValue;
+  if (!Sort64Fits(maxCount)) return hipErrorInvalidValue;
   return Launch(kCopyBack64, Sort64Grid(maxCount), stream, keys, values, keysIn, valuesIn, maxCount, countPtr);
-}
-
-// ---- key orders of the 64-bit sorts ------------------------------------------------------------------
-hipError_t LaunchSplit64Ordered(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other,
-                                uint32_t maxCount, const uint32_t* countPtr, uint32_t order) {
-  if (!Sort64CountFits(maxCount) || !KeyOrderValid(order)) return hipErrorInvalidValue;
-  return Launch(iota ? kSplit64OrderedIota : kSplit64Ordered, Sort64Grid(maxCount), stream, keys, lo, other, maxCount, countPtr,
-                order);
-}
-
-hipError_t LaunchMerge64Ordered(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
-                                const uint32_t* countPtr, uint32_t order) {
-  if (!Sort64CountFits(maxCount) || !KeyOrderValid(order)) return hipErrorInvalidValue;
-  return Launch(kMerge64Ordered, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr, order);
-}
-
-hipError_t LaunchGatherHi64Ordered(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi,
-                                   uint32_t maxCount, const uint32_t* countPtr, uint32_t order) {
-  if (!Sort64CountFits(maxCount) || !KeyOrderValid(order)) return hipErrorInvalidValue;
-  return Launch(kGatherHi64Ordered, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr, order);
-}
-
-hipError_t LaunchPermute64Ordered(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
-                                  uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr,
-                                  uint32_t order) {
-  if (!Sort64CountFits(maxCount) || !KeyOrderValid(order)) return hipErrorInvalidValue;
-  return Launch(kPermute64Ordered, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues, keysOut, maxCount, countPtr,
-                order);
-}
-
-hipError_t LaunchSegmented64Ordered(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
-                                    const Segmented64Args& args, uint32_t order) {
-  if (grid == 0 || !KeyOrderValid(order)) return hipErrorInvalidValue;
-  return Launch(Form(KernelId(kSegmented64OrderedSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args, order);
 }
 
 // ---- the LDS order check and the calibration spin -----------------------------------------------------

@@ -176,29 +176,33 @@ static inline bool LayoutFits(const StorageLayout& l, uint32_t maxElementCount) 
 //                                  segments are disjoint) -- in the reference's partition-histogram area (>= N / 16 words)
 //   keysScratch (128-byte aligned) uint[N] behind the lists, valuesScratch uint[N] behind it: a large segment's passes use
 //                                  the same index range as its elements
-struct SegmentedLayout {
+struct SegmentedLayout {  // of both key widths: MakeSegmentedLayout, MakeSegmented64Layout
   uint64_t midCountOffset, largeCountOffset;
   uint64_t midListOffset, largeListOffset;
   uint32_t midCap, largeCap;
   uint64_t keysScratchOffset, valuesScratchOffset;
-  bool fitsKeys, fitsKeyValue;  // every region lies inside the keys-only / key+value storage requirement
+  bool fits;  // every region lies inside the storage requirement of the requested form (keys-only | key+value)
 };
 
-static inline SegmentedLayout MakeSegmentedLayout(uint32_t maxElementCount, uint32_t align, uint64_t storageAddress = 0) {
-  const StorageLayout l = MakeLayout(maxElementCount, align, 0, storageAddress);
-  SegmentedLayout s;
+// counters and lists, the same for both key widths; largeMin: the smallest large segment; returns the end of the lists
+static inline uint64_t PlaceSegmentLists(SegmentedLayout& s, const StorageLayout& l, uint32_t maxElementCount, uint32_t largeMin) {
   s.midCountOffset = l.histogramOffset;
   s.largeCountOffset = l.histogramOffset + 256;
   s.midCap = maxElementCount / (256u * 16u + 1u);
-  s.largeCap = maxElementCount / (1024u * 16u + 1u);
+  s.largeCap = maxElementCount / largeMin;
   s.midListOffset = l.msdBucketOffset;
   s.largeListOffset = s.midListOffset + 4ull * s.midCap;
-  const uint64_t listsEnd = s.largeListOffset + 4ull * s.largeCap;
+  return s.largeListOffset + 4ull * s.largeCap;
+}
+
+static inline SegmentedLayout MakeSegmentedLayout(uint32_t maxElementCount, uint32_t align, bool keyValue, uint64_t storageAddress = 0) {
+  const StorageLayout l = MakeLayout(maxElementCount, align, 0, storageAddress);
+  SegmentedLayout s;
+  const uint64_t listsEnd = PlaceSegmentLists(s, l, maxElementCount, 1024u * 16u + 1u);
   s.keysScratchOffset = listsEnd + ((0 - (storageAddress + listsEnd)) & 127u);
   s.valuesScratchOffset = s.keysScratchOffset + (((uint64_t)maxElementCount * sizeof(uint32_t) + 127u) & ~(uint64_t)127u);
   const uint64_t bytes = (uint64_t)maxElementCount * sizeof(uint32_t);
-  s.fitsKeys = s.keysScratchOffset + bytes <= l.keysOnlySize;
-  s.fitsKeyValue = s.fitsKeys && s.valuesScratchOffset + bytes <= l.keyValueSize;
+  s.fits = s.keysScratchOffset + bytes <= l.keysOnlySize && (!keyValue || s.valuesScratchOffset + bytes <= l.keyValueSize);
   return s;
 }
 
@@ -232,35 +236,21 @@ static inline Sort64Layout MakeSort64Layout(uint32_t maxElementCount, uint32_t a
   return s;
 }
 
-// The segmented 64-bit sorts' carving of the 64-bit storage (vrdxHipCmdSortSegmented64[KeyValue]; RecordSegmentedSort64 in
-// vrdx_api.cpp): header, list counters and lists where MakeSegmentedLayout keeps them -- inside the inner 32-bit storage --
+// The segmented 64-bit sorts' carving of the 64-bit storage (vrdxHipCmdSortSegmented64[KeyValue]; PlanSegmentedSort in
+// vrdx_plan.h): header, list counters and lists where MakeSegmentedLayout keeps them -- inside the inner 32-bit storage --
 // and the scratch arrays where MakeSort64Layout keeps its word arrays, behind it:
 //   [0, 16)                        header words 0-3
-//   midCountOffset, largeCountOffset, midListOffset, largeListOffset   as in SegmentedLayout; the large list holds
+//   midCountOffset, largeCountOffset, midListOffset, largeListOffset   as in MakeSegmentedLayout; the large list holds
 //                                  N / (midMax + 1) ids: a large segment has more than midMax elements (vrdx_kernels.h:
 //                                  16384 keys-only, 8192 key+value)
 //   keysScratchOffset = loOffset   uint64[N] on a 128-byte line: A and B of the 64-bit sorts, 2 x Align(4 N, 128) bytes
 //   valuesScratchOffset = keysTempOffset   key+value only: uint32[N] in the front half of T
-struct Segmented64Layout {
-  uint64_t midCountOffset, largeCountOffset;
-  uint64_t midListOffset, largeListOffset;
-  uint32_t midCap, largeCap;
-  uint64_t keysScratchOffset, valuesScratchOffset;
-  bool fits;  // every region lies inside the requirement of its form, the lists in front of the scratch arrays
-};
-
-static inline Segmented64Layout MakeSegmented64Layout(uint32_t maxElementCount, uint32_t align, bool keyValue,
-                                                      uint64_t storageAddress = 0) {
+static inline SegmentedLayout MakeSegmented64Layout(uint32_t maxElementCount, uint32_t align, bool keyValue,
+                                                    uint64_t storageAddress = 0) {
   const StorageLayout l = MakeLayout(maxElementCount, align, 0, storageAddress);
   const Sort64Layout w = MakeSort64Layout(maxElementCount, align, storageAddress);
-  Segmented64Layout s;
-  s.midCountOffset = l.histogramOffset;
-  s.largeCountOffset = l.histogramOffset + 256;
-  s.midCap = maxElementCount / (256u * 16u + 1u);
-  s.largeCap = maxElementCount / (keyValue ? 1024u * 8u + 1u : 1024u * 16u + 1u);
-  s.midListOffset = l.msdBucketOffset;
-  s.largeListOffset = s.midListOffset + 4ull * s.midCap;
-  const uint64_t listsEnd = s.largeListOffset + 4ull * s.largeCap;
+  SegmentedLayout s;
+  const uint64_t listsEnd = PlaceSegmentLists(s, l, maxElementCount, keyValue ? 1024u * 8u + 1u : 1024u * 16u + 1u);
   s.keysScratchOffset = w.loOffset;
   s.valuesScratchOffset = w.keysTempOffset;
   const uint64_t keysEnd = s.keysScratchOffset + (uint64_t)maxElementCount * sizeof(uint64_t);

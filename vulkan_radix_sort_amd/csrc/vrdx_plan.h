@@ -2,8 +2,8 @@
 // (CU count, ranking mode, storage alignment, the planning knobs): the plan (one workgroup, eight-bit hybrid, MSD by 10 or
 // 11 bits, four passes), the bucket capacity, the tile geometry and tile plan, block sums, the storage layout, the step
 // list with its timestamp slots, the histogram grid and the fallback taken when a layout does not fit.  No HIP call, no
-// environment, no static state: the recorder (vrdx_api.cpp) builds one PlanContext per recorded sort and calls PlanSort;
-// tests/native/plan_check.cpp and layout_check.cpp call the same functions at every size on a CPU.
+// environment, no static state: the recorder (vrdx_api.cpp) builds one PlanContext per recorded sort and calls PlanSort[Bits],
+// PlanSegmentedSort or PlanSort64; tests/native/plan_check.cpp and layout_check.cpp call the same functions on a CPU.
 #ifndef VRDX_PLAN_H
 #define VRDX_PLAN_H
 
@@ -206,6 +206,7 @@ struct SortPlan {
   TilePlan tilePlan{};
   bool blockSums = false;
   bool fits = true;             // false: not even tiles of full capacity fit the caller's storage (refused)
+  const char* refusal = nullptr;  // fits == false: why, as EnqueueCheck reports it
   StorageLayout layout{};
   SortStep steps[kMaxSortSteps];  // none: the empty sort and the refused one
   uint32_t stepCount = 0;
@@ -296,6 +297,7 @@ static inline SortPlan PlanSort(const PlanContext& c, bool keyValue, uint32_t el
     p.msdBits = 0;
     p.layout = MakeLayout(elementCount, align, p.tilePlan.tiles, storageAddress, false, 0);
     p.fits = LayoutFits(p.layout, elementCount);
+    if (!p.fits) p.refusal = "storage layout (status rows do not fit the reference's partition-histogram area)";
   }
   if (p.fits) ListSteps(p);
   return p;
@@ -307,6 +309,7 @@ static inline SortPlan PlanSort(const PlanContext& c, bool keyValue, uint32_t el
 // fits == false, and the recorder refuses the call like a layout that does not fit.
 // The range of all 32 bits is PlanSort itself; an empty range has no step, like an empty sort; an invalid one (beginBit >
 // endBit, endBit > 32) has none either and is refused.
+constexpr const char* kBitRangeRefused = "bit range (0 <= beginBit <= endBit <= 32)";
 static inline SortPlan PlanSortBits(const PlanContext& c, bool keyValue, uint32_t elementCount, uint32_t beginBit, uint32_t endBit,
                                     uint64_t storageAddress) {
   if (beginBit == 0 && endBit == 32) return PlanSort(c, keyValue, elementCount, storageAddress);
@@ -315,10 +318,12 @@ static inline SortPlan PlanSortBits(const PlanContext& c, bool keyValue, uint32_
   p.elementCount = elementCount;
   p.atomicRank = c.atomicRank;
   p.fits = beginBit <= endBit && endBit <= 32;
+  if (!p.fits) p.refusal = kBitRangeRefused;
   if (!p.fits || beginBit == endBit || elementCount == 0) return p;
   const SortPlan whole = PlanSort(c, keyValue, elementCount, storageAddress);
   if (!whole.oneWorkgroup) {
     p.fits = false;  // beyond one workgroup: not built
+    p.refusal = "bit range over more than 16384 elements (not built)";
     return p;
   }
   p = whole;
@@ -326,6 +331,124 @@ static inline SortPlan PlanSortBits(const PlanContext& c, bool keyValue, uint32_
   p.rangeWidth = endBit - beginBit;  // 1 ... 31: the kernel extracts with v_bfe_u32, which takes a width modulo 32
   p.stepCount = p.launches = 0;
   ListSteps(p);
+  return p;
+}
+
+// ---- the segmented sorts (vrdxHipCmdSortSegmented*; include/vk_radix_sort.h) ----
+// How a segmented sort orders its keys.  4-byte keys: by the bits [beginBit, endBit) -- the full range is the whole key, an
+// empty one orders by nothing (no step), an invalid one is refused.  8-byte keys: by the order word (vrdx_kernels.h,
+// kKeyOrder*; kKeyOrderUint64 is the whole key as it stands, an invalid word is refused); the range is not looked at.
+struct SegmentedKey {
+  uint32_t beginBit = 0, endBit = 32;
+  uint32_t order = kKeyOrderUint64;
+};
+constexpr const char* kKeyOrderRefused = "key order (a key type 0 ... 2, VRDX_HIP_ORDER_DESCENDING or not)";
+
+// The steps of a segmented sort: a fill of the header and the two list counters (a one-wave kernel, not a memset), then three
+// launches whose work is decided on the device from the offsets -- the 256-thread in-LDS form over every segment (it also
+// lists the bigger ones), the 1024-thread in-LDS form over the mid list, one workgroup per large segment.  A launch whose
+// grid would be 0 is absent (no segment can be that large under this bound); its slot coincides with the one before.
+enum class SegmentedStep : uint8_t { kClear, kSmall, kMid, kLarge };  // slots 1 ... 4; kSmall + c = SegmentClass c
+struct SegmentedSortStep { SegmentedStep what; uint8_t slot; const char* name; uint32_t grid; };
+
+// Everything the host decides about a segmented sort.  Grids depend on segmentCount, maxElementCount and the CU count only,
+// so a captured call can be replayed on any segmentation with the same segmentCount.
+struct SegmentedPlan {
+  bool keyValue = false;
+  bool atomicRank = false;
+  const char* refusal = nullptr;           // non-null: refused (no step), and why
+  uint32_t rangeBegin = 0, rangeWidth = 0;  // 4-byte keys by a bit range: width 1 ... 31; 0: the whole key
+  uint32_t order = kKeyOrderUint64;        // 8-byte keys
+  SegmentedLayout layout{};
+  SegmentedSortStep steps[4];              // none: refused, or empty (no elements, no segments, an empty range)
+  uint32_t stepCount = 0;
+};
+
+static inline SegmentedPlan PlanSegmentedSort(const PlanContext& c, uint32_t keyBytes, bool keyValue, uint32_t maxElementCount,
+                                              uint32_t segmentCount, const SegmentedKey& key, uint64_t storageAddress) {
+  static constexpr const char* kNames[4][4] = {
+      {"segmented_clear_kernel", "segmented_small_kernel", "segmented_mid_kernel", "segmented_large_kernel"},
+      {"segmented_clear_kernel", "segmented_small_bits_kernel", "segmented_mid_bits_kernel", "segmented_large_bits_kernel"},
+      {"segmented_clear_kernel", "segmented_small64_kernel", "segmented_mid64_kernel", "segmented_large64_kernel"},
+      {"segmented_clear_kernel", "segmented_small64_ordered_kernel", "segmented_mid64_ordered_kernel", "segmented_large64_ordered_kernel"}};
+  const bool wide = keyBytes == 8;
+  SegmentedPlan p;
+  p.keyValue = keyValue;
+  p.atomicRank = c.atomicRank;  // one answer for the whole sort
+  if (wide ? !KeyOrderValid(key.order) : key.beginBit > key.endBit || key.endBit > 32) {
+    p.refusal = wide ? kKeyOrderRefused : kBitRangeRefused;
+    return p;
+  }
+  if (!wide && key.beginBit == key.endBit) return p;  // nothing to order by
+  if (wide) p.order = key.order;
+  if (!wide && key.endBit - key.beginBit < 32) p.rangeBegin = key.beginBit, p.rangeWidth = key.endBit - key.beginBit;
+  const uint32_t align = c.minStorageBufferOffsetAlignment;
+  p.layout = wide ? MakeSegmented64Layout(maxElementCount, align, keyValue, storageAddress)
+                  : MakeSegmentedLayout(maxElementCount, align, keyValue, storageAddress);
+  if (segmentCount == 0 || maxElementCount == 0) return p;
+  if (!p.layout.fits) {  // (cannot happen for N >= 1: both layouts fit every count)
+    p.refusal = wide ? "segmented 64-bit storage layout" : "segmented storage layout";
+    return p;
+  }
+  // one workgroup per segment up to 2^20 of them (a grid-stride loop beyond); the other two launches take their lists by grid
+  // stride with at most as many workgroups as can be resident: two per CU of the 4-byte forms, one of the 8-byte forms (their
+  // 1024-thread kernels take 66 to 89 registers and 90 to 144 KiB of LDS)
+  const uint32_t resident = (wide ? 1u : 2u) * (uint32_t)c.computeUnits;
+  const uint32_t grids[4] = {1u, std::min<uint32_t>(segmentCount, 1u << 20),
+                             std::min<uint32_t>(std::min<uint32_t>(segmentCount, p.layout.midCap), resident),
+                             std::min<uint32_t>(std::min<uint32_t>(segmentCount, p.layout.largeCap), resident)};
+  const char* const* names = kNames[wide ? (p.order != kKeyOrderUint64 ? 3 : 2) : (p.rangeWidth != 0 ? 1 : 0)];
+  for (uint32_t i = 0; i < 4; ++i)
+    if (grids[i] != 0) p.steps[p.stepCount++] = SegmentedSortStep{SegmentedStep(i), (uint8_t)(i + 1), names[i], grids[i]};
+  return p;
+}
+
+// ---- the 64-bit sorts (vrdxHipCmdSort64[Ordered][KeyValue][Indirect]) ----
+// Two stable 32-bit key+value sorts, low words first and high words second, on word arrays inside the storage (vrdx_layout.h,
+// MakeSort64Layout), with the streaming kernels of vrdx_kernels.hip ("64-bit keys") around them:
+//   keys-only   split (A = lo, B = hi) | sort (A, B) | sort (B, A) | merge (keys = B << 32 | A)
+//   key+value   split (A = lo, I = iota) | sort (A, I) | gather (A = hi of keys[I]) | sort (A, I) |
+//               permute (T = A << 32 | lo of keys[I], A = values[I]) | copy back (keys = T, values = A)
+// Each step ends one slot; keys-only, slot 3 coincides with slot 2 (no step between the sorts).  With an order word other than
+// kKeyOrderUint64 the split, the gather, the permutation and the merge are their ordered forms -- A, B hold the words of T(key)
+// (vrdx_kernels.h), so the inner sorts and the copy back are the same.  Nothing is decided from the data, and an indirect
+// call is planned from its bound alone.
+enum class Step64 : uint8_t { kSplit, kSortLoOther, kSortOtherLo, kGatherHi, kPermute, kCopyBack, kMerge };
+struct Sort64Step { Step64 what; uint8_t slot; const char* name; };  // (name: what EnqueueCheck reports; an inner sort reports its own)
+struct Sort64Plan {
+  bool keyValue = false;
+  uint32_t elementCount = 0;
+  uint32_t order = kKeyOrderUint64;
+  const char* refusal = nullptr;  // non-null: refused (an invalid order word), no step
+  Sort64Layout layout{};
+  Sort64Step steps[6];            // none: refused, or the empty sort
+  uint32_t stepCount = 0;
+};
+
+static inline Sort64Plan PlanSort64(const PlanContext& c, bool keyValue, uint32_t elementCount, uint32_t order, uint64_t storageAddress) {
+  Sort64Plan p;
+  p.keyValue = keyValue;
+  p.elementCount = elementCount;
+  if (!KeyOrderValid(order)) {
+    p.refusal = kKeyOrderRefused;
+    return p;
+  }
+  p.order = order;
+  if (elementCount == 0) return p;
+  p.layout = MakeSort64Layout(elementCount, c.minStorageBufferOffsetAlignment, storageAddress);
+  const bool ordered = order != kKeyOrderUint64;
+  const auto add = [&p](Step64 what, uint32_t slot, const char* name) { p.steps[p.stepCount++] = Sort64Step{what, (uint8_t)slot, name}; };
+  add(Step64::kSplit, 1, ordered ? "split64_ordered_kernel" : "split64_kernel");
+  add(Step64::kSortLoOther, 2, "sort of the low words");
+  if (keyValue) {
+    add(Step64::kGatherHi, 3, ordered ? "gather_hi64_ordered_kernel" : "gather_hi64_kernel");
+    add(Step64::kSortLoOther, 4, "sort of the high words");
+    add(Step64::kPermute, 5, ordered ? "permute64_ordered_kernel" : "permute64_kernel");
+    add(Step64::kCopyBack, 6, "copy_back64_kernel");
+  } else {
+    add(Step64::kSortOtherLo, 4, "sort of the high words");
+    add(Step64::kMerge, 5, ordered ? "merge64_ordered_kernel" : "merge64_kernel");
+  }
   return p;
 }
 
