@@ -282,8 +282,8 @@ constexpr bool KeyOrderValid(uint32_t order) {
 // caller's, 4-byte aligned; every other array lies inside the storage on a 16-byte boundary (MakeSort64Layout).
 constexpr uint32_t kSort64Threads = 256;
 // order: the order word above; kKeyOrderUint64 starts the kernels without one (split64_kernel ...), every other valid word the
-// ordered forms (split64_ordered_kernel ...) with the word behind the same arguments; an invalid word is refused with
-// hipErrorInvalidValue.  T = the identity for kKeyOrderUint64.
+// ordered forms (split64_ordered_kernel ...) with the word behind the same arguments -- one device function per step, the
+// plain kernel with the constant word; an invalid word is refused with hipErrorInvalidValue.  T = the identity for kKeyOrderUint64.
 // lo[i] = low word of T(keys[i]); other[i] = its high word, or i (iota)
 hipError_t LaunchSplit64(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other, uint32_t maxCount,
                          const uint32_t* countPtr, uint32_t order);

@@ -1743,13 +1743,14 @@ __global__ __launch_bounds__(THREADS) void bucket_sort_kernel(BucketSortArgs a) 
 //   * segmented_mid_kernel: SortInWorkgroup<1024, 16> for each id of the mid list.  Taking ids from a list rather than one
 //     workgroup per segment keeps 65536 segments of 256 keys from dispatching 65536 empty 1024-thread workgroups;
 //   * segmented_large_kernel: one workgroup per large segment, a stable LSD sort through memory (SegmentLsd below).
-// Segments never share elements when the offsets are monotone, so workgroups never share data or scratch.  A list slot beyond
-// its capacity (only non-monotone offsets, which raise the bit, can overlap segments and overfill a list) is dropped.
+// Segments never share elements when the offsets are monotone, so workgroups never share data or scratch.  The loops are
+// written once (ForEachSmallSegment, ForEachListedSegment) for these kernels, their bit-range forms and the ordered 64-bit
+// forms (the unordered 64-bit forms keep their own copy, see there): a kernel is its LDS, its class bounds and the sort it runs on a segment.
 constexpr uint32_t kSegmentsInvalid = 0x00000004u;  // VRDX_HIP_STATUS_SEGMENTS_INVALID (include/vk_radix_sort.h)
 
 // The segment's bounds, scalar (wave-uniform) loads; false when the pair is unusable (then the bit is raised if `flag`).
-__device__ __forceinline__ bool SegmentBounds(const SegmentedArgs& a, uint32_t segment, bool flag, uint32_t* begin,
-                                              uint32_t* end) {
+template <typename Args>
+__device__ __forceinline__ bool SegmentBounds(const Args& a, uint32_t segment, bool flag, uint32_t* begin, uint32_t* end) {
   const uint32_t b = a.offsets[segment];
   const uint32_t e = a.offsets[segment + 1];
   if (b <= e && e <= a.maxCount) {
@@ -1773,16 +1774,18 @@ __global__ __launch_bounds__(64) void segmented_clear_kernel(SegmentedArgs a) {
   if (threadIdx.x == 5) *a.largeCount = 0u;
 }
 
-template <bool KV, bool ATOMIC_RANK>
-__global__ __launch_bounds__(256) void segmented_small_kernel(SegmentedArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+// The small kernels' loop, workgroup by segment: checks the pair of offsets, calls sort(begin, n) for 2 <= n <= smallMax and
+// appends the id of a bigger segment to the mid (n <= midMax) or the large list.  A list slot beyond its capacity (only
+// non-monotone offsets, which raise the bit, can overlap segments and overfill a list) is dropped.
+template <typename Args, typename Sort>
+__device__ __forceinline__ void ForEachSmallSegment(const Args& a, uint32_t smallMax, uint32_t midMax, Sort sort) {
   for (uint32_t s = blockIdx.x; s < a.segmentCount; s += gridDim.x) {
     uint32_t begin = 0, end = 0;
     if (!SegmentBounds(a, s, true, &begin, &end)) continue;  // uniform
     const uint32_t n = end - begin;
-    if (n > kSegSmallMax) {
+    if (n > smallMax) {
       if (threadIdx.x == 0) {
-        const bool mid = n <= kSegMidMax;
+        const bool mid = n <= midMax;
         const uint32_t slot = atomicAdd(mid ? a.midCount : a.largeCount, 1u);
         if (slot < (mid ? a.midCap : a.largeCap)) (mid ? a.midList : a.largeList)[slot] = s;
       }
@@ -1790,25 +1793,44 @@ __global__ __launch_bounds__(256) void segmented_small_kernel(SegmentedArgs a) {
     }
     if (n < 2) continue;
     LdsBarrier();  // the previous segment's read-back of the staging buffer is over
+    sort(begin, n);
+  }
+}
+
+// The mid and large kernels' loop, workgroup by entry of the mid or the large (LARGE) list: calls sort(begin, n) for
+// above < n <= upTo.  The list is the small kernel's, which checked the offsets; what it holds is checked again all the same
+// (the id, the pair, the class), so that nothing a list could hold makes a workgroup leave its segment.
+template <bool LARGE, typename Args, typename Sort>
+__device__ __forceinline__ void ForEachListedSegment(const Args& a, uint32_t above, uint32_t upTo, Sort sort) {
+  const uint32_t listed = LARGE ? min(*a.largeCount, a.largeCap) : min(*a.midCount, a.midCap);
+  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
+    const uint32_t s = (LARGE ? a.largeList : a.midList)[i];
+    uint32_t begin = 0, end = 0;
+    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;
+    const uint32_t n = end - begin;
+    if (n <= above || n > upTo) continue;
+    // the previous segment is done: its read-back of the staging buffer | its passes and copy back through memory
+    if constexpr (LARGE) __syncthreads(); else LdsBarrier();
+    sort(begin, n);
+  }
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(256) void segmented_small_kernel(SegmentedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  ForEachSmallSegment(a, kSegSmallMax, kSegMidMax, [&](uint32_t begin, uint32_t n) {
     SortInWorkgroup<256, 16, KV, ATOMIC_RANK>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
                                               KV ? a.values + begin : nullptr, n, VRDX_PASSES, smem);
-  }
+  });
 }
 
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(1024) void segmented_mid_kernel(SegmentedArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const uint32_t listed = min(*a.midCount, a.midCap);
-  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
-    const uint32_t s = a.midList[i];
-    uint32_t begin = 0, end = 0;
-    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
-    const uint32_t n = end - begin;
-    if (n <= kSegSmallMax || n > kSegMidMax) continue;
-    LdsBarrier();
+  ForEachListedSegment<false>(a, kSegSmallMax, kSegMidMax, [&](uint32_t begin, uint32_t n) {
     SortInWorkgroup<1024, 16, KV, ATOMIC_RANK>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
                                                KV ? a.values + begin : nullptr, n, VRDX_PASSES, smem);
-  }
+  });
 }
 
 // One large segment in one workgroup: a stable LSD sort through memory, the way one tile-sequential onesweep would do it.
@@ -1997,73 +2019,39 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(1024) void segmented_large_kernel(SegmentedArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const uint32_t listed = min(*a.largeCount, a.largeCap);
-  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
-    const uint32_t s = a.largeList[i];
-    uint32_t begin = 0, end = 0;
-    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
-    if (end - begin <= kSegMidMax) continue;
-    __syncthreads();  // the previous segment is done (its copy back included)
+  ForEachListedSegment<true>(a, kSegMidMax, ~0u, [&](uint32_t begin, uint32_t n) {
     SegmentLsd<KV, ATOMIC_RANK>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
-                                KV ? a.valuesScratch + begin : nullptr, end - begin, smem);
-  }
+                                KV ? a.valuesScratch + begin : nullptr, n, smem);
+  });
 }
 
-// The segmented sort by a bit range of the key (vrdxHipCmdSortSegmentedBits[KeyValue]): the three kernels above with the range
-// forms of SortInWorkgroup and SegmentLsd.  The range -- beginBit and width = endBit - beginBit, 1 ... 31 -- travels as two
-// scalar arguments BEHIND SegmentedArgs, which segmented_clear_kernel and the whole-key kernels share unchanged.  Offsets are
-// checked, segments classified and listed exactly as above: the size classes do not depend on the range.
+// vrdxHipCmdSortSegmentedBits[KeyValue]: the range forms of the sorts in the same loops; beginBit and width = endBit -
+// beginBit (1 ... 31) travel BEHIND SegmentedArgs, which segmented_clear_kernel and the whole-key kernels share unchanged.
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(256) void segmented_small_bits_kernel(SegmentedArgs a, uint32_t beginBit, uint32_t width) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  for (uint32_t s = blockIdx.x; s < a.segmentCount; s += gridDim.x) {
-    uint32_t begin = 0, end = 0;
-    if (!SegmentBounds(a, s, true, &begin, &end)) continue;  // uniform
-    const uint32_t n = end - begin;
-    if (n > kSegSmallMax) {
-      if (threadIdx.x == 0) {
-        const bool mid = n <= kSegMidMax;
-        const uint32_t slot = atomicAdd(mid ? a.midCount : a.largeCount, 1u);
-        if (slot < (mid ? a.midCap : a.largeCap)) (mid ? a.midList : a.largeList)[slot] = s;
-      }
-      continue;
-    }
-    if (n < 2) continue;
-    LdsBarrier();  // the previous segment's read-back of the staging buffer is over
+  ForEachSmallSegment(a, kSegSmallMax, kSegMidMax, [&](uint32_t begin, uint32_t n) {
     SortInWorkgroup<256, 16, KV, ATOMIC_RANK, true>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
                                                     KV ? a.values + begin : nullptr, n, width, smem, beginBit);
-  }
+  });
 }
 
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(1024) void segmented_mid_bits_kernel(SegmentedArgs a, uint32_t beginBit, uint32_t width) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const uint32_t listed = min(*a.midCount, a.midCap);
-  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
-    const uint32_t s = a.midList[i];
-    uint32_t begin = 0, end = 0;
-    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
-    const uint32_t n = end - begin;
-    if (n <= kSegSmallMax || n > kSegMidMax) continue;
-    LdsBarrier();
+  ForEachListedSegment<false>(a, kSegSmallMax, kSegMidMax, [&](uint32_t begin, uint32_t n) {
     SortInWorkgroup<1024, 16, KV, ATOMIC_RANK, true>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
                                                      KV ? a.values + begin : nullptr, n, width, smem, beginBit);
-  }
+  });
 }
 
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(1024) void segmented_large_bits_kernel(SegmentedArgs a, uint32_t beginBit, uint32_t width) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const uint32_t listed = min(*a.largeCount, a.largeCap);
-  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
-    const uint32_t s = a.largeList[i];
-    uint32_t begin = 0, end = 0;
-    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
-    if (end - begin <= kSegMidMax) continue;
-    __syncthreads();  // the previous segment is done (its copy back included)
+  ForEachListedSegment<true>(a, kSegMidMax, ~0u, [&](uint32_t begin, uint32_t n) {
     SegmentLsd<KV, ATOMIC_RANK, true>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
-                                      KV ? a.valuesScratch + begin : nullptr, end - begin, smem, beginBit, width);
-  }
+                                      KV ? a.valuesScratch + begin : nullptr, n, smem, beginBit, width);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3425,136 +3413,6 @@ __device__ __forceinline__ uint32_t Sort64First(uint32_t n, bool* whole) {
   return i;
 }
 
-// lo[i] = low word; other[i] = high word, or i itself (IOTA: the index the key+value form sorts along)
-template <bool IOTA>
-__global__ __launch_bounds__(kSort64Threads) void split64_kernel(const uint64_t* __restrict__ keys, uint32_t* __restrict__ lo,
-                                                                 uint32_t* __restrict__ other, uint32_t maxCount,
-                                                                 const uint32_t* countPtr) {
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  if (whole) {
-    const u32x4_a8* const pairs = reinterpret_cast<const u32x4_a8*>(keys + i);
-    const u32x4 a = pairs[0], b = pairs[1];
-    *reinterpret_cast<u32x4*>(lo + i) = u32x4{a.x, a.z, b.x, b.z};
-    *reinterpret_cast<u32x4*>(other + i) = IOTA ? u32x4{i, i + 1u, i + 2u, i + 3u} : u32x4{a.y, a.w, b.y, b.w};
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) {
-    const uint64_t k = keys[j];
-    lo[j] = (uint32_t)k;
-    other[j] = IOTA ? j : (uint32_t)(k >> 32);
-  }
-}
-
-// keys[i] = hi[i] << 32 | lo[i]
-__global__ __launch_bounds__(kSort64Threads) void merge64_kernel(uint64_t* __restrict__ keys, const uint32_t* __restrict__ lo,
-                                                                 const uint32_t* __restrict__ hi, uint32_t maxCount,
-                                                                 const uint32_t* countPtr) {
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  if (whole) {
-    const u32x4 l = *reinterpret_cast<const u32x4*>(lo + i), h = *reinterpret_cast<const u32x4*>(hi + i);
-    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(keys + i);
-    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
-    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) keys[j] = (uint64_t)hi[j] << 32 | lo[j];
-}
-
-// hi[j] = high word of keys[index[j]]: the keys of the second sort, in the order the first one left
-__global__ __launch_bounds__(kSort64Threads) void gather_hi64_kernel(const uint64_t* __restrict__ keys,
-                                                                     const uint32_t* __restrict__ index,
-                                                                     uint32_t* __restrict__ hi, uint32_t maxCount,
-                                                                     const uint32_t* countPtr) {
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
-  if (whole) {
-    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
-    *reinterpret_cast<u32x4*>(hi + i) = u32x4{words[2ull * at.x + 1u], words[2ull * at.y + 1u], words[2ull * at.z + 1u],
-                                              words[2ull * at.w + 1u]};
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) hi[j] = words[2ull * index[j] + 1u];
-}
-
-// keysOut[j] = hiThenValues[j] << 32 | low word of keys[index[j]], then hiThenValues[j] = values[index[j]]: the sorted high
-// words are what the second sort left as its keys, and their array takes the permuted values once they are read (every
-// element of it is read and written by the same thread)
-__global__ __launch_bounds__(kSort64Threads) void permute64_kernel(const uint64_t* __restrict__ keys,
-                                                                   const uint32_t* __restrict__ values,
-                                                                   const uint32_t* __restrict__ index,
-                                                                   uint32_t* __restrict__ hiThenValues,
-                                                                   uint64_t* __restrict__ keysOut, uint32_t maxCount,
-                                                                   const uint32_t* countPtr) {
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
-  if (whole) {
-    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
-    const u32x4 h = *reinterpret_cast<const u32x4*>(hiThenValues + i);
-    const u32x4 l = u32x4{words[2ull * at.x], words[2ull * at.y], words[2ull * at.z], words[2ull * at.w]};
-    const u32x4 v = u32x4{values[at.x], values[at.y], values[at.z], values[at.w]};
-    u32x4* const pairs = reinterpret_cast<u32x4*>(keysOut + i);
-    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
-    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
-    *reinterpret_cast<u32x4*>(hiThenValues + i) = v;
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) {
-    const uint32_t at = index[j];
-    keysOut[j] = (uint64_t)hiThenValues[j] << 32 | words[2ull * at];
-    hiThenValues[j] = values[at];
-  }
-}
-
-// keys[i] = keysIn[i], values[i] = valuesIn[i]: the permuted arrays back into the caller's
-__global__ __launch_bounds__(kSort64Threads) void copy_back64_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ values,
-                                                                     const uint64_t* __restrict__ keysIn,
-                                                                     const uint32_t* __restrict__ valuesIn, uint32_t maxCount,
-                                                                     const uint32_t* countPtr) {
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  if (whole) {
-    const u32x4* const in = reinterpret_cast<const u32x4*>(keysIn + i);
-    const u32x4 a = in[0], b = in[1], v = *reinterpret_cast<const u32x4*>(valuesIn + i);
-    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(keys + i);
-    pairs[0] = a;
-    pairs[1] = b;
-    *reinterpret_cast<u32x4_a4*>(values + i) = v;
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) {
-    keys[j] = keysIn[j];
-    values[j] = valuesIn[j];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// segmented sort of 64-bit keys (vrdxHipCmdSortSegmented64[KeyValue]): the segmented sort's three size classes with the
-// key held as two words
-// ---------------------------------------------------------------------------------------------
-// A key is a pair of register arrays, lo[] and hi[]; a ranking pass ranks ONE of them by one of its bytes with the same
-// RankAtomic / RankBallot and wave-private counters as every other kernel, and moves both words (and the value) through
-// the staging buffer: one word plane per array, each with the StagingSlot swizzle of the 4-byte kernels, so every LDS
-// access is a 4-byte one with the bank pattern those kernels were tuned for.  Up to eight passes -- the low word's four
-// bytes, then the high word's -- between one load and one store of the segment.
-// A byte that is the same in every key of the segment is not ranked at all: before the passes the workgroup ORs
-// key ^ first key over the segment's real elements (pads do not take part: they stay behind the real keys in every pass
-// that runs, and a pass that does not run leaves everything where it is), and a pass whose byte of that mask is zero is
-// skipped.  tile id << 32 | depth keys, hashes of fewer than 64 bits and counters take five or six passes instead of eight.
-
 // Key orders (the ORDERED forms, vrdxHipCmdSort64Ordered* and vrdxHipCmdSortSegmented64Ordered*): the kernels sort T(key)
 // ascending as unsigned, T(k) = k ^ flip ^ (float64 and bit 63 of k set ? 0x7FFFFFFFFFFFFFFF : 0), flip = 0 (unsigned) or
 // 1 << 63 (signed, float64), complemented for descending.  As words: the high word's mask depends on the high word alone,
@@ -3598,6 +3456,212 @@ __device__ __forceinline__ void OrderInverse(const KeyOrder64& o, uint32_t& lo, 
   lo = OrderLow(o, lo, neg);
   hi = OrderHigh(o, hi, neg);
 }
+
+// The four steps that touch keys, each written once with the order word as its last argument and started by two kernels:
+// the plain one passes the constant kKeyOrderUint64 (MakeKeyOrder64 gives {0, 0, 0} and every Order* call folds away), the
+// *_ordered one (vrdxHipCmdSort64Ordered*) the word it takes behind the plain kernel's arguments.  The word arrays hold the
+// words of T(key), so the inner 32-bit sorts do not know the order.  A gather still loads ONE word of a key: the high word's
+// mask depends on the high word alone; the merge and the permutation find the low word's sign in the transformed high word.
+
+// lo[i] = low word of T(keys[i]); other[i] = its high word, or i itself (IOTA: the index the key+value form sorts along)
+template <bool IOTA>
+__device__ __forceinline__ void Split64(const uint64_t* __restrict__ keys, uint32_t* __restrict__ lo, uint32_t* __restrict__ other,
+                                        uint32_t maxCount, const uint32_t* countPtr, uint32_t order) {
+  const KeyOrder64 o = MakeKeyOrder64(order);
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4_a8* const pairs = reinterpret_cast<const u32x4_a8*>(keys + i);
+    const u32x4 a = pairs[0], b = pairs[1];
+    const u32x4 neg = u32x4{OrderNegOfKey(o, a.y), OrderNegOfKey(o, a.w), OrderNegOfKey(o, b.y), OrderNegOfKey(o, b.w)};
+    *reinterpret_cast<u32x4*>(lo + i) =
+        u32x4{OrderLow(o, a.x, neg.x), OrderLow(o, a.z, neg.y), OrderLow(o, b.x, neg.z), OrderLow(o, b.z, neg.w)};
+    *reinterpret_cast<u32x4*>(other + i) =
+        IOTA ? u32x4{i, i + 1u, i + 2u, i + 3u}
+             : u32x4{OrderHigh(o, a.y, neg.x), OrderHigh(o, a.w, neg.y), OrderHigh(o, b.y, neg.z), OrderHigh(o, b.w, neg.w)};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    const uint64_t k = keys[j];
+    uint32_t l = (uint32_t)k, h = (uint32_t)(k >> 32);
+    OrderForward(o, l, h);
+    lo[j] = l;
+    other[j] = IOTA ? j : h;
+  }
+}
+template <bool IOTA>
+__global__ __launch_bounds__(kSort64Threads) void split64_kernel(const uint64_t* __restrict__ keys, uint32_t* __restrict__ lo,
+                                                                 uint32_t* __restrict__ other, uint32_t maxCount,
+                                                                 const uint32_t* countPtr) {
+  Split64<IOTA>(keys, lo, other, maxCount, countPtr, kKeyOrderUint64);
+}
+template <bool IOTA>
+__global__ __launch_bounds__(kSort64Threads) void split64_ordered_kernel(const uint64_t* __restrict__ keys,
+                                                                         uint32_t* __restrict__ lo,
+                                                                         uint32_t* __restrict__ other, uint32_t maxCount,
+                                                                         const uint32_t* countPtr, uint32_t order) {
+  Split64<IOTA>(keys, lo, other, maxCount, countPtr, order);
+}
+
+// keys[i] = the key whose T has the words hi[i], lo[i]
+__device__ __forceinline__ void Merge64(uint64_t* __restrict__ keys, const uint32_t* __restrict__ lo,
+                                        const uint32_t* __restrict__ hi, uint32_t maxCount, const uint32_t* countPtr,
+                                        uint32_t order) {
+  const KeyOrder64 o = MakeKeyOrder64(order);
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4 tl = *reinterpret_cast<const u32x4*>(lo + i), th = *reinterpret_cast<const u32x4*>(hi + i);
+    const u32x4 neg = u32x4{OrderNegOfT(o, th.x), OrderNegOfT(o, th.y), OrderNegOfT(o, th.z), OrderNegOfT(o, th.w)};
+    const u32x4 l = u32x4{OrderLow(o, tl.x, neg.x), OrderLow(o, tl.y, neg.y), OrderLow(o, tl.z, neg.z), OrderLow(o, tl.w, neg.w)};
+    const u32x4 h =
+        u32x4{OrderHigh(o, th.x, neg.x), OrderHigh(o, th.y, neg.y), OrderHigh(o, th.z, neg.z), OrderHigh(o, th.w, neg.w)};
+    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(keys + i);
+    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
+    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    uint32_t l = lo[j], h = hi[j];
+    OrderInverse(o, l, h);
+    keys[j] = (uint64_t)h << 32 | l;
+  }
+}
+__global__ __launch_bounds__(kSort64Threads) void merge64_kernel(uint64_t* __restrict__ keys, const uint32_t* __restrict__ lo,
+                                                                 const uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                 const uint32_t* countPtr) {
+  Merge64(keys, lo, hi, maxCount, countPtr, kKeyOrderUint64);
+}
+__global__ __launch_bounds__(kSort64Threads) void merge64_ordered_kernel(uint64_t* __restrict__ keys,
+                                                                         const uint32_t* __restrict__ lo,
+                                                                         const uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                         const uint32_t* countPtr, uint32_t order) {
+  Merge64(keys, lo, hi, maxCount, countPtr, order);
+}
+
+// hi[j] = high word of T(keys[index[j]]), from the key's high word alone: the keys of the second sort, in the order the
+// first one left
+__device__ __forceinline__ void GatherHi64(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ index,
+                                           uint32_t* __restrict__ hi, uint32_t maxCount, const uint32_t* countPtr,
+                                           uint32_t order) {
+  const KeyOrder64 o = MakeKeyOrder64(order);
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
+  if (whole) {
+    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
+    *reinterpret_cast<u32x4*>(hi + i) =
+        u32x4{OrderHighOfKey(o, words[2ull * at.x + 1u]), OrderHighOfKey(o, words[2ull * at.y + 1u]),
+              OrderHighOfKey(o, words[2ull * at.z + 1u]), OrderHighOfKey(o, words[2ull * at.w + 1u])};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) hi[j] = OrderHighOfKey(o, words[2ull * index[j] + 1u]);
+}
+__global__ __launch_bounds__(kSort64Threads) void gather_hi64_kernel(const uint64_t* __restrict__ keys,
+                                                                     const uint32_t* __restrict__ index,
+                                                                     uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                     const uint32_t* countPtr) {
+  GatherHi64(keys, index, hi, maxCount, countPtr, kKeyOrderUint64);
+}
+__global__ __launch_bounds__(kSort64Threads) void gather_hi64_ordered_kernel(const uint64_t* __restrict__ keys,
+                                                                             const uint32_t* __restrict__ index,
+                                                                             uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                             const uint32_t* countPtr, uint32_t order) {
+  GatherHi64(keys, index, hi, maxCount, countPtr, order);
+}
+
+// keysOut[j] = (the high word that hiThenValues[j] is the transformed form of) << 32 | low word of keys[index[j]], raw as it
+// lies in the caller's keys; then hiThenValues[j] = values[index[j]]: the sorted high words are what the second sort left as
+// its keys, and their array takes the permuted values once they are read (every element of it is read and written by the
+// same thread)
+__device__ __forceinline__ void Permute64(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ values,
+                                          const uint32_t* __restrict__ index, uint32_t* __restrict__ hiThenValues,
+                                          uint64_t* __restrict__ keysOut, uint32_t maxCount, const uint32_t* countPtr,
+                                          uint32_t order) {
+  const KeyOrder64 o = MakeKeyOrder64(order);
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
+  if (whole) {
+    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
+    const u32x4 th = *reinterpret_cast<const u32x4*>(hiThenValues + i);
+    const u32x4 h = u32x4{OrderHighOfT(o, th.x), OrderHighOfT(o, th.y), OrderHighOfT(o, th.z), OrderHighOfT(o, th.w)};
+    const u32x4 l = u32x4{words[2ull * at.x], words[2ull * at.y], words[2ull * at.z], words[2ull * at.w]};
+    const u32x4 v = u32x4{values[at.x], values[at.y], values[at.z], values[at.w]};
+    u32x4* const pairs = reinterpret_cast<u32x4*>(keysOut + i);
+    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
+    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
+    *reinterpret_cast<u32x4*>(hiThenValues + i) = v;
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    const uint32_t at = index[j];
+    keysOut[j] = (uint64_t)OrderHighOfT(o, hiThenValues[j]) << 32 | words[2ull * at];
+    hiThenValues[j] = values[at];
+  }
+}
+__global__ __launch_bounds__(kSort64Threads) void permute64_kernel(const uint64_t* __restrict__ keys,
+                                                                   const uint32_t* __restrict__ values,
+                                                                   const uint32_t* __restrict__ index,
+                                                                   uint32_t* __restrict__ hiThenValues,
+                                                                   uint64_t* __restrict__ keysOut, uint32_t maxCount,
+                                                                   const uint32_t* countPtr) {
+  Permute64(keys, values, index, hiThenValues, keysOut, maxCount, countPtr, kKeyOrderUint64);
+}
+__global__ __launch_bounds__(kSort64Threads) void permute64_ordered_kernel(const uint64_t* __restrict__ keys,
+                                                                           const uint32_t* __restrict__ values,
+                                                                           const uint32_t* __restrict__ index,
+                                                                           uint32_t* __restrict__ hiThenValues,
+                                                                           uint64_t* __restrict__ keysOut, uint32_t maxCount,
+                                                                           const uint32_t* countPtr, uint32_t order) {
+  Permute64(keys, values, index, hiThenValues, keysOut, maxCount, countPtr, order);
+}
+
+// keys[i] = keysIn[i], values[i] = valuesIn[i]: the permuted arrays back into the caller's
+__global__ __launch_bounds__(kSort64Threads) void copy_back64_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ values,
+                                                                     const uint64_t* __restrict__ keysIn,
+                                                                     const uint32_t* __restrict__ valuesIn, uint32_t maxCount,
+                                                                     const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4* const in = reinterpret_cast<const u32x4*>(keysIn + i);
+    const u32x4 a = in[0], b = in[1], v = *reinterpret_cast<const u32x4*>(valuesIn + i);
+    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(keys + i);
+    pairs[0] = a;
+    pairs[1] = b;
+    *reinterpret_cast<u32x4_a4*>(values + i) = v;
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    keys[j] = keysIn[j];
+    values[j] = valuesIn[j];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// segmented sort of 64-bit keys (vrdxHipCmdSortSegmented64[KeyValue]): the segmented sort's three size classes with the
+// key held as two words
+// ---------------------------------------------------------------------------------------------
+// A key is a pair of register arrays, lo[] and hi[]; a ranking pass ranks ONE of them by one of its bytes with the same
+// RankAtomic / RankBallot and wave-private counters as every other kernel, and moves both words (and the value) through
+// the staging buffer: one word plane per array, each with the StagingSlot swizzle of the 4-byte kernels, so every LDS
+// access is a 4-byte one with the bank pattern those kernels were tuned for.  Up to eight passes -- the low word's four
+// bytes, then the high word's -- between one load and one store of the segment.
+// A byte that is the same in every key of the segment is not ranked at all: before the passes the workgroup ORs
+// key ^ first key over the segment's real elements (pads do not take part: they stay behind the real keys in every pass
+// that runs, and a pass that does not run leaves everything where it is), and a pass whose byte of that mask is zero is
+// skipped.  tile id << 32 | depth keys, hashes of fewer than 64 bits and counters take five or six passes instead of eight.
 
 // The OR over the 64 lanes of a wave, in lane 63 (the DPP moves of WaveInclusiveScan: lanes that receive nothing get 0).
 __device__ __forceinline__ uint32_t WaveInclusiveOr(uint32_t v) {
@@ -3779,32 +3843,16 @@ __device__ __forceinline__ void SortInWorkgroup64(const uint64_t* keysIn, uint64
   }
 }
 
-// SegmentBounds for any args struct with offsets, maxCount, failure and stickyFailure: ONE statement of the offset rule for
-// the kernels added from here on.  (SegmentBounds itself stays as it is, a non-template on SegmentedArgs: the 32-bit kernels'
-// code is not to move.)
-template <typename Args>
-__device__ __forceinline__ bool SegmentBoundsOf(const Args& a, uint32_t segment, bool flag, uint32_t* begin, uint32_t* end) {
-  const uint32_t b = a.offsets[segment];
-  const uint32_t e = a.offsets[segment + 1];
-  if (b <= e && e <= a.maxCount) {
-    *begin = b;
-    *end = e;
-    return true;
-  }
-  if (flag && threadIdx.x == 0) {
-    atomicOr(a.failure, kSegmentsInvalid);
-    if (a.stickyFailure != nullptr) atomicOr(a.stickyFailure, kSegmentsInvalid);
-  }
-  return false;
-}
-
+// The three kernels of the unordered 64-bit sort keep their loops written out: the same statements as ForEachSmallSegment
+// and ForEachListedSegment (which their ordered forms use), left in place because two of their shapes timed outside the
+// parent build's own range when they were folded (profiles/r15_kernel_families.txt).
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(256) void segmented_small64_kernel(Segmented64Args a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
   for (uint32_t s = blockIdx.x; s < a.segmentCount; s += gridDim.x) {
     uint32_t begin = 0, end = 0;
-    if (!SegmentBoundsOf(a, s, true, &begin, &end)) continue;  // uniform
+    if (!SegmentBounds(a, s, true, &begin, &end)) continue;  // uniform
     const uint32_t n = end - begin;
     if (n > kSeg64SmallMax) {
       if (threadIdx.x == 0) {
@@ -3829,7 +3877,7 @@ __global__ __launch_bounds__(1024) void segmented_mid64_kernel(Segmented64Args a
   for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
     const uint32_t s = a.midList[i];
     uint32_t begin = 0, end = 0;
-    if (s >= a.segmentCount || !SegmentBoundsOf(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
     const uint32_t n = end - begin;
     if (n <= kSeg64SmallMax || n > kMidMax) continue;
     LdsBarrier();
@@ -4049,7 +4097,7 @@ __global__ __launch_bounds__(1024) void segmented_large64_kernel(Segmented64Args
   for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
     const uint32_t s = a.largeList[i];
     uint32_t begin = 0, end = 0;
-    if (s >= a.segmentCount || !SegmentBoundsOf(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
+    if (s >= a.segmentCount || !SegmentBounds(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
     if (end - begin <= kMidMax) continue;
     __syncthreads();  // the previous segment is done (its copy back included)
     SegmentLsd64<KV, ATOMIC_RANK>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
@@ -4057,188 +4105,37 @@ __global__ __launch_bounds__(1024) void segmented_large64_kernel(Segmented64Args
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered*, vrdxHipCmdSortSegmented64Ordered*): signed, float64, descending
-// ---------------------------------------------------------------------------------------------
-// The ordered forms of the kernels above, as kernels of their own: the order word travels as one more argument behind the
-// twin's, and none of the twins' code moves.  The composition's word arrays hold the words of T(key) (KeyOrder64 above), so
-// the two inner 32-bit sorts are the calls they were; the segmented kernels hold T(key) in their registers between the one
-// load and the one store (SortInWorkgroup64) or from the first pass's loads to the last pass's stores (SegmentLsd64).  Access patterns are the
-// twins': four elements per thread, a gather still loads ONE word of a key -- the high word's mask depends on the high word
-// alone, and the merge and the permutation find the sign the low word's mask needs in the transformed high word.
-
-// lo[i] = low word of T(keys[i]); other[i] = its high word, or i itself (IOTA)
-template <bool IOTA>
-__global__ __launch_bounds__(kSort64Threads) void split64_ordered_kernel(const uint64_t* __restrict__ keys,
-                                                                         uint32_t* __restrict__ lo,
-                                                                         uint32_t* __restrict__ other, uint32_t maxCount,
-                                                                         const uint32_t* countPtr, uint32_t order) {
-  const KeyOrder64 o = MakeKeyOrder64(order);
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  if (whole) {
-    const u32x4_a8* const pairs = reinterpret_cast<const u32x4_a8*>(keys + i);
-    const u32x4 a = pairs[0], b = pairs[1];
-    const u32x4 neg = u32x4{OrderNegOfKey(o, a.y), OrderNegOfKey(o, a.w), OrderNegOfKey(o, b.y), OrderNegOfKey(o, b.w)};
-    *reinterpret_cast<u32x4*>(lo + i) =
-        u32x4{OrderLow(o, a.x, neg.x), OrderLow(o, a.z, neg.y), OrderLow(o, b.x, neg.z), OrderLow(o, b.z, neg.w)};
-    *reinterpret_cast<u32x4*>(other + i) =
-        IOTA ? u32x4{i, i + 1u, i + 2u, i + 3u}
-             : u32x4{OrderHigh(o, a.y, neg.x), OrderHigh(o, a.w, neg.y), OrderHigh(o, b.y, neg.z), OrderHigh(o, b.w, neg.w)};
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) {
-    const uint64_t k = keys[j];
-    uint32_t l = (uint32_t)k, h = (uint32_t)(k >> 32);
-    OrderForward(o, l, h);
-    lo[j] = l;
-    other[j] = IOTA ? j : h;
-  }
-}
-
-// keys[i] = the key whose T has the words hi[i], lo[i]
-__global__ __launch_bounds__(kSort64Threads) void merge64_ordered_kernel(uint64_t* __restrict__ keys,
-                                                                         const uint32_t* __restrict__ lo,
-                                                                         const uint32_t* __restrict__ hi, uint32_t maxCount,
-                                                                         const uint32_t* countPtr, uint32_t order) {
-  const KeyOrder64 o = MakeKeyOrder64(order);
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  if (whole) {
-    const u32x4 tl = *reinterpret_cast<const u32x4*>(lo + i), th = *reinterpret_cast<const u32x4*>(hi + i);
-    const u32x4 neg = u32x4{OrderNegOfT(o, th.x), OrderNegOfT(o, th.y), OrderNegOfT(o, th.z), OrderNegOfT(o, th.w)};
-    const u32x4 l = u32x4{OrderLow(o, tl.x, neg.x), OrderLow(o, tl.y, neg.y), OrderLow(o, tl.z, neg.z), OrderLow(o, tl.w, neg.w)};
-    const u32x4 h =
-        u32x4{OrderHigh(o, th.x, neg.x), OrderHigh(o, th.y, neg.y), OrderHigh(o, th.z, neg.z), OrderHigh(o, th.w, neg.w)};
-    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(keys + i);
-    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
-    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) {
-    uint32_t l = lo[j], h = hi[j];
-    OrderInverse(o, l, h);
-    keys[j] = (uint64_t)h << 32 | l;
-  }
-}
-
-// hi[j] = high word of T(keys[index[j]]), from the key's high word alone
-__global__ __launch_bounds__(kSort64Threads) void gather_hi64_ordered_kernel(const uint64_t* __restrict__ keys,
-                                                                             const uint32_t* __restrict__ index,
-                                                                             uint32_t* __restrict__ hi, uint32_t maxCount,
-                                                                             const uint32_t* countPtr, uint32_t order) {
-  const KeyOrder64 o = MakeKeyOrder64(order);
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
-  if (whole) {
-    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
-    *reinterpret_cast<u32x4*>(hi + i) =
-        u32x4{OrderHighOfKey(o, words[2ull * at.x + 1u]), OrderHighOfKey(o, words[2ull * at.y + 1u]),
-              OrderHighOfKey(o, words[2ull * at.z + 1u]), OrderHighOfKey(o, words[2ull * at.w + 1u])};
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) hi[j] = OrderHighOfKey(o, words[2ull * index[j] + 1u]);
-}
-
-// keysOut[j] = (the high word that hiThenValues[j] is the transformed form of) << 32 | low word of keys[index[j]], raw as it
-// lies in the caller's keys; then hiThenValues[j] = values[index[j]]
-__global__ __launch_bounds__(kSort64Threads) void permute64_ordered_kernel(const uint64_t* __restrict__ keys,
-                                                                           const uint32_t* __restrict__ values,
-                                                                           const uint32_t* __restrict__ index,
-                                                                           uint32_t* __restrict__ hiThenValues,
-                                                                           uint64_t* __restrict__ keysOut, uint32_t maxCount,
-                                                                           const uint32_t* countPtr, uint32_t order) {
-  const KeyOrder64 o = MakeKeyOrder64(order);
-  const uint32_t n = ElementCount(maxCount, countPtr);
-  bool whole;
-  const uint32_t i = Sort64First(n, &whole);
-  if (i >= n) return;
-  const uint32_t* const words = reinterpret_cast<const uint32_t*>(keys);
-  if (whole) {
-    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
-    const u32x4 th = *reinterpret_cast<const u32x4*>(hiThenValues + i);
-    const u32x4 h = u32x4{OrderHighOfT(o, th.x), OrderHighOfT(o, th.y), OrderHighOfT(o, th.z), OrderHighOfT(o, th.w)};
-    const u32x4 l = u32x4{words[2ull * at.x], words[2ull * at.y], words[2ull * at.z], words[2ull * at.w]};
-    const u32x4 v = u32x4{values[at.x], values[at.y], values[at.z], values[at.w]};
-    u32x4* const pairs = reinterpret_cast<u32x4*>(keysOut + i);
-    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
-    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
-    *reinterpret_cast<u32x4*>(hiThenValues + i) = v;
-    return;
-  }
-  for (uint32_t j = i; j < n; ++j) {
-    const uint32_t at = index[j];
-    keysOut[j] = (uint64_t)OrderHighOfT(o, hiThenValues[j]) << 32 | words[2ull * at];
-    hiThenValues[j] = values[at];
-  }
-}
-
-// the three size classes of the segmented sort of 64-bit keys: the twins' loops around the ORDERED forms of
-// SortInWorkgroup64 and SegmentLsd64
+// vrdxHipCmdSortSegmented64Ordered*: the ORDERED forms of the sorts in the same loops, the order word behind Segmented64Args.
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(256) void segmented_small64_ordered_kernel(Segmented64Args a, uint32_t order) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
-  for (uint32_t s = blockIdx.x; s < a.segmentCount; s += gridDim.x) {
-    uint32_t begin = 0, end = 0;
-    if (!SegmentBoundsOf(a, s, true, &begin, &end)) continue;  // uniform
-    const uint32_t n = end - begin;
-    if (n > kSeg64SmallMax) {
-      if (threadIdx.x == 0) {
-        const bool mid = n <= kMidMax;
-        const uint32_t slot = atomicAdd(mid ? a.midCount : a.largeCount, 1u);
-        if (slot < (mid ? a.midCap : a.largeCap)) (mid ? a.midList : a.largeList)[slot] = s;
-      }
-      continue;
-    }
-    if (n < 2) continue;
-    LdsBarrier();  // the previous segment's read-back of the staging planes is over
+  ForEachSmallSegment(a, kSeg64SmallMax, kMidMax, [&](uint32_t begin, uint32_t n) {
     SortInWorkgroup64<256, 16, KV, ATOMIC_RANK, true>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
                                                       KV ? a.values + begin : nullptr, n, smem, order);
-  }
+  });
 }
 
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(1024) void segmented_mid64_ordered_kernel(Segmented64Args a, uint32_t order) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
-  const uint32_t listed = min(*a.midCount, a.midCap);
-  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
-    const uint32_t s = a.midList[i];
-    uint32_t begin = 0, end = 0;
-    if (s >= a.segmentCount || !SegmentBoundsOf(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
-    const uint32_t n = end - begin;
-    if (n <= kSeg64SmallMax || n > kMidMax) continue;
-    LdsBarrier();
+  ForEachListedSegment<false>(a, kSeg64SmallMax, kMidMax, [&](uint32_t begin, uint32_t n) {
     SortInWorkgroup64<1024, (int)(kMidMax / 1024u), KV, ATOMIC_RANK, true>(a.keys + begin, a.keys + begin,
                                                                            KV ? a.values + begin : nullptr,
                                                                            KV ? a.values + begin : nullptr, n, smem, order);
-  }
+  });
 }
 
 template <bool KV, bool ATOMIC_RANK>
 __global__ __launch_bounds__(1024) void segmented_large64_ordered_kernel(Segmented64Args a, uint32_t order) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   constexpr uint32_t kMidMax = KV ? kSeg64MidMaxKeyValue : kSeg64MidMax;
-  const uint32_t listed = min(*a.largeCount, a.largeCap);
-  for (uint32_t i = blockIdx.x; i < listed; i += gridDim.x) {
-    const uint32_t s = a.largeList[i];
-    uint32_t begin = 0, end = 0;
-    if (s >= a.segmentCount || !SegmentBoundsOf(a, s, false, &begin, &end)) continue;  // (checked by the small kernel)
-    if (end - begin <= kMidMax) continue;
-    __syncthreads();  // the previous segment is done (its copy back included)
+  ForEachListedSegment<true>(a, kMidMax, ~0u, [&](uint32_t begin, uint32_t n) {
     SegmentLsd64<KV, ATOMIC_RANK, true>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
-                                        KV ? a.valuesScratch + begin : nullptr, end - begin, smem, order);
-  }
+                                        KV ? a.valuesScratch + begin : nullptr, n, smem, order);
+  });
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs

@@ -343,6 +343,11 @@ static hipError_t Launch(KernelId id, uint32_t grid, hipStream_t stream, Args...
 
 // a form of a family of four, listed as [key-value][atomic rank]
 static KernelId Form(KernelId first, bool keyValue, bool atomicRank) { return KernelId(first + 2 * keyValue + atomicRank); }
+// kKeyOrderUint64 starts the plain kernel, which takes no order word; any other word (checked by the caller) its ordered form
+template <typename... Args>
+static hipError_t LaunchInOrder(uint32_t order, KernelId plain, KernelId ordered, uint32_t grid, hipStream_t stream, Args... args) {
+  return order == kKeyOrderUint64 ? Launch(plain, grid, stream, args...) : Launch(ordered, grid, stream, args..., order);
+}
 
 hipError_t PrepareKernels() {
   for (int id = 0; id < kNumKernels; ++id) {
@@ -483,14 +488,13 @@ hipError_t LaunchSegmentedClear(hipStream_t stream, const Segmented64Args& args)
 hipError_t LaunchSegmented64(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
                              const Segmented64Args& args, uint32_t order) {
   if (grid == 0 || !KeyOrderValid(order)) return hipErrorInvalidValue;
-  if (order == kKeyOrderUint64)
-    return Launch(Form(KernelId(kSegmented64Small + 4 * sizeClass), keyValue, atomicRank), grid, stream, args);
-  return Launch(Form(KernelId(kSegmented64OrderedSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args, order);
+  return LaunchInOrder(order, Form(KernelId(kSegmented64Small + 4 * sizeClass), keyValue, atomicRank),
+                       Form(KernelId(kSegmented64OrderedSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args);
 }
 
 // ---- 64-bit keys ------------------------------------------------------------------------------------
 // one thread per four elements of the bound (the kernels take the count from countPtr where there is one); an empty launch
-// is the planner's business (it lists none).  order == kKeyOrderUint64: the kernels without an order word.
+// is the planner's business (it lists none).
 static uint32_t Sort64Grid(uint32_t maxCount) { return (maxCount + 4u * kSort64Threads - 1u) / (4u * kSort64Threads); }
 static bool Sort64Fits(uint32_t maxCount, uint32_t order = kKeyOrderUint64) {
   return maxCount != 0 && maxCount <= VRDX_MAX_ELEMENTS && KeyOrderValid(order);
@@ -499,31 +503,27 @@ static bool Sort64Fits(uint32_t maxCount, uint32_t order = kKeyOrderUint64) {
 hipError_t LaunchSplit64(hipStream_t stream, bool iota, const uint64_t* keys, uint32_t* lo, uint32_t* other, uint32_t maxCount,
                          const uint32_t* countPtr, uint32_t order) {
   if (!Sort64Fits(maxCount, order)) return hipErrorInvalidValue;
-  const uint32_t grid = Sort64Grid(maxCount);
-  if (order == kKeyOrderUint64) return Launch(iota ? kSplit64Iota : kSplit64, grid, stream, keys, lo, other, maxCount, countPtr);
-  return Launch(iota ? kSplit64OrderedIota : kSplit64Ordered, grid, stream, keys, lo, other, maxCount, countPtr, order);
+  return LaunchInOrder(order, iota ? kSplit64Iota : kSplit64, iota ? kSplit64OrderedIota : kSplit64Ordered, Sort64Grid(maxCount),
+                       stream, keys, lo, other, maxCount, countPtr);
 }
 
 hipError_t LaunchMerge64(hipStream_t stream, uint64_t* keys, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
                          const uint32_t* countPtr, uint32_t order) {
   if (!Sort64Fits(maxCount, order)) return hipErrorInvalidValue;
-  if (order == kKeyOrderUint64) return Launch(kMerge64, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr);
-  return Launch(kMerge64Ordered, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr, order);
+  return LaunchInOrder(order, kMerge64, kMerge64Ordered, Sort64Grid(maxCount), stream, keys, lo, hi, maxCount, countPtr);
 }
 
 hipError_t LaunchGatherHi64(hipStream_t stream, const uint64_t* keys, const uint32_t* index, uint32_t* hi, uint32_t maxCount,
                             const uint32_t* countPtr, uint32_t order) {
   if (!Sort64Fits(maxCount, order)) return hipErrorInvalidValue;
-  if (order == kKeyOrderUint64) return Launch(kGatherHi64, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr);
-  return Launch(kGatherHi64Ordered, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr, order);
+  return LaunchInOrder(order, kGatherHi64, kGatherHi64Ordered, Sort64Grid(maxCount), stream, keys, index, hi, maxCount, countPtr);
 }
 
 hipError_t LaunchPermute64(hipStream_t stream, const uint64_t* keys, const uint32_t* values, const uint32_t* index,
                            uint32_t* hiThenValues, uint64_t* keysOut, uint32_t maxCount, const uint32_t* countPtr, uint32_t order) {
   if (!Sort64Fits(maxCount, order)) return hipErrorInvalidValue;
-  if (order == kKeyOrderUint64)
-    return Launch(kPermute64, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues, keysOut, maxCount, countPtr);
-  return Launch(kPermute64Ordered, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues, keysOut, maxCount, countPtr, order);
+  return LaunchInOrder(order, kPermute64, kPermute64Ordered, Sort64Grid(maxCount), stream, keys, values, index, hiThenValues,
+                       keysOut, maxCount, countPtr);
 }
 
 hipError_t LaunchCopyBack64(hipStream_t stream, uint64_t* keys, uint32_t* values, const uint64_t* keysIn,
