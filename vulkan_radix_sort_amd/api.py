@@ -13,21 +13,11 @@ reference (C++ / Vulkan)                        here
 ``vrdxCmdSortIndirect``                         ``Sorter.cmd_sort_indirect(...)``
 ``vrdxCmdSortKeyValue``                         ``Sorter.cmd_sort_key_value(...)``
 ``vrdxCmdSortKeyValueIndirect``                 ``Sorter.cmd_sort_key_value_indirect(...)``
-``vrdxHipCmdSortSegmented`` (HIP only)          ``Sorter.cmd_sort_segmented(...)``
-``vrdxHipCmdSortSegmentedKeyValue`` (HIP only)  ``Sorter.cmd_sort_segmented_key_value(...)``
-``vrdxHipGetSorter64[KeyValue]Storage...``      ``Sorter.storage_requirements64(n, key_value=False)``
-``vrdxHipCmdSort64`` (HIP only)                 ``Sorter.cmd_sort64(...)``
-``vrdxHipCmdSort64KeyValue`` (HIP only)         ``Sorter.cmd_sort64_key_value(...)``
-``vrdxHipCmdSort64Indirect`` (HIP only)         ``Sorter.cmd_sort64_indirect(...)``
-``vrdxHipCmdSort64KeyValueIndirect`` (HIP only) ``Sorter.cmd_sort64_key_value_indirect(...)``
-``vrdxHipCmdSortSegmented64`` (HIP only)        ``Sorter.cmd_sort_segmented64(...)``
-``vrdxHipCmdSortSegmented64KeyValue`` (HIP only) ``Sorter.cmd_sort_segmented64_key_value(...)``
-``vrdxHipCmdSortBits[KeyValue][Indirect]``      ``Sorter.cmd_sort_bits[_key_value][_indirect](...)``
-``vrdxHipDescribeSortBitsPlan`` (HIP only)      ``Sorter.describe_sort_bits_plan(n, key_value, begin_bit, end_bit)``
-``vrdxHipCmdSortSegmentedBits[KeyValue]``       ``Sorter.cmd_sort_segmented_bits[_key_value](...)``
-``vrdxHipCmdSort64Ordered[KeyValue][Indirect]`` ``Sorter.cmd_sort64_ordered[_key_value][_indirect](...)``
-``vrdxHipCmdSortSegmented64Ordered[KeyValue]``  ``Sorter.cmd_sort_segmented64_ordered[_key_value](...)``
 =============================================  ==============================================
+
+The HIP-only recording calls (segmented, 64-bit, by a bit range, in a key order) stand next to those four in
+``RECORDING_CALLS``, one row each: the exported names, the ctypes signatures and the ``Sorter.cmd_*`` methods all come from
+that table.
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
 ``VkBuffer`` is a device address (``tensor.data_ptr()``), offsets are bytes.  Like the reference,
@@ -36,8 +26,10 @@ the ``cmd_*`` calls validate nothing and never block the host.
 from __future__ import annotations
 
 import ctypes
+import linecache
 import os
-from typing import Optional
+import re
+from typing import NamedTuple, Optional
 
 VK_SUCCESS = 0
 VK_NOT_READY = 1
@@ -48,57 +40,196 @@ VK_ERROR_FEATURE_NOT_PRESENT = -8
 # VK_BUFFER_USAGE_STORAGE_BUFFER_BIT | VK_BUFFER_USAGE_TRANSFER_DST_BIT
 STORAGE_USAGE = 0x20 | 0x02
 
-EXPORTED_SYMBOLS = (
-    # the reference's eight entry points (src/vk_radix_sort.h.in:24-81)
-    "vrdxCreateSorter",
-    "vrdxDestroySorter",
-    "vrdxGetSorterStorageRequirements",
-    "vrdxGetSorterKeyValueStorageRequirements",
-    "vrdxCmdSort",
-    "vrdxCmdSortIndirect",
-    "vrdxCmdSortKeyValue",
-    "vrdxCmdSortKeyValueIndirect",
-    # HIP companions of the Vulkan objects callers create themselves
-    "vrdxHipCreateQueryPool",
-    "vrdxHipDestroyQueryPool",
-    "vrdxHipGetQueryPoolResults",
-    "vrdxHipReadStatus",
-    "vrdxHipReadSorterStatus",
-    "vrdxHipRecheck",
-    "vrdxHipEventOverheadNs",
-    "vrdxHipDescribePlan",
-    "vrdxHipReadPlanVerdict",
-    "vrdxHipReadPlanCounters",
-    "vrdxHipVersionString",
+
+class RecordingCall(NamedTuple):
+    """One vrdx*CmdSort* entry point: its C name, the ``Sorter`` method that forwards to it and that method's docstring (what
+    stands behind the C name, which the method puts in front).  The name says what the call takes --
+    ``vrdx[Hip]CmdSort[Segmented][64][Bits|Ordered][KeyValue][Indirect]`` -- and the argument list follows from that alone,
+    always in this order (``parameters``):
+
+        commandBuffer, sorter, count, [segmentCount, offsets, offsetsOffset | indirect, indirectOffset], keys, keysOffset,
+        [values, valuesOffset], [beginBit, endBit | order], storage, storageOffset, queryPool, query
+
+    No call is both segmented and indirect.  A new variant is a new row."""
+    c_name: str
+    method: str
+    doc: str
+
+    @property
+    def facts(self):
+        """(key bits, segmented, indirect, key+value, None | "Bits" | "Ordered"), parsed from the C name"""
+        segmented, wide, extra, key_value, indirect = re.fullmatch(
+            r"vrdx(?:Hip)?CmdSort(Segmented)?(64)?(Bits|Ordered)?(KeyValue)?(Indirect)?", self.c_name).groups()
+        assert not (segmented and indirect), self.c_name
+        return 64 if wide else 32, bool(segmented), bool(indirect), bool(key_value), extra
+
+    @property
+    def parameters(self):
+        """(Python name, ctypes type) of every argument but the sorter, in the C order"""
+        vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
+        _, segmented, indirect, key_value, extra = self.facts
+        out = [("command_buffer", vp), ("max_element_count" if segmented or indirect else "element_count", u32)]
+        if segmented:
+            out += [("segment_count", u32), ("offsets", vp), ("offsets_offset", u64)]
+        if indirect:
+            out += [("indirect", vp), ("indirect_offset", u64)]
+        out += [("keys", vp), ("keys_offset", u64)]
+        if key_value:
+            out += [("values", vp), ("values_offset", u64)]
+        out += {None: [], "Bits": [("begin_bit", u32), ("end_bit", u32)], "Ordered": [("order", u32)]}[extra]
+        return out + [("storage", vp), ("storage_offset", u64), ("query_pool", vp), ("query", u32)]
+
+    @property
+    def argtypes(self):
+        types = [ctype for _, ctype in self.parameters]
+        return types[:1] + [ctypes.c_void_p] + types[1:]   # the sorter comes second
+
+
+_CALL = RecordingCall
+RECORDING_CALLS = (
+    # the reference's four (src/vk_radix_sort.h.in:46-81)
+    _CALL("vrdxCmdSort", "cmd_sort",
+          "uint32 keys, ascending, in place; storage of ``storage_requirements(n)`` bytes."),
+    _CALL("vrdxCmdSortIndirect", "cmd_sort_indirect",
+          "``cmd_sort`` of the first min(count, ``max_element_count``) keys, the count one uint32 at "
+          "``indirect + indirect_offset`` that is read on the device."),
+    _CALL("vrdxCmdSortKeyValue", "cmd_sort_key_value",
+          "the same as ``cmd_sort`` with values that travel with their keys; storage of "
+          "``key_value_storage_requirements(n)`` bytes."),
+    _CALL("vrdxCmdSortKeyValueIndirect", "cmd_sort_key_value_indirect",
+          "``cmd_sort_indirect`` with values that travel with their keys."),
     # many independent arrays in one call
-    "vrdxHipCmdSortSegmented",
-    "vrdxHipCmdSortSegmentedKeyValue",
+    _CALL("vrdxHipCmdSortSegmented", "cmd_sort_segmented",
+          "segment i = elements [o[i], o[i + 1]) of the keys, o = segment_count + 1 uint32 "
+          "offsets read on the device; every segment sorted on its own, in place."),
+    _CALL("vrdxHipCmdSortSegmentedKeyValue", "cmd_sort_segmented_key_value",
+          "the same with values that travel with their keys."),
     # uint64 keys
-    "vrdxHipGetSorter64StorageRequirements",
-    "vrdxHipGetSorter64KeyValueStorageRequirements",
-    "vrdxHipCmdSort64",
-    "vrdxHipCmdSort64KeyValue",
-    "vrdxHipCmdSort64Indirect",
-    "vrdxHipCmdSort64KeyValueIndirect",
+    _CALL("vrdxHipCmdSort64", "cmd_sort64",
+          "uint64 keys (``keys_offset`` a multiple of 8), ascending and stable, in place; storage of "
+          "``storage_requirements64(n)`` bytes."),
+    _CALL("vrdxHipCmdSort64KeyValue", "cmd_sort64_key_value",
+          "the same with one uint32 value per key; storage of "
+          "``storage_requirements64(n, key_value=True)`` bytes."),
+    _CALL("vrdxHipCmdSort64Indirect", "cmd_sort64_indirect",
+          "``cmd_sort64`` of the first min(count, ``max_element_count``) keys, the count one "
+          "uint32 at ``indirect + indirect_offset`` that is read on the device; storage of "
+          "``storage_requirements64(max_element_count)`` bytes."),
+    _CALL("vrdxHipCmdSort64KeyValueIndirect", "cmd_sort64_key_value_indirect",
+          "the same with one uint32 value per key; storage of "
+          "``storage_requirements64(max_element_count, key_value=True)`` bytes."),
     # many independent arrays of uint64 keys in one call
-    "vrdxHipCmdSortSegmented64",
-    "vrdxHipCmdSortSegmented64KeyValue",
-    # by a bit range of the key
-    "vrdxHipCmdSortBits",
-    "vrdxHipCmdSortBitsKeyValue",
-    "vrdxHipCmdSortBitsIndirect",
-    "vrdxHipCmdSortBitsKeyValueIndirect",
-    "vrdxHipDescribeSortBitsPlan",
-    "vrdxHipCmdSortSegmentedBits",
-    "vrdxHipCmdSortSegmentedBitsKeyValue",
-    # int64, float64 and descending orders of the uint64 sorts
-    "vrdxHipCmdSort64Ordered",
-    "vrdxHipCmdSort64OrderedKeyValue",
-    "vrdxHipCmdSort64OrderedIndirect",
-    "vrdxHipCmdSort64OrderedKeyValueIndirect",
-    "vrdxHipCmdSortSegmented64Ordered",
-    "vrdxHipCmdSortSegmented64OrderedKeyValue",
+    _CALL("vrdxHipCmdSortSegmented64", "cmd_sort_segmented64",
+          "``cmd_sort_segmented`` of uint64 keys (``keys_offset`` a multiple of 8); storage of "
+          "``storage_requirements64(max_element_count)`` bytes."),
+    _CALL("vrdxHipCmdSortSegmented64KeyValue", "cmd_sort_segmented64_key_value",
+          "the same with one uint32 value per key; storage of "
+          "``storage_requirements64(max_element_count, key_value=True)`` bytes."),
+    # by a bit range of the key: the range sits right behind the keys (and values)
+    _CALL("vrdxHipCmdSortBits", "cmd_sort_bits",
+          "stable sort by the bits [begin_bit, end_bit) of the uint32 keys, which move whole; storage "
+          "of ``storage_requirements(n)`` bytes.  Up to 16384 elements (more are refused, except with [0, 32))."),
+    _CALL("vrdxHipCmdSortBitsKeyValue", "cmd_sort_bits_key_value",
+          "the same with values that travel with their keys; storage of "
+          "``key_value_storage_requirements(n)`` bytes."),
+    _CALL("vrdxHipCmdSortBitsIndirect", "cmd_sort_bits_indirect",
+          "``cmd_sort_bits`` of the first min(count, ``max_element_count``) keys, the count "
+          "one uint32 at ``indirect + indirect_offset`` that is read on the device."),
+    _CALL("vrdxHipCmdSortBitsKeyValueIndirect", "cmd_sort_bits_key_value_indirect",
+          "the same with values that travel with their keys."),
+    _CALL("vrdxHipCmdSortSegmentedBits", "cmd_sort_segmented_bits",
+          "``cmd_sort_segmented`` by the bits [begin_bit, end_bit) of the keys -- every "
+          "segment stable by that field, keys moved whole; segments of any size."),
+    _CALL("vrdxHipCmdSortSegmentedBitsKeyValue", "cmd_sort_segmented_bits_key_value",
+          "the same with values that travel with their keys."),
+    # int64, float64 and descending orders of the uint64 sorts: the order word sits where the bit-range sorts have their range
+    _CALL("vrdxHipCmdSort64Ordered", "cmd_sort64_ordered",
+          "``cmd_sort64`` in the order of the word ``order`` (``KEY_UINT64``, ``KEY_INT64`` or "
+          "``KEY_FLOAT64``, ``| ORDER_DESCENDING``): stable in both directions, keys come back bit for bit."),
+    _CALL("vrdxHipCmdSort64OrderedKeyValue", "cmd_sort64_ordered_key_value",
+          "the same with one uint32 value per key."),
+    _CALL("vrdxHipCmdSort64OrderedIndirect", "cmd_sort64_ordered_indirect",
+          "``cmd_sort64_indirect`` in the order of the word ``order``."),
+    _CALL("vrdxHipCmdSort64OrderedKeyValueIndirect", "cmd_sort64_ordered_key_value_indirect",
+          "the same with one uint32 value per key."),
+    _CALL("vrdxHipCmdSortSegmented64Ordered", "cmd_sort_segmented64_ordered",
+          "``cmd_sort_segmented64`` with every segment in the order of the word "
+          "``order``."),
+    _CALL("vrdxHipCmdSortSegmented64OrderedKeyValue", "cmd_sort_segmented64_ordered_key_value",
+          "the same with one uint32 value per key."),
 )
+
+
+def _exported_symbols():
+    """Everything the library exports, in the order this tuple has always had: the entry points that record no sort, by hand,
+    each group followed by the next so many rows of RECORDING_CALLS."""
+    layout = (
+        # the reference's eight entry points (src/vk_radix_sort.h.in:24-81)
+        (("vrdxCreateSorter", "vrdxDestroySorter", "vrdxGetSorterStorageRequirements",
+          "vrdxGetSorterKeyValueStorageRequirements"), 4),
+        # HIP companions of the Vulkan objects callers create themselves; behind them the segmented sorts
+        (("vrdxHipCreateQueryPool", "vrdxHipDestroyQueryPool", "vrdxHipGetQueryPoolResults", "vrdxHipReadStatus",
+          "vrdxHipReadSorterStatus", "vrdxHipRecheck", "vrdxHipEventOverheadNs", "vrdxHipDescribePlan",
+          "vrdxHipReadPlanVerdict", "vrdxHipReadPlanCounters", "vrdxHipVersionString"), 2),
+        # uint64 keys: plain, segmented; then the four sorts by a bit range
+        (("vrdxHipGetSorter64StorageRequirements", "vrdxHipGetSorter64KeyValueStorageRequirements"), 10),
+        # behind it the segmented sorts by a bit range and the ordered 64-bit sorts
+        (("vrdxHipDescribeSortBitsPlan",), 8),
+    )
+    rows = iter(RECORDING_CALLS)
+    for names, recording in layout:
+        yield from names
+        yield from (next(rows).c_name for _ in range(recording))
+    assert next(rows, None) is None, "a row of RECORDING_CALLS is missing from EXPORTED_SYMBOLS"
+
+
+EXPORTED_SYMBOLS = tuple(_exported_symbols())
+
+
+def _compiled(name, source, **names):
+    """The function ``name`` that ``source`` defines, compiled once with ``names`` in reach (the technique of
+    ``collections.namedtuple`` and ``dataclasses``); tracebacks and ``inspect.getsource`` find the text under a file name of
+    its own."""
+    filename = f"<vrdx binding {name}>"
+    namespace = dict(names, __name__=__name__)
+    exec(compile(source, filename, "exec"), namespace)
+    linecache.cache[filename] = (len(source), None, source.splitlines(True), filename)
+    return namespace[name]
+
+
+def _recorder(call: RecordingCall):
+    """``record_sort``'s way to ``call``: a function of everything ``record_sort`` takes that lays out what this call takes
+    in the canonical order, every byte offset 0, and calls the method on the sorter it is handed.  Compiled from the row like
+    the methods themselves (``_recording_method``), for the same reason."""
+    spelled = {"command_buffer": "stream", "element_count": "count", "max_element_count": "count",
+               "begin_bit": "bit_range[0]", "end_bit": "bit_range[1]"}
+    arguments = ["0" if name.endswith("_offset") else f"{name}.data_ptr()" if ctype is ctypes.c_void_p and name not in spelled
+                 else spelled.get(name, name) for name, ctype in call.parameters[:-2]]
+    return _compiled(f"record_{call.method}",
+                     f"def record_{call.method}(sorter, stream, count, offsets, segment_count, indirect, keys, values, "
+                     f"bit_range, order, storage):\n    sorter.{call.method}({', '.join(arguments)})\n")
+
+
+def _takes(key_bits, segmented, indirect, key_value, extra):
+    return key_bits, segmented, indirect, key_value, extra == "Bits", extra == "Ordered"
+
+
+_RECORDERS = {_takes(*call.facts): _recorder(call) for call in RECORDING_CALLS}
+
+
+def record_sort(sorter, key_bits, stream, count, offsets, segment_count, indirect, keys, values, bit_range, order, storage):
+    """Records the one sort of RECORDING_CALLS that takes what the caller has, on ``sorter`` (anything with the ``cmd_*``
+    methods), the arguments in the calls' own order.  ``key_bits``: 32 or 64; ``offsets`` (with ``segment_count``), ``indirect``
+    (the count tensor), ``keys``, ``values`` and ``storage``: objects with a ``data_ptr()``, handed over at byte offset 0;
+    ``bit_range``: (begin_bit, end_bit); ``order``: the order word.  ``None`` selects the call without that argument; a
+    combination no row has is a TypeError.  Every argument is positional: the torch front ends call this once per sort, and
+    keywords cost them more than the rest of the function."""
+    takes = (key_bits, offsets is not None, indirect is not None, values is not None, bit_range is not None, order is not None)
+    recorder = _RECORDERS.get(takes)
+    if recorder is None:
+        raise TypeError(f"no recording call takes (key bits, offsets, indirect, values, bit range, order) = {takes}")
+    recorder(sorter, stream, count, offsets, segment_count, indirect, keys, values, bit_range, order, storage)
+
 
 # the order word of vrdxHipCmdSort64Ordered* and vrdxHipCmdSortSegmented64Ordered* (include/vk_radix_sort.h): one key type,
 # ORDER_DESCENDING or-ed in or not
@@ -218,57 +349,10 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = None
         fn.argtypes = [vp, u32, ctypes.POINTER(VrdxSorterStorageRequirements)]
-    lib.vrdxCmdSort.restype = None
-    lib.vrdxCmdSort.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u32]
-    lib.vrdxCmdSortIndirect.restype = None
-    lib.vrdxCmdSortIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxCmdSortKeyValue.restype = None
-    lib.vrdxCmdSortKeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxCmdSortKeyValueIndirect.restype = None
-    lib.vrdxCmdSortKeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortSegmented.restype = None
-    lib.vrdxHipCmdSortSegmented.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortSegmentedKeyValue.restype = None
-    lib.vrdxHipCmdSortSegmentedKeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxHipCmdSort64.restype = None
-    lib.vrdxHipCmdSort64.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u32]
-    lib.vrdxHipCmdSort64KeyValue.restype = None
-    lib.vrdxHipCmdSort64KeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxHipCmdSort64Indirect.restype = None
-    lib.vrdxHipCmdSort64Indirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxHipCmdSort64KeyValueIndirect.restype = None
-    lib.vrdxHipCmdSort64KeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortSegmented64.restype = None
-    lib.vrdxHipCmdSortSegmented64.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortSegmented64KeyValue.restype = None
-    lib.vrdxHipCmdSortSegmented64KeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, u64, vp, u32]
-    # the range sits right behind the keys (and values): (..., keys, keysOffset[, values, valuesOffset], beginBit, endBit, ...)
-    lib.vrdxHipCmdSortBits.restype = None
-    lib.vrdxHipCmdSortBits.argtypes = [vp, vp, u32, vp, u64, u32, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortBitsKeyValue.restype = None
-    lib.vrdxHipCmdSortBitsKeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortBitsIndirect.restype = None
-    lib.vrdxHipCmdSortBitsIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortBitsKeyValueIndirect.restype = None
-    lib.vrdxHipCmdSortBitsKeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
-    # the segmented sort by a bit range: vrdxHipCmdSortSegmented[KeyValue] with beginBit, endBit in front of the storage
-    lib.vrdxHipCmdSortSegmentedBits.restype = None
-    lib.vrdxHipCmdSortSegmentedBits.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortSegmentedBitsKeyValue.restype = None
-    lib.vrdxHipCmdSortSegmentedBitsKeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, u32, u32, vp, u64, vp, u32]
-    # the order word sits right behind the keys (and values), where the bit-range sorts have their range
-    lib.vrdxHipCmdSort64Ordered.restype = None
-    lib.vrdxHipCmdSort64Ordered.argtypes = [vp, vp, u32, vp, u64, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSort64OrderedKeyValue.restype = None
-    lib.vrdxHipCmdSort64OrderedKeyValue.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSort64OrderedIndirect.restype = None
-    lib.vrdxHipCmdSort64OrderedIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSort64OrderedKeyValueIndirect.restype = None
-    lib.vrdxHipCmdSort64OrderedKeyValueIndirect.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortSegmented64Ordered.restype = None
-    lib.vrdxHipCmdSortSegmented64Ordered.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, u32, vp, u64, vp, u32]
-    lib.vrdxHipCmdSortSegmented64OrderedKeyValue.restype = None
-    lib.vrdxHipCmdSortSegmented64OrderedKeyValue.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, u64, u32, vp, u64, vp, u32]
+    for call in RECORDING_CALLS:
+        fn = getattr(lib, call.c_name)
+        fn.restype = None
+        fn.argtypes = call.argtypes
     lib.vrdxHipDescribeSortBitsPlan.restype = None
     lib.vrdxHipDescribeSortBitsPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
@@ -402,195 +486,7 @@ class Sorter:
         fn(self.handle, max_element_count, ctypes.byref(req))
         return req
 
-    # -- recording --------------------------------------------------------------------------
-    def cmd_sort(self, command_buffer, element_count, keys, keys_offset, storage, storage_offset,
-                 query_pool=None, query=0):
-        self._lib.vrdxCmdSort(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
-                              _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys,
-                          keys_offset, storage, storage_offset, query_pool=None, query=0):
-        self._lib.vrdxCmdSortIndirect(_handle(command_buffer), self.handle, max_element_count,
-                                      _handle(indirect), indirect_offset, _handle(keys), keys_offset,
-                                      _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_key_value(self, command_buffer, element_count, keys, keys_offset, values, values_offset,
-                           storage, storage_offset, query_pool=None, query=0):
-        self._lib.vrdxCmdSortKeyValue(_handle(command_buffer), self.handle, element_count, _handle(keys),
-                                      keys_offset, _handle(values), values_offset, _handle(storage),
-                                      storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_key_value_indirect(self, command_buffer, max_element_count, indirect, indirect_offset,
-                                    keys, keys_offset, values, values_offset, storage, storage_offset,
-                                    query_pool=None, query=0):
-        self._lib.vrdxCmdSortKeyValueIndirect(_handle(command_buffer), self.handle, max_element_count,
-                                              _handle(indirect), indirect_offset, _handle(keys), keys_offset,
-                                              _handle(values), values_offset, _handle(storage),
-                                              storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_segmented(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
-                           keys_offset, storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSortSegmented``: segment i = elements [o[i], o[i + 1]) of the keys, o = segment_count + 1 uint32
-        offsets read on the device; every segment sorted on its own, in place."""
-        self._lib.vrdxHipCmdSortSegmented(_handle(command_buffer), self.handle, max_element_count, segment_count,
-                                          _handle(offsets), offsets_offset, _handle(keys), keys_offset, _handle(storage),
-                                          storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_segmented_key_value(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset,
-                                     keys, keys_offset, values, values_offset, storage, storage_offset, query_pool=None,
-                                     query=0):
-        """``vrdxHipCmdSortSegmentedKeyValue``: the same with values that travel with their keys."""
-        self._lib.vrdxHipCmdSortSegmentedKeyValue(_handle(command_buffer), self.handle, max_element_count, segment_count,
-                                                  _handle(offsets), offsets_offset, _handle(keys), keys_offset,
-                                                  _handle(values), values_offset, _handle(storage), storage_offset,
-                                                  _pool(query_pool), query)
-
-    def cmd_sort_segmented_bits(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
-                                keys_offset, begin_bit, end_bit, storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSortSegmentedBits``: ``cmd_sort_segmented`` by the bits [begin_bit, end_bit) of the keys -- every
-        segment stable by that field, keys moved whole; segments of any size."""
-        self._lib.vrdxHipCmdSortSegmentedBits(_handle(command_buffer), self.handle, max_element_count, segment_count,
-                                              _handle(offsets), offsets_offset, _handle(keys), keys_offset, begin_bit,
-                                              end_bit, _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_segmented_bits_key_value(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset,
-                                          keys, keys_offset, values, values_offset, begin_bit, end_bit, storage,
-                                          storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSortSegmentedBitsKeyValue``: the same with values that travel with their keys."""
-        self._lib.vrdxHipCmdSortSegmentedBitsKeyValue(_handle(command_buffer), self.handle, max_element_count,
-                                                      segment_count, _handle(offsets), offsets_offset, _handle(keys),
-                                                      keys_offset, _handle(values), values_offset, begin_bit, end_bit,
-                                                      _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_segmented64(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
-                             keys_offset, storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSortSegmented64``: ``cmd_sort_segmented`` of uint64 keys (``keys_offset`` a multiple of 8); storage of
-        ``storage_requirements64(max_element_count)`` bytes."""
-        self._lib.vrdxHipCmdSortSegmented64(_handle(command_buffer), self.handle, max_element_count, segment_count,
-                                            _handle(offsets), offsets_offset, _handle(keys), keys_offset, _handle(storage),
-                                            storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_segmented64_key_value(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset,
-                                       keys, keys_offset, values, values_offset, storage, storage_offset, query_pool=None,
-                                       query=0):
-        """``vrdxHipCmdSortSegmented64KeyValue``: the same with one uint32 value per key; storage of
-        ``storage_requirements64(max_element_count, key_value=True)`` bytes."""
-        self._lib.vrdxHipCmdSortSegmented64KeyValue(_handle(command_buffer), self.handle, max_element_count, segment_count,
-                                                    _handle(offsets), offsets_offset, _handle(keys), keys_offset,
-                                                    _handle(values), values_offset, _handle(storage), storage_offset,
-                                                    _pool(query_pool), query)
-
-    def cmd_sort64(self, command_buffer, element_count, keys, keys_offset, storage, storage_offset, query_pool=None,
-                   query=0):
-        """``vrdxHipCmdSort64``: uint64 keys (``keys_offset`` a multiple of 8), ascending and stable, in place; storage of
-        ``storage_requirements64(n)`` bytes."""
-        self._lib.vrdxHipCmdSort64(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
-                                   _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort64_key_value(self, command_buffer, element_count, keys, keys_offset, values, values_offset, storage,
-                             storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSort64KeyValue``: the same with one uint32 value per key; storage of
-        ``storage_requirements64(n, key_value=True)`` bytes."""
-        self._lib.vrdxHipCmdSort64KeyValue(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
-                                           _handle(values), values_offset, _handle(storage), storage_offset,
-                                           _pool(query_pool), query)
-
-    def cmd_sort64_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys, keys_offset, storage,
-                            storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSort64Indirect``: ``cmd_sort64`` of the first min(count, ``max_element_count``) keys, the count
-        one uint32 at ``indirect + indirect_offset`` that is read on the device; storage of
-        ``storage_requirements64(max_element_count)`` bytes."""
-        self._lib.vrdxHipCmdSort64Indirect(_handle(command_buffer), self.handle, max_element_count, _handle(indirect),
-                                           indirect_offset, _handle(keys), keys_offset, _handle(storage), storage_offset,
-                                           _pool(query_pool), query)
-
-    def cmd_sort64_key_value_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys, keys_offset,
-                                      values, values_offset, storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSort64KeyValueIndirect``: the same with one uint32 value per key; storage of
-        ``storage_requirements64(max_element_count, key_value=True)`` bytes."""
-        self._lib.vrdxHipCmdSort64KeyValueIndirect(_handle(command_buffer), self.handle, max_element_count,
-                                                   _handle(indirect), indirect_offset, _handle(keys), keys_offset,
-                                                   _handle(values), values_offset, _handle(storage), storage_offset,
-                                                   _pool(query_pool), query)
-
-    def cmd_sort64_ordered(self, command_buffer, element_count, keys, keys_offset, order, storage, storage_offset,
-                           query_pool=None, query=0):
-        """``vrdxHipCmdSort64Ordered``: ``cmd_sort64`` in the order of the word ``order`` (``KEY_UINT64``, ``KEY_INT64`` or
-        ``KEY_FLOAT64``, ``| ORDER_DESCENDING``): stable in both directions, keys come back bit for bit."""
-        self._lib.vrdxHipCmdSort64Ordered(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
-                                          order, _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort64_ordered_key_value(self, command_buffer, element_count, keys, keys_offset, values, values_offset, order,
-                                     storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSort64OrderedKeyValue``: the same with one uint32 value per key."""
-        self._lib.vrdxHipCmdSort64OrderedKeyValue(_handle(command_buffer), self.handle, element_count, _handle(keys),
-                                                  keys_offset, _handle(values), values_offset, order, _handle(storage),
-                                                  storage_offset, _pool(query_pool), query)
-
-    def cmd_sort64_ordered_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys, keys_offset,
-                                    order, storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSort64OrderedIndirect``: ``cmd_sort64_indirect`` in the order of the word ``order``."""
-        self._lib.vrdxHipCmdSort64OrderedIndirect(_handle(command_buffer), self.handle, max_element_count,
-                                                  _handle(indirect), indirect_offset, _handle(keys), keys_offset, order,
-                                                  _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort64_ordered_key_value_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys,
-                                              keys_offset, values, values_offset, order, storage, storage_offset,
-                                              query_pool=None, query=0):
-        """``vrdxHipCmdSort64OrderedKeyValueIndirect``: the same with one uint32 value per key."""
-        self._lib.vrdxHipCmdSort64OrderedKeyValueIndirect(_handle(command_buffer), self.handle, max_element_count,
-                                                          _handle(indirect), indirect_offset, _handle(keys), keys_offset,
-                                                          _handle(values), values_offset, order, _handle(storage),
-                                                          storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_segmented64_ordered(self, command_buffer, max_element_count, segment_count, offsets, offsets_offset, keys,
-                                     keys_offset, order, storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSortSegmented64Ordered``: ``cmd_sort_segmented64`` with every segment in the order of the word
-        ``order``."""
-        self._lib.vrdxHipCmdSortSegmented64Ordered(_handle(command_buffer), self.handle, max_element_count, segment_count,
-                                                   _handle(offsets), offsets_offset, _handle(keys), keys_offset, order,
-                                                   _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_segmented64_ordered_key_value(self, command_buffer, max_element_count, segment_count, offsets,
-                                               offsets_offset, keys, keys_offset, values, values_offset, order, storage,
-                                               storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSortSegmented64OrderedKeyValue``: the same with one uint32 value per key."""
-        self._lib.vrdxHipCmdSortSegmented64OrderedKeyValue(_handle(command_buffer), self.handle, max_element_count,
-                                                           segment_count, _handle(offsets), offsets_offset, _handle(keys),
-                                                           keys_offset, _handle(values), values_offset, order,
-                                                           _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_bits(self, command_buffer, element_count, keys, keys_offset, begin_bit, end_bit, storage, storage_offset,
-                      query_pool=None, query=0):
-        """``vrdxHipCmdSortBits``: stable sort by the bits [begin_bit, end_bit) of the uint32 keys, which move whole;
-        storage of ``storage_requirements(n)`` bytes.  Up to 16384 elements (more are refused, except with [0, 32))."""
-        self._lib.vrdxHipCmdSortBits(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
-                                     begin_bit, end_bit, _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_bits_key_value(self, command_buffer, element_count, keys, keys_offset, values, values_offset, begin_bit,
-                                end_bit, storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSortBitsKeyValue``: the same with values that travel with their keys; storage of
-        ``key_value_storage_requirements(n)`` bytes."""
-        self._lib.vrdxHipCmdSortBitsKeyValue(_handle(command_buffer), self.handle, element_count, _handle(keys), keys_offset,
-                                             _handle(values), values_offset, begin_bit, end_bit, _handle(storage),
-                                             storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_bits_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys, keys_offset,
-                               begin_bit, end_bit, storage, storage_offset, query_pool=None, query=0):
-        """``vrdxHipCmdSortBitsIndirect``: ``cmd_sort_bits`` of the first min(count, ``max_element_count``) keys, the count
-        one uint32 at ``indirect + indirect_offset`` that is read on the device."""
-        self._lib.vrdxHipCmdSortBitsIndirect(_handle(command_buffer), self.handle, max_element_count, _handle(indirect),
-                                             indirect_offset, _handle(keys), keys_offset, begin_bit, end_bit,
-                                             _handle(storage), storage_offset, _pool(query_pool), query)
-
-    def cmd_sort_bits_key_value_indirect(self, command_buffer, max_element_count, indirect, indirect_offset, keys,
-                                         keys_offset, values, values_offset, begin_bit, end_bit, storage, storage_offset,
-                                         query_pool=None, query=0):
-        """``vrdxHipCmdSortBitsKeyValueIndirect``: the same with values that travel with their keys."""
-        self._lib.vrdxHipCmdSortBitsKeyValueIndirect(_handle(command_buffer), self.handle, max_element_count,
-                                                     _handle(indirect), indirect_offset, _handle(keys), keys_offset,
-                                                     _handle(values), values_offset, begin_bit, end_bit, _handle(storage),
-                                                     storage_offset, _pool(query_pool), query)
+    # -- recording: the cmd_* methods, one per row of RECORDING_CALLS, are attached below the class ------------------
 
     # -- diagnostics ------------------------------------------------------------------------
     def read_status(self, command_buffer, storage, storage_offset=0) -> int:
@@ -650,3 +546,22 @@ def _pool(p) -> Optional[int]:
     if isinstance(p, QueryPool):
         return p.handle
     return _handle(p)
+
+
+def _recording_method(call: RecordingCall):
+    """``Sorter.<call.method>``, compiled from source text built from the row, so that a call costs what a hand-written method
+    costs: pointer-like arguments go through ``_handle``, the query pool through ``_pool``, everything else as it comes,
+    ``self.handle`` second."""
+    names = [name for name, _ in call.parameters]
+    forwarded = ["_pool(query_pool)" if name == "query_pool" else f"_handle({name})" if ctype is ctypes.c_void_p else name
+                 for name, ctype in call.parameters]
+    forwarded.insert(1, "self.handle")
+    method = _compiled(call.method, f"def {call.method}(self, {', '.join(names[:-2])}, query_pool=None, query=0):\n"
+                                    f"    self._lib.{call.c_name}({', '.join(forwarded)})\n", _handle=_handle, _pool=_pool)
+    method.__qualname__ = f"Sorter.{call.method}"
+    method.__doc__ = f"``{call.c_name}``: {call.doc}"
+    return method
+
+
+for _call in RECORDING_CALLS:
+    setattr(Sorter, _call.method, _recording_method(_call))

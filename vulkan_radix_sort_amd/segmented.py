@@ -8,31 +8,9 @@ their segment alone and raise ``STATUS_SEGMENTS_INVALID`` (``Sorter.read_status`
 """
 from __future__ import annotations
 
-from .api import Sorter
-
-MAX_ELEMENTS = 0x3FFFFFFC  # VRDX_MAX_ELEMENTS (vrdx_layout.h)
-
-
-def _four_byte_integer_dtypes(torch):
-    dtypes = [torch.int32]
-    if hasattr(torch, "uint32"):
-        dtypes.append(torch.uint32)
-    return tuple(dtypes)
-
-
-def _check_array(torch, name, t, device=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
-    if t.dtype not in _four_byte_integer_dtypes(torch):
-        raise TypeError(f"{name} must hold 4-byte integers (int32 or uint32, sorted as uint32), got {t.dtype}")
-    if t.dim() != 1:
-        raise ValueError(f"{name} must be one-dimensional, got shape {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    if t.device.type != "cuda":
-        raise ValueError(f"{name} must live on a GPU, got {t.device}")
-    if device is not None and t.device != device:
-        raise ValueError(f"{name} is on {t.device}, keys are on {device}")
+from . import _checks as check
+from ._checks import MAX_ELEMENTS  # noqa: F401 -- importable from here as it always was
+from .api import Sorter, record_sort
 
 
 def sort_segments(sorter: Sorter, keys, offsets, values=None, storage=None):
@@ -41,33 +19,18 @@ def sort_segments(sorter: Sorter, keys, offsets, values=None, storage=None):
     bytes on the keys' device, allocated here when omitted.  Returns the storage used (one sort in flight per storage)."""
     import torch
 
-    _check_array(torch, "keys", keys)
-    _check_array(torch, "offsets", offsets, keys.device)
-    if offsets.numel() < 1:
-        raise ValueError("offsets must hold segment_count + 1 >= 1 entries")
+    what = "4-byte integers (int32 or uint32, sorted as uint32)"
+    check.check_tensor(torch, "keys", keys, check.integer_dtypes(torch)[0], what, gpu=True)
+    device = keys.device
+    check.check_offsets(torch, offsets, what, device)
     if values is not None:
-        _check_array(torch, "values", values, keys.device)
-        if values.numel() != keys.numel():
-            raise ValueError(f"values hold {values.numel()} elements, keys {keys.numel()}")
-    n = keys.numel()
-    if n > MAX_ELEMENTS:
-        raise ValueError(f"{n} keys: at most {MAX_ELEMENTS} per call")
-    segment_count = offsets.numel() - 1
+        check.check_values(torch, values, keys, what, device)
+    n = check.key_count(keys)
     required = (sorter.key_value_storage_requirements(n) if values is not None else sorter.storage_requirements(n)).size
-    if storage is None:
-        storage = torch.empty(required, dtype=torch.uint8, device=keys.device)
-    else:
-        if not isinstance(storage, torch.Tensor) or storage.dtype != torch.uint8 or not storage.is_contiguous():
-            raise TypeError("storage must be a contiguous uint8 torch.Tensor")
-        if storage.device != keys.device:
-            raise ValueError(f"storage is on {storage.device}, keys are on {keys.device}")
-        if storage.numel() < required:
-            raise ValueError(f"storage holds {storage.numel()} bytes, the sort needs {required}")
-    stream = torch.cuda.current_stream(keys.device).cuda_stream
-    if values is None:
-        sorter.cmd_sort_segmented(stream, n, segment_count, offsets.data_ptr(), 0, keys.data_ptr(), 0,
-                                  storage.data_ptr(), 0)
-    else:
-        sorter.cmd_sort_segmented_key_value(stream, n, segment_count, offsets.data_ptr(), 0, keys.data_ptr(), 0,
-                                            values.data_ptr(), 0, storage.data_ptr(), 0)
+    if storage is not None:
+        check.check_storage(torch, storage, device)
+    storage = check.storage_or_new(torch, storage, required, device)
+    # (sorter, key bits, stream, count, offsets, segment count, indirect, keys, values, bit range, order, storage)
+    record_sort(sorter, 32, torch.cuda.current_stream(device).cuda_stream, n, offsets, offsets.numel() - 1, None, keys, values,
+                None, None, storage)
     return storage

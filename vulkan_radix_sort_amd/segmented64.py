@@ -12,9 +12,8 @@ alone and raise ``STATUS_SEGMENTS_INVALID``.
 """
 from __future__ import annotations
 
-from .api import Sorter
-from .segmented import MAX_ELEMENTS, _four_byte_integer_dtypes
-from .sort64 import _check_array, _check_keys
+from . import _checks as check
+from .api import Sorter, record_sort
 
 
 def sort_segments64(sorter: Sorter, keys, offsets, values=None, storage=None, order=None, descending=False):
@@ -25,43 +24,17 @@ def sort_segments64(sorter: Sorter, keys, offsets, values=None, storage=None, or
     ``descending=False`` is the unsigned ascending sort.  Returns the storage used (one sort in flight per storage)."""
     import torch
 
-    four = _four_byte_integer_dtypes(torch)
-    word = _check_keys(torch, keys, order, descending)
-    _check_array(torch, "offsets", offsets, four, "4-byte integers (int32 or uint32)", keys.device)
-    if offsets.numel() < 1:
-        raise ValueError("offsets must hold segment_count + 1 >= 1 entries")
+    word = check.check_keys(torch, keys, order, descending)
+    device = keys.device
+    check.check_offsets(torch, offsets, "4-byte integers (int32 or uint32)", device)
     if values is not None:
-        _check_array(torch, "values", values, four, "4-byte integers (int32 or uint32)", keys.device)
-        if values.numel() != keys.numel():
-            raise ValueError(f"values hold {values.numel()} elements, keys {keys.numel()}")
-    n = keys.numel()
-    if n > MAX_ELEMENTS:
-        raise ValueError(f"{n} keys: at most {MAX_ELEMENTS} per call")
-    segment_count = offsets.numel() - 1
+        check.check_values(torch, values, keys, "4-byte integers (int32 or uint32)", device)
+    n = check.key_count(keys)
     if storage is not None:
-        if not isinstance(storage, torch.Tensor) or storage.dtype != torch.uint8 or not storage.is_contiguous():
-            raise TypeError("storage must be a contiguous uint8 torch.Tensor")
-        if storage.device != keys.device:
-            raise ValueError(f"storage is on {storage.device}, keys are on {keys.device}")
-        if storage.data_ptr() % 16 != 0:
-            raise ValueError("storage must start on a 16-byte boundary")
+        check.check_storage(torch, storage, device, True)
     required = sorter.storage_requirements64(n, key_value=values is not None).size
-    if storage is None:
-        storage = torch.empty(required, dtype=torch.uint8, device=keys.device)
-    elif storage.numel() < required:
-        raise ValueError(f"storage holds {storage.numel()} bytes, the sort needs {required}")
-    stream = torch.cuda.current_stream(keys.device).cuda_stream
-    if word is not None:
-        if values is None:
-            sorter.cmd_sort_segmented64_ordered(stream, n, segment_count, offsets.data_ptr(), 0, keys.data_ptr(), 0, word,
-                                                storage.data_ptr(), 0)
-        else:
-            sorter.cmd_sort_segmented64_ordered_key_value(stream, n, segment_count, offsets.data_ptr(), 0, keys.data_ptr(), 0,
-                                                          values.data_ptr(), 0, word, storage.data_ptr(), 0)
-    elif values is None:
-        sorter.cmd_sort_segmented64(stream, n, segment_count, offsets.data_ptr(), 0, keys.data_ptr(), 0,
-                                    storage.data_ptr(), 0)
-    else:
-        sorter.cmd_sort_segmented64_key_value(stream, n, segment_count, offsets.data_ptr(), 0, keys.data_ptr(), 0,
-                                              values.data_ptr(), 0, storage.data_ptr(), 0)
+    storage = check.storage_or_new(torch, storage, required, device)
+    # (sorter, key bits, stream, count, offsets, segment count, indirect, keys, values, bit range, order, storage)
+    record_sort(sorter, 64, torch.cuda.current_stream(device).cuda_stream, n, offsets, offsets.numel() - 1, None, keys, values,
+                None, word, storage)
     return storage

@@ -17,9 +17,8 @@ values are never read, so the call does not synchronise and can be captured into
 """
 from __future__ import annotations
 
-from .api import Sorter
-from .segmented import MAX_ELEMENTS
-from .sort_bits import _check_device, _check_tensor, _four_byte_integers
+from . import _checks as check
+from .api import Sorter, record_sort
 
 
 def sort_segments_bits(sorter: Sorter, keys, offsets, begin_bit, end_bit, values=None, storage=None):
@@ -29,42 +28,24 @@ def sort_segments_bits(sorter: Sorter, keys, offsets, begin_bit, end_bit, values
     Returns the storage used (one sort in flight per storage)."""
     import torch
 
-    for name, bit in (("begin_bit", begin_bit), ("end_bit", end_bit)):
-        if isinstance(bit, bool) or not isinstance(bit, int):
-            raise TypeError(f"{name} must be an int, got {type(bit).__name__}")
-    if not 0 <= begin_bit <= end_bit <= 32:
-        raise ValueError(f"the bit range [{begin_bit}, {end_bit}) is not inside [0, 32] with begin_bit <= end_bit")
-    four_bytes = _four_byte_integers(torch)
-    _check_tensor(torch, "keys", keys, four_bytes, "4-byte integers (int32 or uint32, ordered as uint32 fields)")
-    _check_tensor(torch, "offsets", offsets, four_bytes, "4-byte integers (int32 or uint32)")
-    if offsets.numel() < 1:
-        raise ValueError("offsets must hold segment_count + 1 >= 1 entries")
+    check.check_bit_range(begin_bit, end_bit)
+    check.check_tensor(torch, "keys", keys, check.integer_dtypes(torch)[0],
+                       "4-byte integers (int32 or uint32, ordered as uint32 fields)")
+    check.check_offsets(torch, offsets, "4-byte integers (int32 or uint32)")
     if values is not None:
-        _check_tensor(torch, "values", values, four_bytes, "4-byte integers (int32 or uint32)")
-        if values.numel() != keys.numel():
-            raise ValueError(f"values hold {values.numel()} elements, keys {keys.numel()}")
-    n = keys.numel()
-    if n > MAX_ELEMENTS:
-        raise ValueError(f"{n} keys: at most {MAX_ELEMENTS} per call")
-    if storage is not None and (not isinstance(storage, torch.Tensor) or storage.dtype != torch.uint8
-                                or not storage.is_contiguous()):
-        raise TypeError("storage must be a contiguous uint8 torch.Tensor")
+        check.check_values(torch, values, keys, "4-byte integers (int32 or uint32)")
+    n = check.key_count(keys)
+    if storage is not None:
+        check.check_storage(torch, storage)
     # where they live
-    _check_device("keys", keys, keys)
+    check.check_device("keys", keys)
+    device = keys.device
     for name, t in (("offsets", offsets), ("values", values), ("storage", storage)):
         if t is not None:
-            _check_device(name, t, keys)
-    segment_count = offsets.numel() - 1
+            check.check_device(name, t, device)
     required = (sorter.key_value_storage_requirements(n) if values is not None else sorter.storage_requirements(n)).size
-    if storage is None:
-        storage = torch.empty(required, dtype=torch.uint8, device=keys.device)
-    elif storage.numel() < required:
-        raise ValueError(f"storage holds {storage.numel()} bytes, the sort needs {required}")
-    stream = torch.cuda.current_stream(keys.device).cuda_stream
-    if values is None:
-        sorter.cmd_sort_segmented_bits(stream, n, segment_count, offsets.data_ptr(), 0, keys.data_ptr(), 0, begin_bit, end_bit,
-                                       storage.data_ptr(), 0)
-    else:
-        sorter.cmd_sort_segmented_bits_key_value(stream, n, segment_count, offsets.data_ptr(), 0, keys.data_ptr(), 0,
-                                                 values.data_ptr(), 0, begin_bit, end_bit, storage.data_ptr(), 0)
+    storage = check.storage_or_new(torch, storage, required, device)
+    # (sorter, key bits, stream, count, offsets, segment count, indirect, keys, values, bit range, order, storage)
+    record_sort(sorter, 32, torch.cuda.current_stream(device).cuda_stream, n, offsets, offsets.numel() - 1, None, keys, values,
+                (begin_bit, end_bit), None, storage)
     return storage
