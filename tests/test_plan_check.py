@@ -5,6 +5,7 @@ import subprocess
 
 import pytest
 
+import hybrid_bucket_cases
 import msd_bucket_cases
 import plan_check_tool as tool
 import plan_model as model
@@ -45,6 +46,7 @@ PLANTED_ATOMIC = (
        (storage_reuse_cases.TAIL_SPLIT_N, "msd", storage_reuse_cases.MSD_BITS, 18432),
        (storage_reuse_cases.BLOCK_SUMS_N, "msd", storage_reuse_cases.MSD_BITS, 18432), (ROUND, "msd", 10, 18432)]
     + [(f.bound, "msd", f.bits, f.cap) for f in msd_bucket_cases.FORMS.values()]
+    + [(n, "hybrid-8", 8, 0) for f in hybrid_bucket_cases.FORMS.values() for n in (f.bound, f.filled) if n is not None]
     + [(n, "one-workgroup", 0, 0) for n in alignment.ONE_WORKGROUP_SIZES]
     + [(n, "hybrid-8", 8, 0) for n, _ in alignment.HYBRID_ROWS]
     + [(n, "msd", 10, 18432) for n, _, _ in _params(alignment.test_msd_plan_with_half_size_buckets, "n,a_keys,a_values")]
