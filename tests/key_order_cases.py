@@ -88,6 +88,12 @@ def expected_segments(keys, values, offsets, max_count, order, descending=False)
     return T_inverse(tk, order, descending), ev
 
 
+def assert_same(got_keys, got_values, want, what=""):
+    assert np.array_equal(got_keys, want[0]), f"{what}: keys"
+    if got_values is not None:
+        assert np.array_equal(got_values, want[1]), f"{what}: values"
+
+
 # ---- key builders ----------------------------------------------------------------------------------------------------------
 
 INT_EDGES = np.array([1 << 63, (1 << 64) - 1, 0, (1 << 63) - 1, 1, (1 << 63) + 1, (1 << 64) - 2], np.uint64)  # MIN -1 0 MAX ...

@@ -1,26 +1,17 @@
-"""What the GPU tests of the segmented sort of 64-bit keys share (tests/test_segmented64_gpu.py): key patterns, and one
-guarded call of vrdxHipCmdSortSegmented64[KeyValue].  The sorters of both ranking forms, the payloads, the reference --
-np.lexsort((keys, segment id)) over the whole call -- and the offset builder are those of segmented_cases.py, which works
-on keys of any width.  A plain module, imported the same way."""
+"""What the GPU tests of the segmented sort of 64-bit keys share (tests/test_segmented64_gpu.py): key patterns; the guarded
+call is segmented_cases.run_segmented, which takes the key width from the keys' dtype.  The sorters of both ranking forms,
+the payloads, the reference -- np.lexsort((keys, segment id)) over the whole call -- and the offset builder are those of
+segmented_cases.py, which works on keys of any width.  A plain module, imported the same way."""
 import numpy as np
 
-from segmented_cases import GUARD, _dev, _host
+from segmented_cases import run_segmented as run_segmented64   # (the key width is the keys' dtype)
 
-GUARD64 = 0x5A5A5A5A5A5A5A5A
 ONES = 0xFFFFFFFFFFFFFFFF
 
 SMALL_MAX = 4096
 MID_MAX = 16384            # keys-only
 MID_MAX_KEY_VALUE = 8192   # key+value
 LARGE_TILE = 8192
-
-
-def _dev64(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).cuda()
-
-
-def _host64(t):
-    return t.cpu().numpy().view(np.uint64)
 
 
 def uniform64(n, rng):
@@ -69,60 +60,6 @@ def make_keys64(kind, n, rng):
         u[:16384] = (u[:16384] & np.uint64(ONES ^ (0xFF << (8 * p)))) | np.uint64(0x5A << (8 * p))
         return u
     raise ValueError(kind)
-
-
-def run_segmented64(torch, sorter, keys, offsets, values=None, *, keys_off=0, values_off=0, offsets_off=0, storage_off=0,
-                    guard=256, pool=None, expect_status=0, storage=None, max_count=None):
-    """One vrdxHipCmdSortSegmented64[KeyValue] with maxElementCount = len(keys): the keys (values) sit `*_off` bytes into
-    buffers that carry `guard` elements of guard words in front of them and behind maxElementCount, the storage has a guard
-    band behind its requirement; every guard, the bytes in front of the storage offset and the offsets themselves are
-    checked afterwards, and the failure word is compared with `expect_status`.  Returns the keys and values as sorted by
-    the device and the storage tensor."""
-    n = len(keys) if max_count is None else max_count
-    assert keys_off % 8 == 0 and values_off % 4 == 0 and offsets_off % 4 == 0 and storage_off % 16 == 0
-    stream = torch.cuda.current_stream().cuda_stream
-    kw, vw = guard + keys_off // 8, guard + values_off // 4
-    kb = np.full(kw + n + guard, GUARD64, np.uint64)
-    kb[kw:kw + len(keys)] = keys
-    dk = _dev64(torch, kb)
-    dv = None
-    if values is not None:
-        vb = np.full(vw + n + guard, GUARD, np.uint32)
-        vb[vw:vw + len(values)] = values
-        dv = _dev(torch, vb)
-    ob = np.full(offsets_off // 4 + len(offsets) + 4, GUARD, np.uint32)
-    ob[offsets_off // 4:offsets_off // 4 + len(offsets)] = np.asarray(offsets, dtype=np.uint32)
-    do = _dev(torch, ob)
-    req = sorter.storage_requirements64(n, key_value=values is not None).size
-    if storage is None:
-        storage = torch.full((storage_off + req + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-        storage[storage_off + req:] = 0x5A
-    assert storage.data_ptr() % 16 == 0
-    end = storage_off + req
-    front = storage[:storage_off].clone()
-    behind = storage[end:].clone()
-    if values is None:
-        sorter.cmd_sort_segmented64(stream, n, len(offsets) - 1, do.data_ptr(), offsets_off, dk.data_ptr(), 8 * kw,
-                                    storage.data_ptr(), storage_off, pool, 0)
-    else:
-        sorter.cmd_sort_segmented64_key_value(stream, n, len(offsets) - 1, do.data_ptr(), offsets_off, dk.data_ptr(),
-                                              8 * kw, dv.data_ptr(), 4 * vw, storage.data_ptr(), storage_off, pool, 0)
-    torch.cuda.synchronize()
-    status = sorter.read_status(stream, storage.data_ptr(), storage_off)
-    assert status == expect_status, (status, expect_status)
-    assert bool((storage[:storage_off] == front).all()), "wrote in front of the storage offset"
-    assert bool((storage[end:] == behind).all()), "wrote past the storage requirement"
-    assert np.array_equal(_host(do), ob), "the offsets changed"
-    hk = _host64(dk)
-    assert (hk[:kw] == GUARD64).all(), "wrote in front of the keys"
-    assert (hk[kw + n:] == GUARD64).all(), "wrote behind maxElementCount (keys)"
-    gk, gv = hk[kw:kw + n].copy(), None
-    if dv is not None:
-        hv = _host(dv)
-        assert (hv[:vw] == GUARD).all(), "wrote in front of the values"
-        assert (hv[vw + n:] == GUARD).all(), "wrote behind maxElementCount (values)"
-        gv = hv[vw:vw + n].copy()
-    return gk, gv, storage
 
 
 def both_forms(torch, sorter, keys, offsets, values, want=None, **kw):

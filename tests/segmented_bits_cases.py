@@ -17,7 +17,7 @@ import zlib
 import numpy as np
 
 import sort_bits_cases as bits
-from segmented_cases import (GUARD, _dev, _host, ballot_sorter, mixed_offsets, sorter, torch_mod)  # noqa: F401
+from segmented_cases import mixed_offsets, run_segmented
 from sort_bits_cases import EMPTY_RANGE, FULL_RANGE, RANGES, digits_of, field, non_degenerate, payload  # noqa: F401
 
 SMALL_MAX, MID_MAX, TILE = 4096, 16384, 16384   # kSegSmallMax, kSegMidMax, kSegLargeTile (vrdx_kernels.h)
@@ -89,57 +89,9 @@ def expected(keys, values, offsets, max_count, begin, end):
     return ek, ev
 
 
-def run_segmented_bits(torch, sorter, keys, offsets, begin, end, values=None, *, keys_off=0, values_off=0, offsets_off=0,
-                       storage_off=0, guard=256, pool=None, expect_status=0, storage=None):
-    """One vrdxHipCmdSortSegmentedBits[KeyValue] with maxElementCount = len(keys), guarded like
-    segmented_cases.run_segmented: `guard` words of GUARD behind the keys and the values, a guard band behind the storage
-    requirement, the bytes in front of every offset and the offsets themselves checked afterwards.  Returns the keys and
-    values as the device left them and the storage tensor."""
-    n = len(keys)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def buffer(a, off):
-        w = off // 4
-        buf = np.full(w + n + guard, GUARD, np.uint32)
-        buf[w:w + n] = a
-        return _dev(torch, buf)
-
-    dk = buffer(keys, keys_off)
-    dv = buffer(values, values_off) if values is not None else None
-    ob = np.full(offsets_off // 4 + len(offsets) + 4, GUARD, np.uint32)
-    ob[offsets_off // 4:offsets_off // 4 + len(offsets)] = np.asarray(offsets, dtype=np.uint32)
-    do = _dev(torch, ob)
-    req = (sorter.key_value_storage_requirements(n) if values is not None else sorter.storage_requirements(n)).size
-    if storage is None:
-        storage = torch.full((storage_off + req + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-        storage[storage_off + req:] = 0x5A
-    stop = storage_off + req
-    front = storage[:storage_off].clone()
-    behind = storage[stop:].clone()
-    if values is None:
-        sorter.cmd_sort_segmented_bits(stream, n, len(offsets) - 1, do.data_ptr(), offsets_off, dk.data_ptr(), keys_off,
-                                       begin, end, storage.data_ptr(), storage_off, pool, 0)
-    else:
-        sorter.cmd_sort_segmented_bits_key_value(stream, n, len(offsets) - 1, do.data_ptr(), offsets_off, dk.data_ptr(),
-                                                 keys_off, dv.data_ptr(), values_off, begin, end, storage.data_ptr(),
-                                                 storage_off, pool, 0)
-    torch.cuda.synchronize()
-    if expect_status is not None:
-        assert sorter.read_status(stream, storage.data_ptr(), storage_off) == expect_status
-    assert bool((storage[:storage_off] == front).all()), "wrote in front of the storage offset"
-    assert bool((storage[stop:] == behind).all()), "wrote past the storage requirement"
-    assert np.array_equal(_host(do), ob), "the offsets changed"
-    outs = []
-    for d, off in ((dk, keys_off), (dv, values_off)):
-        if d is None:
-            outs.append(None)
-            continue
-        h = _host(d)
-        w = off // 4
-        assert (h[:w] == GUARD).all(), "wrote in front of the keys / values offset"
-        assert (h[w + n:] == GUARD).all(), "wrote behind maxElementCount"
-        outs.append(h[w:w + n].copy())
-    return outs[0], outs[1], storage
+def run_segmented_bits(torch, sorter, keys, offsets, begin, end, values=None, **kw):
+    """segmented_cases.run_segmented by the bits [begin, end); expect_status=None: the failure word is not read"""
+    return run_segmented(torch, sorter, keys, offsets, values, bit_range=(begin, end), **kw)
 
 
 def check(got_k, got_v, keys, values, offsets, begin, end, want=None):

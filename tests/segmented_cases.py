@@ -1,51 +1,12 @@
 """What the GPU tests of the segmented sort share (tests/test_segmented_gpu.py, tests/test_segmented_reuse_gpu.py): the
 sorters of both ranking forms, key and payload patterns, the reference -- np.lexsort((keys, segment id)) over the whole
-call -- and one guarded call of vrdxHipCmdSortSegmented[KeyValue].  A plain module next to plan_model.py, imported the same
-way; the fixtures are module-scoped, so every test file that imports them gets sorters of its own."""
-import os
-
+call -- and the guarded call of the segmented sorts.  A plain module next to plan_model.py, imported the same way; the
+fixtures are those of guarded_call.py."""
 import numpy as np
-import pytest
 
-GUARD = 0x5A5A5A5A
+from guarded_call import ballot_sorter, guarded_call, sorter, torch_mod  # noqa: F401 (fixtures, re-exported)
 
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    return torch
-
-
-@pytest.fixture(scope="module")
-def sorter(torch_mod):
-    import vulkan_radix_sort_amd as vrdx
-    s = vrdx.Sorter()
-    yield s
-    s.destroy()
-
-
-@pytest.fixture(scope="module")
-def ballot_sorter(torch_mod):
-    import vulkan_radix_sort_amd as vrdx
-    old = os.environ.get("VRDX_RANK")
-    os.environ["VRDX_RANK"] = "ballot"  # read by vrdxCreateSorter
-    try:
-        s = vrdx.Sorter()
-    finally:
-        if old is None:
-            del os.environ["VRDX_RANK"]
-        else:
-            os.environ["VRDX_RANK"] = old
-    yield s
-    s.destroy()
-
-
-def _dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint32)
+GUARD = 0x5A5A5A5A   # the word tests put around arrays they lay out themselves
 
 
 def make_keys(kind, n, rng):
@@ -114,55 +75,13 @@ def expected(keys, values, offsets, max_count):
     return ek, ev
 
 
-def run_segmented(torch, sorter, keys, offsets, values=None, *, keys_off=0, values_off=0, offsets_off=0, storage_off=0,
-                  guard=256, pool=None, expect_status=0, storage=None):
-    """One vrdxHipCmdSortSegmented[KeyValue] with maxElementCount = len(keys): the keys (values) sit `*_off` bytes into
-    buffers that carry `guard` words of GUARD behind maxElementCount, the storage has a guard band behind its requirement;
-    every guard, the bytes in front of the offsets and the offsets themselves are checked afterwards.  Returns the keys and
-    values as sorted by the device and the storage tensor."""
-    n = len(keys)
-    stream = torch.cuda.current_stream().cuda_stream
-
-    def buffer(a, off):
-        w = off // 4
-        buf = np.full(w + n + guard, GUARD, np.uint32)
-        buf[w:w + n] = a
-        return _dev(torch, buf)
-
-    dk = buffer(keys, keys_off)
-    dv = buffer(values, values_off) if values is not None else None
-    ob = np.full(offsets_off // 4 + len(offsets) + 4, GUARD, np.uint32)
-    ob[offsets_off // 4:offsets_off // 4 + len(offsets)] = np.asarray(offsets, dtype=np.uint32)
-    do = _dev(torch, ob)
-    req = (sorter.key_value_storage_requirements(n) if values is not None else sorter.storage_requirements(n)).size
-    if storage is None:
-        storage = torch.full((storage_off + req + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-        storage[storage_off + req:] = 0x5A
-    end = storage_off + req
-    front = storage[:storage_off].clone()
-    behind = storage[end:].clone()
-    if values is None:
-        sorter.cmd_sort_segmented(stream, n, len(offsets) - 1, do.data_ptr(), offsets_off, dk.data_ptr(), keys_off,
-                                  storage.data_ptr(), storage_off, pool, 0)
-    else:
-        sorter.cmd_sort_segmented_key_value(stream, n, len(offsets) - 1, do.data_ptr(), offsets_off, dk.data_ptr(),
-                                            keys_off, dv.data_ptr(), values_off, storage.data_ptr(), storage_off, pool, 0)
-    torch.cuda.synchronize()
-    assert sorter.read_status(stream, storage.data_ptr(), storage_off) == expect_status
-    assert bool((storage[:storage_off] == front).all()), "wrote in front of the storage offset"
-    assert bool((storage[end:] == behind).all()), "wrote past the storage requirement"
-    assert np.array_equal(_host(do), ob), "the offsets changed"
-    outs = []
-    for d, off in ((dk, keys_off), (dv, values_off)):
-        if d is None:
-            outs.append(None)
-            continue
-        h = _host(d)
-        w = off // 4
-        assert (h[:w] == GUARD).all(), "wrote in front of the keys / values offset"
-        assert (h[w + n:] == GUARD).all(), "wrote behind maxElementCount"
-        outs.append(h[w:w + n].copy())
-    return outs[0], outs[1], storage
+def run_segmented(torch, sorter, keys, offsets, values=None, *, guard=256, bit_range=None, **kw):
+    """One vrdxHipCmdSortSegmented[64][Bits][KeyValue] with maxElementCount = len(keys) (guarded_call: keys_off, values_off,
+    offsets_off, storage_off, pool, expect_status, storage), `guard` guard elements behind the keys and the values; the
+    failure word is read after every call.  Returns the keys and values as sorted by the device and the storage tensor."""
+    got = guarded_call(torch, sorter, keys, values, offsets=offsets, bit_range=bit_range, tail=keys.itemsize * guard,
+                       recorded=True, **kw)
+    return got.keys, got.values, got.storage
 
 
 def check(got_k, got_v, keys, values, offsets, oracle=None, want=None):

@@ -22,7 +22,8 @@ import pytest
 
 import plan_model as model
 from test_plan_choice_gpu import plan_storage_word
-from test_sort_gpu import torch_mod, sorter, gpu_sort, MSD_HALF_UP_TO  # noqa: F401 (fixtures)
+from guarded_call import sorter, torch_mod  # noqa: F401 (fixtures)
+from test_sort_gpu import gpu_sort, MSD_HALF_UP_TO
 
 STREAMING_ABOVE = 1 << 24     # vrdx_kernels.h kStreamingLoadsAbove
 TEN_BITS_UP_TO = 36_649_984   # vrdx_plan.h MsdBits (pinned by tests/test_plan_check.py): ceil(n / 1024) * 103 // 100 <= 36864

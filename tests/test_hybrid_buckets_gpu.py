@@ -22,7 +22,7 @@ import pytest
 
 import hybrid_bucket_cases as cases
 import plan_model as model
-from segmented_cases import ballot_sorter, torch_mod  # noqa: F401 (fixtures)
+from guarded_call import ballot_sorter, torch_mod  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 

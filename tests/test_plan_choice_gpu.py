@@ -15,7 +15,8 @@ import pytest
 
 import plan_check_tool
 import plan_model as model
-from test_sort_gpu import torch_mod, sorter, ballot_sorter, gpu_sort, msd_capacity, MSD_FROM, MSD_HALF_UP_TO  # noqa: F401 (fixtures)
+from guarded_call import ballot_sorter, sorter, torch_mod  # noqa: F401 (fixtures)
+from test_sort_gpu import gpu_sort, msd_capacity, MSD_FROM, MSD_HALF_UP_TO  # noqa: F401
 
 HALF = 8_600_003      # the half-size bucket kernel (10 bits, buckets of 18432); n % 4 == 3
 FULL10 = 19_000_001   # the full-size bucket kernel, 10 bits (36864)

@@ -11,8 +11,9 @@ import zlib
 import numpy as np
 import pytest
 
-from segmented_cases import (_dev, _host, ballot_sorter, expected, mixed_offsets, payload, sorter, torch_mod)  # noqa: F401
-from segmented64_cases import (LARGE_TILE, MID_MAX, MID_MAX_KEY_VALUE, SMALL_MAX, _dev64, _host64, both_forms, make_keys64,
+from guarded_call import ballot_sorter, sorter, to_device, to_host, torch_mod  # noqa: F401
+from segmented_cases import expected, mixed_offsets, payload
+from segmented64_cases import (LARGE_TILE, MID_MAX, MID_MAX_KEY_VALUE, SMALL_MAX, both_forms, make_keys64,
                                run_segmented64, uniform64)
 
 pytestmark = pytest.mark.gpu
@@ -234,8 +235,8 @@ def test_degenerate_calls_record_nothing(torch_mod, sorter, ballot_sorter, ranki
     sorter = _pick(ranking, sorter, ballot_sorter)
     stream = torch.cuda.current_stream().cuda_stream
     host = np.arange(1000, 0, -1, dtype=np.uint64) << np.uint64(33)
-    keys, values = _dev64(torch, host), _dev(torch, np.arange(1000, dtype=np.uint32))
-    offsets = _dev(torch, np.array([0, 1000], np.uint32))
+    keys, values = to_device(torch, host), to_device(torch, np.arange(1000, dtype=np.uint32))
+    offsets = to_device(torch, np.array([0, 1000], np.uint32))
     storage = torch.full((sorter.storage_requirements64(1000, key_value=True).size,), 0xA5, dtype=torch.uint8, device="cuda")
     sorter.cmd_sort_segmented64(stream, 1000, 0, offsets.data_ptr(), 0, keys.data_ptr(), 0, storage.data_ptr(), 0)
     sorter.cmd_sort_segmented64(stream, 0, 1, offsets.data_ptr(), 0, keys.data_ptr(), 0, storage.data_ptr(), 0)
@@ -244,7 +245,7 @@ def test_degenerate_calls_record_nothing(torch_mod, sorter, ballot_sorter, ranki
     sorter.cmd_sort_segmented64_key_value(stream, 0, 1, offsets.data_ptr(), 0, keys.data_ptr(), 0, values.data_ptr(), 0,
                                           storage.data_ptr(), 0)
     torch.cuda.synchronize()
-    assert np.array_equal(_host64(keys), host) and np.array_equal(_host(values), np.arange(1000, dtype=np.uint32))
+    assert np.array_equal(to_host(keys), host) and np.array_equal(to_host(values), np.arange(1000, dtype=np.uint32))
     assert bool((storage == 0xA5).all())
 
 
@@ -255,9 +256,9 @@ def test_degenerate_calls_record_their_timestamps(torch_mod, sorter, ballot_sort
     torch = torch_mod
     sorter = _pick(ranking, sorter, ballot_sorter)
     stream = torch.cuda.current_stream().cuda_stream
-    keys = _dev64(torch, np.arange(8, dtype=np.uint64))
-    values = _dev(torch, np.arange(8, dtype=np.uint32))
-    offsets = _dev(torch, np.array([0, 8], np.uint32))
+    keys = to_device(torch, np.arange(8, dtype=np.uint64))
+    values = to_device(torch, np.arange(8, dtype=np.uint32))
+    offsets = to_device(torch, np.array([0, 8], np.uint32))
     storage = torch.empty(sorter.storage_requirements64(8, key_value=key_value).size, dtype=torch.uint8, device="cuda")
     for n, segments in ((8, 0), (0, 1)):
         pool = vrdx.QueryPool(15)
@@ -271,7 +272,7 @@ def test_degenerate_calls_record_their_timestamps(torch_mod, sorter, ballot_sort
         ts = pool.results_ns(0, 15)
         assert len(ts) == 15 and all(b >= a for a, b in zip(ts, ts[1:]))
         pool.destroy()
-    assert np.array_equal(_host64(keys), np.arange(8, dtype=np.uint64))
+    assert np.array_equal(to_host(keys), np.arange(8, dtype=np.uint64))
 
 
 @pytest.mark.parametrize("ranking", RANKINGS)
@@ -346,8 +347,8 @@ def test_captured_graph_replays_on_new_keys_and_a_new_segmentation(torch_mod, so
         rng.shuffle(sizes)
         offsets_list.append(np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32))
     assert len({len(o) for o in offsets_list}) == 1 and all(o[-1] <= n for o in offsets_list)
-    dk, do = _dev64(torch, np.zeros(n, np.uint64)), _dev(torch, offsets_list[0])
-    dv = _dev(torch, np.zeros(n, np.uint32)) if key_value else None
+    dk, do = to_device(torch, np.zeros(n, np.uint64)), to_device(torch, offsets_list[0])
+    dv = to_device(torch, np.zeros(n, np.uint32)) if key_value else None
     storage = torch.empty(sorter.storage_requirements64(n, key_value=key_value).size, dtype=torch.uint8, device="cuda")
     vrdx.sort_segments64(sorter, dk, do, values=dv, storage=storage)  # one eager call first
     torch.cuda.synchronize()
@@ -357,17 +358,17 @@ def test_captured_graph_replays_on_new_keys_and_a_new_segmentation(torch_mod, so
     values = payload(n) if key_value else None
     for replay, offsets in enumerate(offsets_list + offsets_list[::-1]):
         keys = make_keys64("uniform" if replay % 2 == 0 else "tile_depth", n, rng)
-        dk.copy_(_dev64(torch, keys))
+        dk.copy_(to_device(torch, keys))
         if key_value:
-            dv.copy_(_dev(torch, values))
-        do.copy_(_dev(torch, offsets))
+            dv.copy_(to_device(torch, values))
+        do.copy_(to_device(torch, offsets))
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
         ek, ev = expected(keys, values, offsets, n)
-        assert np.array_equal(_host64(dk), ek)
+        assert np.array_equal(to_host(dk), ek)
         if key_value:
-            assert np.array_equal(_host(dv), ev)
+            assert np.array_equal(to_host(dv), ev)
         assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
 
 
@@ -390,7 +391,7 @@ def test_sort_segments64_python_front_end(torch_mod, sorter, ballot_sorter, with
     values = payload(n) if with_values else None
     dk = torch.from_numpy(keys.view(np.int64).copy()).cuda()
     assert dk.dtype == torch.int64
-    dv, do = (_dev(torch, values) if with_values else None), _dev(torch, offsets)
+    dv, do = (to_device(torch, values) if with_values else None), to_device(torch, offsets)
     mine = None
     if own_storage:
         mine = torch.empty(sorter.storage_requirements64(n, key_value=with_values).size + 64, dtype=torch.uint8, device="cuda")
@@ -398,9 +399,9 @@ def test_sort_segments64_python_front_end(torch_mod, sorter, ballot_sorter, with
     torch.cuda.synchronize()
     assert mine is None or storage is mine
     ek, ev = expected(keys, values, offsets, n)
-    assert np.array_equal(_host64(dk), ek)
+    assert np.array_equal(to_host(dk), ek)
     if with_values:
-        assert np.array_equal(_host(dv), ev)
+        assert np.array_equal(to_host(dv), ev)
     assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
 
 

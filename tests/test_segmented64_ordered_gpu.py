@@ -1,18 +1,30 @@
 """GPU tests of the key orders of the segmented sort of 64-bit keys (vrdxHipCmdSortSegmented64Ordered[KeyValue],
 vulkan_radix_sort_amd.sort_segments64 with `order` / `descending`), through the C ABI and bit for bit against the reference
 of tests/key_order_cases.py: np.lexsort((T(keys), segment id)).  Every call runs between guard words
-(tests/key_order_gpu.py).  Segment sizes sit at the edges of the three size classes of both forms: 4096 | 4097, keys-only
+(tests/guarded_call.py).  Segment sizes sit at the edges of the three size classes of both forms: 4096 | 4097, keys-only
 16384 | 16385, key+value 8192 | 8193, large segments that end inside a tile of 8192 and that are whole tiles."""
 import functools
 
 import numpy as np
 import pytest
 
-from key_order_cases import (DIRECTIONS, ORDERS, SIGN, all_ones_key, expected_segments, order_word, payload, segment_case)
-from key_order_gpu import assert_same, ballot_sorter, run_segmented64_ordered, sorter, torch_mod  # noqa: F401
+from guarded_call import ballot_sorter, guarded_call, sorter, torch_mod  # noqa: F401
+from key_order_cases import (DIRECTIONS, ORDERS, SIGN, all_ones_key, assert_same, expected_segments, order_word, payload,
+                             segment_case)
 from segmented64_cases import run_segmented64
 
 pytestmark = pytest.mark.gpu
+
+
+def run_segmented64_ordered(torch, s, keys, offsets, values, word, *, expect_status=0, storage_out=None, **kw):
+    """One segmented call with the order word `word` and maxElementCount = len(keys) (guarded_call: keys_off, values_off,
+    storage_off, pool, expect_refused).  Unless the call is refused, the failure word and the sorter's sticky word must both be
+    expect_status afterwards.  Returns keys and values as the device left them."""
+    got = guarded_call(torch, s, keys, values, offsets=offsets, order=word, tail=8 * 256, expect_status=expect_status,
+                       recorded=True, sticky=expect_status, **kw)
+    if storage_out is not None:
+        storage_out.append(got.storage)
+    return got.keys, got.values
 
 # both in-LDS kernels at their edges for both forms, the large kernel with one tile plus one key (key+value), two tiles plus
 # one key (keys-only), a last tile that is ragged, exactly two tiles (key+value) and exactly three (both)

@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 
 import segmented_cases
-from segmented_bits_cases import (BUILDERS, EMPTY_RANGE, FULL_RANGE, GUARD, PASS_CASES, PASS_SIZES, RANGES, _dev, _host,  # noqa: F401
-                                  ballot_sorter, case_inputs, check, expected, make_keys, mixed_offsets, payload,
-                                  run_segmented_bits, sorter, torch_mod)
+from guarded_call import ballot_sorter, sorter, to_device, to_host, torch_mod  # noqa: F401
+from segmented_bits_cases import (BUILDERS, EMPTY_RANGE, FULL_RANGE, PASS_CASES, PASS_SIZES, RANGES, case_inputs, check,  # noqa: F401
+                                  expected, make_keys, mixed_offsets, payload, run_segmented_bits)
+from segmented_cases import GUARD
 
 pytestmark = pytest.mark.gpu
 
@@ -211,7 +212,7 @@ def test_captured_graph_replays_on_new_keys_and_a_new_segmentation(torch_mod, so
         rng.shuffle(sizes)
         offsets_list.append(np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32))
     assert len({len(o) for o in offsets_list}) == 1 and all(o[-1] <= n for o in offsets_list)
-    dk, dv, do = _dev(torch, np.zeros(n, np.uint32)), _dev(torch, np.zeros(n, np.uint32)), _dev(torch, offsets_list[0])
+    dk, dv, do = to_device(torch, np.zeros(n, np.uint32)), to_device(torch, np.zeros(n, np.uint32)), to_device(torch, offsets_list[0])
     storage = torch.empty(sorter.key_value_storage_requirements(n).size, dtype=torch.uint8, device="cuda")
     vrdx.sort_segments_bits(sorter, dk, do, begin, end, values=dv, storage=storage)  # one eager call first
     torch.cuda.synchronize()
@@ -221,13 +222,13 @@ def test_captured_graph_replays_on_new_keys_and_a_new_segmentation(torch_mod, so
     values = payload(n)
     for replay, offsets in enumerate([offsets_list[0], offsets_list[0], offsets_list[1], offsets_list[0]]):
         keys = make_keys("uniform" if replay % 2 == 0 else "few", n, begin, end, rng)
-        dk.copy_(_dev(torch, keys))
-        dv.copy_(_dev(torch, values))
-        do.copy_(_dev(torch, offsets))
+        dk.copy_(to_device(torch, keys))
+        dv.copy_(to_device(torch, values))
+        do.copy_(to_device(torch, offsets))
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
-        check(_host(dk), _host(dv), keys, values, offsets, begin, end)
+        check(to_host(dk), to_host(dv), keys, values, offsets, begin, end)
         assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
     assert sorter.read_sorter_status(torch.cuda.current_stream().cuda_stream) == 0
 
@@ -243,7 +244,7 @@ def test_status_is_clear_and_the_plan_verdict_is_none(torch_mod, sorter):
     assert sorter.describe_plan(big, False).name == "msd"
     rng = np.random.default_rng(9)
     storage = torch.empty(sorter.storage_requirements(big).size + 256, dtype=torch.uint8, device="cuda")
-    dk = _dev(torch, rng.integers(0, 1 << 32, size=big, dtype=np.uint64).astype(np.uint32))
+    dk = to_device(torch, rng.integers(0, 1 << 32, size=big, dtype=np.uint64).astype(np.uint32))
     sorter.cmd_sort(stream, big, dk.data_ptr(), 0, storage.data_ptr(), 0)
     assert sorter.read_plan_verdict(stream, storage.data_ptr(), 0) == vrdx.VERDICT_MSD_RUNS
     offsets, n = mixed_offsets(rng, [300, 5000, 20000, 0, 1])
@@ -284,24 +285,24 @@ def test_sort_segments_bits_python_front_end(torch_mod, sorter):
     keys = make_keys("uniform", n, begin, end, rng)
     values = payload(n)
     want = expected(keys, values, offsets, n, begin, end)
-    dk, dv, do = _dev(torch, keys), _dev(torch, values), _dev(torch, offsets)
+    dk, dv, do = to_device(torch, keys), to_device(torch, values), to_device(torch, offsets)
     storage = vrdx.sort_segments_bits(sorter, dk, do, begin, end, values=dv)
     torch.cuda.synchronize()
-    check(_host(dk), _host(dv), keys, values, offsets, begin, end, want=want)
+    check(to_host(dk), to_host(dv), keys, values, offsets, begin, end, want=want)
     assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
-    big = _dev(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
-    other = _dev(torch, np.concatenate([np.full(3, GUARD, np.uint32), values, np.full(64, GUARD, np.uint32)]))
+    big = to_device(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
+    other = to_device(torch, np.concatenate([np.full(3, GUARD, np.uint32), values, np.full(64, GUARD, np.uint32)]))
     vk, vv = big[1:1 + n], other[3:3 + n]
     assert big.data_ptr() % 16 == 0 and vk.data_ptr() % 16 == 4 and vv.data_ptr() % 16 == 12
     vrdx.sort_segments_bits(sorter, vk, do, begin, end, values=vv, storage=storage)
     torch.cuda.synchronize()
-    whole, whole_values = _host(big), _host(other)
+    whole, whole_values = to_host(big), to_host(other)
     check(whole[1:1 + n], whole_values[3:3 + n], keys, values, offsets, begin, end, want=want)
     assert whole[0] == GUARD and bool((whole[1 + n:] == GUARD).all())
     assert bool((whole_values[:3] == GUARD).all()) and bool((whole_values[3 + n:] == GUARD).all())
-    keys_only = _dev(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
+    keys_only = to_device(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
     vrdx.sort_segments_bits(sorter, keys_only[1:1 + n], do, begin, end)
     torch.cuda.synchronize()
-    whole = _host(keys_only)
+    whole = to_host(keys_only)
     check(whole[1:1 + n], None, keys, None, offsets, begin, end, want=want)
     assert whole[0] == GUARD and bool((whole[1 + n:] == GUARD).all())

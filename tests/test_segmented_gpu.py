@@ -10,8 +10,8 @@ import zlib
 import numpy as np
 import pytest
 
-from segmented_cases import (GUARD, _dev, _host, ballot_sorter, check, expected, make_keys, mixed_offsets,  # noqa: F401
-                             run_segmented, sorter, torch_mod)
+from guarded_call import ballot_sorter, sorter, to_device, to_host, torch_mod  # noqa: F401
+from segmented_cases import GUARD, check, expected, make_keys, mixed_offsets, run_segmented
 
 pytestmark = pytest.mark.gpu
 
@@ -83,7 +83,7 @@ def test_status_is_clear_and_the_plan_verdict_is_none(torch_mod, sorter):
     assert sorter.describe_plan(big, False).name == "msd"
     rng = np.random.default_rng(9)
     storage = torch.empty(sorter.storage_requirements(big).size + 256, dtype=torch.uint8, device="cuda")
-    dk = _dev(torch, make_keys("uniform", big, rng))
+    dk = to_device(torch, make_keys("uniform", big, rng))
     sorter.cmd_sort(stream, big, dk.data_ptr(), 0, storage.data_ptr(), 0)
     assert sorter.read_plan_verdict(stream, storage.data_ptr(), 0) == vrdx.VERDICT_MSD_RUNS
     offsets, n = mixed_offsets(rng, [300, 5000, 20000, 0, 1])
@@ -113,13 +113,13 @@ def test_degenerate_calls_record_nothing(torch_mod, sorter):
     """segmentCount == 0 and maxElementCount == 0 touch nothing (every byte of the storage stays as it was)."""
     torch = torch_mod
     stream = torch.cuda.current_stream().cuda_stream
-    keys = _dev(torch, np.arange(1000, 0, -1, dtype=np.uint32))
-    offsets = _dev(torch, np.array([0, 1000], np.uint32))
+    keys = to_device(torch, np.arange(1000, 0, -1, dtype=np.uint32))
+    offsets = to_device(torch, np.array([0, 1000], np.uint32))
     storage = torch.full((sorter.storage_requirements(1000).size,), 0xA5, dtype=torch.uint8, device="cuda")
     sorter.cmd_sort_segmented(stream, 1000, 0, offsets.data_ptr(), 0, keys.data_ptr(), 0, storage.data_ptr(), 0)
     sorter.cmd_sort_segmented(stream, 0, 1, offsets.data_ptr(), 0, keys.data_ptr(), 0, storage.data_ptr(), 0)
     torch.cuda.synchronize()
-    assert np.array_equal(_host(keys), np.arange(1000, 0, -1, dtype=np.uint32))
+    assert np.array_equal(to_host(keys), np.arange(1000, 0, -1, dtype=np.uint32))
     assert bool((storage == 0xA5).all())
 
 
@@ -133,10 +133,10 @@ def test_sort_segments_python_front_end(torch_mod, sorter):
     n = int(offsets[-1])
     keys = make_keys("uniform", n, rng)
     iota = np.arange(n, dtype=np.uint32)
-    dk, dv, do = _dev(torch, keys), _dev(torch, iota), _dev(torch, offsets)
+    dk, dv, do = to_device(torch, keys), to_device(torch, iota), to_device(torch, offsets)
     storage = vrdx.sort_segments(sorter, dk, do, values=dv)
     torch.cuda.synchronize()
-    check(_host(dk), _host(dv), keys, iota, offsets)
+    check(to_host(dk), to_host(dv), keys, iota, offsets)
     assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
 
 
@@ -152,22 +152,22 @@ def test_sort_segments_accepts_views_off_a_sixteen_byte_boundary(torch_mod, sort
     n = int(offsets[-1])
     keys = make_keys("uniform", n, rng)
     values = rng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
-    big = _dev(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
-    other = _dev(torch, np.concatenate([np.full(3, GUARD, np.uint32), values, np.full(64, GUARD, np.uint32)]))
-    dk, dv, do = big[1:1 + n], other[3:3 + n], _dev(torch, offsets)
+    big = to_device(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
+    other = to_device(torch, np.concatenate([np.full(3, GUARD, np.uint32), values, np.full(64, GUARD, np.uint32)]))
+    dk, dv, do = big[1:1 + n], other[3:3 + n], to_device(torch, offsets)
     assert big.data_ptr() % 16 == 0 and dk.data_ptr() % 16 == 4 and dv.data_ptr() % 16 == 12
     assert dk.is_contiguous() and dv.is_contiguous()
     storage = vrdx.sort_segments(sorter, dk, do, values=dv)
     torch.cuda.synchronize()
-    check(_host(dk), _host(dv), keys, values, offsets)
-    whole, whole_values = _host(big), _host(other)
+    check(to_host(dk), to_host(dv), keys, values, offsets)
+    whole, whole_values = to_host(big), to_host(other)
     assert whole[0] == GUARD and bool((whole[1 + n:] == GUARD).all())
     assert bool((whole_values[:3] == GUARD).all()) and bool((whole_values[3 + n:] == GUARD).all())
     assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
-    keys_only = _dev(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
+    keys_only = to_device(torch, np.concatenate([np.full(1, GUARD, np.uint32), keys, np.full(64, GUARD, np.uint32)]))
     vrdx.sort_segments(sorter, keys_only[1:1 + n], do)
     torch.cuda.synchronize()
-    whole = _host(keys_only)
+    whole = to_host(keys_only)
     check(whole[1:1 + n], None, keys, None, offsets)
     assert whole[0] == GUARD and bool((whole[1 + n:] == GUARD).all())
 
@@ -187,7 +187,7 @@ def test_captured_graph_replays_on_new_keys_and_a_new_segmentation(torch_mod, so
         rng.shuffle(sizes)
         offsets_list.append(np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32))
     assert len({len(o) for o in offsets_list}) == 1 and all(o[-1] <= n for o in offsets_list)
-    dk, dv, do = _dev(torch, np.zeros(n, np.uint32)), _dev(torch, np.zeros(n, np.uint32)), _dev(torch, offsets_list[0])
+    dk, dv, do = to_device(torch, np.zeros(n, np.uint32)), to_device(torch, np.zeros(n, np.uint32)), to_device(torch, offsets_list[0])
     storage = torch.empty(sorter.key_value_storage_requirements(n).size, dtype=torch.uint8, device="cuda")
     vrdx.sort_segments(sorter, dk, do, values=dv, storage=storage)  # one eager call first (test_sort_gpu.py explains why)
     torch.cuda.synchronize()
@@ -197,13 +197,13 @@ def test_captured_graph_replays_on_new_keys_and_a_new_segmentation(torch_mod, so
     iota = np.arange(n, dtype=np.uint32)
     for replay, offsets in enumerate(offsets_list + offsets_list[::-1]):
         keys = make_keys("uniform" if replay % 2 == 0 else "24-bit", n, rng)
-        dk.copy_(_dev(torch, keys))
-        dv.copy_(_dev(torch, iota))
-        do.copy_(_dev(torch, offsets))
+        dk.copy_(to_device(torch, keys))
+        dv.copy_(to_device(torch, iota))
+        do.copy_(to_device(torch, offsets))
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
-        check(_host(dk), _host(dv), keys, iota, offsets)
+        check(to_host(dk), to_host(dv), keys, iota, offsets)
         assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
 
 

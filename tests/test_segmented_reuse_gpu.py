@@ -14,8 +14,8 @@ import zlib
 import numpy as np
 import pytest
 
-from segmented_cases import (_dev, _host, ballot_sorter, check, expected, make_keys, payload,  # noqa: F401
-                             run_segmented, sorter, torch_mod)
+from guarded_call import ballot_sorter, sorter, to_device, to_host, torch_mod  # noqa: F401
+from segmented_cases import check, expected, make_keys, payload, run_segmented
 
 pytestmark = pytest.mark.gpu
 
@@ -320,7 +320,7 @@ def test_captured_graph_keys_only_moves_segments_across_the_classes(torch_mod, s
         offsets_list.append(_offsets(sizes, 1))
     n = max(int(o[-1]) for o in offsets_list) + 10
     assert len({len(o) for o in offsets_list}) == 1 and mids > 2 * cus
-    dk, do = _dev(torch, np.zeros(n, np.uint32)), _dev(torch, offsets_list[0])
+    dk, do = to_device(torch, np.zeros(n, np.uint32)), to_device(torch, offsets_list[0])
     storage = torch.empty(sorter.storage_requirements(n).size, dtype=torch.uint8, device="cuda")
     vrdx.sort_segments(sorter, dk, do, storage=storage)  # one eager call first (test_sort_gpu.py explains why)
     torch.cuda.synchronize()
@@ -329,10 +329,10 @@ def test_captured_graph_keys_only_moves_segments_across_the_classes(torch_mod, s
         vrdx.sort_segments(sorter, dk, do, storage=storage)
     for replay, offsets in enumerate(offsets_list + offsets_list[:2]):
         keys = make_keys("uniform" if replay % 2 == 0 else "24-bit", n, rng)
-        dk.copy_(_dev(torch, keys))
-        do.copy_(_dev(torch, offsets))
+        dk.copy_(to_device(torch, keys))
+        do.copy_(to_device(torch, offsets))
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
-        check(_host(dk), None, keys, None, offsets)
+        check(to_host(dk), None, keys, None, offsets)
         assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0

@@ -6,7 +6,7 @@ give.  Each of the four forms (whole key, bit range, 64-bit keys, 64-bit keys wi
 import numpy as np
 import pytest
 
-from segmented_cases import sorter, torch_mod  # noqa: F401
+from guarded_call import sorter, torch_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

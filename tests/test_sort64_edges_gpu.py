@@ -22,9 +22,11 @@ import pytest
 import plan_model
 import segmented_cases
 import sort64_model as model
-from segmented_cases import sorter, torch_mod  # noqa: F401
+from guarded_call import BAND_BYTE as STORAGE_GUARD
+from guarded_call import GUARD_BYTE as GUARD
+from guarded_call import sorter, torch_mod  # noqa: F401
 from sort64_model import case_inputs, check64, with_tail
-from test_sort64_gpu import GUARD, STORAGE_GUARD, run64
+from test_sort64_gpu import run64
 from test_sort_gpu import msd_capacity
 
 pytestmark = pytest.mark.gpu

@@ -11,7 +11,8 @@ import zlib
 import numpy as np
 import pytest
 
-from segmented_cases import ballot_sorter, sorter, torch_mod  # noqa: F401
+from guarded_call import BAND_BYTE as STORAGE_GUARD
+from guarded_call import ballot_sorter, guarded_call, sorter, torch_mod  # noqa: F401
 from sort64_model import check64, expected64, make_keys64, payload64  # noqa: F401 (shared with test_sort64_edges_gpu.py)
 
 pytestmark = pytest.mark.gpu
@@ -19,56 +20,17 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [0, 1, 2, 1000, 16384, 16385, (1 << 18) + 3, 1 << 22, 8_200_000]  # every plan of the inner sorts
 PATTERNS = ["uniform", "high-constant", "low-constant", "identical", "descending", "8-distinct", "bit63-mixed", "tile-depth"]
-GUARD = 0xA5
-STORAGE_GUARD = 0x5A
-
-
-def _guarded(torch, payload, offset, tail):
-    """`payload`'s bytes at byte `offset` of a device buffer filled with the guard byte, `tail` guard bytes behind them."""
-    raw = np.full(offset + payload.nbytes + tail, GUARD, dtype=np.uint8)
-    raw[offset:offset + payload.nbytes] = payload.view(np.uint8)
-    return torch.from_numpy(raw).cuda()
-
-
-def _unguard(buffer, offset, nbytes, dtype):
-    raw = buffer.cpu().numpy()
-    assert (raw[:offset] == GUARD).all(), "bytes in front of the array were written"
-    assert (raw[offset + nbytes:] == GUARD).all(), "bytes behind elementCount were written"
-    return raw[offset:offset + nbytes].copy().view(dtype)
 
 
 def run64(torch, s, keys, values=None, keys_off=0, values_off=0, storage_off=0, pool=None, count=None, storage_out=None):
-    """One call through the C ABI.  count (default: all of keys) elements are sorted; the rest of `keys` / `values` and 256
-    bytes more are guard words.  Returns the whole arrays as the device left them; storage_out: a list that receives the
-    storage tensor (its header is at storage_off)."""
-    stream = torch.cuda.current_stream().cuda_stream
-    n = len(keys) if count is None else count
-    key_value = values is not None
-    required = s.storage_requirements64(n, key_value).size
-    storage = torch.full((storage_off + required + 256,), STORAGE_GUARD, dtype=torch.uint8, device="cuda")
-    assert storage.data_ptr() % 16 == 0
-    dk = _guarded(torch, keys, keys_off, 256)
-    assert dk.data_ptr() % 16 == 0 and keys_off % 8 == 0
-    if key_value:
-        dv = _guarded(torch, values, values_off, 256)
-        assert dv.data_ptr() % 16 == 0 and values_off % 4 == 0
-        s.cmd_sort64_key_value(stream, n, dk.data_ptr(), keys_off, dv.data_ptr(), values_off, storage.data_ptr(), storage_off,
-                               pool, 0)
-    else:
-        s.cmd_sort64(stream, n, dk.data_ptr(), keys_off, storage.data_ptr(), storage_off, pool, 0)
-    torch.cuda.synchronize()
-    if n > 0:  # (an empty call writes no header)
-        assert s.read_status(stream, storage.data_ptr(), storage_off) == 0
-    assert s.read_sorter_status(stream) == 0
-    front = storage[:storage_off].cpu().numpy()
-    back = storage[storage_off + required:].cpu().numpy()
-    assert (front == STORAGE_GUARD).all(), "the storage buffer in front of storageOffset was written"
-    assert (back == STORAGE_GUARD).all(), "the storage buffer behind the requirement was written"
-    got_keys = _unguard(dk, keys_off, keys.nbytes, np.uint64)
-    got_values = _unguard(dv, values_off, values.nbytes, np.uint32) if key_value else None
+    """One call through the C ABI (guarded_call).  count (default: all of keys) elements are sorted; the rest of `keys` /
+    `values` is followed by guard bytes.  The sorter's sticky word must be 0 afterwards.  Returns the whole arrays as the
+    device left them; storage_out: a list that receives the storage tensor (its header is at storage_off)."""
+    got = guarded_call(torch, s, keys, values, count=count, keys_off=keys_off, values_off=values_off, storage_off=storage_off,
+                       pool=pool, sticky=0)
     if storage_out is not None:
-        storage_out.append(storage)
-    return got_keys, got_values
+        storage_out.append(got.storage)
+    return got.keys, got.values
 
 
 @pytest.mark.parametrize("key_value", [False, True], ids=["keys", "pairs"])

@@ -1,8 +1,8 @@
 """GPU tests of the 64-bit sorts by a device-side count (vrdxHipCmdSort64[KeyValue]Indirect, vulkan_radix_sort_amd.sort64
 with `count`), through the C ABI and element for element against numpy.  With n = min(count, bound) the first n elements
 must be what the direct form leaves for n -- np.sort of the keys, np.argsort(kind="stable") applied to keys and values --
-and every element from n on, inside the bound or behind it, bit for bit what it was.  The guard scheme is run64's
-(tests/test_sort64_gpu.py): guard bytes around the caller's arrays and around the storage requirement OF THE BOUND, the
+and every element from n on, inside the bound or behind it, bit for bit what it was.  The guard scheme is guarded_call's
+(tests/guarded_call.py): guard bytes around the caller's arrays and around the storage requirement OF THE BOUND, the
 status words read after every call; the count word is checked to be what it was.  Values are payload64, nowhere their own
 index."""
 import functools
@@ -12,9 +12,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from segmented_cases import sorter, torch_mod  # noqa: F401
+from guarded_call import BAND_BYTE as STORAGE_GUARD
+from guarded_call import guarded_call, sorter, torch_mod  # noqa: F401
 from sort64_model import case_inputs, check64, with_tail
-from test_sort64_gpu import GUARD, STORAGE_GUARD, _guarded, _unguard
 
 pytestmark = pytest.mark.gpu
 
@@ -52,54 +52,13 @@ def _want(pattern, bound, n, key_value):
     return keys[order], (values[order] if key_value else None)
 
 
-def run64_indirect(torch, s, keys, values, bound, count, *, keys_off=0, values_off=0, storage_off=0, pool=None,
-                   count_in_keys=False, indirect_off=0):
-    """One call through the C ABI with the count in a device word.  The arrays lie between guard bytes, the storage holds
-    the requirement of `bound` between guard bytes; the count word lies in a buffer of its own at byte `indirect_off`, or
-    (count_in_keys) in the keys' buffer, 12 bytes behind the last key.  Returns the whole arrays as the device left them."""
-    stream = torch.cuda.current_stream().cuda_stream
-    key_value = values is not None
-    required = s.storage_requirements64(bound, key_value).size
-    storage = torch.full((storage_off + required + 256,), STORAGE_GUARD, dtype=torch.uint8, device="cuda")
-    assert storage.data_ptr() % 16 == 0 and storage_off % 16 == 0
-    dk = _guarded(torch, keys, keys_off, 256)
-    assert dk.data_ptr() % 16 == 0 and keys_off % 8 == 0
-    word = np.array([count], dtype=np.uint32)
-    if count_in_keys:
-        indirect, indirect_off = dk, keys_off + keys.nbytes + 12
-        assert indirect_off % 8 == 4
-        dk[indirect_off:indirect_off + 4] = torch.from_numpy(word.view(np.uint8)).cuda()
-    else:
-        assert indirect_off % 4 == 0
-        words = np.full(indirect_off // 4 + 3, 0xA5A5A5A5, dtype=np.uint32)
-        words[indirect_off // 4] = count
-        indirect = torch.from_numpy(words.view(np.uint8).copy()).cuda()
-    before = indirect.cpu().numpy().copy() if not count_in_keys else None
-    if key_value:
-        dv = _guarded(torch, values, values_off, 256)
-        assert dv.data_ptr() % 16 == 0 and values_off % 4 == 0
-        s.cmd_sort64_key_value_indirect(stream, bound, indirect.data_ptr(), indirect_off, dk.data_ptr(), keys_off,
-                                        dv.data_ptr(), values_off, storage.data_ptr(), storage_off, pool, 0)
-    else:
-        s.cmd_sort64_indirect(stream, bound, indirect.data_ptr(), indirect_off, dk.data_ptr(), keys_off, storage.data_ptr(),
-                              storage_off, pool, 0)
-    torch.cuda.synchronize()
-    if bound > 0:  # (a call with an empty bound writes no header)
-        assert s.read_status(stream, storage.data_ptr(), storage_off) == 0
-    assert s.read_sorter_status(stream) == 0
-    front = storage[:storage_off].cpu().numpy()
-    back = storage[storage_off + required:].cpu().numpy()
-    assert (front == STORAGE_GUARD).all(), "the storage buffer in front of storageOffset was written"
-    assert (back == STORAGE_GUARD).all(), "the storage buffer behind the requirement of the bound was written"
-    if count_in_keys:
-        left = dk[indirect_off:indirect_off + 4].cpu().numpy().view(np.uint32)
-        assert left[0] == count, "the count word was written"
-        dk[indirect_off:indirect_off + 4] = GUARD  # (so that _unguard sees nothing but guard bytes behind the keys)
-    else:
-        assert np.array_equal(indirect.cpu().numpy(), before), "the count word or its neighbours were written"
-    got_keys = _unguard(dk, keys_off, keys.nbytes, np.uint64)
-    got_values = _unguard(dv, values_off, values.nbytes, np.uint32) if key_value else None
-    return got_keys, got_values
+def run64_indirect(torch, s, keys, values, bound, count, count_in_keys=False, **where):
+    """One call with the count in a device word (guarded_call: keys_off, values_off, storage_off, indirect_off, pool), the
+    storage sized for `bound`; count_in_keys: the word lies in the keys' buffer, 12 bytes behind the last key, at an address
+    that is 4 mod 8.  The sorter's sticky word must be 0 afterwards.  Returns the whole arrays as the device left them."""
+    got = guarded_call(torch, s, keys, values, count=bound, device_count=count, sticky=0,
+                       count_behind_keys=12 if count_in_keys else None, **where)
+    return got.keys, got.values
 
 
 def _parity(torch, s, pattern, bound, count, key_value, **where):

@@ -1,7 +1,7 @@
 """GPU tests of the key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered[KeyValue][Indirect], vulkan_radix_sort_amd.sort64
 with `order` / `descending`), through the C ABI and bit for bit against the reference of tests/key_order_cases.py:
 np.argsort(T(keys), kind="stable") applied to keys and values.  Elements from the count on, guard bytes around the arrays
-and around the storage requirement, and the status words are checked after every call (tests/key_order_gpu.py).  Sizes: the
+and around the storage requirement, and the status words are checked after every call (tests/guarded_call.py).  Sizes: the
 scalar tail, the edge of a 256 x 4 workgroup, where the inner sorts leave the one-workgroup plan, and the hybrid plan --
 nothing larger, because the inner sorts are the calls the unordered sorts make."""
 import functools
@@ -11,11 +11,21 @@ import subprocess
 import numpy as np
 import pytest
 
-from key_order_cases import BUILDERS, DIRECTIONS, ORDERS, case_keys, expected, order_word
-from key_order_gpu import assert_same, run64_ordered, sorter, torch_mod  # noqa: F401
+from guarded_call import guarded_call, sorter, torch_mod  # noqa: F401
+from key_order_cases import BUILDERS, DIRECTIONS, ORDERS, assert_same, case_keys, expected, order_word
 from test_sort64_gpu import run64
 
 pytestmark = pytest.mark.gpu
+
+
+def run64_ordered(torch, s, keys, values, word, *, storage_out=None, **kw):
+    """One call with the order word `word` (guarded_call: count -- the elementCount, or with device_count the bound --
+    keys_off, values_off, storage_off, pool, expect_refused), the count word at 4 mod 16.  Unless the call is refused the
+    sorter's sticky word must be 0 afterwards.  Returns the whole arrays as the device left them."""
+    got = guarded_call(torch, s, keys, values, order=word, indirect_off=4, sticky=0, **kw)
+    if storage_out is not None:
+        storage_out.append(got.storage)
+    return got.keys, got.values
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [1, 3, 4, 5, 1023, 1024, 1025, 16384, 16385, 300001]

@@ -21,13 +21,13 @@ import numpy as np
 import pytest
 
 import plan_model as model
-from test_sort_gpu import torch_mod, sorter, ballot_sorter, msd_capacity, MSD_FROM, MSD_HALF_UP_TO  # noqa: F401 (fixtures)
+from guarded_call import (BAND_BYTE, FRONT, TAIL, address, ballot_sorter, guarded_call, poisoned_storage, sorter, to_device,  # noqa: F401
+                          to_host, torch_mod)
+from test_sort_gpu import msd_capacity, MSD_FROM, MSD_HALF_UP_TO
 from test_plan_choice_gpu import plan_storage_word, expected_word, model_verdict
 
 pytestmark = pytest.mark.gpu
 
-BAND = 256          # sentinel bytes in front of every array (plus its residue) and behind it
-SENTINEL = 0xC7     # no byte of the storage's poison (0xA5) or guard (0x5A)
 RESIDUES = (0, 4, 8, 12)
 LAST = 1 << 26      # the MSD plan's last size
 
@@ -55,40 +55,10 @@ def reference(oracle, keys, values=None, count=None):
     return ek, None
 
 
-def _place(torch, a, *arrays):
-    """A uint8 device buffer: BAND + a sentinel bytes, the arrays back to back, BAND sentinel bytes.  Returns (buffer, byte
-    offset of the first array)."""
-    assert a in RESIDUES
-    body = np.concatenate([np.ascontiguousarray(x, dtype=np.uint32).ravel() for x in arrays]).view(np.uint8)
-    host = np.full(BAND + a + body.size + BAND, SENTINEL, dtype=np.uint8)
-    host[BAND + a:BAND + a + body.size] = body
-    dev = torch.from_numpy(host).cuda()
-    assert dev.data_ptr() % 16 == 0
-    return dev, BAND + a
-
-
-def _fetch(dev, offset, words, what):
-    """the `words` uint32 at `offset` of the buffer, after checking that both sentinel bands around them are intact"""
-    out = dev.cpu().numpy()
-    end = offset + 4 * words
-    assert out.size == end + BAND
-    assert bool((out[:offset] == SENTINEL).all()), (what, "wrote in front of the array", np.flatnonzero(out[:offset] != SENTINEL)[:8])
-    assert bool((out[end:] == SENTINEL).all()), (what, "wrote behind the array", np.flatnonzero(out[end:] != SENTINEL)[:8])
-    return out[offset:end].copy().view(np.uint32)
-
-
-def _storage(torch, sorter, bound, key_value):
-    req = sorter.key_value_storage_requirements(bound) if key_value else sorter.storage_requirements(bound)
-    storage = torch.full((req.size + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-    storage[req.size:] = 0x5A  # guard band behind the storage
-    assert storage.data_ptr() % 16 == 0
-    return storage, req.size
-
-
 def run_placed(torch, sorter, keys, values, a_keys, a_values, want, count=None, count_at=None, a_count=0, word=None, what=""):
-    """One vrdxCmdSort* on arrays this helper places: keys at byte BAND + a_keys of a buffer of their own, values at BAND +
-    a_values of another, both between sentinel bands, the offsets passed as keysOffset / valuesOffset.  count: the indirect
-    form, bound = len(keys), the count word at BAND + a_count of its own buffer (count_at = "own") or right behind the last
+    """One vrdxCmdSort* on arrays guarded_call places: keys at a_keys mod 16 of a buffer of their own, values at a_values
+    mod 16 of another, both between sentinel bands, the offsets passed as keysOffset / valuesOffset.  count: the indirect
+    form, bound = len(keys), the count word at a_count mod 16 of its own buffer (count_at = "own") or right behind the last
     key in the keys' buffer ("keys": its residue is then a_keys + 4 len(keys) mod 16).  want: (keys, values) of `reference`.
     Checks keys and values (the tail behind the count with them), every sentinel band, the count word, the guard behind the
     storage requirement, read_status == 0 and, where given, the plan word the device left in the storage."""
@@ -97,45 +67,20 @@ def run_placed(torch, sorter, keys, values, a_keys, a_values, want, count=None, 
     n = count if indirect else n_buf
     key_value = values is not None
     what = (what, f"n={n_buf} count={count} at {count_at} a_keys={a_keys} a_values={a_values} a_count={a_count} kv={key_value}")
-    behind = indirect and count_at == "keys"
-    dk, keys_off = _place(torch, a_keys, keys, np.array([count], np.uint32)) if behind else _place(torch, a_keys, keys)
-    dv, values_off = _place(torch, a_values, values) if key_value else (None, 0)
-    dc = count_off = None
-    if indirect:
-        assert count_at in ("own", "keys")
-        dc, count_off = (dk, keys_off + 4 * n_buf) if behind else _place(torch, a_count, np.array([count], np.uint32))
-        assert (dc.data_ptr() + count_off) % 16 == ((a_keys + 4 * n_buf) % 16 if behind else a_count)
-    assert (dk.data_ptr() + keys_off) % 16 == a_keys and (not key_value or (dv.data_ptr() + values_off) % 16 == a_values)
-    storage, size = _storage(torch, sorter, n_buf, key_value)
-    stream = torch.cuda.current_stream().cuda_stream
-    if indirect and key_value:
-        sorter.cmd_sort_key_value_indirect(stream, n_buf, dc.data_ptr(), count_off, dk.data_ptr(), keys_off, dv.data_ptr(),
-                                           values_off, storage.data_ptr(), 0)
-    elif indirect:
-        sorter.cmd_sort_indirect(stream, n_buf, dc.data_ptr(), count_off, dk.data_ptr(), keys_off, storage.data_ptr(), 0)
-    elif key_value:
-        sorter.cmd_sort_key_value(stream, n_buf, dk.data_ptr(), keys_off, dv.data_ptr(), values_off, storage.data_ptr(), 0)
-    else:
-        sorter.cmd_sort(stream, n_buf, dk.data_ptr(), keys_off, storage.data_ptr(), 0)
-    torch.cuda.synchronize()
-    got = _fetch(dk, keys_off, n_buf + (1 if behind else 0), (what, "keys"))
-    if behind:
-        assert int(got[n_buf]) == count, (what, "the count word behind the keys changed")
-        got = got[:n_buf]
-    assert np.array_equal(got[n:], keys[n:]), (what, "keys from the count on were touched")
-    assert np.array_equal(got, want[0]), (what, "keys")
+    assert {a_keys, a_values, a_count} <= set(RESIDUES) and FRONT % 16 == 0 and (not indirect or count_at in ("own", "keys"))
+    try:
+        got = guarded_call(torch, sorter, keys, values, device_count=count, keys_off=a_keys, values_off=a_values,
+                           indirect_off=a_count, count_behind_keys=0 if indirect and count_at == "keys" else None, recorded=n > 0)
+    except AssertionError as e:
+        raise AssertionError(f"{what}: {e}") from e
+    assert np.array_equal(got.keys[n:], keys[n:]), (what, "keys from the count on were touched")
+    assert np.array_equal(got.keys, want[0]), (what, "keys")
     if key_value:
-        got = _fetch(dv, values_off, n_buf, (what, "values"))
-        assert np.array_equal(got[n:], values[n:]), (what, "values from the count on were touched")
-        assert np.array_equal(got, want[1]), (what, "values")
-    if indirect and not behind:
-        assert int(_fetch(dc, count_off, 1, (what, "count"))[0]) == count, (what, "the count word changed")
-    assert bool((storage[size:] == 0x5A).all()), (what, "wrote past the storage requirement")
-    if n > 0:
-        assert sorter.read_status(stream, storage.data_ptr(), 0) == 0, (what, "look-back spin expired")
+        assert np.array_equal(got.values[n:], values[n:]), (what, "values from the count on were touched")
+        assert np.array_equal(got.values, want[1]), (what, "values")
     if word is not None:
-        assert plan_storage_word(storage) == word, (what, hex(plan_storage_word(storage)), hex(word))
-    return storage
+        assert plan_storage_word(got.storage) == word, (what, hex(plan_storage_word(got.storage)), hex(word))
+    return got.storage
 
 
 def other_residue(a, k):
@@ -374,12 +319,12 @@ def test_graph_replay_on_misaligned_arrays(torch_mod, sorter, oracle):
     n = 8_150_003
     uniform, v = _uniform()[:n].copy(), _payload()[:n].copy()
     inputs = [("uniform", uniform), ("24-bit", model.narrow_keys(uniform, 24)), ("identical", np.full(n, model.PREFIX, np.uint32))]
-    dk, keys_off = _place(torch, 4, uniform)
-    dv, values_off = _place(torch, 12, v)
-    storage, size = _storage(torch, sorter, n, True)
+    dk, dv = to_device(torch, uniform, FRONT + 4, TAIL), to_device(torch, v, FRONT + 12, TAIL)
+    size = sorter.key_value_storage_requirements(n).size
+    storage = poisoned_storage(torch, size)
 
     def record(stream):
-        sorter.cmd_sort_key_value(stream, n, dk.data_ptr(), keys_off, dv.data_ptr(), values_off, storage.data_ptr(), 0)
+        sorter.cmd_sort_key_value(stream, n, *address(dk), *address(dv), storage.data_ptr(), 0)
 
     record(torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
@@ -388,14 +333,14 @@ def test_graph_replay_on_misaligned_arrays(torch_mod, sorter, oracle):
         record(torch.cuda.current_stream().cuda_stream)
     stream = torch.cuda.current_stream().cuda_stream
     for name, k in inputs:
-        dk[keys_off:keys_off + 4 * n].copy_(torch.from_numpy(k.view(np.uint8)))
-        dv[values_off:values_off + 4 * n].copy_(torch.from_numpy(v.view(np.uint8)))
+        dk.copy_(torch.from_numpy(k.view(np.int32)))
+        dv.copy_(torch.from_numpy(v.view(np.int32)))
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
         ek, ev = (k, v) if name == "identical" else reference(oracle, k, v)
-        assert np.array_equal(_fetch(dk, keys_off, n, (name, "keys")), ek), name
-        assert np.array_equal(_fetch(dv, values_off, n, (name, "values")), ev), name
+        assert np.array_equal(to_host(dk, guarded=True, what=f"{name} keys"), ek), name
+        assert np.array_equal(to_host(dv, guarded=True, what=f"{name} values"), ev), name
         assert plan_storage_word(storage) == msd_word(sorter, k)[0], name
-        assert bool((storage[size:] == 0x5A).all()), name
+        assert bool((storage[size:] == BAND_BYTE).all()), name
         assert sorter.read_status(stream, storage.data_ptr(), 0) == 0, name

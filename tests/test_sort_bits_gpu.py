@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import sort_bits_cases as cases
-from segmented_cases import GUARD, _dev, _host, ballot_sorter, sorter, torch_mod  # noqa: F401
+from guarded_call import ballot_sorter, guarded_call, sorter, to_device, to_host, torch_mod  # noqa: F401
+from segmented_cases import GUARD
 
 pytestmark = pytest.mark.gpu
 
@@ -18,43 +19,20 @@ FEW_RANGES = [(3, 12), (7, 24)]
 
 def run(torch, sorter, keys, values, begin, end, count=None, indirect=False, bound=None, query_pool=None, storage_out=None,
         lead=0):
-    """One vrdxHipCmdSortBits* call on torch's current stream.  keys / values: the FULL host buffers, of which the first
-    `count` (default: all) are sorted; indirect: the count travels in a device word and `bound` (default: the buffer's length)
-    is maxElementCount.  lead: words of GUARD in front of the arrays inside their allocations (4-byte alignment cases).
-    Returns (keys, values, count word) as the call left them."""
+    """One vrdxHipCmdSortBits* call on torch's current stream (guarded_call).  keys / values: the FULL host buffers, of which
+    the first `count` (default: all) are sorted; indirect: the count travels in a device word and `bound` (default: the
+    buffer's length) is maxElementCount.  lead: the arrays start that many words past a 16-byte boundary (4-byte alignment
+    cases).  storage_out: a list that receives the storage before and after the call.  Returns (keys, values) as the call left
+    them."""
     n = len(keys) if count is None else count
     bound = (len(keys) if indirect else n) if bound is None else bound
-    dk = _dev(torch, np.concatenate([np.full(lead, GUARD, np.uint32), keys]))
-    dv = _dev(torch, np.concatenate([np.full(lead, GUARD, np.uint32), values])) if values is not None else None
-    req = sorter.key_value_storage_requirements(bound) if values is not None else sorter.storage_requirements(bound)
-    storage = torch.full((req.size + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-    storage[req.size:] = 0x5A  # guard band behind the storage
-    before = storage.clone() if storage_out is not None else None
-    stream = torch.cuda.current_stream().cuda_stream
-    off = 4 * lead
-    dcount = _dev(torch, np.array([GUARD, n, GUARD, GUARD], dtype=np.uint32)) if indirect else None
-    if indirect and values is None:
-        sorter.cmd_sort_bits_indirect(stream, bound, dcount.data_ptr(), 4, dk.data_ptr(), off, begin, end, storage.data_ptr(), 0,
-                                      query_pool, 0)
-    elif indirect:
-        sorter.cmd_sort_bits_key_value_indirect(stream, bound, dcount.data_ptr(), 4, dk.data_ptr(), off, dv.data_ptr(), off, begin,
-                                                end, storage.data_ptr(), 0, query_pool, 0)
-    elif values is None:
-        sorter.cmd_sort_bits(stream, n, dk.data_ptr(), off, begin, end, storage.data_ptr(), 0, query_pool, 0)
-    else:
-        sorter.cmd_sort_bits_key_value(stream, n, dk.data_ptr(), off, dv.data_ptr(), off, begin, end, storage.data_ptr(), 0,
-                                       query_pool, 0)
-    torch.cuda.synchronize()
-    if min(n, bound) > 0 and begin < end <= 32 and (bound <= 16384 or (begin, end) == cases.FULL_RANGE):   # (a sort was recorded)
-        assert sorter.read_status(stream, storage.data_ptr(), 0) == 0
-    assert bool((storage[req.size:] == 0x5A).all()), "wrote past the storage requirement"
+    assert indirect or bound == n
+    got = guarded_call(torch, sorter, keys, values, count=bound, device_count=n if indirect else None, bit_range=(begin, end),
+                       keys_off=4 * lead, values_off=4 * lead, indirect_off=4, pool=query_pool, keep_before=storage_out is not None,
+                       recorded=min(n, bound) > 0 and begin < end <= 32 and (bound <= 16384 or (begin, end) == cases.FULL_RANGE))
     if storage_out is not None:
-        storage_out.extend([before, storage])
-    hk, hv = _host(dk), (_host(dv) if dv is not None else None)
-    assert (hk[:lead] == GUARD).all() and (hv is None or (hv[:lead] == GUARD).all()), "wrote in front of the arrays"
-    if indirect:
-        assert np.array_equal(_host(dcount), [GUARD, n, GUARD, GUARD]), "the count word changed"
-    return hk[lead:], (hv[lead:] if hv is not None else None)
+        storage_out.extend([got.before, got.storage])
+    return got.keys, got.values
 
 
 def check(torch, sorter, keys, values, begin, end, want=None, **kw):
@@ -113,13 +91,13 @@ def test_empty_range_touches_nothing(torch_mod, sorter, n, indirect):
 @pytest.mark.parametrize("n", [4097, 65539, 1048583])   # (the full range is the whole-key sort: every size)
 def test_full_range_is_the_whole_key_sort(torch_mod, sorter, n):
     """(0, 32): the result, the plan and the device's verdict of vrdxCmdSort[KeyValue]"""
-    import test_sort_gpu
+    from test_sort_gpu import gpu_sort
     torch = torch_mod
     stream = torch.cuda.current_stream().cuda_stream
     keys, values = cases.case_inputs("uniform", n, 0, 32)
     for vals in (None, values):
         a, b = [], []
-        whole_keys, whole_values = test_sort_gpu.gpu_sort(torch, sorter, keys, vals, storage_out=a)
+        whole_keys, whole_values = gpu_sort(torch, sorter, keys, vals, storage_out=a)
         got_keys, got_values = run(torch, sorter, keys, vals, 0, 32, storage_out=b)
         assert np.array_equal(got_keys, whole_keys) and (vals is None or np.array_equal(got_values, whole_values))
         assert np.array_equal(got_keys, np.sort(keys))
@@ -206,21 +184,21 @@ def test_verdict_on_storage_an_msd_sort_used(torch_mod, sorter):
     keys = rng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
     assert sorter.describe_plan(n, False).name == "msd"
     storage = torch.full((sorter.storage_requirements(n).size,), 0xA5, dtype=torch.uint8, device="cuda")
-    dk = _dev(torch, keys)
+    dk = to_device(torch, keys)
     small, mid = cases.case_inputs("uniform", 4096, 3, 12)[0], cases.case_inputs("uniform", 16384, 7, 24)[0]
     for range_keys, (begin, end) in ((small, (3, 12)), (mid, (7, 24))):
-        dk.copy_(_dev(torch, keys))
+        dk.copy_(to_device(torch, keys))
         sorter.cmd_sort(stream, n, dk.data_ptr(), 0, storage.data_ptr(), 0)
         assert sorter.read_plan_verdict(stream, storage.data_ptr(), 0) == vrdx.VERDICT_MSD_RUNS
-        dr = _dev(torch, range_keys)
+        dr = to_device(torch, range_keys)
         sorter.cmd_sort_bits(stream, len(range_keys), dr.data_ptr(), 0, begin, end, storage.data_ptr(), 0)
         assert sorter.read_plan_verdict(stream, storage.data_ptr(), 0) == vrdx.VERDICT_NONE
         assert sorter.read_status(stream, storage.data_ptr(), 0) == 0
-        assert np.array_equal(_host(dr), cases.reference(range_keys, None, begin, end)[0])
-    dk.copy_(_dev(torch, keys))
+        assert np.array_equal(to_host(dr), cases.reference(range_keys, None, begin, end)[0])
+    dk.copy_(to_device(torch, keys))
     sorter.cmd_sort(stream, n, dk.data_ptr(), 0, storage.data_ptr(), 0)
     assert sorter.read_plan_verdict(stream, storage.data_ptr(), 0) == vrdx.VERDICT_MSD_RUNS
-    assert np.array_equal(_host(dk), np.sort(keys))
+    assert np.array_equal(to_host(dk), np.sort(keys))
 
 
 @pytest.mark.parametrize("n", [4096, 16384])
@@ -253,8 +231,8 @@ def test_captured_graph_replays_on_other_data_and_counts(torch_mod, sorter, n, i
             g.replay()
             torch.cuda.synchronize()
             want_keys, want_values = cases.reference(keys, values, begin, end, count if indirect else n)
-            assert np.array_equal(_host(dk), want_keys), (builder, key_value)
-            assert not key_value or np.array_equal(_host(dv), want_values), (builder, key_value)
+            assert np.array_equal(to_host(dk), want_keys), (builder, key_value)
+            assert not key_value or np.array_equal(to_host(dv), want_values), (builder, key_value)
             assert not indirect or int(dcount.item()) == count
             assert sorter.read_status(stream, storage.data_ptr(), 0) == 0
         assert sorter.read_sorter_status(stream) == 0
@@ -277,13 +255,13 @@ def test_sort_bits_python_front_end(torch_mod, sorter):
     torch = torch_mod
     n = 12_345
     keys, values = cases.case_inputs("few", n, 5, 21)
-    dk, dv = _dev(torch, keys), _dev(torch, values)
+    dk, dv = to_device(torch, keys), to_device(torch, values)
     storage = vrdx.sort_bits(sorter, dk, 5, 21, values=dv)
     want = cases.reference(keys, values, 5, 21)
-    assert np.array_equal(_host(dk), want[0]) and np.array_equal(_host(dv), want[1])
+    assert np.array_equal(to_host(dk), want[0]) and np.array_equal(to_host(dv), want[1])
     assert storage.numel() == sorter.key_value_storage_requirements(n).size
-    dk = _dev(torch, keys)
+    dk = to_device(torch, keys)
     count = torch.tensor([1000], dtype=torch.int32, device="cuda")
     assert vrdx.sort_bits(sorter, dk, 5, 21, count=count, storage=storage) is storage
-    assert np.array_equal(_host(dk), cases.reference(keys, None, 5, 21, 1000)[0])
+    assert np.array_equal(to_host(dk), cases.reference(keys, None, 5, 21, 1000)[0])
     assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0

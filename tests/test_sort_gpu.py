@@ -13,69 +13,26 @@ import subprocess
 import numpy as np
 import pytest
 
+from guarded_call import ballot_sorter, guarded_call, sorter, to_device, to_host, torch_mod  # noqa: F401 (fixtures)
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    return torch
-
-
-@pytest.fixture(scope="module")
-def sorter(torch_mod):
-    import vulkan_radix_sort_amd as vrdx
-    s = vrdx.Sorter()  # raises VrdxError if the HIP library cannot drive this GPU: no fallback
-    yield s
-    s.destroy()
-
-
-def _u32_to_dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def _to_u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
 def gpu_sort(torch, sorter, keys, values=None, count=None, indirect=False, max_count=None, poison=True,
              query_pool=None, storage_out=None):
-    """Runs one vrdxCmdSort* on torch's current stream; returns (keys, values) numpy arrays of the
-    FULL buffers (so callers can check the untouched tail).  storage_out: a list that receives the storage tensor."""
-    n_buf = len(keys)
-    n = n_buf if count is None else count
-    dk = _u32_to_dev(torch, keys)
-    dv = _u32_to_dev(torch, values) if values is not None else None
-    max_count = n if max_count is None else max_count
-    req = (sorter.key_value_storage_requirements(max_count) if values is not None
-           else sorter.storage_requirements(max_count))
-    assert req.usage == 0x22
-    storage = torch.full((req.size + 256,), 0xA5 if poison else 0, dtype=torch.uint8, device="cuda")
-    storage[req.size:] = 0x5A  # guard band behind the storage
-    stream = torch.cuda.current_stream().cuda_stream
-    if indirect:
-        dcount = _u32_to_dev(torch, np.array([n, 0, 0, 0], dtype=np.uint32))
-        if values is None:
-            sorter.cmd_sort_indirect(stream, max_count, dcount.data_ptr(), 0, dk.data_ptr(), 0,
-                                     storage.data_ptr(), 0, query_pool, 0)
-        else:
-            sorter.cmd_sort_key_value_indirect(stream, max_count, dcount.data_ptr(), 0, dk.data_ptr(), 0,
-                                               dv.data_ptr(), 0, storage.data_ptr(), 0, query_pool, 0)
-    else:
-        if values is None:
-            sorter.cmd_sort(stream, n, dk.data_ptr(), 0, storage.data_ptr(), 0, query_pool, 0)
-        else:
-            sorter.cmd_sort_key_value(stream, n, dk.data_ptr(), 0, dv.data_ptr(), 0, storage.data_ptr(), 0,
-                                      query_pool, 0)
-    torch.cuda.synchronize()
-    if n > 0:
-        assert sorter.read_status(stream, storage.data_ptr(), 0) == 0, "look-back spin expired"
-    assert bool((storage[req.size:] == 0x5A).all()), "wrote past the storage requirement"
+    """Runs one vrdxCmdSort* on torch's current stream (guarded_call: guard bytes around the arrays, the count word and the
+    storage requirement); returns (keys, values) numpy arrays of the FULL buffers (so callers can check the untouched tail).
+    storage_out: a list that receives the storage tensor."""
+    n = len(keys) if count is None else count
+    assert indirect or max_count is None
+    got = guarded_call(torch, sorter, np.ascontiguousarray(keys, dtype=np.uint32), values,
+                       count=max_count if max_count is not None else n, device_count=n if indirect else None, poison=poison,
+                       pool=query_pool, recorded=n > 0)
     if storage_out is not None:
-        storage_out.append(storage)
-    return _to_u32(dk), (_to_u32(dv) if dv is not None else None)
+        storage_out.append(got.storage)
+    return got.keys, got.values
 
 
 def check_against_oracle(torch, sorter, oracle, keys, values=None, **kw):
@@ -313,13 +270,13 @@ def test_clean_storage_reuse_and_repeat(torch_mod, sorter, oracle):
     outs = []
     for seed in (1, 2, 3):
         kk, vv = oracle.generate(seed, n, 32)
-        dk, dv = _u32_to_dev(torch, kk), _u32_to_dev(torch, vv)
+        dk, dv = to_device(torch, kk), to_device(torch, vv)
         sorter.cmd_sort_key_value(stream, n, dk.data_ptr(), 0, dv.data_ptr(), 0, storage.data_ptr(), 0)
         outs.append((kk, vv, dk, dv))
     torch.cuda.synchronize()
     for kk, vv, dk, dv in outs:
         ek, ev, _ = oracle.sort(kk, vv)
-        assert np.array_equal(_to_u32(dk), ek) and np.array_equal(_to_u32(dv), ev)
+        assert np.array_equal(to_host(dk), ek) and np.array_equal(to_host(dv), ev)
     # idempotence: sorting sorted data changes nothing
     gk2, gv2 = gpu_sort(torch, sorter, ek, ev)
     assert np.array_equal(gk2, ek) and np.array_equal(gv2, ev)
@@ -386,7 +343,7 @@ def test_sorts_on_a_side_stream_and_two_sorters_concurrently(torch_mod, oracle):
     for i, (s, st) in enumerate(zip(sorters, streams)):
         k, v = oracle.generate(20 + i, n, 32)
         with torch.cuda.stream(st):
-            dk, dv = _u32_to_dev(torch, k), _u32_to_dev(torch, v)
+            dk, dv = to_device(torch, k), to_device(torch, v)
             storage = torch.empty(s.key_value_storage_requirements(n).size, dtype=torch.uint8, device="cuda")
             for _ in range(3):  # re-sorting sorted data is a no-op, keeps both streams busy
                 s.cmd_sort_key_value(st.cuda_stream, n, dk.data_ptr(), 0, dv.data_ptr(), 0, storage.data_ptr(), 0)
@@ -394,7 +351,7 @@ def test_sorts_on_a_side_stream_and_two_sorters_concurrently(torch_mod, oracle):
     torch.cuda.synchronize()
     for k, v, dk, dv, _ in data:
         ek, ev, _h = oracle.sort(k, v)
-        assert np.array_equal(_to_u32(dk), ek) and np.array_equal(_to_u32(dv), ev)
+        assert np.array_equal(to_host(dk), ek) and np.array_equal(to_host(dv), ev)
     for s in sorters:
         s.destroy()
 
@@ -409,9 +366,9 @@ def test_capturable_into_a_hip_graph(torch_mod, sorter, oracle):
     torch = torch_mod
     n = 200000
     k, v = oracle.generate(31, n, 32)
-    dk, dv = _u32_to_dev(torch, k), _u32_to_dev(torch, v)
+    dk, dv = to_device(torch, k), to_device(torch, v)
     storage = torch.empty(sorter.key_value_storage_requirements(n).size, dtype=torch.uint8, device="cuda")
-    warm_k, warm_v = _u32_to_dev(torch, k), _u32_to_dev(torch, v)
+    warm_k, warm_v = to_device(torch, k), to_device(torch, v)
     sorter.cmd_sort_key_value(torch.cuda.current_stream().cuda_stream, n, warm_k.data_ptr(), 0, warm_v.data_ptr(), 0,
                               storage.data_ptr(), 0)
     torch.cuda.synchronize()
@@ -421,12 +378,12 @@ def test_capturable_into_a_hip_graph(torch_mod, sorter, oracle):
                                   storage.data_ptr(), 0)
     ek, ev, _ = oracle.sort(k, v)
     for _ in range(2):  # replay twice: fresh unsorted input each time
-        dk.copy_(_u32_to_dev(torch, k))
-        dv.copy_(_u32_to_dev(torch, v))
+        dk.copy_(to_device(torch, k))
+        dv.copy_(to_device(torch, v))
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
-        assert np.array_equal(_to_u32(dk), ek) and np.array_equal(_to_u32(dv), ev)
+        assert np.array_equal(to_host(dk), ek) and np.array_equal(to_host(dv), ev)
         assert sorter.read_status(torch.cuda.current_stream().cuda_stream, storage.data_ptr(), 0) == 0
 
 
@@ -452,7 +409,7 @@ def test_one_captured_graph_sorts_whatever_keys_it_is_replayed_on(torch_mod, sor
     stream = torch.cuda.current_stream().cuda_stream
     for key_value in (False, True):
         assert sorter.describe_plan(n, key_value).name == "msd"
-        dk, dv = _u32_to_dev(torch, r), _u32_to_dev(torch, iota)
+        dk, dv = to_device(torch, r), to_device(torch, iota)
         size = (sorter.key_value_storage_requirements(n) if key_value else sorter.storage_requirements(n)).size
         storage = torch.empty(size, dtype=torch.uint8, device="cuda")
         record = ((lambda st: sorter.cmd_sort_key_value(st, n, dk.data_ptr(), 0, dv.data_ptr(), 0, storage.data_ptr(), 0))
@@ -463,14 +420,14 @@ def test_one_captured_graph_sorts_whatever_keys_it_is_replayed_on(torch_mod, sor
         with torch.cuda.graph(g):
             record(torch.cuda.current_stream().cuda_stream)
         for name, k, verdict in inputs:
-            dk.copy_(_u32_to_dev(torch, k))
-            dv.copy_(_u32_to_dev(torch, iota))
+            dk.copy_(to_device(torch, k))
+            dv.copy_(to_device(torch, iota))
             torch.cuda.synchronize()
             g.replay()
             torch.cuda.synchronize()
             ek, ep, _ = oracle.sort(k, iota)
-            assert np.array_equal(_to_u32(dk), ek), (name, key_value)
-            assert not key_value or np.array_equal(_to_u32(dv), ep), (name, key_value)
+            assert np.array_equal(to_host(dk), ek), (name, key_value)
+            assert not key_value or np.array_equal(to_host(dv), ep), (name, key_value)
             assert sorter.read_plan_verdict(stream, storage.data_ptr(), 0) == verdict, (name, key_value)
             assert sorter.read_status(stream, storage.data_ptr(), 0) == 0
 
@@ -1109,22 +1066,6 @@ def test_ballot_ranking_native_battery(config):
     assert r.returncode == 0 and ", 0 failures" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
-@pytest.fixture(scope="module")
-def ballot_sorter(torch_mod):
-    import vulkan_radix_sort_amd as vrdx
-    old = os.environ.get("VRDX_RANK")
-    os.environ["VRDX_RANK"] = "ballot"  # read by vrdxCreateSorter
-    try:
-        s = vrdx.Sorter()
-    finally:
-        if old is None:
-            del os.environ["VRDX_RANK"]
-        else:
-            os.environ["VRDX_RANK"] = old
-    yield s
-    s.destroy()
-
-
 @pytest.mark.parametrize("n", [1, 255, 4096, 4097, 16383, 16384, 16385])
 def test_ballot_ranking_small_sort_boundary_sizes(torch_mod, ballot_sorter, oracle, n):
     k, _ = oracle.generate(5, n, 8)
@@ -1151,13 +1092,13 @@ def test_ballot_ranking_every_size_regime(torch_mod, ballot_sorter, oracle, n):
 def _histogram_table_after_sort(torch, sorter, keys, count=None, indirect=False, values=None):
     n_buf = len(keys)
     n = n_buf if count is None else count
-    dk = _u32_to_dev(torch, keys)
-    dv = _u32_to_dev(torch, values) if values is not None else None
+    dk = to_device(torch, keys)
+    dv = to_device(torch, values) if values is not None else None
     req = sorter.key_value_storage_requirements(n_buf) if values is not None else sorter.storage_requirements(n_buf)
     storage = torch.full((req.size,), 0xA5, dtype=torch.uint8, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     if indirect:
-        dcount = _u32_to_dev(torch, np.array([n, 0, 0, 0], dtype=np.uint32))
+        dcount = to_device(torch, np.array([n, 0, 0, 0], dtype=np.uint32))
         sorter.cmd_sort_indirect(stream, n_buf, dcount.data_ptr(), 0, dk.data_ptr(), 0, storage.data_ptr(), 0)
     elif values is not None:
         sorter.cmd_sort_key_value(stream, n, dk.data_ptr(), 0, dv.data_ptr(), 0, storage.data_ptr(), 0)
@@ -1166,7 +1107,7 @@ def _histogram_table_after_sort(torch, sorter, keys, count=None, indirect=False,
     torch.cuda.synchronize()
     # uint32[4][256] at byte 16 of the storage: where the reference keeps globalHistogram
     # (src/vk_radix_sort.h.in:405-406); raw counts of the valid keys here
-    return storage[16:16 + 4096].cpu().numpy().view(np.uint32).reshape(4, 256), _to_u32(dk)
+    return storage[16:16 + 4096].cpu().numpy().view(np.uint32).reshape(4, 256), to_host(dk)
 
 
 @pytest.mark.parametrize("n", [16385, 100_003, (1 << 20) + 7, 5_000_011, (1 << 24) + 3])
@@ -1211,13 +1152,13 @@ def test_sorter_status_is_sticky_across_sorts_sharing_one_storage(torch_mod, sor
     expected, buffers = [], []
     for seed in range(4):
         k, v = oracle.generate(20 + seed, n - 1000 * seed, 32)
-        dk, dv = _u32_to_dev(torch, k), _u32_to_dev(torch, v)
+        dk, dv = to_device(torch, k), to_device(torch, v)
         sorter.cmd_sort_key_value(stream, len(k), dk.data_ptr(), 0, dv.data_ptr(), 0, storage.data_ptr(), 0)
         buffers.append((dk, dv))
         expected.append(oracle.sort(k, v))
     assert sorter.read_sorter_status(stream) == 0
     for (dk, dv), (ek, ev, _) in zip(buffers, expected):
-        assert np.array_equal(_to_u32(dk), ek) and np.array_equal(_to_u32(dv), ev)
+        assert np.array_equal(to_host(dk), ek) and np.array_equal(to_host(dv), ev)
 
 
 def test_recheck_and_event_overhead_helpers(torch_mod, oracle):

@@ -57,9 +57,10 @@ import numpy as np
 import pytest
 
 import storage_reuse_cases as cases
+from guarded_call import ballot_sorter, sorter, to_device, torch_mod  # noqa: F401 (fixtures)
 from storage_reuse_cases import CALLS, INHERITED, NAMES
 from test_plan_choice_gpu import expected_word, plan_storage_word
-from test_sort_gpu import ballot_sorter, sorter, torch_mod  # noqa: F401 (fixtures)
+from vulkan_radix_sort_amd import api
 
 pytestmark = pytest.mark.gpu
 
@@ -72,12 +73,6 @@ FILLS = [("zero", 0x00000000), ("ones", 0xFFFFFFFF), ("one", 0x00000001), ("aggr
          ("inclusive-1", 0x80000001), ("block-arrival-1", 0x04000001), ("random", None)]
 
 RAN = set()           # (leaver, follower, storage_off) of every pair the matrix has run
-
-
-def _dev(torch, a):
-    """a uint32 | uint64 host array as an int32 | int64 device tensor of the same bits"""
-    signed = np.int64 if a.dtype == np.uint64 else np.int32
-    return torch.from_numpy(np.ascontiguousarray(a).view(signed).copy()).cuda()
 
 
 @pytest.fixture(scope="module")
@@ -98,9 +93,9 @@ def world(torch_mod, sorter, ballot_sorter):
             assert call.plan != "msd" or int(info.bits) == cases.MSD_BITS, (call.name, int(info.bits))
         if call.inputs not in shared:
             keys, values, offsets = cases.input_set(call.inputs)
-            pristine = SimpleNamespace(keys=_dev(torch, cases.padded(keys)),
-                                       values=_dev(torch, cases.padded(values)) if values is not None else None,
-                                       offsets=_dev(torch, offsets) if offsets is not None else None)
+            pristine = SimpleNamespace(keys=to_device(torch, cases.padded(keys)),
+                                       values=to_device(torch, cases.padded(values)) if values is not None else None,
+                                       offsets=to_device(torch, offsets) if offsets is not None else None)
             shared[call.inputs] = SimpleNamespace(
                 pristine=pristine, keys=pristine.keys.clone(),
                 values=pristine.values.clone() if values is not None else None,
@@ -109,8 +104,8 @@ def world(torch_mod, sorter, ballot_sorter):
         which = (key_value, cases.sorted_count(call))
         if which not in d.expected:
             want_keys, want_values = cases.expected_of(call)
-            d.expected[which] = (_dev(torch, cases.padded(want_keys)),
-                                 _dev(torch, cases.padded(want_values)) if key_value else None)
+            d.expected[which] = (to_device(torch, cases.padded(want_keys)),
+                                 to_device(torch, cases.padded(want_values)) if key_value else None)
         required = {"keys": lambda: s.storage_requirements(call.bound),
                     "key-value": lambda: s.key_value_storage_requirements(call.bound),
                     "keys64": lambda: s.storage_requirements64(call.bound, False),
@@ -120,7 +115,7 @@ def world(torch_mod, sorter, ballot_sorter):
         assert verdict == call.verdict, (call.name, verdict)
         count = None
         if call.count is not None:
-            count = _dev(torch, np.array([call.count, 0, 0, 0], np.uint32))
+            count = to_device(torch, np.array([call.count, 0, 0, 0], np.uint32))
         w.device[call.name] = SimpleNamespace(
             buffers=d, key_value=key_value, expected_keys=d.expected[which][0], expected_values=d.expected[which][1],
             required=required, count=count, count_pristine=count.clone() if count is not None else None,
@@ -153,33 +148,19 @@ def _prepare_storage(w, off, word=None, random=False):
     w.storage[off + w.largest:] = BAND_BYTE
 
 
+ROWS = {row.c_name: row for row in api.RECORDING_CALLS}
+
+
 def _record(s, stream, call, d, storage, off):
+    """the row of RECORDING_CALLS that `call.entry` names, on the world's buffers at byte offset 0"""
     b = d.buffers
-    keys, values = b.keys.data_ptr(), (b.values.data_ptr() if d.key_value else None)
-    count = d.count.data_ptr() if d.count is not None else None
-    segments = len(b.offsets) - 1 if b.offsets is not None else None
-    offsets = b.offsets.data_ptr() if b.offsets is not None else None
-    e = call.entry
-    if e == "vrdxCmdSort":
-        s.cmd_sort(stream, call.bound, keys, 0, storage, off)
-    elif e == "vrdxCmdSortKeyValue":
-        s.cmd_sort_key_value(stream, call.bound, keys, 0, values, 0, storage, off)
-    elif e == "vrdxCmdSortIndirect":
-        s.cmd_sort_indirect(stream, call.bound, count, 0, keys, 0, storage, off)
-    elif e == "vrdxCmdSortKeyValueIndirect":
-        s.cmd_sort_key_value_indirect(stream, call.bound, count, 0, keys, 0, values, 0, storage, off)
-    elif e == "vrdxHipCmdSortSegmented":
-        s.cmd_sort_segmented(stream, call.bound, segments, offsets, 0, keys, 0, storage, off)
-    elif e == "vrdxHipCmdSortSegmentedKeyValue":
-        s.cmd_sort_segmented_key_value(stream, call.bound, segments, offsets, 0, keys, 0, values, 0, storage, off)
-    elif e == "vrdxHipCmdSortSegmented64":
-        s.cmd_sort_segmented64(stream, call.bound, segments, offsets, 0, keys, 0, storage, off)
-    elif e == "vrdxHipCmdSort64KeyValue":
-        s.cmd_sort64_key_value(stream, call.bound, keys, 0, values, 0, storage, off)
-    elif e == "vrdxHipCmdSort64Indirect":
-        s.cmd_sort64_indirect(stream, call.bound, count, 0, keys, 0, storage, off)
-    else:
-        raise ValueError(e)
+    row = ROWS[call.entry]
+    given = {"command_buffer": stream, "element_count": call.bound, "max_element_count": call.bound,
+             "segment_count": len(b.offsets) - 1 if b.offsets is not None else None, "offsets": b.offsets, "indirect": d.count,
+             "keys": b.keys, "values": b.values if d.key_value else None}
+    given = {name: t.data_ptr() if hasattr(t, "data_ptr") else t for name, t in given.items()}
+    given.update(storage=storage, storage_offset=off, offsets_offset=0, indirect_offset=0, keys_offset=0, values_offset=0)
+    getattr(s, row.method)(*(given[name] for name, _ in row.parameters[:-2]))   # (no query pool)
 
 
 def run(w, call, off):
