@@ -390,7 +390,8 @@ void vrdxHipCmdSortSegmented64KeyValue(VkCommandBuffer commandBuffer, VrdxSorter
  *   order == VRDX_HIP_KEY_UINT64 records exactly what the twin records: the same kernels, bit for bit the same work.
  *   An order word with any other bit set, or a key type above VRDX_HIP_KEY_FLOAT64, is refused like an invalid bit range: the
  *   timestamps are recorded, nothing else is touched, and the sorter's word raises VRDX_HIP_STATUS_ENQUEUE_REFUSED.
- * Out of scope: orders for the 32-bit sorts and the bit-range sorts; float32; ranges for the 64-bit sorts.
+ * Out of scope: orders for the bit-range sorts; ranges for the 64-bit sorts.  Orders for the 32-bit sorts (int32, float32,
+ * descending): vrdxHipCmdOrderedSort* below.
  */
 #define VRDX_HIP_KEY_UINT64 0u
 #define VRDX_HIP_KEY_INT64 1u
@@ -457,8 +458,8 @@ void vrdxHipCmdSortSegmented64OrderedKeyValue(VkCommandBuffer commandBuffer, Vrd
  * Timestamps: the 15-slot contract as for ONE_WORKGROUP above.
  *
  * Out of scope: range sorts of more than 16384 elements (the range forms of the histogram and pass kernels are not part of
- * this library yet: DESIGN.md section 4.13); ranges for the 64-bit sorts; descending, signed and floating-point orders of
- * 32-bit keys (the 64-bit sorts have them: vrdxHipCmdSort64Ordered* above).
+ * this library yet: DESIGN.md section 4.13); ranges for the 64-bit sorts; a range combined with a descending, signed or
+ * floating-point order (whole 32-bit keys have those orders: vrdxHipCmdOrderedSort* below).
  * Ranges for the segmented sort: vrdxHipCmdSortSegmentedBits below.
  */
 void vrdxHipCmdSortBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
@@ -511,6 +512,75 @@ void vrdxHipCmdSortSegmentedBitsKeyValue(VkCommandBuffer commandBuffer, VrdxSort
                                          VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
                                          VkDeviceSize valuesOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
                                          VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+
+/**
+ * Key orders of the 32-bit sorts (not part of the reference API): int32 and float32 keys, ascending or descending.  The four
+ * flat calls and the two segmented calls with one order word, `order`, in front of storageBuffer -- the position it has in
+ * vrdxHipCmdSort64Ordered* -- and everything else in the order of the matching call (the twin):
+ *   vrdxHipCmdOrderedSort[KeyValue][Indirect]      vrdxCmdSort[KeyValue][Indirect]
+ *   vrdxHipCmdOrderedSortSegmented[KeyValue]       vrdxHipCmdSortSegmented[KeyValue]
+ *
+ * The order word: one key type, VRDX_HIP_KEY32_UINT32, VRDX_HIP_KEY32_INT32 or VRDX_HIP_KEY32_FLOAT32, with
+ * VRDX_HIP_ORDER_DESCENDING or-ed in or not.
+ * Order: let T(k) = k ^ flip ^ (FLOAT32 and bit 31 of k set ? 0x7FFFFFFF : 0) on the key's 32 bits, with flip = 0 for UINT32,
+ * 1 << 31 for INT32 and FLOAT32, and the complement of that for descending.  After the call the elements (of every segment)
+ * are in ascending unsigned order of T(key).  T is a bijection, so:
+ *   UINT32, INT32   ascending (descending) as unsigned, as two's-complement signed integers;
+ *   FLOAT32         IEEE-754 totalOrder on the bits: NaNs with the sign bit set first, then -inf ... -0.0, then +0.0 ... +inf,
+ *                   NaNs with the sign bit clear last, NaNs among themselves by their payload bits; descending is the reverse;
+ *   stability       elements of EQUAL key keep their input order, for descending too (not the reverse of the ascending
+ *                   result): what CUB's SortKeysDescending / SortPairsDescending and a stable torch.sort(descending=True) give;
+ *   keys come back bit for bit as they went in, values travel with their keys.
+ * FLOAT32 differs from torch.sort (and numpy.sort) in two ways: torch.sort puts ALL NaNs last (first when descending),
+ * whatever their sign bit, and treats -0.0 and +0.0 as equal, leaving them in input order; here -0.0 sorts in front of +0.0.
+ * On keys without NaNs and without zeros of both signs the two agree.
+ * Everything else is the twin's, word for word: the storage (vrdxGetSorter[KeyValue]StorageRequirements), the alignment
+ * rules (keys, values, count and offsets on 4 bytes, the storage on 16), the clamp at 2^30 - 4, the device-side count of the
+ * indirect forms and its clamp to the bound -- elements from the count on are neither read nor written --, bad offsets
+ * (VRDX_HIP_STATUS_SEGMENTS_INVALID), the status and verdict words, capture and replay with a NULL pool.
+ *   order == VRDX_HIP_KEY32_UINT32 records exactly what the twin records: the same kernels, the same steps.
+ *   An order word with any other bit set, or a key type above VRDX_HIP_KEY32_FLOAT32, is refused like an invalid bit range:
+ *   the timestamps are recorded, nothing else is touched, and the sorter's word raises VRDX_HIP_STATUS_ENQUEUE_REFUSED.
+ * How: up to 16384 elements, and in every segment of the segmented calls, the order costs a few instructions -- the kernels
+ * apply T behind their loads and its inverse in front of their stores (a large segment: in its first and its last pass
+ * through memory); measured at 0-3 % of the twin in LDS and up to 6 % on large segments.  A flat sort of MORE than 16384 elements runs one streaming launch that rewrites keys[0, n) with
+ * T(key) in place, then the twin's plan unchanged (MSD, hybrid or four passes, verdict and fallback on the device as ever),
+ * then one launch that rewrites keys[0, n) with the keys: two launches and 16 bytes per key on top of the twin, which
+ * vrdxHipDescribeOrderedSortPlan reports.  While such a call runs the caller's key array holds T(key).
+ * Timestamps: up to 16384 elements the ONE_WORKGROUP contract, the segmented calls their twin's.  Beyond 16384 elements the
+ * forward transform lies in [0,1] in front of the fill, the inverse in [13,14] (which no step of the twin ends), and everything
+ * between is the twin's contract.
+ * Out of scope: T fused into the plan's first reader and last writer (the histogram, scatter, bucket and pass kernels):
+ * which launch reads the caller's keys first and writes them last is settled on the device, and those kernels are tuned to
+ * the register.  An order combined with a bit range.
+ */
+#define VRDX_HIP_KEY32_UINT32 0u
+#define VRDX_HIP_KEY32_INT32 1u
+#define VRDX_HIP_KEY32_FLOAT32 2u
+void vrdxHipCmdOrderedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                           VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                           VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdOrderedSortKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                                   VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset, uint32_t order,
+                                   VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdOrderedSortIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                   VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                   VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                   VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdOrderedSortKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                           VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                           VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                           uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                           VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdOrderedSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                    uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                    VkBuffer keysBuffer, VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer,
+                                    VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdOrderedSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                            uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                            VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                            VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
+                                            VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
 
 /* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves
@@ -590,6 +660,11 @@ void vrdxHipDescribePlan(VrdxSorter sorter, uint32_t elementCount, int keyValue,
  * elements (which is refused), report VRDX_HIP_PLAN_NONE. */
 void vrdxHipDescribeSortBitsPlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, uint32_t beginBit, uint32_t endBit,
                                  VrdxHipPlanInfo* info);
+/* The same for vrdxHipCmdOrderedSort[KeyValue][Indirect] with the order word `order`: what vrdxHipDescribePlan reports, plus,
+ * beyond one workgroup and for a word other than VRDX_HIP_KEY32_UINT32, the two transform launches and their 16 bytes per
+ * element (in bytesPerElement and fallbackBytesPerElement); an invalid word (which is refused) reports VRDX_HIP_PLAN_NONE. */
+void vrdxHipDescribeOrderedSortPlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, uint32_t order,
+                                    VrdxHipPlanInfo* info);
 
 /* What the DEVICE made of the plan of the last sort that used this storage (word 1 of the storage; synchronises the
  * stream): vrdxHipDescribePlan is the host's intention, this is the verdict.  Meaningful for the two plans that are

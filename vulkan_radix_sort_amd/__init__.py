@@ -37,12 +37,18 @@ from .api import (  # noqa: F401
     ORDER_DESCENDING,
     KEY_ORDERS,
     order_word,
+    KEY32_UINT32,
+    KEY32_INT32,
+    KEY32_FLOAT32,
+    KEY32_ORDERS,
+    order_word32,
 )
 from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
 from .segmented64 import sort_segments64  # noqa: F401
 from .sort_bits import sort_bits  # noqa: F401
 from .segmented_bits import sort_segments_bits  # noqa: F401
+from .ordered import sort_ordered, sort_segments_ordered  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -78,4 +84,11 @@ __all__ = [
     "sort_segments64",
     "sort_bits",
     "sort_segments_bits",
+    "KEY32_UINT32",
+    "KEY32_INT32",
+    "KEY32_FLOAT32",
+    "KEY32_ORDERS",
+    "order_word32",
+    "sort_ordered",
+    "sort_segments_ordered",
 ]

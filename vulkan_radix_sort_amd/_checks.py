@@ -16,12 +16,14 @@ Known differences between the front ends.  They are behaviour -- a caller sees t
   (``check_storage`` with ``device=``); the range sorts tell it "storage must live on a GPU" (``check_device``).
 * sort64 words its refusal of a count of several elements itself ("one element", ``holds=``); sort_bits says "1 element(s)".
 * Each front end names what its keys, offsets and values must hold in its own words (``what``).
+* sort_ordered and sort_segments_ordered (ordered.py) came later and follow sort64: ``check_keys32`` for dtype and order word,
+  every array's device right behind its shape, the storage on a 16-byte boundary.
 * sort_segments_bits checks the bit range before the tensors, sort_bits behind keys and values; only sort_bits bounds the
   number of keys of a partial range (``check_range_count``).
 """
 from __future__ import annotations
 
-from .api import order_word
+from .api import order_word, order_word32
 
 MAX_ELEMENTS = 0x3FFFFFFC   # VRDX_MAX_ELEMENTS (vrdx_layout.h)
 MAX_RANGE_ELEMENTS = 16384  # kSmallSortMaxElements (vrdx_kernels.h): range sorts are one-workgroup sorts
@@ -86,6 +88,20 @@ def check_keys(torch, keys, order, descending):
         check_tensor(torch, "keys", keys, (torch.float64,) + integers, "float64, or 8-byte integers holding float64 bits", gpu=True)
     else:
         check_tensor(torch, "keys", keys, integers, f"8-byte integers (int64 or uint64, sorted as {order})", gpu=True)
+    return word
+
+
+def check_keys32(torch, keys, order, descending):
+    """The dtype rule of ``sort_ordered`` and ``sort_segments_ordered``, and the order word: ``"uint32"`` and ``"int32"`` take
+    the 4-byte integer dtypes, ``"float32"`` takes ``torch.float32`` and 4-byte integers holding the bits."""
+    if not isinstance(descending, bool):
+        raise TypeError(f"descending must be a bool, got {type(descending).__name__}")
+    word = order_word32(order, descending)
+    integers = integer_dtypes(torch)[0]
+    if order == "float32":
+        check_tensor(torch, "keys", keys, (torch.float32,) + integers, "float32, or 4-byte integers holding float32 bits", gpu=True)
+    else:
+        check_tensor(torch, "keys", keys, integers, f"4-byte integers (int32 or uint32, sorted as {order})", gpu=True)
     return word
 
 

@@ -17,7 +17,8 @@ reference (C++ / Vulkan)                        here
 
 The HIP-only recording calls (segmented, 64-bit, by a bit range, in a key order) stand next to those four in
 ``RECORDING_CALLS``, one row each: the exported names, the ctypes signatures and the ``Sorter.cmd_*`` methods all come from
-that table.
+that table.  The ordered sorts of 32-bit keys (``vrdxHipCmdOrderedSort*``: int32, float32, descending) have a second table of the
+same kind, ``ORDERED_SORT_CALLS``, and ``record_ordered_sort`` next to ``record_sort``.
 
 ``VkCommandBuffer`` is a ``hipStream_t`` (an ``int`` handle, e.g. ``torch.cuda.current_stream().cuda_stream``),
 ``VkBuffer`` is a device address (``tensor.data_ptr()``), offsets are bytes.  Like the reference,
@@ -44,7 +45,8 @@ STORAGE_USAGE = 0x20 | 0x02
 class RecordingCall(NamedTuple):
     """One vrdx*CmdSort* entry point: its C name, the ``Sorter`` method that forwards to it and that method's docstring (what
     stands behind the C name, which the method puts in front).  The name says what the call takes --
-    ``vrdx[Hip]CmdSort[Segmented][64][Bits|Ordered][KeyValue][Indirect]`` -- and the argument list follows from that alone,
+    ``vrdx[Hip]CmdSort[Segmented][64][Bits|Ordered][KeyValue][Indirect]``, or, for the rows of ``ORDERED_SORT_CALLS``,
+    ``vrdxHipCmdOrderedSort[Segmented][KeyValue][Indirect]`` -- and the argument list follows from that alone,
     always in this order (``parameters``):
 
         commandBuffer, sorter, count, [segmentCount, offsets, offsetsOffset | indirect, indirectOffset], keys, keysOffset,
@@ -58,8 +60,13 @@ class RecordingCall(NamedTuple):
     @property
     def facts(self):
         """(key bits, segmented, indirect, key+value, None | "Bits" | "Ordered"), parsed from the C name"""
-        segmented, wide, extra, key_value, indirect = re.fullmatch(
-            r"vrdx(?:Hip)?CmdSort(Segmented)?(64)?(Bits|Ordered)?(KeyValue)?(Indirect)?", self.c_name).groups()
+        ordered32 = re.fullmatch(r"vrdxHipCmdOrderedSort(Segmented)?(KeyValue)?(Indirect)?", self.c_name)
+        if ordered32:   # the ordered 32-bit sorts carry the word in front: their names are not of the CmdSort family
+            segmented, key_value, indirect = ordered32.groups()
+            wide, extra = None, "Ordered"
+        else:
+            segmented, wide, extra, key_value, indirect = re.fullmatch(
+                r"vrdx(?:Hip)?CmdSort(Segmented)?(64)?(Bits|Ordered)?(KeyValue)?(Indirect)?", self.c_name).groups()
         assert not (segmented and indirect), self.c_name
         return 64 if wide else 32, bool(segmented), bool(indirect), bool(key_value), extra
 
@@ -159,6 +166,24 @@ RECORDING_CALLS = (
           "the same with one uint32 value per key."),
 )
 
+# int32, float32 and descending orders of the uint32 sorts: a table of its own (the CmdSort family above is closed), the same
+# kind of row; the order word sits where the 64-bit ordered sorts have theirs
+ORDERED_SORT_CALLS = (
+    _CALL("vrdxHipCmdOrderedSort", "cmd_ordered_sort",
+          "``cmd_sort`` in the order of the word ``order`` (``KEY32_UINT32``, ``KEY32_INT32`` or ``KEY32_FLOAT32``, "
+          "``| ORDER_DESCENDING``): stable in both directions, keys come back bit for bit."),
+    _CALL("vrdxHipCmdOrderedSortKeyValue", "cmd_ordered_sort_key_value",
+          "the same with values that travel with their keys."),
+    _CALL("vrdxHipCmdOrderedSortIndirect", "cmd_ordered_sort_indirect",
+          "``cmd_sort_indirect`` in the order of the word ``order``."),
+    _CALL("vrdxHipCmdOrderedSortKeyValueIndirect", "cmd_ordered_sort_key_value_indirect",
+          "the same with values that travel with their keys."),
+    _CALL("vrdxHipCmdOrderedSortSegmented", "cmd_ordered_sort_segmented",
+          "``cmd_sort_segmented`` with every segment in the order of the word ``order``."),
+    _CALL("vrdxHipCmdOrderedSortSegmentedKeyValue", "cmd_ordered_sort_segmented_key_value",
+          "the same with values that travel with their keys."),
+)
+
 
 def _exported_symbols():
     """Everything the library exports, in the order this tuple has always had: the entry points that record no sort, by hand,
@@ -181,6 +206,9 @@ def _exported_symbols():
         yield from names
         yield from (next(rows).c_name for _ in range(recording))
     assert next(rows, None) is None, "a row of RECORDING_CALLS is missing from EXPORTED_SYMBOLS"
+    # the ordered 32-bit sorts
+    yield from (call.c_name for call in ORDERED_SORT_CALLS)
+    yield "vrdxHipDescribeOrderedSortPlan"
 
 
 EXPORTED_SYMBOLS = tuple(_exported_symbols())
@@ -231,6 +259,20 @@ def record_sort(sorter, key_bits, stream, count, offsets, segment_count, indirec
     recorder(sorter, stream, count, offsets, segment_count, indirect, keys, values, bit_range, order, storage)
 
 
+_ORDERED_RECORDERS = {_takes(*call.facts)[1:4]: _recorder(call) for call in ORDERED_SORT_CALLS}
+
+
+def record_ordered_sort(sorter, stream, count, offsets, segment_count, indirect, keys, values, order, storage):
+    """``record_sort`` for the rows of ORDERED_SORT_CALLS: records the one ordered sort of uint32 keys that takes what the caller
+    has.  ``order``: the order word, always handed on; ``offsets`` / ``indirect`` / ``values``: ``None`` selects the call without
+    that argument; offsets together with a count is a TypeError, as no row takes both."""
+    takes = (offsets is not None, indirect is not None, values is not None)
+    recorder = _ORDERED_RECORDERS.get(takes)
+    if recorder is None:
+        raise TypeError(f"no ordered recording call takes (offsets, indirect, values) = {takes}")
+    recorder(sorter, stream, count, offsets, segment_count, indirect, keys, values, None, order, storage)
+
+
 # the order word of vrdxHipCmdSort64Ordered* and vrdxHipCmdSortSegmented64Ordered* (include/vk_radix_sort.h): one key type,
 # ORDER_DESCENDING or-ed in or not
 KEY_UINT64 = 0
@@ -247,6 +289,24 @@ def order_word(order: str, descending: bool = False) -> int:
     if order not in KEY_ORDERS:
         raise ValueError(f"order must be one of {', '.join(map(repr, KEY_ORDERS))}, got {order!r}")
     return KEY_ORDERS[order] | (ORDER_DESCENDING if descending else 0)
+
+
+
+# the key types of vrdxHipCmdOrderedSort* (include/vk_radix_sort.h); the direction bit is ORDER_DESCENDING
+KEY32_UINT32 = 0
+KEY32_INT32 = 1
+KEY32_FLOAT32 = 2
+KEY32_ORDERS = {"uint32": KEY32_UINT32, "int32": KEY32_INT32, "float32": KEY32_FLOAT32}
+
+
+def order_word32(order: str, descending: bool = False) -> int:
+    """The order word for ``order`` in ``KEY32_ORDERS`` (``"uint32"``, ``"int32"``, ``"float32"``) and a direction."""
+    if not isinstance(order, str):
+        raise TypeError(f"order must be one of {', '.join(map(repr, KEY32_ORDERS))}, got {type(order).__name__}")
+    if order not in KEY32_ORDERS:
+        raise ValueError(f"order must be one of {', '.join(map(repr, KEY32_ORDERS))}, got {order!r}")
+    return KEY32_ORDERS[order] | (ORDER_DESCENDING if descending else 0)
+
 
 # bits of vrdxHipReadSorterStatus (include/vk_radix_sort.h)
 STATUS_LOOKBACK_GAVE_UP = 0x00000001
@@ -349,10 +409,12 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = None
         fn.argtypes = [vp, u32, ctypes.POINTER(VrdxSorterStorageRequirements)]
-    for call in RECORDING_CALLS:
+    for call in RECORDING_CALLS + ORDERED_SORT_CALLS:
         fn = getattr(lib, call.c_name)
         fn.restype = None
         fn.argtypes = call.argtypes
+    lib.vrdxHipDescribeOrderedSortPlan.restype = None
+    lib.vrdxHipDescribeOrderedSortPlan.argtypes = [vp, u32, ctypes.c_int, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipDescribeSortBitsPlan.restype = None
     lib.vrdxHipDescribeSortBitsPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
@@ -512,6 +574,13 @@ class Sorter:
                                               ctypes.byref(info))
         return info
 
+    def describe_ordered_sort_plan(self, element_count: int, key_value: bool, order: int) -> VrdxHipPlanInfo:
+        """``vrdxHipDescribeOrderedSortPlan``: the plan ``cmd_ordered_sort*`` records for that many elements and that order word
+        (beyond one workgroup: ``describe_plan``'s, plus two launches and 16 bytes per element)."""
+        info = VrdxHipPlanInfo()
+        self._lib.vrdxHipDescribeOrderedSortPlan(self.handle, element_count, 1 if key_value else 0, order, ctypes.byref(info))
+        return info
+
     def read_plan_verdict(self, command_buffer, storage, storage_offset=0) -> int:
         """``vrdxHipReadPlanVerdict``: what the device made of the plan of the last sort on this storage (``VERDICT_*``):
         ``describe_plan`` is the host's intention, this is what ran.  Synchronises the stream."""
@@ -563,5 +632,5 @@ def _recording_method(call: RecordingCall):
     return method
 
 
-for _call in RECORDING_CALLS:
+for _call in RECORDING_CALLS + ORDERED_SORT_CALLS:
     setattr(Sorter, _call.method, _recording_method(_call))

@@ -427,6 +427,12 @@ hipError_t EnqueueStep(const VrdxSorter_T* sorter, const vrdx::PlanContext& cont
     case Step::kSmallSortBits:
       return vrdx::LaunchSmallSortBits(stream, atomicRank, b.keys, b.values, plan.elementCount, b.countPtr, b.failure,
                                        plan.rangeBegin, plan.rangeWidth);
+    // an ordered sort: the order word behind the arguments of the one-workgroup kernel | the transforms around the plan
+    case Step::kSmallSortOrdered:
+      return vrdx::LaunchSmallSortOrdered(stream, atomicRank, b.keys, b.values, plan.elementCount, b.countPtr, b.failure,
+                                          plan.order);
+    case Step::kOrderForward: return vrdx::LaunchOrder32(stream, false, b.keys, plan.elementCount, b.countPtr, plan.order);
+    case Step::kOrderInverse: return vrdx::LaunchOrder32(stream, true, b.keys, plan.elementCount, b.countPtr, plan.order);
   }
   return hipErrorInvalidValue;
 }
@@ -463,17 +469,20 @@ struct Recording {
 // beginBit, endBit: the whole key for vrdxCmdSort*; vrdxHipCmdSortBits* hand their range on (include/vk_radix_sort.h) -- the
 // full range takes the whole-key plan (PlanSortBits forwards it), an empty one has no step, an invalid one and one beyond one
 // workgroup's reach are refused.
+// order: VRDX_HIP_KEY32_UINT32 for all of those; vrdxHipCmdOrderedSort* hand their order word on (with the whole key):
+// PlanOrderedSort, whose transform steps share slot 1 with the fill behind the first and end slot 14 behind pass 3.
 void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount,
                 VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
                 VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                 VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
-                uint32_t query, uint32_t beginBit = 0, uint32_t endBit = 32) {
+                uint32_t query, uint32_t beginBit = 0, uint32_t endBit = 32, uint32_t order = VRDX_HIP_KEY32_UINT32) {
   Recording r(commandBuffer, sorter, elementCount, queryPool, query);
   const bool keyValue = valuesBuffer != nullptr;
   uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
   const vrdx::PlanContext context = PlanContextOf(sorter);
-  const SortPlan plan =
-      vrdx::PlanSortBits(context, keyValue, r.count, beginBit, endBit, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  const uint64_t storageAddress = (uint64_t)reinterpret_cast<uintptr_t>(storage);
+  const SortPlan plan = order != VRDX_HIP_KEY32_UINT32 ? vrdx::PlanOrderedSort(context, keyValue, r.count, order, storageAddress)
+                                                       : vrdx::PlanSortBits(context, keyValue, r.count, beginBit, endBit, storageAddress);
   if (r.NothingToRecord(sorter, plan.refusal, plan.stepCount)) return;
   const SortBuffers b = ResolveBuffers(
       sorter, plan.layout, storage, reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset)),
@@ -486,7 +495,8 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
   }
   for (uint32_t i = 0; i < plan.stepCount; ++i) {
     EnqueueCheck(sorter, plan.steps[i].name, EnqueueStep(sorter, context, r.stream, plan, b, msd, plan.steps[i]));
-    r.stamps.AdvanceTo(plan.steps[i].slot);
+    // (a step that shares its slot with the next one -- the forward transform in front of the fill -- leaves the stamp to it)
+    if (i + 1 == plan.stepCount || plan.steps[i + 1].slot != plan.steps[i].slot) r.stamps.AdvanceTo(plan.steps[i].slot);
   }
   r.stamps.Finish();
   if (plan.stepCount > 1) MaybeRecheckOrder(sorter, r.stream, plan.atomicRank);  // (the general path)
@@ -495,11 +505,15 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
 static_assert(VRDX_HIP_KEY_UINT64 == vrdx::kKeyOrderUint64 && VRDX_HIP_KEY_INT64 == vrdx::kKeyOrderInt64 &&
                   VRDX_HIP_KEY_FLOAT64 == vrdx::kKeyOrderFloat64 && VRDX_HIP_ORDER_DESCENDING == vrdx::kKeyOrderDescending,
               "the order word of the header is the kernels'");
+static_assert(VRDX_HIP_KEY32_UINT32 == vrdx::kKeyOrderUint32 && VRDX_HIP_KEY32_INT32 == vrdx::kKeyOrderInt32 &&
+                  VRDX_HIP_KEY32_FLOAT32 == vrdx::kKeyOrderFloat32,
+              "the 32-bit key types of the header are the kernels'");
 
 // The segmented sorts (include/vk_radix_sort.h, vrdxHipCmdSortSegmented*), all eight entry points: the steps of
 // PlanSegmentedSort (vrdx_plan.h) -- a fill and up to three launches -- on the 32-bit storage (Args = SegmentedArgs, Key =
 // uint32_t; key: the whole key or the bit range of vrdxHipCmdSortSegmentedBits*) or on the 64-bit storage (Segmented64Args,
-// uint64_t; key: the order word, VRDX_HIP_KEY_UINT64 or that of vrdxHipCmdSortSegmented64Ordered*).
+// uint64_t; key: the order word, VRDX_HIP_KEY_UINT64 or that of vrdxHipCmdSortSegmented64Ordered*).  On the 32-bit storage the
+// whole key may come with an order word too (vrdxHipCmdOrderedSortSegmented*): the ordered forms of the three kernels.
 template <typename Args, typename Key>
 void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
                          VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
@@ -537,6 +551,8 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
       e = vrdx::LaunchSegmentedClear(r.stream, a);
     else if constexpr (sizeof(Key) == 8)
       e = vrdx::LaunchSegmented64(r.stream, sizeClass, step.grid, keyValue, plan.atomicRank, a, plan.order);
+    else if (plan.order != vrdx::kKeyOrderUint32)
+      e = vrdx::LaunchSegmentedOrdered(r.stream, sizeClass, step.grid, keyValue, plan.atomicRank, a, plan.order);
     else
       e = vrdx::LaunchSegmented(r.stream, sizeClass, step.grid, keyValue, plan.atomicRank, a, plan.rangeBegin, plan.rangeWidth);
     EnqueueCheck(sorter, step.name, e);
@@ -909,6 +925,54 @@ void vrdxHipCmdSort64OrderedKeyValueIndirect(VkCommandBuffer commandBuffer, Vrdx
                valuesOffset, order, storageBuffer, storageOffset, queryPool, query);
 }
 
+void vrdxHipCmdOrderedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                           VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                           VkQueryPool queryPool, uint32_t query) {
+  RecordSort(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, nullptr, 0, storageBuffer, storageOffset,
+             queryPool, query, 0, 32, order);
+}
+
+void vrdxHipCmdOrderedSortKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                                   VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset, uint32_t order,
+                                   VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSort(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, valuesBuffer, valuesOffset, storageBuffer,
+             storageOffset, queryPool, query, 0, 32, order);
+}
+
+void vrdxHipCmdOrderedSortIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                   VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                   VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                   VkQueryPool queryPool, uint32_t query) {
+  RecordSort(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, nullptr, 0,
+             storageBuffer, storageOffset, queryPool, query, 0, 32, order);
+}
+
+void vrdxHipCmdOrderedSortKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                           VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                           VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                           uint32_t order, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                           VkQueryPool queryPool, uint32_t query) {
+  RecordSort(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, valuesBuffer,
+             valuesOffset, storageBuffer, storageOffset, queryPool, query, 0, 32, order);
+}
+
+void vrdxHipCmdOrderedSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                    uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                    VkBuffer keysBuffer, VkDeviceSize keysOffset, uint32_t order, VkBuffer storageBuffer,
+                                    VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                        nullptr, 0, {0, 32, order}, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdOrderedSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                            uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                            VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                            VkDeviceSize valuesOffset, uint32_t order, VkBuffer storageBuffer,
+                                            VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
+                        valuesBuffer, valuesOffset, {0, 32, order}, storageBuffer, storageOffset, queryPool, query);
+}
+
 VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {
   if (pQueryPool == nullptr || queryCount == 0) return VK_ERROR_INITIALIZATION_FAILED;
   VrdxHipQueryPool* pool = new (std::nothrow) VrdxHipQueryPool;
@@ -1042,6 +1106,21 @@ void vrdxHipDescribeSortBitsPlan(VrdxSorter sorter, uint32_t elementCount, int k
   if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
   const SortPlan plan = vrdx::PlanSortBits(PlanContextOf(sorter), keyValue != 0, elementCount, beginBit, endBit, 0);
   if (plan.stepCount != 0) vrdx::DescribePlan(plan, info);  // (no step: refused -- an invalid range, one beyond one workgroup -- or empty)
+}
+
+void vrdxHipDescribeOrderedSortPlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, uint32_t order, VrdxHipPlanInfo* info) {
+  if (info == nullptr) return;
+  std::memset(info, 0, sizeof(*info));
+  if (sorter == nullptr) return;
+  if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
+  const SortPlan plan = vrdx::PlanOrderedSort(PlanContextOf(sorter), keyValue != 0, elementCount, order, 0);
+  if (plan.stepCount == 0) return;  // (refused -- an invalid order word -- or empty)
+  vrdx::DescribePlan(plan, info);
+  if (plan.order != vrdx::kKeyOrderUint32 && !plan.oneWorkgroup) {
+    // the two transforms (counted among the launches): each reads and writes every key once
+    info->bytesPerElement += 16u;
+    info->fallbackBytesPerElement += 16u;
+  }
 }
 
 uint32_t vrdxHipReadPlanVerdict(VkCommandBuffer commandBuffer, VkBuffer storageBuffer, VkDeviceSize storageOffset) {

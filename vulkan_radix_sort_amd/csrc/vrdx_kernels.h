@@ -337,6 +337,26 @@ hipError_t LaunchSegmentedClear(hipStream_t stream, const Segmented64Args& args)
 hipError_t LaunchSegmented64(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
                              const Segmented64Args& args, uint32_t order);
 
+// ---- key orders of the 32-bit sorts (vrdxHipCmdOrderedSort*; vrdx_kernels.hip, "key orders of the 32-bit sorts") ----
+// The same order word on 32 bits: the key types are uint32, int32 and float32 (KeyOrderValid serves both widths).  The kernels
+// sort T(key) ascending as unsigned 32-bit, T(k) = k ^ flip ^ (float32 and bit 31 of k set ? 0x7FFFFFFF : 0) with flip = 0
+// (uint32) or 1 << 31 (int32, float32), complemented for descending.  Every launcher below takes a VALID word other than
+// kKeyOrderUint32 (the planner hands that one to the unordered kernels) and refuses anything else with hipErrorInvalidValue.
+constexpr uint32_t kKeyOrderUint32 = 0, kKeyOrderInt32 = 1, kKeyOrderFloat32 = 2;
+constexpr bool KeyOrder32Launchable(uint32_t order) { return order != kKeyOrderUint32 && KeyOrderValid(order); }
+// small_sort_ordered_kernel: LaunchSmallSort with every element as T(key) between the load and the store
+hipError_t LaunchSmallSortOrdered(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
+                                  const uint32_t* countPtr, uint32_t* failure, uint32_t order);
+// order32_kernel: keys[i] = T(keys[i]) (inverse: T^-1) for i < min(*countPtr, maxCount) (countPtr == nullptr: maxCount), in
+// place, four keys per thread; keys: the caller's, 4-byte aligned.  Around the unchanged plan of a flat sort beyond one workgroup.
+constexpr uint32_t kOrder32Threads = 256;
+hipError_t LaunchOrder32(hipStream_t stream, bool inverse, uint32_t* keys, uint32_t maxCount, const uint32_t* countPtr,
+                         uint32_t order);
+// segmented_small_ordered / mid_ordered / large_ordered_kernel: the whole-key segmented kernels with every segment in
+// ascending order of T(key); the order word travels behind SegmentedArgs, which does not change.
+hipError_t LaunchSegmentedOrdered(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                                  const SegmentedArgs& args, uint32_t order);
+
 // ---- the kernels' dynamic LDS and the MSD plan's grids: one definition for the kernels (vrdx_kernels.hip) and for both
 // launch backends (vrdx_launch.inc) ----
 // Key+value tiles replay the permutation for the values through the SAME staging buffer after the

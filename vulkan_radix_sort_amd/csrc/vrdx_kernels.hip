@@ -1517,10 +1517,37 @@ __global__ __launch_bounds__(THREADS, (PairMinWavesPerSimd<THREADS, KPT>())) voi
 // onesweep_kernel), so a bucket or small sort costs what its elements cost, not what the kernel could hold.
 // RANGE (small_sort_bits_kernel): by the `bytes` BITS of the key from bit beginBit instead -- ceil(bytes / 8) digits, the
 // last one of the bits that are left (RangeDigit); pads have all ones in every digit of every range and stay last.
-template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK, bool RANGE = false>
+// ORDERED (small_sort_ordered_kernel, the ordered segmented in-LDS forms): real elements become T(key) right behind the
+// load and keys again in front of the store (KeyOrder32 below), so the ranking and the staging code see T(key).  Pads are
+// never transformed: they stay all ones, the largest word of T-space, and the key whose T is all ones ties with them and,
+// being in front of them in memory order, stays in front.
+
+// Key orders of the 32-bit sorts (vrdxHipCmdOrderedSort*; vrdx_kernels.h): T(k) = k ^ flip ^ (float32 and bit 31 of k set ?
+// 0x7FFFFFFF : 0), flip = 0 (uint32) or 1 << 31 (int32, float32), complemented for descending.  The float mask never touches
+// bit 31, so bit 31 of T(k) ^ flip is the key's sign and the way back finds its mask there.  With the constant order 0 the
+// struct is {0, 0} and both functions fold to the identity.
+struct KeyOrder32 {
+  uint32_t flip;
+  uint32_t floatMask;  // 0x7FFFFFFF for float32
+};
+__device__ __forceinline__ KeyOrder32 MakeKeyOrder32(uint32_t order) {
+  const uint32_t type = order & kKeyOrderTypeMask;
+  const uint32_t descending = (order & kKeyOrderDescending) != 0 ? ~0u : 0u;
+  return KeyOrder32{(type != kKeyOrderUint32 ? 0x80000000u : 0u) ^ descending, type == kKeyOrderFloat32 ? 0x7FFFFFFFu : 0u};
+}
+__device__ __forceinline__ uint32_t OrderForward32(const KeyOrder32& o, uint32_t key) {
+  return key ^ o.flip ^ ((uint32_t)((int32_t)key >> 31) & o.floatMask);
+}
+__device__ __forceinline__ uint32_t OrderInverse32(const KeyOrder32& o, uint32_t t) {
+  const uint32_t u = t ^ o.flip;  // bit 31: the key's
+  return u ^ ((uint32_t)((int32_t)u >> 31) & o.floatMask);
+}
+
+template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK, bool RANGE = false, bool ORDERED = false>
 __device__ __forceinline__ void SortInWorkgroup(const uint32_t* keysIn, uint32_t* keysOut, const uint32_t* valuesIn,
                                                 uint32_t* valuesOut, uint32_t n, uint32_t bytes, uint32_t* smem,
-                                                const uint32_t beginBit = 0) {
+                                                const uint32_t beginBit = 0, const uint32_t order = 0) {
+  static_assert(!(RANGE && ORDERED), "an order combined with a bit range is not built");
   constexpr int WAVES = THREADS / 64;
   constexpr uint32_t TILE = THREADS * KPT;
   constexpr bool SHARED = SharedStage(THREADS, KPT, KV);
@@ -1556,6 +1583,14 @@ __device__ __forceinline__ void SortInWorkgroup(const uint32_t* keysIn, uint32_t
   // (the "full" shortcut would skip the per-element bound check: only when no wave was shortened)
   LoadStriped<KPT, false, DYN>(keysIn, first, n, false, 0xFFFFFFFFu, key, slots);  // pad: downsweep.slang:81
   if constexpr (KV) LoadStriped<KPT, false, DYN>(valuesIn, first, n, false, 0u, val, slots);  // pad: downsweep.slang:85
+  if constexpr (ORDERED) {
+    const KeyOrder32 o = MakeKeyOrder32(order);
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      if (DYN && i % 4 == 0 && (uint32_t)i >= slots) break;
+      if (first + 64 * i < n) key[i] = OrderForward32(o, key[i]);  // (the pads stay all ones)
+    }
+  }
 
   // SHARED: ranks, then staging slots, two to a register (< TILE <= 65536): keys, values and positions of 32 elements
   // per lane have to fit 128 registers
@@ -1658,7 +1693,10 @@ __device__ __forceinline__ void SortInWorkgroup(const uint32_t* keysIn, uint32_t
     if (DYN && i % 4 == 0 && (uint32_t)i >= slots) break;
     const uint32_t index = first + 64 * i;
     if (index < n) {
-      keysOut[index] = key[i];
+      if constexpr (ORDERED)
+        keysOut[index] = OrderInverse32(MakeKeyOrder32(order), key[i]);
+      else
+        keysOut[index] = key[i];
       if constexpr (KV) valuesOut[index] = val[i];
     }
   }
@@ -1852,9 +1890,17 @@ __global__ __launch_bounds__(1024) void segmented_mid_kernel(SegmentedArgs a) {
 constexpr uint32_t kSegHistCopies = 8;
 static_assert(4 * 256 * kSegHistCopies <= kSegLargeTile, "the histogram replicas alias the staging buffer");
 
-template <bool KV, bool ATOMIC_RANK, bool RANGE = false>
+// ORDERED (segmented_large_ordered_kernel): by T(key) (KeyOrder32).  Step 1 counts the four bytes of T(key), so the bases and
+// the mask of active passes are T's (under float32 a segment of +x and -x differs in one raw bit and in up to 31 bits of T).
+// The FIRST active pass applies T behind its loads and the LAST active pass the inverse in front of its stores (one pass:
+// both); between them the segment's range of the caller's array and of the scratch array hold T(key).  The copy back after
+// an odd number of passes copies keys that are raw again; with no active pass nothing is transformed.  A tile's pads are
+// never transformed and stay all ones, digit 255's last keys.
+template <bool KV, bool ATOMIC_RANK, bool RANGE = false, bool ORDERED = false>
 __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uint32_t* keysScratch, uint32_t* valuesScratch,
-                                           uint32_t n, uint32_t* smem, const uint32_t beginBit = 0, const uint32_t width = 0) {
+                                           uint32_t n, uint32_t* smem, const uint32_t beginBit = 0, const uint32_t width = 0,
+                                           const uint32_t order = 0) {
+  static_assert(!(RANGE && ORDERED), "an order combined with a bit range is not built");
   constexpr int THREADS = 1024, KPT = 16, WAVES = THREADS / 64;
   constexpr uint32_t TILE = kSegLargeTile;
   uint32_t* const stagedKeys = smem;
@@ -1873,7 +1919,9 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
   if (tid == 0) misc[0] = 0;
   LdsBarrier();
   const uint32_t copy = tid & (kSegHistCopies - 1);
+  const KeyOrder32 keyOrder = MakeKeyOrder32(ORDERED ? order : 0u);  // (ORDERED only)
   auto count = [&](uint32_t key) {
+    if constexpr (ORDERED) key = OrderForward32(keyOrder, key);
 #pragma unroll
     for (uint32_t p = 0; p < 4; ++p) {
       if constexpr (RANGE) {
@@ -1913,6 +1961,13 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
   }
   LdsBarrier();
   const uint32_t active = misc[0];
+  // (ORDERED) the passes that take the keys into T-space and back: the lowest and the highest set bit of `active`
+  uint32_t firstPass = 0, lastPass = 0;
+  if constexpr (ORDERED) {
+    const uint32_t uniform = (uint32_t)__builtin_amdgcn_readfirstlane((int)active);
+    firstPass = uniform != 0 ? (uint32_t)__builtin_ctz(uniform) : 0u;
+    lastPass = uniform != 0 ? 31u - (uint32_t)__builtin_clz(uniform) : 0u;
+  }
 
   // 2. the passes
   uint32_t* src = keys;
@@ -1939,6 +1994,15 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
       uint32_t val[KV ? KPT : 1];
       LoadStriped<KPT, false, true>(src + t0, first, m, false, 0xFFFFFFFFu, key, slots);
       if constexpr (KV) LoadStriped<KPT, false, true>(srcV + t0, first, m, false, 0u, val, slots);
+      if constexpr (ORDERED) {
+        if (pass == firstPass) {  // uniform
+#pragma unroll
+          for (int i = 0; i < KPT; ++i) {
+            if (i % 4 == 0 && (uint32_t)i >= slots) break;
+            if (first + 64 * i < m) key[i] = OrderForward32(keyOrder, key[i]);
+          }
+        }
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;
       uint32_t rank[KPT];
@@ -1989,7 +2053,10 @@ __device__ __forceinline__ void SegmentLsd(uint32_t* keys, uint32_t* values, uin
           // always < n while the segment is this workgroup's alone; segments that overlap (offsets that are not monotone,
           // flagged by the small kernel) may change keys under the counts, and must still never write outside the range
           if (to < n) {
-            dst[to] = k;
+            if constexpr (ORDERED)
+              dst[to] = pass == lastPass ? OrderInverse32(keyOrder, k) : k;  // uniform
+            else
+              dst[to] = k;
             if constexpr (KV) dstV[to] = stagedValues[slot];
           }
         }
@@ -4138,13 +4205,83 @@ __global__ __launch_bounds__(1024) void segmented_large64_ordered_kernel(Segment
 }
 
 // ---------------------------------------------------------------------------------------------
+// key orders of the 32-bit sorts (vrdxHipCmdOrderedSort*): int32, float32 and descending
+// ---------------------------------------------------------------------------------------------
+// New kernels next to the unordered ones, which stay as they are: the ORDERED forms of SortInWorkgroup and SegmentLsd (see
+// there) in the unordered kernels' loops, and one streaming kernel around the unchanged plan of a flat sort beyond one
+// workgroup.  T is NOT fused into that plan's first reader and last writer (histogram*, msd_scatter_or_pass0,
+// msd_buckets_or_pass1, bucket_sort*, onesweep*): which launch reads the caller's keys first and writes them last is settled
+// on the device, and those kernels are tuned to the register.
+
+// small_sort_kernel with the order word behind its arguments
+template <int THREADS, int KPT, bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(THREADS) void small_sort_ordered_kernel(uint32_t* keys, uint32_t* values, uint32_t maxCount,
+                                                                      const uint32_t* countPtr, uint32_t* failure,
+                                                                      uint32_t order) {
+  static_assert(THREADS >= 256 && THREADS % 256 == 0, "one thread per digit");
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  if (threadIdx.x < 3) failure[(int)threadIdx.x - 2] = 0;  // header words 1-3, see small_sort_kernel
+  SortInWorkgroup<THREADS, KPT, KV, ATOMIC_RANK, false, true>(keys, keys, values, values, n, VRDX_PASSES, smem, 0, order);
+}
+
+// keys[i] = T(keys[i]) (INVERSE: the key whose T is keys[i]) for i < n = ElementCount(maxCount, countPtr), in place.  Every
+// thread owns four consecutive keys and moves them as one 16-byte access that needs the keys' own 4-byte alignment only; the
+// last n mod 4 keys go one by one, so nothing from element n on is read or written.  The grid covers maxCount (LaunchOrder32);
+// with a device-side count the workgroups from element n on return.  No LDS.
+template <bool INVERSE>
+__global__ __launch_bounds__(kOrder32Threads) void order32_kernel(uint32_t* keys, uint32_t maxCount, const uint32_t* countPtr,
+                                                                  uint32_t order) {
+  const KeyOrder32 o = MakeKeyOrder32(order);
+  const auto f = [&o](uint32_t word) { return INVERSE ? OrderInverse32(o, word) : OrderForward32(o, word); };
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  const uint32_t i = (blockIdx.x * kOrder32Threads + threadIdx.x) * 4u;  // (n <= 2^30 - 4: no wrap)
+  if (i >= n) return;
+  if (i + 4u <= n) {
+    u32x4_a4* const four = reinterpret_cast<u32x4_a4*>(keys + i);
+    const u32x4 k = *four;
+    *four = u32x4{f(k.x), f(k.y), f(k.z), f(k.w)};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) keys[j] = f(keys[j]);
+}
+
+// The segmented sort's three kernels in their own loops, the order word behind SegmentedArgs.
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(256) void segmented_small_ordered_kernel(SegmentedArgs a, uint32_t order) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  ForEachSmallSegment(a, kSegSmallMax, kSegMidMax, [&](uint32_t begin, uint32_t n) {
+    SortInWorkgroup<256, 16, KV, ATOMIC_RANK, false, true>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
+                                                           KV ? a.values + begin : nullptr, n, VRDX_PASSES, smem, 0, order);
+  });
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_mid_ordered_kernel(SegmentedArgs a, uint32_t order) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  ForEachListedSegment<false>(a, kSegSmallMax, kSegMidMax, [&](uint32_t begin, uint32_t n) {
+    SortInWorkgroup<1024, 16, KV, ATOMIC_RANK, false, true>(a.keys + begin, a.keys + begin, KV ? a.values + begin : nullptr,
+                                                            KV ? a.values + begin : nullptr, n, VRDX_PASSES, smem, 0, order);
+  });
+}
+
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_large_ordered_kernel(SegmentedArgs a, uint32_t order) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  ForEachListedSegment<true>(a, kSegMidMax, ~0u, [&](uint32_t begin, uint32_t n) {
+    SegmentLsd<KV, ATOMIC_RANK, false, true>(a.keys + begin, KV ? a.values + begin : nullptr, a.keysScratch + begin,
+                                             KV ? a.valuesScratch + begin : nullptr, n, smem, 0, 0, order);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs
 // ---------------------------------------------------------------------------------------------
 #include "vrdx_launch.inc"
 
-static const void* const kStubs[kNumKernels] = {
+static const void* const kStubs[kNumAllKernels] = {
 #define VRDX_KERNEL_STUB(id, stub, threads, ldsBytes, name) reinterpret_cast<const void*>(stub),
-    VRDX_KERNELS(VRDX_KERNEL_STUB)
+    VRDX_ALL_KERNELS(VRDX_KERNEL_STUB)
 #undef VRDX_KERNEL_STUB
 };
 

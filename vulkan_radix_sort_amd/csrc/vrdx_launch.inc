@@ -311,22 +311,79 @@
   X(kSegmented64OrderedLargeVA, (&segmented_large64_ordered_kernel<true, true>), 1024, Segment64LargeLdsWords(true) * 4, \
     "_ZN4vrdx32segmented_large64_ordered_kernelILb1ELb1EEEvNS_15Segmented64ArgsEj")
 
+// The kernels of the ordered 32-bit sorts (vrdxHipCmdOrderedSort*) stand in a list of their own BEHIND VRDX_KERNELS: that list,
+// its ids and kNumKernels are what tests/native/record_trace prints, and no entry point it records starts one of these.  The
+// backends expand VRDX_ALL_KERNELS (kNumAllKernels ids), so the library's stubs and the single header find both lists.
+#define VRDX_ORDERED32_KERNELS(X) \
+  /* small_sort_ordered_kernel [256 | 1024 threads][key-value][atomic rank] */ \
+  X(kSmallOrdered256, (&small_sort_ordered_kernel<256, 16, false, false>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx25small_sort_ordered_kernelILi256ELi16ELb0ELb0EEEvPjS1_jPKjS1_j") \
+  X(kSmallOrdered256A, (&small_sort_ordered_kernel<256, 16, false, true>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx25small_sort_ordered_kernelILi256ELi16ELb0ELb1EEEvPjS1_jPKjS1_j") \
+  X(kSmallOrdered256V, (&small_sort_ordered_kernel<256, 16, true, false>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx25small_sort_ordered_kernelILi256ELi16ELb1ELb0EEEvPjS1_jPKjS1_j") \
+  X(kSmallOrdered256VA, (&small_sort_ordered_kernel<256, 16, true, true>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx25small_sort_ordered_kernelILi256ELi16ELb1ELb1EEEvPjS1_jPKjS1_j") \
+  X(kSmallOrdered1024, (&small_sort_ordered_kernel<1024, 16, false, false>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx25small_sort_ordered_kernelILi1024ELi16ELb0ELb0EEEvPjS1_jPKjS1_j") \
+  X(kSmallOrdered1024A, (&small_sort_ordered_kernel<1024, 16, false, true>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx25small_sort_ordered_kernelILi1024ELi16ELb0ELb1EEEvPjS1_jPKjS1_j") \
+  X(kSmallOrdered1024V, (&small_sort_ordered_kernel<1024, 16, true, false>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx25small_sort_ordered_kernelILi1024ELi16ELb1ELb0EEEvPjS1_jPKjS1_j") \
+  X(kSmallOrdered1024VA, (&small_sort_ordered_kernel<1024, 16, true, true>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx25small_sort_ordered_kernelILi1024ELi16ELb1ELb1EEEvPjS1_jPKjS1_j") \
+  /* order32_kernel [forward | inverse] */ \
+  X(kOrder32Forward, (&order32_kernel<false>), kOrder32Threads, 0, \
+    "_ZN4vrdx14order32_kernelILb0EEEvPjjPKjj") \
+  X(kOrder32Inverse, (&order32_kernel<true>), kOrder32Threads, 0, \
+    "_ZN4vrdx14order32_kernelILb1EEEvPjjPKjj") \
+  /* the ordered forms of the three segmented kernels [small | mid | large][key-value][atomic rank] */ \
+  X(kSegmentedOrderedSmall, (&segmented_small_ordered_kernel<false, false>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx30segmented_small_ordered_kernelILb0ELb0EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedSmallA, (&segmented_small_ordered_kernel<false, true>), 256, SmallSortLdsWords(256, 16, false) * 4, \
+    "_ZN4vrdx30segmented_small_ordered_kernelILb0ELb1EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedSmallV, (&segmented_small_ordered_kernel<true, false>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx30segmented_small_ordered_kernelILb1ELb0EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedSmallVA, (&segmented_small_ordered_kernel<true, true>), 256, SmallSortLdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx30segmented_small_ordered_kernelILb1ELb1EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedMid, (&segmented_mid_ordered_kernel<false, false>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx28segmented_mid_ordered_kernelILb0ELb0EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedMidA, (&segmented_mid_ordered_kernel<false, true>), 1024, SmallSortLdsWords(1024, 16, false) * 4, \
+    "_ZN4vrdx28segmented_mid_ordered_kernelILb0ELb1EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedMidV, (&segmented_mid_ordered_kernel<true, false>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx28segmented_mid_ordered_kernelILb1ELb0EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedMidVA, (&segmented_mid_ordered_kernel<true, true>), 1024, SmallSortLdsWords(1024, 16, true) * 4, \
+    "_ZN4vrdx28segmented_mid_ordered_kernelILb1ELb1EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedLarge, (&segmented_large_ordered_kernel<false, false>), 1024, SegmentLargeLdsWords(false) * 4, \
+    "_ZN4vrdx30segmented_large_ordered_kernelILb0ELb0EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedLargeA, (&segmented_large_ordered_kernel<false, true>), 1024, SegmentLargeLdsWords(false) * 4, \
+    "_ZN4vrdx30segmented_large_ordered_kernelILb0ELb1EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedLargeV, (&segmented_large_ordered_kernel<true, false>), 1024, SegmentLargeLdsWords(true) * 4, \
+    "_ZN4vrdx30segmented_large_ordered_kernelILb1ELb0EEEvNS_13SegmentedArgsEj") \
+  X(kSegmentedOrderedLargeVA, (&segmented_large_ordered_kernel<true, true>), 1024, SegmentLargeLdsWords(true) * 4, \
+    "_ZN4vrdx30segmented_large_ordered_kernelILb1ELb1EEEvNS_13SegmentedArgsEj")
+#define VRDX_ALL_KERNELS(X) VRDX_KERNELS(X) VRDX_ORDERED32_KERNELS(X)
+
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
   VRDX_KERNELS(VRDX_KERNEL_ID)
+  kNumKernels,
+  kLastListedKernel = kNumKernels - 1,  // (the ordered list's first id is kNumKernels)
+  VRDX_ORDERED32_KERNELS(VRDX_KERNEL_ID)
 #undef VRDX_KERNEL_ID
-  kNumKernels
+  kNumAllKernels
 };
 
 struct KernelShape {
   uint32_t threads;
   uint32_t ldsBytes;
 };
-static constexpr KernelShape kKernelShapes[kNumKernels] = {
+static constexpr KernelShape kKernelShapes[kNumAllKernels] = {
 #define VRDX_KERNEL_SHAPE(id, stub, threads, ldsBytes, name) {threads, (uint32_t)(ldsBytes)},
-    VRDX_KERNELS(VRDX_KERNEL_SHAPE)
+    VRDX_ALL_KERNELS(VRDX_KERNEL_SHAPE)
 #undef VRDX_KERNEL_SHAPE
 };
+static_assert(kSmallOrdered256 == kNumKernels, "the ordered list follows the first one");
 
 // The backend's primitives (defined behind this file).  PrepareKernel readies kernel `id` on the current device: it raises
 // the kernel's dynamic-LDS limit if it takes dynamic LDS.  LaunchKernel starts it with the list's block size and LDS and
@@ -350,7 +407,7 @@ static hipError_t LaunchInOrder(uint32_t order, KernelId plain, KernelId ordered
 }
 
 hipError_t PrepareKernels() {
-  for (int id = 0; id < kNumKernels; ++id) {
+  for (int id = 0; id < kNumAllKernels; ++id) {
     const hipError_t e = PrepareKernel(KernelId(id));
     if (e != hipSuccess) return e;
   }
@@ -558,4 +615,26 @@ hipError_t LaunchLdsOrderRecheck(hipStream_t stream, uint32_t* sticky) {
 
 hipError_t LaunchSpin(hipStream_t stream, unsigned long long* out, uint32_t ticks) {
   return Launch(kSpin, 1, stream, out, ticks);
+}
+
+// ---- key orders of the 32-bit sorts (VRDX_ORDERED32_KERNELS) ----------------------------------------
+hipError_t LaunchSmallSortOrdered(hipStream_t stream, bool atomicRank, uint32_t* keys, uint32_t* values, uint32_t maxCount,
+                                  const uint32_t* countPtr, uint32_t* failure, uint32_t order) {
+  if (!KeyOrder32Launchable(order) || maxCount > kSmallSortMaxElements) return hipErrorInvalidValue;
+  const KernelId first = maxCount <= 256u * 16u ? kSmallOrdered256 : kSmallOrdered1024;
+  return Launch(Form(first, values != nullptr, atomicRank), 1, stream, keys, values, maxCount, countPtr, failure, order);
+}
+
+// one thread per four keys of the bound
+hipError_t LaunchOrder32(hipStream_t stream, bool inverse, uint32_t* keys, uint32_t maxCount, const uint32_t* countPtr,
+                         uint32_t order) {
+  if (!KeyOrder32Launchable(order) || maxCount == 0 || maxCount > VRDX_MAX_ELEMENTS) return hipErrorInvalidValue;
+  const uint32_t grid = (maxCount + 4u * kOrder32Threads - 1u) / (4u * kOrder32Threads);
+  return Launch(inverse ? kOrder32Inverse : kOrder32Forward, grid, stream, keys, maxCount, countPtr, order);
+}
+
+hipError_t LaunchSegmentedOrdered(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
+                                  const SegmentedArgs& args, uint32_t order) {
+  if (grid == 0 || !KeyOrder32Launchable(order)) return hipErrorInvalidValue;
+  return Launch(Form(KernelId(kSegmentedOrderedSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args, order);
 }

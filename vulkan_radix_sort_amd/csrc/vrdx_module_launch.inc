@@ -19,9 +19,9 @@ namespace {
 
 constexpr int kMaxDevices = 64;
 
-const char* const kKernelNames[kNumKernels] = {
+const char* const kKernelNames[kNumAllKernels] = {
 #define VRDX_KERNEL_NAME(id, stub, threads, ldsBytes, name) name,
-    VRDX_KERNELS(VRDX_KERNEL_NAME)
+    VRDX_ALL_KERNELS(VRDX_KERNEL_NAME)
 #undef VRDX_KERNEL_NAME
 };
 
@@ -33,7 +33,7 @@ const char* const kKernelNames[kNumKernels] = {
 // exists: the library launches its spin kernel then, this backend finds an empty slot and the call returns all ones.
 struct DeviceKernels {
   hipModule_t module = nullptr;
-  hipFunction_t fn[kNumKernels] = {};
+  hipFunction_t fn[kNumAllKernels] = {};
 };
 DeviceKernels g_devices[kMaxDevices];
 std::mutex g_moduleMutex;  // module load and handle resolution only (sorter creation), never a launch

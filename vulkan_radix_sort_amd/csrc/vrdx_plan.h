@@ -185,9 +185,13 @@ enum class Step : uint8_t {
   kPass,               // slot 4 + 3 p, "downsweep": pass p, look-back fused into it ("spine" = "upsweep" = the slot before)
   kSmallSort,          // slot 14: the one-workgroup sort
   kSmallSortBits,      // slot 14: the one-workgroup sort by the digits of a bit range (PlanSortBits)
+  // a key order of the 32-bit sorts (PlanOrderedSort)
+  kSmallSortOrdered,   // slot 14: the one-workgroup sort by T(key)
+  kOrderForward,       // slot 1, in front of the fill (which ends the same slot): keys -> T(key), in place
+  kOrderInverse,       // slot 14, behind pass 3 (slot 13): T(key) -> keys, in place
 };
 struct SortStep { Step what; uint8_t pass, slot; const char* name; };  // (pass: kPass only; name: what EnqueueCheck reports)
-constexpr uint32_t kMaxSortSteps = 8;  // fill, histogram, spine, scatter, half-size buckets, passes 1-3
+constexpr uint32_t kMaxSortSteps = 10;  // fill, histogram, spine, scatter, half-size buckets, passes 1-3; the two transforms
 
 // Everything the host decides about a sort, in ONE place: RecordSort records it and vrdxHipDescribePlan reports it.
 // storageAddress: the absolute address the storage is handed over at -- only its low seven bits matter (the pads in front
@@ -213,6 +217,8 @@ struct SortPlan {
   uint32_t launches = 0;        // kernels among the steps
   // a bit-range sort (PlanSortBits): by the rangeWidth bits (1 ... 31) of the key from bit rangeBegin; 0: the whole key
   uint32_t rangeBegin = 0, rangeWidth = 0;
+  // an ordered sort (PlanOrderedSort): the order word (vrdx_kernels.h); kKeyOrderUint32: the whole key as it stands
+  uint32_t order = kKeyOrderUint32;
 };
 
 // The MSD plan's scatter launch is ALSO pass 0 of the fallback and its bucket launch pass 1 (one branch on the verdict, on
@@ -225,8 +231,13 @@ static inline void ListSteps(SortPlan& p) {
     if (what != Step::kFill) ++p.launches;
   };
   const bool msd = p.msdBits != 0, halfBuckets = msd && p.msdCap == kMsdHalfCap;
+  const bool ordered = p.order != kKeyOrderUint32;
   if (p.oneWorkgroup && p.rangeWidth != 0) return add(Step::kSmallSortBits, "small_sort_bits_kernel", 14);
+  if (p.oneWorkgroup && ordered) return add(Step::kSmallSortOrdered, "small_sort_ordered_kernel", 14);
   if (p.oneWorkgroup) return add(Step::kSmallSort, "small_sort_kernel", 14);
+  // an ordered sort beyond one workgroup: the plan below, unchanged, on T(key) -- one streaming launch in front of it and
+  // one behind it, both in place on the caller's keys
+  if (ordered) add(Step::kOrderForward, "order32_kernel", 1);
   add(Step::kFill, "hipMemcpyAsync(count)", 1);
   if (msd)
     add(Step::kHistogramMsd, "histogram_msd_kernel", 2);
@@ -244,6 +255,7 @@ static inline void ListSteps(SortPlan& p) {
     if (pass == 1 && p.hybridCap != 0) add(Step::kBucketSort, "bucket_sort_kernel", 5);
     add(Step::kPass, "onesweep_kernel", 4 + 3 * pass, pass);
   }
+  if (ordered) add(Step::kOrderInverse, "order32_kernel", 14);
 }
 
 static inline SortPlan PlanSort(const PlanContext& c, bool keyValue, uint32_t elementCount, uint64_t storageAddress) {
@@ -334,15 +346,42 @@ static inline SortPlan PlanSortBits(const PlanContext& c, bool keyValue, uint32_
   return p;
 }
 
+// The plan of an ordered 32-bit sort (vrdxHipCmdOrderedSort[KeyValue][Indirect]; include/vk_radix_sort.h) in the order of the
+// word `order` (vrdx_kernels.h, kKeyOrder*): kKeyOrderUint32 is PlanSort itself; an invalid word has no step and is refused.
+// Otherwise the plan is PlanSort's with its steps listed again: one workgroup runs small_sort_ordered_kernel, and beyond that
+// the same steps -- MSD, hybrid or four passes, verdict and fallback on the device as ever -- sort T(key) between the two
+// transform steps.  An empty sort and one PlanSort refuses stay what they are: no step, no transform.
+constexpr const char* kKeyOrderRefused = "key order (a key type 0 ... 2, VRDX_HIP_ORDER_DESCENDING or not)";
+static inline SortPlan PlanOrderedSort(const PlanContext& c, bool keyValue, uint32_t elementCount, uint32_t order,
+                                       uint64_t storageAddress) {
+  if (order == kKeyOrderUint32) return PlanSort(c, keyValue, elementCount, storageAddress);
+  if (!KeyOrderValid(order)) {
+    SortPlan p;
+    p.keyValue = keyValue;
+    p.elementCount = elementCount;
+    p.atomicRank = c.atomicRank;
+    p.fits = false;
+    p.refusal = kKeyOrderRefused;
+    return p;
+  }
+  SortPlan p = PlanSort(c, keyValue, elementCount, storageAddress);
+  if (p.stepCount == 0) return p;
+  p.order = order;
+  p.stepCount = p.launches = 0;
+  ListSteps(p);
+  return p;
+}
+
 // ---- the segmented sorts (vrdxHipCmdSortSegmented*; include/vk_radix_sort.h) ----
 // How a segmented sort orders its keys.  4-byte keys: by the bits [beginBit, endBit) -- the full range is the whole key, an
-// empty one orders by nothing (no step), an invalid one is refused.  8-byte keys: by the order word (vrdx_kernels.h,
+// empty one orders by nothing (no step), an invalid one is refused; with the full range also by an order word
+// (vrdxHipCmdOrderedSortSegmented*: kKeyOrderUint32 is the whole key as it stands, an invalid word is refused, and a word
+// combined with a partial range is not built and refused).  8-byte keys: by the order word (vrdx_kernels.h,
 // kKeyOrder*; kKeyOrderUint64 is the whole key as it stands, an invalid word is refused); the range is not looked at.
 struct SegmentedKey {
   uint32_t beginBit = 0, endBit = 32;
   uint32_t order = kKeyOrderUint64;
 };
-constexpr const char* kKeyOrderRefused = "key order (a key type 0 ... 2, VRDX_HIP_ORDER_DESCENDING or not)";
 
 // The steps of a segmented sort: a fill of the header and the two list counters (a one-wave kernel, not a memset), then three
 // launches whose work is decided on the device from the offsets -- the 256-thread in-LDS form over every segment (it also
@@ -358,7 +397,7 @@ struct SegmentedPlan {
   bool atomicRank = false;
   const char* refusal = nullptr;           // non-null: refused (no step), and why
   uint32_t rangeBegin = 0, rangeWidth = 0;  // 4-byte keys by a bit range: width 1 ... 31; 0: the whole key
-  uint32_t order = kKeyOrderUint64;        // 8-byte keys
+  uint32_t order = kKeyOrderUint64;        // 8-byte keys, and 4-byte keys by the whole key
   SegmentedLayout layout{};
   SegmentedSortStep steps[4];              // none: refused, or empty (no elements, no segments, an empty range)
   uint32_t stepCount = 0;
@@ -366,11 +405,12 @@ struct SegmentedPlan {
 
 static inline SegmentedPlan PlanSegmentedSort(const PlanContext& c, uint32_t keyBytes, bool keyValue, uint32_t maxElementCount,
                                               uint32_t segmentCount, const SegmentedKey& key, uint64_t storageAddress) {
-  static constexpr const char* kNames[4][4] = {
+  static constexpr const char* kNames[5][4] = {
       {"segmented_clear_kernel", "segmented_small_kernel", "segmented_mid_kernel", "segmented_large_kernel"},
       {"segmented_clear_kernel", "segmented_small_bits_kernel", "segmented_mid_bits_kernel", "segmented_large_bits_kernel"},
       {"segmented_clear_kernel", "segmented_small64_kernel", "segmented_mid64_kernel", "segmented_large64_kernel"},
-      {"segmented_clear_kernel", "segmented_small64_ordered_kernel", "segmented_mid64_ordered_kernel", "segmented_large64_ordered_kernel"}};
+      {"segmented_clear_kernel", "segmented_small64_ordered_kernel", "segmented_mid64_ordered_kernel", "segmented_large64_ordered_kernel"},
+      {"segmented_clear_kernel", "segmented_small_ordered_kernel", "segmented_mid_ordered_kernel", "segmented_large_ordered_kernel"}};
   const bool wide = keyBytes == 8;
   SegmentedPlan p;
   p.keyValue = keyValue;
@@ -379,8 +419,13 @@ static inline SegmentedPlan PlanSegmentedSort(const PlanContext& c, uint32_t key
     p.refusal = wide ? kKeyOrderRefused : kBitRangeRefused;
     return p;
   }
+  if (!wide && key.order != kKeyOrderUint32) {
+    if (!KeyOrderValid(key.order)) p.refusal = kKeyOrderRefused;
+    else if (key.endBit - key.beginBit != 32) p.refusal = "key order combined with a bit range (not built)";
+    if (p.refusal != nullptr) return p;
+  }
   if (!wide && key.beginBit == key.endBit) return p;  // nothing to order by
-  if (wide) p.order = key.order;
+  p.order = key.order;
   if (!wide && key.endBit - key.beginBit < 32) p.rangeBegin = key.beginBit, p.rangeWidth = key.endBit - key.beginBit;
   const uint32_t align = c.minStorageBufferOffsetAlignment;
   p.layout = wide ? MakeSegmented64Layout(maxElementCount, align, keyValue, storageAddress)
@@ -397,7 +442,7 @@ static inline SegmentedPlan PlanSegmentedSort(const PlanContext& c, uint32_t key
   const uint32_t grids[4] = {1u, std::min<uint32_t>(segmentCount, 1u << 20),
                              std::min<uint32_t>(std::min<uint32_t>(segmentCount, p.layout.midCap), resident),
                              std::min<uint32_t>(std::min<uint32_t>(segmentCount, p.layout.largeCap), resident)};
-  const char* const* names = kNames[wide ? (p.order != kKeyOrderUint64 ? 3 : 2) : (p.rangeWidth != 0 ? 1 : 0)];
+  const char* const* names = kNames[wide ? (p.order != kKeyOrderUint64 ? 3 : 2) : p.order != kKeyOrderUint32 ? 4 : (p.rangeWidth != 0 ? 1 : 0)];
   for (uint32_t i = 0; i < 4; ++i)
     if (grids[i] != 0) p.steps[p.stepCount++] = SegmentedSortStep{SegmentedStep(i), (uint8_t)(i + 1), names[i], grids[i]};
   return p;
