@@ -583,6 +583,62 @@ void vrdxHipCmdOrderedSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxS
                                             VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
 
 /* ------------------------------------------------------------------------------------------
+ * 32-bit keys with 64-bit values (HIP backend only)
+ *
+ * vrdxHipCmdWideValueSort is vrdxCmdSortKeyValue with values of 8 bytes: a pointer or handle, a pair of uint32 ids, a
+ * float64, an int64 index.  Elements [0, n) of the uint32 keys come back ascending and stable; element i of the values is
+ * 8 OPAQUE bytes at valuesBuffer + valuesOffset + 8 i, valuesOffset a multiple of 8, and every value travels with its key.
+ * Keys and the count word need 4-byte alignment, the storage 16.
+ * Storage: vrdxHipGetSorterWideValueStorageRequirements(maxElementCount) bytes -- the key+value storage of
+ * vrdxGetSorterKeyValueStorageRequirements for that count (its header is this call's header) plus 12 bytes per element
+ * plus a fixed pad; the size does not depend on the address.
+ * As for vrdxCmdSortKeyValue[Indirect]: elementCount == 0 records nothing but the timestamps; a count beyond 2^30 - 4 is
+ * clamped and raises VRDX_HIP_STATUS_COUNT_CLAMPED; all 15 timestamp slots are recorded; with a NULL pool the call is legal
+ * inside a stream capture; vrdxHipReadStatus and vrdxHipReadPlanVerdict read the storage's header.
+ * Indirect (the contract of vrdxHipCmdSort64[KeyValue]Indirect, word for word): the count is one uint32 at indirectBuffer +
+ * indirectOffset that every step reads on the device when it runs; it is clamped to maxElementCount; elements from n on are
+ * neither read nor written; plans and grids come from maxElementCount alone, so one captured call replays on any count; the
+ * count word must not lie inside the storage range, and nothing writes it.
+ * How (vrdxHipDescribeWideValueSortPlan reports which, with the launches and the HBM bytes per element):
+ *   ONE_WORKGROUP  up to 8192 elements: one launch, keys and values sorted together in LDS (the header's verdict word
+ *                  reads VRDX_HIP_VERDICT_NONE); timestamps: the ONE_WORKGROUP contract, the launch ends slot 14.
+ *   GATHER         an index array in the storage is sorted along the caller's keys (one vrdxCmdSortKeyValue, recorded
+ *                  inside), the values are gathered through it into the storage and copied back: four steps ending slots
+ *                  1 (index), 2 (sort), 3 (gather), 4 (copy back).
+ *   TWO_SORTS      from twoSortsFrom elements: the values' two words are sorted along the keys in two stable sorts of the
+ *                  same key sequence, which apply the same permutation: slots 1 (split), 2 (sort of the key copy with the
+ *                  low words), 3 (sort of the caller's keys with the high words), 4 (merge).  No random access.
+ * The slots no step ends coincide with the one before.  Beyond ONE_WORKGROUP the status and verdict words are those of the
+ * last inner sort.
+ * Out of scope: two-payload forms of the MSD, hybrid and pass kernels (they would slot in behind the same plan function);
+ * segmented, ordered and bit-range variants; 64-bit keys with 64-bit values.
+ * ------------------------------------------------------------------------------------------ */
+void vrdxHipGetSorterWideValueStorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
+                                                  VrdxSorterStorageRequirements* requirements);
+void vrdxHipCmdWideValueSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                             VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                             VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdWideValueSortIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                     VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                     VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                     VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                                     uint32_t query);
+#define VRDX_HIP_WIDE_VALUE_NONE 0u          /* elementCount == 0: nothing is recorded */
+#define VRDX_HIP_WIDE_VALUE_ONE_WORKGROUP 1u
+#define VRDX_HIP_WIDE_VALUE_GATHER 2u
+#define VRDX_HIP_WIDE_VALUE_TWO_SORTS 3u
+typedef struct VrdxHipWideValuePlanInfo {
+  uint32_t form;             /* VRDX_HIP_WIDE_VALUE_* */
+  uint32_t launches;         /* kernels recorded, those of the inner sorts included */
+  uint32_t bytesPerElement;  /* HBM bytes per element the recorded form moves (inner sorts: where their plan runs) */
+  uint32_t innerPlan;        /* VRDX_HIP_PLAN_* of the inner sorts (GATHER, TWO_SORTS) */
+  uint32_t oneWorkgroupMax;  /* the largest count of the ONE_WORKGROUP form */
+  uint32_t twoSortsFrom;     /* the smallest count of the TWO_SORTS form */
+} VrdxHipWideValuePlanInfo;
+/* The form vrdxHipCmdWideValueSort[Indirect] records on `sorter` for elementCount (the bound of an indirect call). */
+void vrdxHipDescribeWideValueSortPlan(VrdxSorter sorter, uint32_t elementCount, VrdxHipWideValuePlanInfo* info);
+
+/* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves
  * (vkCreateQueryPool / vkGetQueryPoolResults, bench/vulkan_benchmark.cc:195-198,318-321).
  * They are not part of the reference API; they exist so a caller without a Vulkan device can

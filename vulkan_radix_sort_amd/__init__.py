@@ -42,6 +42,8 @@ from .api import (  # noqa: F401
     KEY32_FLOAT32,
     KEY32_ORDERS,
     order_word32,
+    VrdxHipWideValuePlanInfo,
+    WIDE_VALUE_FORM_NAMES,
 )
 from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
@@ -49,6 +51,7 @@ from .segmented64 import sort_segments64  # noqa: F401
 from .sort_bits import sort_bits  # noqa: F401
 from .segmented_bits import sort_segments_bits  # noqa: F401
 from .ordered import sort_ordered, sort_segments_ordered  # noqa: F401
+from .wide_value import sort_key_value64  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -91,4 +94,7 @@ __all__ = [
     "order_word32",
     "sort_ordered",
     "sort_segments_ordered",
+    "VrdxHipWideValuePlanInfo",
+    "WIDE_VALUE_FORM_NAMES",
+    "sort_key_value64",
 ]

@@ -61,6 +61,9 @@ class RecordingCall(NamedTuple):
     def facts(self):
         """(key bits, segmented, indirect, key+value, None | "Bits" | "Ordered"), parsed from the C name"""
         ordered32 = re.fullmatch(r"vrdxHipCmdOrderedSort(Segmented)?(KeyValue)?(Indirect)?", self.c_name)
+        wide_value = re.fullmatch(r"vrdxHipCmdWideValueSort(Indirect)?", self.c_name)
+        if wide_value:   # the rows of WIDE_VALUE_CALLS: uint32 keys, always with values (of 8 bytes: the argument list is the same)
+            return 32, False, bool(wide_value.group(1)), True, None
         if ordered32:   # the ordered 32-bit sorts carry the word in front: their names are not of the CmdSort family
             segmented, key_value, indirect = ordered32.groups()
             wide, extra = None, "Ordered"
@@ -184,6 +187,18 @@ ORDERED_SORT_CALLS = (
           "the same with values that travel with their keys."),
 )
 
+# uint32 keys with values of 8 bytes: a third table (the names are outside the CmdSort family on purpose), the same kind of row;
+# the arguments are those of vrdxCmdSortKeyValue[Indirect]
+WIDE_VALUE_CALLS = (
+    _CALL("vrdxHipCmdWideValueSort", "cmd_wide_value_sort",
+          "``cmd_sort_key_value`` with values of 8 opaque bytes each (``values_offset`` a multiple of 8); storage of "
+          "``wide_value_storage_requirements(n)`` bytes."),
+    _CALL("vrdxHipCmdWideValueSortIndirect", "cmd_wide_value_sort_indirect",
+          "``cmd_wide_value_sort`` of the first min(count, ``max_element_count``) elements, the count one uint32 at "
+          "``indirect + indirect_offset`` that is read on the device; storage of "
+          "``wide_value_storage_requirements(max_element_count)`` bytes."),
+)
+
 
 def _exported_symbols():
     """Everything the library exports, in the order this tuple has always had: the entry points that record no sort, by hand,
@@ -206,6 +221,10 @@ def _exported_symbols():
         yield from names
         yield from (next(rows).c_name for _ in range(recording))
     assert next(rows, None) is None, "a row of RECORDING_CALLS is missing from EXPORTED_SYMBOLS"
+    # uint32 keys with 8-byte values
+    yield "vrdxHipGetSorterWideValueStorageRequirements"
+    yield from (call.c_name for call in WIDE_VALUE_CALLS)
+    yield "vrdxHipDescribeWideValueSortPlan"
     # the ordered 32-bit sorts
     yield from (call.c_name for call in ORDERED_SORT_CALLS)
     yield "vrdxHipDescribeOrderedSortPlan"
@@ -355,6 +374,20 @@ class VrdxHipPlanInfo(ctypes.Structure):
         return PLAN_NAMES.get(int(self.plan), "?")
 
 
+# VRDX_HIP_WIDE_VALUE_* (include/vk_radix_sort.h)
+WIDE_VALUE_FORM_NAMES = {0: "none", 1: "one-workgroup", 2: "gather", 3: "two-sorts"}
+
+
+class VrdxHipWideValuePlanInfo(ctypes.Structure):
+    # include/vk_radix_sort.h
+    _fields_ = [("form", ctypes.c_uint32), ("launches", ctypes.c_uint32), ("bytesPerElement", ctypes.c_uint32),
+                ("innerPlan", ctypes.c_uint32), ("oneWorkgroupMax", ctypes.c_uint32), ("twoSortsFrom", ctypes.c_uint32)]
+
+    @property
+    def name(self) -> str:
+        return WIDE_VALUE_FORM_NAMES.get(int(self.form), "?")
+
+
 def in_tree_library_path() -> str:
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvrdx_hip.so")
 
@@ -405,14 +438,17 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxDestroySorter.restype = None
     lib.vrdxDestroySorter.argtypes = [vp]
     for name in ("vrdxGetSorterStorageRequirements", "vrdxGetSorterKeyValueStorageRequirements",
-                 "vrdxHipGetSorter64StorageRequirements", "vrdxHipGetSorter64KeyValueStorageRequirements"):
+                 "vrdxHipGetSorter64StorageRequirements", "vrdxHipGetSorter64KeyValueStorageRequirements",
+                 "vrdxHipGetSorterWideValueStorageRequirements"):
         fn = getattr(lib, name)
         fn.restype = None
         fn.argtypes = [vp, u32, ctypes.POINTER(VrdxSorterStorageRequirements)]
-    for call in RECORDING_CALLS + ORDERED_SORT_CALLS:
+    for call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS:
         fn = getattr(lib, call.c_name)
         fn.restype = None
         fn.argtypes = call.argtypes
+    lib.vrdxHipDescribeWideValueSortPlan.restype = None
+    lib.vrdxHipDescribeWideValueSortPlan.argtypes = [vp, u32, ctypes.POINTER(VrdxHipWideValuePlanInfo)]
     lib.vrdxHipDescribeOrderedSortPlan.restype = None
     lib.vrdxHipDescribeOrderedSortPlan.argtypes = [vp, u32, ctypes.c_int, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipDescribeSortBitsPlan.restype = None
@@ -548,6 +584,12 @@ class Sorter:
         fn(self.handle, max_element_count, ctypes.byref(req))
         return req
 
+    def wide_value_storage_requirements(self, max_element_count: int) -> VrdxSorterStorageRequirements:
+        """``vrdxHipGetSorterWideValueStorageRequirements``: the storage of a sort of uint32 keys with 8-byte values."""
+        req = VrdxSorterStorageRequirements()
+        self._lib.vrdxHipGetSorterWideValueStorageRequirements(self.handle, max_element_count, ctypes.byref(req))
+        return req
+
     # -- recording: the cmd_* methods, one per row of RECORDING_CALLS, are attached below the class ------------------
 
     # -- diagnostics ------------------------------------------------------------------------
@@ -579,6 +621,13 @@ class Sorter:
         (beyond one workgroup: ``describe_plan``'s, plus two launches and 16 bytes per element)."""
         info = VrdxHipPlanInfo()
         self._lib.vrdxHipDescribeOrderedSortPlan(self.handle, element_count, 1 if key_value else 0, order, ctypes.byref(info))
+        return info
+
+    def describe_wide_value_sort_plan(self, element_count: int) -> VrdxHipWideValuePlanInfo:
+        """``vrdxHipDescribeWideValueSortPlan``: the form ``cmd_wide_value_sort*`` records for that many elements (``.name``),
+        its launches and HBM bytes per element, and the two sizes at which the form changes."""
+        info = VrdxHipWideValuePlanInfo()
+        self._lib.vrdxHipDescribeWideValueSortPlan(self.handle, element_count, ctypes.byref(info))
         return info
 
     def read_plan_verdict(self, command_buffer, storage, storage_offset=0) -> int:
@@ -632,5 +681,5 @@ def _recording_method(call: RecordingCall):
     return method
 
 
-for _call in RECORDING_CALLS + ORDERED_SORT_CALLS:
+for _call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS:
     setattr(Sorter, _call.method, _recording_method(_call))

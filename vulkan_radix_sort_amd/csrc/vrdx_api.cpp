@@ -612,6 +612,68 @@ void RecordSort64(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t ele
   r.stamps.Finish();
 }
 
+static_assert(VRDX_HIP_WIDE_VALUE_NONE == (uint32_t)vrdx::WideValueForm::kNone &&
+                  VRDX_HIP_WIDE_VALUE_ONE_WORKGROUP == (uint32_t)vrdx::WideValueForm::kOneWorkgroup &&
+                  VRDX_HIP_WIDE_VALUE_GATHER == (uint32_t)vrdx::WideValueForm::kGather &&
+                  VRDX_HIP_WIDE_VALUE_TWO_SORTS == (uint32_t)vrdx::WideValueForm::kTwoSorts,
+              "the forms of the header are the planner's");
+
+// The sorts of 32-bit keys with 64-bit values (include/vk_radix_sort.h, vrdxHipCmdWideValueSort[Indirect]): the steps of
+// PlanWideValueSort (vrdx_plan.h).  The inner sorts go through RecordSort, without a query pool, on the caller's keys or on
+// their copy, with a word array inside the storage as their values.  Indirect (indirectBuffer != nullptr): elementCount is the
+// bound; layout, plan and grids come from it alone, and every step reads the count from the caller's word when it runs.
+void RecordWideValueSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer indirectBuffer,
+                         VkDeviceSize indirectOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                         VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                         uint32_t query) {
+  Recording r(commandBuffer, sorter, elementCount, queryPool, query);
+  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
+  const vrdx::WideValuePlan plan =
+      vrdx::PlanWideValueSort(PlanContextOf(sorter), r.count, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (r.NothingToRecord(sorter, nullptr, plan.stepCount)) return;
+  const vrdx::WideValueLayout& layout = plan.layout;
+  const uint32_t n = r.count;
+  uint32_t* const keys = reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset));
+  uint64_t* const values = reinterpret_cast<uint64_t*>(BufferAddress(valuesBuffer, valuesOffset));
+  uint32_t* const a = reinterpret_cast<uint32_t*>(storage + layout.aOffset);
+  uint32_t* const b = reinterpret_cast<uint32_t*>(storage + layout.bOffset);
+  uint32_t* const c = reinterpret_cast<uint32_t*>(storage + layout.cOffset);
+  uint64_t* const t = reinterpret_cast<uint64_t*>(storage + layout.tOffset);
+  const uint32_t* const countPtr =
+      indirectBuffer != nullptr ? reinterpret_cast<const uint32_t*>(BufferAddress(indirectBuffer, indirectOffset)) : nullptr;
+  // an inner sort: the caller's keys, or the words at `sortKeys` of the storage, with those at `payload` as their values
+  const auto sortCallerKeys = [&](uint64_t payload) {
+    RecordSort(commandBuffer, sorter, n, indirectBuffer, indirectOffset, keysBuffer, keysOffset, storageBuffer,
+               storageOffset + payload, storageBuffer, storageOffset, nullptr, 0);
+    return hipSuccess;  // (the inner sort has reported its own enqueues)
+  };
+  const auto sortWords = [&](uint64_t sortKeys, uint64_t payload) {
+    RecordSort(commandBuffer, sorter, n, indirectBuffer, indirectOffset, storageBuffer, storageOffset + sortKeys, storageBuffer,
+               storageOffset + payload, storageBuffer, storageOffset, nullptr, 0);
+    return hipSuccess;
+  };
+  for (uint32_t i = 0; i < plan.stepCount; ++i) {
+    hipError_t e = hipErrorInvalidValue;
+    switch (plan.steps[i].what) {
+      case vrdx::StepWide::kSmallSort:
+        e = vrdx::LaunchSmallSortWide(r.stream, plan.atomicRank, keys, values, n, countPtr,
+                                      reinterpret_cast<uint32_t*>(storage + VRDX_OFF_FAILURE));
+        break;
+      case vrdx::StepWide::kIota: e = vrdx::LaunchIotaWide(r.stream, a, n, countPtr); break;
+      case vrdx::StepWide::kSortKeysA: e = sortCallerKeys(layout.aOffset); break;
+      case vrdx::StepWide::kGather: e = vrdx::LaunchGatherWide(r.stream, values, a, t, n, countPtr); break;
+      case vrdx::StepWide::kCopyBack: e = vrdx::LaunchCopyBackWide(r.stream, values, t, n, countPtr); break;
+      case vrdx::StepWide::kSplit: e = vrdx::LaunchSplitWide(r.stream, keys, values, a, b, c, n, countPtr); break;
+      case vrdx::StepWide::kSortAB: e = sortWords(layout.aOffset, layout.bOffset); break;
+      case vrdx::StepWide::kSortKeysC: e = sortCallerKeys(layout.cOffset); break;
+      case vrdx::StepWide::kMerge: e = vrdx::LaunchMergeWide(r.stream, values, b, c, n, countPtr); break;
+    }
+    EnqueueCheck(sorter, plan.steps[i].name, e);
+    r.stamps.AdvanceTo(plan.steps[i].slot);
+  }
+  r.stamps.Finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -971,6 +1033,37 @@ void vrdxHipCmdOrderedSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxS
                                             VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
                         valuesBuffer, valuesOffset, {0, 32, order}, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipGetSorterWideValueStorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
+                                                  VrdxSorterStorageRequirements* requirements) {
+  requirements->size = vrdx::MakeWideValueLayout(maxElementCount, sorter->minStorageBufferOffsetAlignment).size;
+  requirements->usage = VK_BUFFER_USAGE_STORAGE_BUFFER_BIT | VK_BUFFER_USAGE_TRANSFER_DST_BIT;
+}
+
+void vrdxHipCmdWideValueSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                             VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                             VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordWideValueSort(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, valuesBuffer, valuesOffset,
+                      storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdWideValueSortIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                     VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                     VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                     VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                                     uint32_t query) {
+  RecordWideValueSort(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset,
+                      valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipDescribeWideValueSortPlan(VrdxSorter sorter, uint32_t elementCount, VrdxHipWideValuePlanInfo* info) {
+  if (info == nullptr) return;
+  std::memset(info, 0, sizeof(*info));
+  if (sorter == nullptr) return;
+  if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
+  const vrdx::PlanContext context = PlanContextOf(sorter);
+  vrdx::DescribeWideValuePlan(context, vrdx::PlanWideValueSort(context, elementCount, 0), info);
 }
 
 VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {

@@ -357,6 +357,33 @@ hipError_t LaunchOrder32(hipStream_t stream, bool inverse, uint32_t* keys, uint3
 hipError_t LaunchSegmentedOrdered(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
                                   const SegmentedArgs& args, uint32_t order);
 
+// ---- 32-bit keys with 64-bit values (vrdxHipCmdWideValueSort[Indirect]; vrdx_kernels.hip, "32-bit keys with 64-bit
+// values") ----
+// small_sort_wide_kernel: up to kWideSmallMaxElements elements in one workgroup, key and both value words through three
+// staging planes (the body of SortInWorkgroup64 with only the key ranked): 256 threads x 16 up to 4096 elements, 1024 x 8
+// beyond.  keys: 4-byte aligned; values: 8-byte aligned, one 8-byte access per element; failure: word 3 of the header.
+constexpr uint32_t kWideSmall256Max = 256u * 16u;
+constexpr uint32_t kWideSmallMaxElements = 1024u * 8u;
+hipError_t LaunchSmallSortWide(hipStream_t stream, bool atomicRank, uint32_t* keys, uint64_t* values, uint32_t maxCount,
+                               const uint32_t* countPtr, uint32_t* failure);
+// The streaming steps of the two larger forms, in the shape of the 64-bit sorts' (kSort64Threads threads, four consecutive
+// elements per thread, min(*countPtr, maxCount) elements).  keys: the caller's, 4-byte aligned; values: the caller's, 8-byte
+// aligned; every other array lies inside the storage on a 16-byte boundary (MakeWideValueLayout).
+// index[i] = i
+hipError_t LaunchIotaWide(hipStream_t stream, uint32_t* index, uint32_t maxCount, const uint32_t* countPtr);
+// out[j] = values[index[j]]
+hipError_t LaunchGatherWide(hipStream_t stream, const uint64_t* values, const uint32_t* index, uint64_t* out, uint32_t maxCount,
+                            const uint32_t* countPtr);
+// values[j] = in[j]
+hipError_t LaunchCopyBackWide(hipStream_t stream, uint64_t* values, const uint64_t* in, uint32_t maxCount,
+                              const uint32_t* countPtr);
+// keysCopy[i] = keys[i]; lo[i], hi[i] = the words of values[i]
+hipError_t LaunchSplitWide(hipStream_t stream, const uint32_t* keys, const uint64_t* values, uint32_t* keysCopy, uint32_t* lo,
+                           uint32_t* hi, uint32_t maxCount, const uint32_t* countPtr);
+// values[i] = hi[i] << 32 | lo[i]
+hipError_t LaunchMergeWide(hipStream_t stream, uint64_t* values, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
+                           const uint32_t* countPtr);
+
 // ---- the kernels' dynamic LDS and the MSD plan's grids: one definition for the kernels (vrdx_kernels.hip) and for both
 // launch backends (vrdx_launch.inc) ----
 // Key+value tiles replay the permutation for the values through the SAME staging buffer after the

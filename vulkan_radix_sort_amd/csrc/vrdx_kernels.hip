@@ -4275,6 +4275,178 @@ __global__ __launch_bounds__(1024) void segmented_large_ordered_kernel(Segmented
 }
 
 // ---------------------------------------------------------------------------------------------
+// 32-bit keys with 64-bit values (vrdxHipCmdWideValueSort[Indirect])
+// ---------------------------------------------------------------------------------------------
+// New kernels next to the others, which stay as they are.  A value is 8 opaque bytes: two words that travel with their key.
+
+// The whole sort in ONE workgroup and ONE launch: the body of SortInWorkgroup64 with the planes (key, value low, value high)
+// -- RankPass64's key+value form, which ranks one of three word arrays and moves all three -- and only the key's four bytes
+// ranked.  A byte that is the same in every key costs no pass: the OR of key ^ key[0] over the REAL elements; pads do not
+// take part (key 0xFFFFFFFF, last in memory order, so every stable pass that runs leaves them behind the real elements, real
+// 0xFFFFFFFF keys included, and a pass that does not run leaves everything where it is); they are never stored.
+// keys: 4-byte aligned; values: 8-byte aligned, one 8-byte load and one 8-byte store per element.
+// LDS: SortInWorkgroup64LdsWords(THREADS, KPT, true).
+template <int THREADS, int KPT, bool ATOMIC_RANK>
+__global__ __launch_bounds__(THREADS) void small_sort_wide_kernel(uint32_t* keys, uint64_t* values, uint32_t maxCount,
+                                                                   const uint32_t* countPtr, uint32_t* failure) {
+  static_assert(THREADS >= 256 && THREADS % 256 == 0, "one thread per digit");
+  static_assert(KPT % 4 == 0, "chunks of four slots");
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr int WAVES = THREADS / 64;
+  constexpr uint32_t TILE = THREADS * KPT;
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  if (threadIdx.x < 3) failure[(int)threadIdx.x - 2] = 0;  // header words 1-3, see small_sort_kernel
+  if (n == 0) return;                                       // (uniform; an indirect count may be 0)
+  uint32_t* const varying = smem + TILE * 3 + WAVES * 256 + 8;  // behind the scan's scratch
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the ceil(n / 256) chunks of four 64-element slots dealt out evenly over the waves, as in SortInWorkgroup64
+  const uint32_t chunks = (n + 255u) / 256u;
+  const uint32_t base = chunks / WAVES, extra = chunks % WAVES;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+  const uint32_t slots = 4u * (base + (w < extra ? 1u : 0u));
+  const uint32_t first = 256u * (w * base + (w < extra ? w : extra)) + lane;
+
+  uint32_t key[KPT], lo[KPT], hi[KPT];
+  if (tid == 0) varying[0] = 0;
+  const uint32_t key0 = keys[0];  // uniform (n >= 1)
+  LoadStriped<KPT, false, true>(keys, first, n, false, 0xFFFFFFFFu, key, slots);
+  LoadStriped64<KPT>(values, first, n, lo, hi, slots);
+
+  uint32_t diff = 0;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    if (first + 64 * i < n) diff |= key[i] ^ key0;
+  }
+  diff = WaveInclusiveOr(diff);
+  LdsBarrier();  // varying[0] is zero
+  if (lane == 63 && diff != 0) atomicOr(&varying[0], diff);
+  LdsBarrier();
+  const uint32_t varyingKey = (uint32_t)__builtin_amdgcn_readfirstlane((int)varying[0]);
+
+#pragma unroll 1
+  for (uint32_t shift = 0; shift < 32; shift += 8) {
+    if (((varyingKey >> shift) & 0xFFu) == 0) continue;  // uniform: every key has the same byte here
+    RankPass64<THREADS, KPT, true, ATOMIC_RANK>(key, key, lo, hi, shift, first, slots, smem);
+  }
+
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    const uint32_t index = first + 64 * i;
+    if (index < n) {
+      keys[index] = key[i];
+      values[index] = (uint64_t)hi[i] << 32 | lo[i];
+    }
+  }
+}
+
+// The streaming steps of the two larger forms, in the shape of the 64-bit sorts': kSort64Threads threads, four consecutive
+// elements per thread.  The caller's values move as two 16-byte accesses of two values each, which need the values' own
+// 8-byte alignment only, the caller's keys as one that needs 4-byte alignment, the arrays in the storage (MakeWideValueLayout)
+// as aligned 16-byte accesses; the last n mod 4 elements go one by one, so nothing from element n on is read or written.
+// n = ElementCount(maxCount, countPtr); the grid covers maxCount.  No LDS.
+
+// index[i] = i
+__global__ __launch_bounds__(kSort64Threads) void iota_wide_kernel(uint32_t* __restrict__ index, uint32_t maxCount,
+                                                                   const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    *reinterpret_cast<u32x4*>(index + i) = u32x4{i, i + 1u, i + 2u, i + 3u};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) index[j] = j;
+}
+
+// out[j] = values[index[j]]: the values in the order the sort of (keys, index) left the index in
+__global__ __launch_bounds__(kSort64Threads) void gather_wide_kernel(const uint64_t* __restrict__ values,
+                                                                     const uint32_t* __restrict__ index,
+                                                                     uint64_t* __restrict__ out, uint32_t maxCount,
+                                                                     const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4 at = *reinterpret_cast<const u32x4*>(index + i);
+    const uint64_t a = values[at.x], b = values[at.y], c = values[at.z], d = values[at.w];
+    u32x4* const pairs = reinterpret_cast<u32x4*>(out + i);
+    pairs[0] = u32x4{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
+    pairs[1] = u32x4{(uint32_t)c, (uint32_t)(c >> 32), (uint32_t)d, (uint32_t)(d >> 32)};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) out[j] = values[index[j]];
+}
+
+// values[j] = in[j]: the permuted values back into the caller's array
+__global__ __launch_bounds__(kSort64Threads) void copy_back_wide_kernel(uint64_t* __restrict__ values,
+                                                                        const uint64_t* __restrict__ in, uint32_t maxCount,
+                                                                        const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4* const from = reinterpret_cast<const u32x4*>(in + i);
+    const u32x4 a = from[0], b = from[1];
+    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(values + i);
+    pairs[0] = a;
+    pairs[1] = b;
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) values[j] = in[j];
+}
+
+// keysCopy[i] = keys[i]; lo[i], hi[i] = the words of values[i]
+__global__ __launch_bounds__(kSort64Threads) void split_wide_kernel(const uint32_t* __restrict__ keys,
+                                                                    const uint64_t* __restrict__ values,
+                                                                    uint32_t* __restrict__ keysCopy, uint32_t* __restrict__ lo,
+                                                                    uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                    const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4 k = *reinterpret_cast<const u32x4_a4*>(keys + i);
+    const u32x4_a8* const pairs = reinterpret_cast<const u32x4_a8*>(values + i);
+    const u32x4 a = pairs[0], b = pairs[1];
+    *reinterpret_cast<u32x4*>(keysCopy + i) = k;
+    *reinterpret_cast<u32x4*>(lo + i) = u32x4{a.x, a.z, b.x, b.z};
+    *reinterpret_cast<u32x4*>(hi + i) = u32x4{a.y, a.w, b.y, b.w};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) {
+    const uint64_t v = values[j];
+    keysCopy[j] = keys[j];
+    lo[j] = (uint32_t)v;
+    hi[j] = (uint32_t)(v >> 32);
+  }
+}
+
+// values[i] = hi[i] << 32 | lo[i]
+__global__ __launch_bounds__(kSort64Threads) void merge_wide_kernel(uint64_t* __restrict__ values,
+                                                                    const uint32_t* __restrict__ lo,
+                                                                    const uint32_t* __restrict__ hi, uint32_t maxCount,
+                                                                    const uint32_t* countPtr) {
+  const uint32_t n = ElementCount(maxCount, countPtr);
+  bool whole;
+  const uint32_t i = Sort64First(n, &whole);
+  if (i >= n) return;
+  if (whole) {
+    const u32x4 l = *reinterpret_cast<const u32x4*>(lo + i), h = *reinterpret_cast<const u32x4*>(hi + i);
+    u32x4_a8* const pairs = reinterpret_cast<u32x4_a8*>(values + i);
+    pairs[0] = u32x4{l.x, h.x, l.y, h.y};
+    pairs[1] = u32x4{l.z, h.z, l.w, h.w};
+    return;
+  }
+  for (uint32_t j = i; j < n; ++j) values[j] = (uint64_t)hi[j] << 32 | lo[j];
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs
 // ---------------------------------------------------------------------------------------------
 #include "vrdx_launch.inc"

@@ -362,7 +362,31 @@
     "_ZN4vrdx30segmented_large_ordered_kernelILb1ELb0EEEvNS_13SegmentedArgsEj") \
   X(kSegmentedOrderedLargeVA, (&segmented_large_ordered_kernel<true, true>), 1024, SegmentLargeLdsWords(true) * 4, \
     "_ZN4vrdx30segmented_large_ordered_kernelILb1ELb1EEEvNS_13SegmentedArgsEj")
-#define VRDX_ALL_KERNELS(X) VRDX_KERNELS(X) VRDX_ORDERED32_KERNELS(X)
+
+// The kernels of the sorts of 32-bit keys with 64-bit values (vrdxHipCmdWideValueSort*), in a third list behind the other two
+// for the same reason.
+#define VRDX_WIDE_VALUE_KERNELS(X) \
+  /* small_sort_wide_kernel [256 x 16 | 1024 x 8][atomic rank] */ \
+  X(kSmallWide256, (&small_sort_wide_kernel<256, 16, false>), 256, SortInWorkgroup64LdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx22small_sort_wide_kernelILi256ELi16ELb0EEEvPjPmjPKjS1_") \
+  X(kSmallWide256A, (&small_sort_wide_kernel<256, 16, true>), 256, SortInWorkgroup64LdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx22small_sort_wide_kernelILi256ELi16ELb1EEEvPjPmjPKjS1_") \
+  X(kSmallWide1024, (&small_sort_wide_kernel<1024, 8, false>), 1024, SortInWorkgroup64LdsWords(1024, 8, true) * 4, \
+    "_ZN4vrdx22small_sort_wide_kernelILi1024ELi8ELb0EEEvPjPmjPKjS1_") \
+  X(kSmallWide1024A, (&small_sort_wide_kernel<1024, 8, true>), 1024, SortInWorkgroup64LdsWords(1024, 8, true) * 4, \
+    "_ZN4vrdx22small_sort_wide_kernelILi1024ELi8ELb1EEEvPjPmjPKjS1_") \
+  /* the streaming steps: index, gather, copy back (the gather form); split, merge (the two-sorts form) */ \
+  X(kIotaWide, (&iota_wide_kernel), kSort64Threads, 0, \
+    "_ZN4vrdx16iota_wide_kernelEPjjPKj") \
+  X(kGatherWide, (&gather_wide_kernel), kSort64Threads, 0, \
+    "_ZN4vrdx18gather_wide_kernelEPKmPKjPmjS3_") \
+  X(kCopyBackWide, (&copy_back_wide_kernel), kSort64Threads, 0, \
+    "_ZN4vrdx21copy_back_wide_kernelEPmPKmjPKj") \
+  X(kSplitWide, (&split_wide_kernel), kSort64Threads, 0, \
+    "_ZN4vrdx17split_wide_kernelEPKjPKmPjS4_S4_jS1_") \
+  X(kMergeWide, (&merge_wide_kernel), kSort64Threads, 0, \
+    "_ZN4vrdx17merge_wide_kernelEPmPKjS2_jS2_")
+#define VRDX_ALL_KERNELS(X) VRDX_KERNELS(X) VRDX_ORDERED32_KERNELS(X) VRDX_WIDE_VALUE_KERNELS(X)
 
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
@@ -370,6 +394,7 @@ enum KernelId : int {
   kNumKernels,
   kLastListedKernel = kNumKernels - 1,  // (the ordered list's first id is kNumKernels)
   VRDX_ORDERED32_KERNELS(VRDX_KERNEL_ID)
+  VRDX_WIDE_VALUE_KERNELS(VRDX_KERNEL_ID)
 #undef VRDX_KERNEL_ID
   kNumAllKernels
 };
@@ -637,4 +662,44 @@ hipError_t LaunchSegmentedOrdered(hipStream_t stream, SegmentClass sizeClass, ui
                                   const SegmentedArgs& args, uint32_t order) {
   if (grid == 0 || !KeyOrder32Launchable(order)) return hipErrorInvalidValue;
   return Launch(Form(KernelId(kSegmentedOrderedSmall + 4 * sizeClass), keyValue, atomicRank), grid, stream, args, order);
+}
+
+// ---- 32-bit keys with 64-bit values (VRDX_WIDE_VALUE_KERNELS) ---------------------------------------
+// (three staging planes of the 1024 x 8 form and its wave counters must fit one CU's LDS)
+static_assert(kWideSmallMaxElements == 1024u * 8u && SortInWorkgroup64LdsWords(1024, 8, true) * 4 <= 160u * 1024u,
+              "small_sort_wide_kernel's largest form");
+hipError_t LaunchSmallSortWide(hipStream_t stream, bool atomicRank, uint32_t* keys, uint64_t* values, uint32_t maxCount,
+                               const uint32_t* countPtr, uint32_t* failure) {
+  if (maxCount == 0 || maxCount > kWideSmallMaxElements) return hipErrorInvalidValue;
+  const KernelId first = maxCount <= kWideSmall256Max ? kSmallWide256 : kSmallWide1024;
+  return Launch(KernelId(first + atomicRank), 1, stream, keys, values, maxCount, countPtr, failure);
+}
+
+hipError_t LaunchIotaWide(hipStream_t stream, uint32_t* index, uint32_t maxCount, const uint32_t* countPtr) {
+  if (!Sort64Fits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kIotaWide, Sort64Grid(maxCount), stream, index, maxCount, countPtr);
+}
+
+hipError_t LaunchGatherWide(hipStream_t stream, const uint64_t* values, const uint32_t* index, uint64_t* out, uint32_t maxCount,
+                            const uint32_t* countPtr) {
+  if (!Sort64Fits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kGatherWide, Sort64Grid(maxCount), stream, values, index, out, maxCount, countPtr);
+}
+
+hipError_t LaunchCopyBackWide(hipStream_t stream, uint64_t* values, const uint64_t* in, uint32_t maxCount,
+                              const uint32_t* countPtr) {
+  if (!Sort64Fits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kCopyBackWide, Sort64Grid(maxCount), stream, values, in, maxCount, countPtr);
+}
+
+hipError_t LaunchSplitWide(hipStream_t stream, const uint32_t* keys, const uint64_t* values, uint32_t* keysCopy, uint32_t* lo,
+                           uint32_t* hi, uint32_t maxCount, const uint32_t* countPtr) {
+  if (!Sort64Fits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kSplitWide, Sort64Grid(maxCount), stream, keys, values, keysCopy, lo, hi, maxCount, countPtr);
+}
+
+hipError_t LaunchMergeWide(hipStream_t stream, uint64_t* values, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
+                           const uint32_t* countPtr) {
+  if (!Sort64Fits(maxCount)) return hipErrorInvalidValue;
+  return Launch(kMergeWide, Sort64Grid(maxCount), stream, values, lo, hi, maxCount, countPtr);
 }

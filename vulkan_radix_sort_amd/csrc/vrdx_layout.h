@@ -236,6 +236,37 @@ static inline Sort64Layout MakeSort64Layout(uint32_t maxElementCount, uint32_t a
   return s;
 }
 
+// The storage of a sort of 32-bit keys with 64-bit values (vrdxHipCmdWideValueSort[Indirect]; PlanWideValueSort in
+// vrdx_plan.h): the unchanged 32-bit key+value storage for N first -- the inner sorts use it, and its header is this call's
+// header -- and behind it three word arrays, each on a 128-byte line of the absolute address:
+//   [0, innerSize)                 vrdxGetSorterKeyValueStorageRequirements(N), carved by MakeLayout as ever
+//   aOffset  (128-byte aligned)    uint32 A[N]: the index (gather form) | the copy of the keys (two-sorts form)
+//   bOffset  = Align(aOffset + 4 N, 128)          uint32 B[N]: the values' low words (two-sorts form)
+//   cOffset  = bOffset + Align(4 N, 128)          uint32 C[N]: the values' high words (two-sorts form)
+//   tOffset  = bOffset             uint64 T[N] over B and C together (gather form): 8 N <= Align(4 N, 128) + 4 N
+// The size does not depend on the address: every pad is counted at its largest (the one in front of A: 128 - align bytes;
+// the two between the arrays: 124 bytes each, as 4 N is a multiple of 4).  12 bytes per element and kWideValuePadBytes on
+// top of the inner storage.
+struct WideValueLayout {
+  uint64_t innerSize;
+  uint64_t aOffset, bOffset, cOffset, tOffset;
+  uint64_t size;  // what the caller allocates
+};
+constexpr uint64_t WideValuePadBytes(uint32_t align) { return (align < 128u ? 128u - align : 0u) + 2u * 124u; }
+
+static inline WideValueLayout MakeWideValueLayout(uint32_t maxElementCount, uint32_t align, uint64_t storageAddress = 0) {
+  WideValueLayout w;
+  w.innerSize = MakeLayout(maxElementCount, align, 0).keyValueSize;
+  const uint64_t bytes = (uint64_t)maxElementCount * sizeof(uint32_t);
+  const uint64_t words = (bytes + 127u) & ~(uint64_t)127u;
+  w.aOffset = w.innerSize + ((0 - (storageAddress + w.innerSize)) & 127u);
+  w.bOffset = w.aOffset + words;
+  w.cOffset = w.bOffset + words;
+  w.tOffset = w.bOffset;
+  w.size = w.innerSize + 3 * bytes + WideValuePadBytes(align);
+  return w;
+}
+
 // The segmented 64-bit sorts' carving of the 64-bit storage (vrdxHipCmdSortSegmented64[KeyValue]; PlanSegmentedSort in
 // vrdx_plan.h): header, list counters and lists where MakeSegmentedLayout keeps them -- inside the inner 32-bit storage --
 // and the scratch arrays where MakeSort64Layout keeps its word arrays, behind it:

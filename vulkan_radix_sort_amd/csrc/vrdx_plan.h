@@ -497,6 +497,63 @@ static inline Sort64Plan PlanSort64(const PlanContext& c, bool keyValue, uint32_
   return p;
 }
 
+// ---- 32-bit keys with 64-bit values (vrdxHipCmdWideValueSort[Indirect]) ----
+// One of three step lists, on the storage of MakeWideValueLayout (vrdx_layout.h); nothing is decided from the data, and an
+// indirect call is planned from its bound alone:
+//   one workgroup  n <= kWideSmallMaxElements (and PlanContext::smallSort): small_sort_wide_kernel, slot 14
+//   gather         iota (A[i] = i) | sort (keys, A) on the caller's keys in place | gather (T[j] = values[A[j]]) |
+//                  copy back (values[j] = T[j]); slots 1-4
+//   two sorts      from kWideValueTwoSortsFrom elements: split (A = keys, B = value low, C = value high) | sort (A, B) |
+//                  sort (keys, C) | merge (values[i] = C[i] << 32 | B[i]); slots 1-4.  Both inner sorts are stable sorts of
+//                  the same key sequence, so they apply the same permutation whatever plan or verdict each takes.
+// A native two-payload form of the MSD, hybrid and pass kernels would become a fourth list here.
+// kWideValueTwoSortsFrom: where the gathered array has left the caches and one more streaming sort costs less than the random
+// reads -- the smallest measured size from which the two-sorts form wins by more than the box's 3 %: equal at 2^22 (0.171
+// against 0.167 ms), 13 % faster at 2^24, 10 % at 2^26.  tools/build_variants.sh with
+// name:-DVRDX_WIDE_VALUE_TWO_SORTS_FROM=... builds the always-gather (0xFFFFFFFF) and always-two-sorts (0) libraries of that
+// measurement.
+#ifndef VRDX_WIDE_VALUE_TWO_SORTS_FROM
+#define VRDX_WIDE_VALUE_TWO_SORTS_FROM (1u << 24)
+#endif
+constexpr uint32_t kWideValueTwoSortsFrom = VRDX_WIDE_VALUE_TWO_SORTS_FROM;
+enum class WideValueForm : uint8_t { kNone, kOneWorkgroup, kGather, kTwoSorts };  // VRDX_HIP_WIDE_VALUE_*
+enum class StepWide : uint8_t { kSmallSort, kIota, kSortKeysA, kGather, kCopyBack, kSplit, kSortAB, kSortKeysC, kMerge };
+struct WideValueStep { StepWide what; uint8_t slot; const char* name; };  // (name: what EnqueueCheck reports; an inner sort reports its own)
+struct WideValuePlan {
+  uint32_t elementCount = 0;
+  bool atomicRank = false;
+  WideValueForm form = WideValueForm::kNone;
+  WideValueLayout layout{};
+  WideValueStep steps[4];  // none: the empty sort
+  uint32_t stepCount = 0;
+};
+
+static inline WideValuePlan PlanWideValueSort(const PlanContext& c, uint32_t elementCount, uint64_t storageAddress) {
+  WideValuePlan p;
+  p.elementCount = elementCount;
+  p.atomicRank = c.atomicRank;
+  if (elementCount == 0) return p;
+  p.layout = MakeWideValueLayout(elementCount, c.minStorageBufferOffsetAlignment, storageAddress);
+  const auto add = [&p](StepWide what, uint32_t slot, const char* name) { p.steps[p.stepCount++] = WideValueStep{what, (uint8_t)slot, name}; };
+  if (elementCount <= kWideSmallMaxElements && c.smallSort) {
+    p.form = WideValueForm::kOneWorkgroup;
+    add(StepWide::kSmallSort, 14, "small_sort_wide_kernel");
+  } else if (elementCount < kWideValueTwoSortsFrom) {
+    p.form = WideValueForm::kGather;
+    add(StepWide::kIota, 1, "iota_wide_kernel");
+    add(StepWide::kSortKeysA, 2, "sort of the keys with the index");
+    add(StepWide::kGather, 3, "gather_wide_kernel");
+    add(StepWide::kCopyBack, 4, "copy_back_wide_kernel");
+  } else {
+    p.form = WideValueForm::kTwoSorts;
+    add(StepWide::kSplit, 1, "split_wide_kernel");
+    add(StepWide::kSortAB, 2, "sort of the key copy with the low words");
+    add(StepWide::kSortKeysC, 3, "sort of the keys with the high words");
+    add(StepWide::kMerge, 4, "merge_wide_kernel");
+  }
+  return p;
+}
+
 // Grid of the fused histogram.  Every workgroup ends with up to 1024 global atomics on the same 1024 words, so few, long-lived
 // workgroups win for large inputs: one per CU and at least two groups of 16384 keys each (tools/hist_grid.sh, removed, last at
 // commit 3645810: 17.4 us with 256 workgroups against 21.1 us with 512 at N = 2^23; equal at 2^25).  Small inputs want the
@@ -531,6 +588,30 @@ static inline void DescribePlan(const SortPlan& plan, VrdxHipPlanInfo* info) {
   } else {
     info->plan = VRDX_HIP_PLAN_FOUR_PASSES;
     info->bytesPerElement = fourPasses;
+  }
+}
+
+// What vrdxHipDescribeWideValueSortPlan reports of a plan (include/vk_radix_sort.h); *info zeroed by the caller.  The inner
+// sorts are priced where their own plan runs (DescribePlan).
+static inline void DescribeWideValuePlan(const PlanContext& c, const WideValuePlan& plan, VrdxHipWideValuePlanInfo* info) {
+  info->form = (uint32_t)plan.form;
+  info->oneWorkgroupMax = c.smallSort ? kWideSmallMaxElements : 0u;
+  info->twoSortsFrom = kWideValueTwoSortsFrom;
+  if (plan.form == WideValueForm::kNone) return;
+  if (plan.form == WideValueForm::kOneWorkgroup) {
+    info->launches = 1;
+    info->bytesPerElement = 24;  // 12 read, 12 written
+    return;
+  }
+  VrdxHipPlanInfo inner{};
+  DescribePlan(PlanSort(c, true, plan.elementCount, 0), &inner);
+  info->innerPlan = inner.plan;
+  if (plan.form == WideValueForm::kGather) {
+    info->launches = 3 + inner.launches;
+    info->bytesPerElement = 4 + inner.bytesPerElement + 20 + 16;  // index | sort | gather (4 + 8 at random + 8) | copy back
+  } else {
+    info->launches = 2 + 2 * inner.launches;
+    info->bytesPerElement = 24 + 2 * inner.bytesPerElement + 16;  // split | two sorts | merge
   }
 }
 
