@@ -611,7 +611,7 @@ void vrdxHipCmdOrderedSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxS
  * The slots no step ends coincide with the one before.  Beyond ONE_WORKGROUP the status and verdict words are those of the
  * last inner sort.
  * Out of scope: two-payload forms of the MSD, hybrid and pass kernels (they would slot in behind the same plan function);
- * segmented, ordered and bit-range variants; 64-bit keys with 64-bit values.
+ * ordered and bit-range variants, of the segmented form below too; 64-bit keys with 64-bit values.
  * ------------------------------------------------------------------------------------------ */
 void vrdxHipGetSorterWideValueStorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
                                                   VrdxSorterStorageRequirements* requirements);
@@ -637,6 +637,38 @@ typedef struct VrdxHipWideValuePlanInfo {
 } VrdxHipWideValuePlanInfo;
 /* The form vrdxHipCmdWideValueSort[Indirect] records on `sorter` for elementCount (the bound of an indirect call). */
 void vrdxHipDescribeWideValueSortPlan(VrdxSorter sorter, uint32_t elementCount, VrdxHipWideValuePlanInfo* info);
+
+/* ------------------------------------------------------------------------------------------
+ * Segmented sort of 32-bit keys with 64-bit values (HIP backend only)
+ *
+ * vrdxHipCmdWideValueSortSegmented is vrdxHipCmdSortSegmentedKeyValue with values of 8 opaque bytes (per-row argsort with
+ * int64 indices, per-tile lists of pointers, per-expert token lists): the same arguments, name for name.
+ * Order: every segment [o[i], o[i+1]) of the uint32 keys comes back ascending and stable, and every value -- 8 OPAQUE bytes at
+ * valuesBuffer + valuesOffset + 8 i -- travels with its key.
+ * Offsets: segmentCount + 1 uint32 CSR offsets, read on the device only.  Elements in front of o[0] and from
+ * o[segmentCount] on are not written at all, and neither are segments of fewer than 2 elements.
+ * Alignment: keys and offsets 4 bytes; valuesBuffer + valuesOffset a multiple of 8; the storage a multiple of 16.
+ * Storage: vrdxHipGetSorterWideValueStorageRequirements(maxElementCount) bytes, the calculator of vrdxHipCmdWideValueSort.
+ * Bad offsets, as in the other segmented sorts: a segment with o[i] > o[i+1] or o[i+1] > maxElementCount is left alone, and
+ * any offsets that are not monotone raise VRDX_HIP_STATUS_SEGMENTS_INVALID in the storage's failure word and in the
+ * sorter's word; nothing is ever written outside [0, maxElementCount) of the caller's arrays or outside the storage
+ * requirement.
+ * segmentCount == 0 or maxElementCount == 0 records only the timestamps; maxElementCount beyond 2^30 - 4 is clamped and
+ * raises VRDX_HIP_STATUS_COUNT_CLAMPED; word 1 of the header reads VRDX_HIP_VERDICT_NONE afterwards.
+ * Timestamps: all 15 slots are recorded; slots 1 to 4 end the fill, the small, the mid and the large launch, as in
+ * vrdxHipCmdSortSegmented64KeyValue; a launch that cannot have work under this bound is absent and its slot coincides with
+ * the one before; the later slots coincide with slot 4.
+ * With a NULL pool the call is legal inside a stream capture; grids depend on segmentCount, maxElementCount and the CU count
+ * only, so the graph replays on other keys and on another segmentation with the same segmentCount.
+ * How: three size classes decided on the device.  Segments of up to 4096 and of up to 8192 elements are sorted in LDS, key and
+ * both value words together, between one load and one store (24 bytes of HBM traffic per element); a larger segment is
+ * sorted by one workgroup through memory, one walk per byte of the key that differs between its keys.
+ * ------------------------------------------------------------------------------------------ */
+void vrdxHipCmdWideValueSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                      uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                      VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                      VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                      VkQueryPool queryPool, uint32_t query);
 
 /* ------------------------------------------------------------------------------------------
  * HIP-side companions of the Vulkan objects the reference's callers create themselves

@@ -44,6 +44,7 @@ from .api import (  # noqa: F401
     order_word32,
     VrdxHipWideValuePlanInfo,
     WIDE_VALUE_FORM_NAMES,
+    WIDE_VALUE_SEGMENTED_CALLS,
 )
 from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
@@ -51,7 +52,7 @@ from .segmented64 import sort_segments64  # noqa: F401
 from .sort_bits import sort_bits  # noqa: F401
 from .segmented_bits import sort_segments_bits  # noqa: F401
 from .ordered import sort_ordered, sort_segments_ordered  # noqa: F401
-from .wide_value import sort_key_value64  # noqa: F401
+from .wide_value import sort_key_value64, sort_segments_key_value64  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -97,4 +98,6 @@ __all__ = [
     "VrdxHipWideValuePlanInfo",
     "WIDE_VALUE_FORM_NAMES",
     "sort_key_value64",
+    "sort_segments_key_value64",
+    "WIDE_VALUE_SEGMENTED_CALLS",
 ]

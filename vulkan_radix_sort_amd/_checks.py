@@ -18,6 +18,8 @@ Known differences between the front ends.  They are behaviour -- a caller sees t
 * Each front end names what its keys, offsets and values must hold in its own words (``what``).
 * sort_ordered and sort_segments_ordered (ordered.py) came later and follow sort64: ``check_keys32`` for dtype and order word,
   every array's device right behind its shape, the storage on a 16-byte boundary.
+* sort_segments_key_value64 (wide_value.py) checks every type, shape, length and the values' alignment first, then that offsets,
+  values and storage live where the keys live, then the storage's alignment and size, and only then that the place is a GPU.
 * sort_segments_bits checks the bit range before the tensors, sort_bits behind keys and values; only sort_bits bounds the
   number of keys of a partial range (``check_range_count``).
 """

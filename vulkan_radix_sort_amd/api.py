@@ -62,6 +62,8 @@ class RecordingCall(NamedTuple):
         """(key bits, segmented, indirect, key+value, None | "Bits" | "Ordered"), parsed from the C name"""
         ordered32 = re.fullmatch(r"vrdxHipCmdOrderedSort(Segmented)?(KeyValue)?(Indirect)?", self.c_name)
         wide_value = re.fullmatch(r"vrdxHipCmdWideValueSort(Indirect)?", self.c_name)
+        if self.c_name == "vrdxHipCmdWideValueSortSegmented":   # the row of WIDE_VALUE_SEGMENTED_CALLS
+            return 32, True, False, True, None
         if wide_value:   # the rows of WIDE_VALUE_CALLS: uint32 keys, always with values (of 8 bytes: the argument list is the same)
             return 32, False, bool(wide_value.group(1)), True, None
         if ordered32:   # the ordered 32-bit sorts carry the word in front: their names are not of the CmdSort family
@@ -199,6 +201,14 @@ WIDE_VALUE_CALLS = (
           "``wide_value_storage_requirements(max_element_count)`` bytes."),
 )
 
+# the segmented form of it: a one-row table of its own (WIDE_VALUE_CALLS stays the two flat calls); the arguments are those of
+# vrdxHipCmdSortSegmentedKeyValue
+WIDE_VALUE_SEGMENTED_CALLS = (
+    _CALL("vrdxHipCmdWideValueSortSegmented", "cmd_wide_value_sort_segmented",
+          "``cmd_sort_segmented_key_value`` with values of 8 opaque bytes each (``values_offset`` a multiple of 8); storage of "
+          "``wide_value_storage_requirements(max_element_count)`` bytes."),
+)
+
 
 def _exported_symbols():
     """Everything the library exports, in the order this tuple has always had: the entry points that record no sort, by hand,
@@ -221,7 +231,8 @@ def _exported_symbols():
         yield from names
         yield from (next(rows).c_name for _ in range(recording))
     assert next(rows, None) is None, "a row of RECORDING_CALLS is missing from EXPORTED_SYMBOLS"
-    # uint32 keys with 8-byte values
+    # uint32 keys with 8-byte values: the segmented call, then the flat group
+    yield from (call.c_name for call in WIDE_VALUE_SEGMENTED_CALLS)
     yield "vrdxHipGetSorterWideValueStorageRequirements"
     yield from (call.c_name for call in WIDE_VALUE_CALLS)
     yield "vrdxHipDescribeWideValueSortPlan"
@@ -443,7 +454,7 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = None
         fn.argtypes = [vp, u32, ctypes.POINTER(VrdxSorterStorageRequirements)]
-    for call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS:
+    for call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS:
         fn = getattr(lib, call.c_name)
         fn.restype = None
         fn.argtypes = call.argtypes
@@ -681,5 +692,5 @@ def _recording_method(call: RecordingCall):
     return method
 
 
-for _call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS:
+for _call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS:
     setattr(Sorter, _call.method, _recording_method(_call))

@@ -674,6 +674,49 @@ void RecordWideValueSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
   r.stamps.Finish();
 }
 
+// The segmented sort of 32-bit keys with 64-bit values (include/vk_radix_sort.h, vrdxHipCmdWideValueSortSegmented): the steps
+// of PlanWideValueSortSegmented (vrdx_plan.h) -- a fill and up to three launches -- on the wide-value storage, recorded the
+// way RecordSegmentedSort records its own.
+void RecordWideValueSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                  uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer,
+                                  VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                  VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  Recording r(commandBuffer, sorter, maxElementCount, queryPool, query);
+  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
+  const vrdx::WideValueSegmentedPlan plan = vrdx::PlanWideValueSortSegmented(
+      PlanContextOf(sorter), r.count, segmentCount, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (r.NothingToRecord(sorter, plan.refusal, plan.stepCount)) return;
+  const auto words = [storage](uint64_t offset) { return reinterpret_cast<uint32_t*>(storage + offset); };
+  vrdx::SegmentedWideArgs a;
+  a.keys = reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset));
+  a.values = reinterpret_cast<uint64_t*>(BufferAddress(valuesBuffer, valuesOffset));
+  a.keysScratch = words(plan.layout.keysScratchOffset);
+  a.valuesScratch = reinterpret_cast<uint64_t*>(storage + plan.layout.valuesScratchOffset);
+  a.offsets = reinterpret_cast<const uint32_t*>(BufferAddress(offsetsBuffer, offsetsOffset));
+  a.segmentCount = segmentCount;
+  a.maxCount = r.count;
+  a.midCount = words(plan.layout.midCountOffset);
+  a.midList = words(plan.layout.midListOffset);
+  a.midCap = plan.layout.midCap;
+  a.largeCount = words(plan.layout.largeCountOffset);
+  a.largeList = words(plan.layout.largeListOffset);
+  a.largeCap = plan.layout.largeCap;
+  a.failure = words(VRDX_OFF_FAILURE);
+  a.stickyFailure = sorter->stickyStatus;
+  for (uint32_t i = 0; i < plan.stepCount; ++i) {
+    const vrdx::SegmentedSortStep& step = plan.steps[i];
+    const vrdx::SegmentClass sizeClass = vrdx::SegmentClass((int)step.what - (int)vrdx::SegmentedStep::kSmall);
+    // header (plan verdict = VRDX_HIP_VERDICT_NONE, failure word) and the two list counters, in front of the first launch
+    const hipError_t e = step.what == vrdx::SegmentedStep::kClear
+                             ? vrdx::LaunchSegmentedClear(r.stream, a)
+                             : vrdx::LaunchSegmentedWide(r.stream, sizeClass, step.grid, plan.atomicRank, a);
+    EnqueueCheck(sorter, step.name, e);
+    r.stamps.AdvanceTo(step.slot);
+  }
+  r.stamps.Finish();
+  MaybeRecheckOrder(sorter, r.stream, plan.atomicRank);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1064,6 +1107,15 @@ void vrdxHipDescribeWideValueSortPlan(VrdxSorter sorter, uint32_t elementCount, 
   if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
   const vrdx::PlanContext context = PlanContextOf(sorter);
   vrdx::DescribeWideValuePlan(context, vrdx::PlanWideValueSort(context, elementCount, 0), info);
+}
+
+void vrdxHipCmdWideValueSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                      uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                      VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                      VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                      VkQueryPool queryPool, uint32_t query) {
+  RecordWideValueSortSegmented(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
+                               keysOffset, valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
 }
 
 VkResult vrdxHipCreateQueryPool(uint32_t queryCount, VkQueryPool* pQueryPool) {

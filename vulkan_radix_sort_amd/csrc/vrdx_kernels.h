@@ -384,6 +384,39 @@ hipError_t LaunchSplitWide(hipStream_t stream, const uint32_t* keys, const uint6
 hipError_t LaunchMergeWide(hipStream_t stream, uint64_t* values, const uint32_t* lo, const uint32_t* hi, uint32_t maxCount,
                            const uint32_t* countPtr);
 
+// ---- segmented sort of 32-bit keys with 64-bit values (vrdxHipCmdWideValueSortSegmented; vrdx_kernels.hip, "segmented sort
+// of 32-bit keys with 64-bit values"): the three size classes of the key+value segmented 64-bit sort with the planes (key,
+// value low, value high); every segment moves through memory once in the in-LDS classes ----
+//   segmented_small_wide_kernel  256 threads, one workgroup per segment by grid stride: checks the offsets, sorts segments of
+//                                2 ... kSegWideSmallMax elements in LDS (256 x 16), lists the bigger ones;
+//   segmented_mid_wide_kernel    1024 threads over the mid list: 1024 x 8, three planes of 32 KiB;
+//   segmented_large_wide_kernel  1024 threads over the large list: SegmentLsdWide, tiles of kSegWideLargeTile elements.
+// keys, offsets: 4-byte aligned; values: 8-byte aligned, one 8-byte access per element and pass.
+constexpr uint32_t kSegWideSmallMax = 256u * 16u;
+constexpr uint32_t kSegWideMidMax = 1024u * 8u;
+constexpr uint32_t kSegWideLargeTile = 1024u * 8u;
+struct SegmentedWideArgs {
+  uint32_t* keys;
+  uint64_t* values;
+  uint32_t* keysScratch;        // large segments: the same index range as in keys
+  uint64_t* valuesScratch;      //                 and as in values
+  const uint32_t* offsets;      // segmentCount + 1 words, read on the device
+  uint32_t segmentCount;
+  uint32_t maxCount;            // no segment may end behind it
+  uint32_t* midCount;           // appended to by the small kernel (zeroed by the fill in front of it)
+  uint32_t* midList;            // [midCap] segment ids
+  uint32_t midCap;
+  uint32_t* largeCount;
+  uint32_t* largeList;          // [largeCap] segment ids
+  uint32_t largeCap;
+  uint32_t* failure;            // the storage's failure word (word 3 of the header): VRDX_HIP_STATUS_SEGMENTS_INVALID
+  uint32_t* stickyFailure;      // the sorter's word
+};
+// The fill in front of the first launch is segmented_clear_kernel as it is: the same header words and list counters.
+hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedWideArgs& args);
+hipError_t LaunchSegmentedWide(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool atomicRank,
+                               const SegmentedWideArgs& args);
+
 // ---- the kernels' dynamic LDS and the MSD plan's grids: one definition for the kernels (vrdx_kernels.hip) and for both
 // launch backends (vrdx_launch.inc) ----
 // Key+value tiles replay the permutation for the values through the SAME staging buffer after the
@@ -433,6 +466,12 @@ constexpr size_t Segment64LargeLdsWords(bool kv) {
   // staging (low words, high words, values) | wave counters 16 x 256 | scan scratch 32 | bases 8 x 256 | tile starts 256 |
   // tile counts 256 | 16: 90 KiB keys-only, 122 KiB key+value
   return (size_t)kSeg64LargeTile * (kv ? 3 : 2) + 16 * 256 + 32 + 8 * 256 + 256 + 256 + 16;
+}
+
+constexpr size_t SegmentWideLargeLdsWords() {
+  // staging (keys, value low words, value high words) | wave counters 16 x 256 | scan scratch 32 | bases 4 x 256 | tile
+  // starts 256 | tile counts 256 | 16: 118.2 KiB
+  return (size_t)kSegWideLargeTile * 3 + 16 * 256 + 32 + 4 * 256 + 256 + 256 + 16;
 }
 
 // histogram_msd_kernel

@@ -4447,6 +4447,255 @@ __global__ __launch_bounds__(kSort64Threads) void merge_wide_kernel(uint64_t* __
 }
 
 // ---------------------------------------------------------------------------------------------
+// segmented sort of 32-bit keys with 64-bit values (vrdxHipCmdWideValueSortSegmented)
+// ---------------------------------------------------------------------------------------------
+// The three size classes of the key+value segmented 64-bit sort -- the same loops (ForEachSmallSegment, ForEachListedSegment),
+// lists and offset checks -- with the planes (key, value low, value high) of small_sort_wide_kernel instead of (key low, key
+// high, value): only the key's four bytes are ranked, a value moves as one 8-byte access, a key as a 4-byte one.
+// small_sort_wide_kernel stays as it is; its body is written again here as a device function of one segment.
+
+// n <= THREADS * KPT elements of one segment inside one workgroup, in place: the body of small_sort_wide_kernel.  A byte that
+// is the same in every key costs no pass (the OR of key ^ key[0] over the REAL elements; pads are key 0xFFFFFFFF behind them
+// and are never stored); a segment whose keys are all equal is in order already and is not stored at all.
+// LDS: SortInWorkgroup64LdsWords(THREADS, KPT, true).
+template <int THREADS, int KPT, bool ATOMIC_RANK>
+__device__ __forceinline__ void SortInWorkgroupWide(uint32_t* keys, uint64_t* values, uint32_t n, uint32_t* smem) {
+  static_assert(THREADS >= 256 && THREADS % 256 == 0, "one thread per digit");
+  static_assert(KPT % 4 == 0, "chunks of four slots");
+  constexpr int WAVES = THREADS / 64;
+  constexpr uint32_t TILE = THREADS * KPT;
+  uint32_t* const varying = smem + TILE * 3 + WAVES * 256 + 8;  // behind the scan's scratch
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the ceil(n / 256) chunks of four 64-element slots dealt out evenly over the waves, as in SortInWorkgroup64
+  const uint32_t chunks = (n + 255u) / 256u;
+  const uint32_t base = chunks / WAVES, extra = chunks % WAVES;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+  const uint32_t slots = 4u * (base + (w < extra ? 1u : 0u));
+  const uint32_t first = 256u * (w * base + (w < extra ? w : extra)) + lane;
+
+  uint32_t key[KPT], lo[KPT], hi[KPT];
+  if (tid == 0) varying[0] = 0;
+  const uint32_t key0 = keys[0];  // uniform (n >= 1)
+  LoadStriped<KPT, false, true>(keys, first, n, false, 0xFFFFFFFFu, key, slots);
+  LoadStriped64<KPT>(values, first, n, lo, hi, slots);
+
+  uint32_t diff = 0;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    if (first + 64 * i < n) diff |= key[i] ^ key0;
+  }
+  diff = WaveInclusiveOr(diff);
+  LdsBarrier();  // varying[0] is zero
+  if (lane == 63 && diff != 0) atomicOr(&varying[0], diff);
+  LdsBarrier();
+  const uint32_t varyingKey = (uint32_t)__builtin_amdgcn_readfirstlane((int)varying[0]);
+  if (varyingKey == 0) return;  // uniform: all keys equal, the values keep their input order
+
+#pragma unroll 1
+  for (uint32_t shift = 0; shift < 32; shift += 8) {
+    if (((varyingKey >> shift) & 0xFFu) == 0) continue;  // uniform: every key has the same byte here
+    RankPass64<THREADS, KPT, true, ATOMIC_RANK>(key, key, lo, hi, shift, first, slots, smem);
+  }
+
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (i % 4 == 0 && (uint32_t)i >= slots) break;
+    const uint32_t index = first + 64 * i;
+    if (index < n) {
+      keys[index] = key[i];
+      values[index] = (uint64_t)hi[i] << 32 | lo[i];
+    }
+  }
+}
+
+template <bool ATOMIC_RANK>
+__global__ __launch_bounds__(256) void segmented_small_wide_kernel(SegmentedWideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  ForEachSmallSegment(a, kSegWideSmallMax, kSegWideMidMax, [&](uint32_t begin, uint32_t n) {
+    SortInWorkgroupWide<256, 16, ATOMIC_RANK>(a.keys + begin, a.values + begin, n, smem);
+  });
+}
+
+template <bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_mid_wide_kernel(SegmentedWideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  ForEachListedSegment<false>(a, kSegWideSmallMax, kSegWideMidMax, [&](uint32_t begin, uint32_t n) {
+    SortInWorkgroupWide<1024, (int)(kSegWideMidMax / 1024u), ATOMIC_RANK>(a.keys + begin, a.values + begin, n, smem);
+  });
+}
+
+// One large segment in one workgroup: the shape of SegmentLsd64 with the planes (key, value low, value high).  One read of
+// the KEYS alone builds the four byte histograms; a pass whose byte is the same in every key is skipped; the others walk the
+// segment in tiles of kSegWideLargeTile elements, in order, ping-ponging between the caller's range and the same index range
+// of the two scratch arrays; an odd number of passes ends with a copy back, and with no pass to run nothing is written.
+// LDS: SegmentWideLargeLdsWords (vrdx_kernels.h).
+static_assert(4 * 256 * kSegHistCopies <= 3 * kSegWideLargeTile, "the histogram replicas alias the staging planes");
+
+template <bool ATOMIC_RANK>
+__device__ __forceinline__ void SegmentLsdWide(uint32_t* keys, uint64_t* values, uint32_t* keysScratch, uint64_t* valuesScratch,
+                                               uint32_t n, uint32_t* smem) {
+  constexpr int THREADS = 1024, KPT = (int)(kSegWideLargeTile / 1024u), WAVES = THREADS / 64;
+  constexpr uint32_t TILE = kSegWideLargeTile;
+  uint32_t* const stagedKeys = smem;
+  uint32_t* const stagedLo = smem + TILE;
+  uint32_t* const stagedHi = smem + 2 * TILE;
+  uint32_t* const waveHist = smem + 3 * TILE;
+  uint32_t* const scanScratch = waveHist + WAVES * 256;  // 32 (16 used: one round of the table scan)
+  uint32_t* const bases = scanScratch + 32;      // [pass][digit]: where the next key of digit d goes, this pass
+  uint32_t* const tileStart = bases + 4 * 256;   // tile-local position of digit d's first key
+  uint32_t* const tileCount = tileStart + 256;
+  uint32_t* const misc = tileCount + 256;        // [0]: bit p = pass p is not trivial
+  uint32_t* const bins = smem;                   // [pass][digit][copy], before the passes (aliases the staging planes)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // 1. histograms
+  for (uint32_t i = tid; i < 4 * 256 * kSegHistCopies; i += THREADS) bins[i] = 0;
+  if (tid == 0) misc[0] = 0;
+  LdsBarrier();
+  const uint32_t copy = tid & (kSegHistCopies - 1);
+  auto count = [&](uint32_t key) {
+#pragma unroll
+    for (uint32_t p = 0; p < 4; ++p) atomicAdd(&bins[(p * 256 + ((key >> (8 * p)) & 0xFFu)) * kSegHistCopies + copy], 1u);
+  };
+  {
+    constexpr uint32_t U = 4;  // loads in flight per lane
+    uint32_t i = tid;
+    for (; i + (U - 1) * THREADS < n; i += U * THREADS) {
+      uint32_t k[U];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) k[u] = keys[i + u * THREADS];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) count(k[u]);
+    }
+    for (; i < n; i += THREADS) count(keys[i]);
+  }
+  LdsBarrier();
+  {
+    // thread t: pass t / 256, digit t % 256 -- the exclusive scan over the 256 digits of each pass (four waves per pass)
+    const uint32_t p = (uint32_t)tid >> 8, d = (uint32_t)tid & 255u;
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kSegHistCopies; ++r) c += bins[(p * 256 + d) * kSegHistCopies + ((r + tid) & (kSegHistCopies - 1))];
+    const uint32_t x = WaveInclusiveScan(c);
+    if (lane == 63) scanScratch[wave] = x;
+    if (c != 0 && c != n) atomicOr(&misc[0], 1u << p);  // two digits at least: the pass moves keys
+    LdsBarrier();
+    uint32_t add = 0;
+    for (int v = wave & ~3; v < wave; ++v) add += scanScratch[v];
+    bases[p * 256 + d] = x - c + add;
+  }
+  LdsBarrier();
+  const uint32_t active = (uint32_t)__builtin_amdgcn_readfirstlane((int)misc[0]);
+
+  // 2. the passes
+  uint32_t* src = keys;
+  uint32_t* dst = keysScratch;
+  uint64_t* srcV = values;
+  uint64_t* dstV = valuesScratch;
+  uint32_t* const myHist = waveHist + wave * 256;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+#pragma unroll 1
+  for (uint32_t pass = 0; pass < 4; ++pass) {
+    if (((active >> pass) & 1u) == 0) continue;  // uniform
+    const uint32_t shift = 8 * pass;
+    uint32_t* const base = bases + pass * 256;
+#pragma unroll 1
+    for (uint32_t t0 = 0; t0 < n; t0 += TILE) {
+      const uint32_t m = min(TILE, n - t0);
+      // the chunks of four 64-key slots dealt out evenly over the waves, as in SortInWorkgroup: pads (the largest key) only
+      // in the last chunk, behind every real key of the tile
+      const uint32_t chunks = (m + 255u) / 256u;
+      const uint32_t per = chunks / WAVES, extra = chunks % WAVES;
+      const uint32_t slots = 4u * (per + (w < extra ? 1u : 0u));
+      const uint32_t first = 256u * (w * per + (w < extra ? w : extra)) + lane;
+      uint32_t key[KPT], lo[KPT], hi[KPT];
+      LoadStriped<KPT, false, true>(src + t0, first, m, false, 0xFFFFFFFFu, key, slots);
+      LoadStriped64<KPT>(srcV + t0, first, m, lo, hi, slots);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;
+      uint32_t rank[KPT];
+      if constexpr (ATOMIC_RANK)
+        RankAtomic<KPT, false, true>(key, shift, myHist, lane, rank, slots);
+      else
+        RankBallot<KPT, false, true>(key, shift, myHist, lane, rank, slots);
+      LdsBarrier();
+      uint32_t c = 0;
+      if (tid < 256) {
+#pragma unroll
+        for (int v = 0; v < WAVES; ++v) c += waveHist[v * 256 + tid];
+      }
+      const uint32_t exclusive = BlockExclusiveScan256(tid < 256 ? c : 0u, scanScratch, tid);
+      if (tid < 256) {
+        uint32_t run = exclusive;
+#pragma unroll
+        for (int v = 0; v < WAVES; ++v) {
+          const uint32_t h = waveHist[v * 256 + tid];
+          waveHist[v * 256 + tid] = run;
+          run += h;
+        }
+        tileStart[tid] = exclusive;
+        tileCount[tid] = tid == 255 ? c - (256u * chunks - m) : c;  // (the pads are digit 255's last keys)
+      }
+      LdsBarrier();
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        if (i % 4 == 0 && (uint32_t)i >= slots) break;
+        const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[(key[i] >> shift) & 0xFFu]);
+        stagedKeys[slot] = key[i];
+        stagedLo[slot] = lo[i];
+        stagedHi[slot] = hi[i];
+      }
+      LdsBarrier();
+      // sorted position q of the tile -> base[d] + q - tileStart[d]: runs of one digit land contiguously
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        if (i % 4 == 0 && (uint32_t)i >= slots) break;
+        const uint32_t q = first + 64 * i;
+        if (q < m) {
+          const uint32_t slot = StagingSlot<TILE>(q);
+          const uint32_t k = stagedKeys[slot];
+          const uint32_t d = (k >> shift) & 0xFFu;
+          const uint32_t to = base[d] + q - tileStart[d];
+          // always < n while the segment is this workgroup's alone; segments that overlap (offsets that are not monotone,
+          // flagged by the small kernel) may change keys under the counts, and must still never write outside the range
+          if (to < n) {
+            dst[to] = k;
+            dstV[to] = (uint64_t)stagedHi[slot] << 32 | stagedLo[slot];
+          }
+        }
+      }
+      LdsBarrier();  // every lane has read base[] and tileStart[] of this tile
+      if (tid < 256) base[tid] += tileCount[tid];
+      // (the next tile reads base[] two barriers later, and writes the staging planes and tileStart[] one barrier later)
+    }
+    __syncthreads();  // this pass's stores are complete before the next pass (or the copy back) reads them
+    uint32_t* const t = src;
+    src = dst;
+    dst = t;
+    uint64_t* const tv = srcV;
+    srcV = dstV;
+    dstV = tv;
+  }
+
+  // 3. an odd number of passes left the result in the scratch range
+  if (src != keys) {
+    for (uint32_t i = tid; i < n; i += THREADS) {
+      keys[i] = src[i];
+      values[i] = srcV[i];
+    }
+  }
+}
+
+template <bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_large_wide_kernel(SegmentedWideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  ForEachListedSegment<true>(a, kSegWideMidMax, ~0u, [&](uint32_t begin, uint32_t n) {
+    SegmentLsdWide<ATOMIC_RANK>(a.keys + begin, a.values + begin, a.keysScratch + begin, a.valuesScratch + begin, n, smem);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs
 // ---------------------------------------------------------------------------------------------
 #include "vrdx_launch.inc"

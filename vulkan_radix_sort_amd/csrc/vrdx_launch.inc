@@ -385,7 +385,20 @@
   X(kSplitWide, (&split_wide_kernel), kSort64Threads, 0, \
     "_ZN4vrdx17split_wide_kernelEPKjPKmPjS4_S4_jS1_") \
   X(kMergeWide, (&merge_wide_kernel), kSort64Threads, 0, \
-    "_ZN4vrdx17merge_wide_kernelEPmPKjS2_jS2_")
+    "_ZN4vrdx17merge_wide_kernelEPmPKjS2_jS2_") \
+  /* ---- vrdxHipCmdWideValueSortSegmented: segmented_small_wide / mid_wide / large_wide_kernel [atomic rank] ---- */ \
+  X(kSegmentedWideSmall, (&segmented_small_wide_kernel<false>), 256, SortInWorkgroup64LdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx27segmented_small_wide_kernelILb0EEEvNS_17SegmentedWideArgsE") \
+  X(kSegmentedWideSmallA, (&segmented_small_wide_kernel<true>), 256, SortInWorkgroup64LdsWords(256, 16, true) * 4, \
+    "_ZN4vrdx27segmented_small_wide_kernelILb1EEEvNS_17SegmentedWideArgsE") \
+  X(kSegmentedWideMid, (&segmented_mid_wide_kernel<false>), 1024, SortInWorkgroup64LdsWords(1024, 8, true) * 4, \
+    "_ZN4vrdx25segmented_mid_wide_kernelILb0EEEvNS_17SegmentedWideArgsE") \
+  X(kSegmentedWideMidA, (&segmented_mid_wide_kernel<true>), 1024, SortInWorkgroup64LdsWords(1024, 8, true) * 4, \
+    "_ZN4vrdx25segmented_mid_wide_kernelILb1EEEvNS_17SegmentedWideArgsE") \
+  X(kSegmentedWideLarge, (&segmented_large_wide_kernel<false>), 1024, SegmentWideLargeLdsWords() * 4, \
+    "_ZN4vrdx27segmented_large_wide_kernelILb0EEEvNS_17SegmentedWideArgsE") \
+  X(kSegmentedWideLargeA, (&segmented_large_wide_kernel<true>), 1024, SegmentWideLargeLdsWords() * 4, \
+    "_ZN4vrdx27segmented_large_wide_kernelILb1EEEvNS_17SegmentedWideArgsE")
 #define VRDX_ALL_KERNELS(X) VRDX_KERNELS(X) VRDX_ORDERED32_KERNELS(X) VRDX_WIDE_VALUE_KERNELS(X)
 
 enum KernelId : int {
@@ -702,4 +715,23 @@ hipError_t LaunchMergeWide(hipStream_t stream, uint64_t* values, const uint32_t*
                            const uint32_t* countPtr) {
   if (!Sort64Fits(maxCount)) return hipErrorInvalidValue;
   return Launch(kMergeWide, Sort64Grid(maxCount), stream, values, lo, hi, maxCount, countPtr);
+}
+
+// ---- segmented sort of 32-bit keys with 64-bit values ---------------------------------------------------
+static_assert(kSegWideSmallMax == 256u * 16u && kSegWideMidMax == 1024u * 8u && kSegWideLargeTile == 1024u * 8u &&
+                  SegmentWideLargeLdsWords() * 4 <= 160u * 1024u,
+              "the segmented wide-value kernels' forms and the large kernel's LDS");
+hipError_t LaunchSegmentedClear(hipStream_t stream, const SegmentedWideArgs& args) {
+  // segmented_clear_kernel reads the failure word and the two counters only
+  SegmentedArgs clear = {};
+  clear.midCount = args.midCount;
+  clear.largeCount = args.largeCount;
+  clear.failure = args.failure;
+  return Launch(kSegmentedClear, 1, stream, clear);
+}
+
+hipError_t LaunchSegmentedWide(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool atomicRank,
+                               const SegmentedWideArgs& args) {
+  if (grid == 0) return hipErrorInvalidValue;
+  return Launch(KernelId(kSegmentedWideSmall + 2 * sizeClass + atomicRank), grid, stream, args);
 }

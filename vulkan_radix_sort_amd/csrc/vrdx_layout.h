@@ -291,6 +291,29 @@ static inline SegmentedLayout MakeSegmented64Layout(uint32_t maxElementCount, ui
   return s;
 }
 
+// The segmented wide-value sort's carving of the wide-value storage (vrdxHipCmdWideValueSortSegmented;
+// PlanWideValueSortSegmented in vrdx_plan.h): header, list counters and lists where MakeSegmentedLayout keeps them -- inside
+// the inner 32-bit key+value storage -- and the scratch arrays where MakeWideValueLayout keeps its word arrays, behind it:
+//   [0, 16)                        header words 0-3
+//   midCountOffset, largeCountOffset, midListOffset, largeListOffset   as in MakeSegmentedLayout; the large list holds
+//                                  N / 8193 ids: a large segment has more than 8192 elements (vrdx_kernels.h)
+//   keysScratchOffset = aOffset    uint32[N] on a 128-byte line
+//   valuesScratchOffset = tOffset  uint64[N] on a 128-byte line, over B and C together: aOffset <= innerSize + 128 - align and
+//                                  Align(4 N, 128) <= 4 N + 124, so it ends at most at innerSize + 12 N + 252 - align <=
+//                                  MakeWideValueLayout(N).size at every address
+static inline SegmentedLayout MakeSegmentedWideLayout(uint32_t maxElementCount, uint32_t align, uint64_t storageAddress = 0) {
+  const StorageLayout l = MakeLayout(maxElementCount, align, 0, storageAddress);
+  const WideValueLayout w = MakeWideValueLayout(maxElementCount, align, storageAddress);
+  SegmentedLayout s;
+  const uint64_t listsEnd = PlaceSegmentLists(s, l, maxElementCount, 1024u * 8u + 1u);
+  s.keysScratchOffset = w.aOffset;
+  s.valuesScratchOffset = w.tOffset;
+  const uint64_t keysEnd = s.keysScratchOffset + (uint64_t)maxElementCount * sizeof(uint32_t);
+  const uint64_t valuesEnd = s.valuesScratchOffset + (uint64_t)maxElementCount * sizeof(uint64_t);
+  s.fits = listsEnd <= w.innerSize && keysEnd <= s.valuesScratchOffset && valuesEnd <= w.size;
+  return s;
+}
+
 // The MSD plan's scatter (msd_scatter_or_pass0_kernel, one workgroup per CU and tile) cuts the sort into EQUAL tiles that fill whole
 // rounds of `cus` tiles: keys per tile, a multiple of 4096 (four 64-key slots per wave of its 1024 threads), at most 32768.
 // 520 tiles of 32768 keys would cost three rounds, the third for eight tiles; 768 tiles of 24576 cost three rounds of three

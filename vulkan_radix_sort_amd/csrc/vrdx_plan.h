@@ -554,6 +554,43 @@ static inline WideValuePlan PlanWideValueSort(const PlanContext& c, uint32_t ele
   return p;
 }
 
+// ---- segmented sort of 32-bit keys with 64-bit values (vrdxHipCmdWideValueSortSegmented) ----
+// Its own plan function, in the shape of PlanSegmentedSort (whose steps it lists: a fill, then segmented_small_wide /
+// mid_wide / large_wide_kernel, slots 1 ... 4) on the wide-value storage carved by MakeSegmentedWideLayout.  Nothing is
+// decided from the data: grids depend on segmentCount, maxElementCount and the CU count only, so a captured call replays on
+// any segmentation with the same segmentCount.  A launch whose grid would be 0 is absent; its slot coincides with the one
+// before.  No order word, no bit range: the keys are uint32, whole.
+struct WideValueSegmentedPlan {
+  bool atomicRank = false;
+  const char* refusal = nullptr;  // non-null: refused (no step), and why
+  SegmentedLayout layout{};
+  SegmentedSortStep steps[4];     // none: refused, or empty (no elements, no segments)
+  uint32_t stepCount = 0;
+};
+
+static inline WideValueSegmentedPlan PlanWideValueSortSegmented(const PlanContext& c, uint32_t maxElementCount,
+                                                                uint32_t segmentCount, uint64_t storageAddress) {
+  static constexpr const char* kNames[4] = {"segmented_clear_kernel", "segmented_small_wide_kernel",
+                                            "segmented_mid_wide_kernel", "segmented_large_wide_kernel"};
+  WideValueSegmentedPlan p;
+  p.atomicRank = c.atomicRank;  // one answer for the whole sort
+  p.layout = MakeSegmentedWideLayout(maxElementCount, c.minStorageBufferOffsetAlignment, storageAddress);
+  if (segmentCount == 0 || maxElementCount == 0) return p;
+  if (!p.layout.fits) {  // (cannot happen for N >= 1: the layout fits every count)
+    p.refusal = "segmented wide-value storage layout";
+    return p;
+  }
+  // one workgroup per segment up to 2^20 of them (a grid-stride loop beyond); the other two launches take their lists by grid
+  // stride with at most as many workgroups as can be resident: one per CU (112 and 118 KiB of LDS)
+  const uint32_t resident = (uint32_t)c.computeUnits;
+  const uint32_t grids[4] = {1u, std::min<uint32_t>(segmentCount, 1u << 20),
+                             std::min<uint32_t>(std::min<uint32_t>(segmentCount, p.layout.midCap), resident),
+                             std::min<uint32_t>(std::min<uint32_t>(segmentCount, p.layout.largeCap), resident)};
+  for (uint32_t i = 0; i < 4; ++i)
+    if (grids[i] != 0) p.steps[p.stepCount++] = SegmentedSortStep{SegmentedStep(i), (uint8_t)(i + 1), kNames[i], grids[i]};
+  return p;
+}
+
 // Grid of the fused histogram.  Every workgroup ends with up to 1024 global atomics on the same 1024 words, so few, long-lived
 // workgroups win for large inputs: one per CU and at least two groups of 16384 keys each (tools/hist_grid.sh, removed, last at
 // commit 3645810: 17.4 us with 256 workgroups against 21.1 us with 512 at N = 2^23; equal at 2^25).  Small inputs want the
