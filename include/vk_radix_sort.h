@@ -454,7 +454,8 @@ void vrdxHipCmdSortSegmented64OrderedKeyValue(VkCommandBuffer commandBuffer, Vrd
  * range (the last one of the bits that are left) -- up to 16384 elements (maxElementCount for the indirect forms).  A call
  * with more elements and a range other than [0, 32) is REFUSED like an invalid range: the timestamps are recorded, nothing
  * else is touched, VRDX_HIP_STATUS_ENQUEUE_REFUSED is raised.  vrdxHipDescribeSortBitsPlan reports ONE_WORKGROUP (8 / 16 bytes
- * per element) for what is sorted and VRDX_HIP_PLAN_NONE for what is refused.
+ * per element) for what is sorted and VRDX_HIP_PLAN_NONE for what is refused.  Range sorts ignore VRDX_SMALL_SORT and
+ * VRDX_TILE_CONFIG: size alone decides; only the range [0, 32), which is the whole-key sort, follows them.
  * Timestamps: the 15-slot contract as for ONE_WORKGROUP above.
  *
  * Out of scope: range sorts of more than 16384 elements (the range forms of the histogram and pass kernels are not part of

@@ -9,12 +9,18 @@
 //   plan_check describe <cus> <atomic> <n>...   one line per (n, key+value): n, 0 | 1, the plan's name (those of
 //                                           vulkan_radix_sort_amd/api.py, PLAN_NAMES), its bits, hybridCap, msdCap, launches and
 //                                           tile geometry -- what the Python tests hold their hand-kept numbers to.
+//   plan_check describe <cus> <atomic> NAME=VALUE... <n>...   the same under planning knobs, spelled as in the environment
+//                                           (VRDX_SMALL_SORT=0, VRDX_HYBRID=0, VRDX_MSD=0, VRDX_BLOCK_SUMS=0, VRDX_TILE_CONFIG=1024x8
+//                                           ...; read as EnvKnobs of vrdx_api.cpp reads them), with three more fields per line:
+//                                           the plan's name of a sort by the bits [8, 16), the form of the wide-value sort
+//                                           (api.py, WIDE_VALUE_FORM_NAMES) and its oneWorkgroupMax.
 // Built by tests/native/Makefile; nothing of HIP is linked (vrdx_kernels.h needs one of its headers).
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <iterator>
+#include <string>
 #include <string_view>
 #include <vector>
 
@@ -52,15 +58,58 @@ const char* PlanName(uint32_t plan) {
   }
 }
 
+// one knob as the environment spells it; what EnvKnobs (vrdx_api.cpp) makes of it
+bool SetKnob(vrdx::PlanContext& c, std::string_view knob) {
+  const size_t eq = knob.find('=');
+  const std::string_view name = knob.substr(0, eq), value = knob.substr(eq + 1);
+  const bool off = !value.empty() && value[0] == '0';
+  if (name == "VRDX_SMALL_SORT") c.smallSort = !off;
+  else if (name == "VRDX_HYBRID") c.hybrid = !off;
+  else if (name == "VRDX_MSD") c.msd = !off;
+  else if (name == "VRDX_BLOCK_SUMS") c.blockSums = std::atoi(std::string(value).c_str()) != 0;
+  else if (name == "VRDX_TILE_CONFIG") {
+    c.forcedConfig = -1;
+    for (int i = 0; i < vrdx::kNumTileConfigs; ++i) {
+      char config[32];
+      vrdx::ConfigName(vrdx::kTileConfigs[i], config, sizeof(config));
+      if (value == config) c.forcedConfig = i;
+    }
+    return c.forcedConfig >= 0;
+  } else
+    return false;
+  return true;
+}
+
+const char* WideFormName(vrdx::WideValueForm form) {
+  switch (form) {
+    case vrdx::WideValueForm::kOneWorkgroup: return "one-workgroup";
+    case vrdx::WideValueForm::kGather: return "gather";
+    case vrdx::WideValueForm::kTwoSorts: return "two-sorts";
+    default: return "none";
+  }
+}
+
 int Describe(int argc, char** argv) {
-  if (argc < 5) {
-    std::fprintf(stderr, "usage: plan_check describe <cus> <atomic: 0 | 1> <n>...\n");
+  vrdx::PlanContext c;
+  int first = 4;
+  bool knobs = false;
+  if (argc >= 5) {
+    c.computeUnits = std::atoi(argv[2]);
+    c.atomicRank = std::atoi(argv[3]) != 0;
+    for (; first < argc && std::string_view(argv[first]).find('=') != std::string_view::npos; ++first) {
+      knobs = true;
+      if (!SetKnob(c, argv[first])) {
+        std::fprintf(stderr, "plan_check describe: unknown knob '%s'\n", argv[first]);
+        return 2;
+      }
+    }
+    c.msd = c.msd && c.hybrid;  // (VRDX_HYBRID=0 switches the MSD plan off as well)
+  }
+  if (first >= argc) {
+    std::fprintf(stderr, "usage: plan_check describe <cus> <atomic: 0 | 1> [NAME=VALUE]... <n>...\n");
     return 2;
   }
-  vrdx::PlanContext c;
-  c.computeUnits = std::atoi(argv[2]);
-  c.atomicRank = std::atoi(argv[3]) != 0;
-  for (int i = 4; i < argc; ++i) {
+  for (int i = first; i < argc; ++i) {
     const uint32_t n = (uint32_t)std::strtoul(argv[i], nullptr, 10);
     for (int keyValue = 0; keyValue < 2; ++keyValue) {
       const vrdx::SortPlan p = vrdx::PlanSort(c, keyValue != 0, n, 0);  // (address 0, like vrdxHipDescribePlan)
@@ -68,8 +117,18 @@ int Describe(int argc, char** argv) {
       if (n != 0) vrdx::DescribePlan(p, &info);
       char config[32] = "-";
       if (p.stepCount > 1) vrdx::ConfigName(vrdx::kTileConfigs[p.configIndex], config, sizeof(config));
-      std::printf("%u %d %s %u %u %u %u %s\n", n, keyValue, PlanName(info.plan), info.bits, p.hybridCap, p.msdBits != 0 ? p.msdCap : 0u,
+      std::printf("%u %d %s %u %u %u %u %s", n, keyValue, PlanName(info.plan), info.bits, p.hybridCap, p.msdBits != 0 ? p.msdCap : 0u,
                   info.launches, config);
+      if (knobs) {
+        const vrdx::SortPlan ranged = vrdx::PlanSortBits(c, keyValue != 0, n, 8, 16, 0);
+        VrdxHipPlanInfo rangedInfo = {};
+        if (ranged.stepCount != 0) vrdx::DescribePlan(ranged, &rangedInfo);  // (as vrdxHipDescribeSortBitsPlan)
+        VrdxHipWideValuePlanInfo wide = {};
+        const vrdx::WideValuePlan w = vrdx::PlanWideValueSort(c, n, 0);
+        vrdx::DescribeWideValuePlan(c, w, &wide);
+        std::printf(" %s %s %u", PlanName(rangedInfo.plan), WideFormName(w.form), wide.oneWorkgroupMax);
+      }
+      std::printf("\n");
     }
   }
   return 0;

@@ -4,6 +4,10 @@
 //   up to 16384 elements one step, small_sort_bits_kernel at slot 14, one launch, 8 / 16 bytes per element, a layout that fits;
 //   beyond: no step and fits == false (range sorts beyond one workgroup are refused);
 //   no hybrid or MSD step anywhere; (0, 32) equals PlanSort; empty and invalid ranges have no step.
+// All of it under every planning knob that sends PlanSort down the general path at small sizes -- smallSort on and off times
+// forcedConfig -1, 0 ... 3: a range over part of the key is planned by size alone, the plan being PlanSort's under the default
+// knobs field by field (a range sort has no general-path form for a knob to select), and (0, 32) follows the knobs as PlanSort
+// does.
 // Prints one line per size, ranking and value mode: `plan <n> <atomic: 0 | 1> <key+value: 0 | 1> <one-workgroup | refused>`.
 // Nothing of HIP is linked (vrdx_kernels.h needs one of its headers).
 #include <cstdint>
@@ -44,47 +48,61 @@ int main(int argc, char** argv) {
   for (uint32_t n : sizes)
     for (int atomic = 1; atomic >= 0; --atomic)
       for (int keyValue = 0; keyValue < 2; ++keyValue) {
-        vrdx::PlanContext c;
-        c.computeUnits = 256;
-        c.atomicRank = atomic != 0;
         const bool kv = keyValue != 0;
         char geometry[64] = "";
-        for (uint32_t b = 0; b <= 32; ++b)
-          for (uint32_t e = b; e <= 33; ++e) {
-            const vrdx::SortPlan p = vrdx::PlanSortBits(c, kv, n, b, e, 0);
-            ++cases;
-            if (e == b || e > 32) {  // the empty range records nothing and is fine; the invalid one is refused
-              if (p.stepCount != 0 || p.launches != 0 || p.fits != (e <= 32)) Fail("empty or invalid range", n, atomic, keyValue, b, e);
-              continue;
-            }
-            if (b == 0 && e == 32) {
-              if (!SamePlan(p, vrdx::PlanSort(c, kv, n, 0)) || p.rangeWidth != 0) Fail("(0, 32) is not PlanSort", n, atomic, keyValue, b, e);
-              VrdxHipPlanInfo whole = {}, ranged = {};
-              vrdx::DescribePlan(vrdx::PlanSort(c, kv, n, 0), &whole);
-              vrdx::DescribePlan(p, &ranged);
-              if (std::memcmp(&whole, &ranged, sizeof(whole)) != 0) Fail("(0, 32) described", n, atomic, keyValue, b, e);
-              continue;
-            }
-            const uint32_t width = e - b;
-            bool ok = p.hybridCap == 0 && p.msdBits == 0 && p.atomicRank == c.atomicRank && p.keyValue == kv && p.elementCount == n;
-            VrdxHipPlanInfo info = {};
-            char now[64];
-            if (n <= vrdx::kSmallSortMaxElements) {
-              vrdx::DescribePlan(p, &info);
-              ok = ok && p.fits && p.rangeBegin == b && p.rangeWidth == width && p.oneWorkgroup && p.stepCount == 1 && p.launches == 1 &&
-                   p.steps[0].what == vrdx::Step::kSmallSortBits && p.steps[0].slot == 14 && p.steps[0].name != nullptr &&
-                   info.plan == VRDX_HIP_PLAN_ONE_WORKGROUP && info.bits == 0 && info.launches == 1 &&
-                   info.bytesPerElement == (kv ? 16u : 8u) && info.fallbackBytesPerElement == info.bytesPerElement &&
-                   vrdx::LayoutFits(p.layout, n);
-              std::snprintf(now, sizeof(now), "one-workgroup");
-            } else {
-              ok = ok && !p.fits && p.stepCount == 0 && p.launches == 0 && !p.oneWorkgroup;
-              std::snprintf(now, sizeof(now), "refused");
-            }
-            if (!ok) Fail("range plan", n, atomic, keyValue, b, e);
-            // one answer per (n, ranking, value mode), whatever the range
-            if (geometry[0] == 0) std::snprintf(geometry, sizeof(geometry), "%s", now);
-            if (std::strcmp(geometry, now) != 0) Fail("the plan depends on the range", n, atomic, keyValue, b, e);
+        for (int smallSort = 1; smallSort >= 0; --smallSort)
+          for (int forced = -1; forced < vrdx::kNumTileConfigs; ++forced) {
+            vrdx::PlanContext c, defaults;
+            c.computeUnits = defaults.computeUnits = 256;
+            c.atomicRank = defaults.atomicRank = atomic != 0;
+            c.smallSort = smallSort != 0;
+            c.forcedConfig = forced;
+            for (uint32_t b = 0; b <= 32; ++b)
+              for (uint32_t e = b; e <= 33; ++e) {
+                const vrdx::SortPlan p = vrdx::PlanSortBits(c, kv, n, b, e, 0);
+                ++cases;
+                if (e == b || e > 32) {  // the empty range records nothing and is fine; the invalid one is refused
+                  if (p.stepCount != 0 || p.launches != 0 || p.fits != (e <= 32)) Fail("empty or invalid range", n, atomic, keyValue, b, e);
+                  continue;
+                }
+                if (b == 0 && e == 32) {  // the whole key: PlanSort under the same knobs
+                  const vrdx::SortPlan sort = vrdx::PlanSort(c, kv, n, 0);
+                  if (!SamePlan(p, sort) || p.rangeWidth != 0) Fail("(0, 32) is not PlanSort", n, atomic, keyValue, b, e);
+                  if (n != 0 && n <= vrdx::kSmallSortMaxElements && sort.oneWorkgroup != (smallSort != 0 && forced < 0))
+                    Fail("(0, 32) does not follow the knobs", n, atomic, keyValue, b, e);
+                  VrdxHipPlanInfo whole = {}, ranged = {};
+                  vrdx::DescribePlan(sort, &whole);
+                  vrdx::DescribePlan(p, &ranged);
+                  if (std::memcmp(&whole, &ranged, sizeof(whole)) != 0) Fail("(0, 32) described", n, atomic, keyValue, b, e);
+                  continue;
+                }
+                const uint32_t width = e - b;
+                bool ok = p.hybridCap == 0 && p.msdBits == 0 && p.atomicRank == c.atomicRank && p.keyValue == kv && p.elementCount == n;
+                VrdxHipPlanInfo info = {};
+                char now[64];
+                if (n <= vrdx::kSmallSortMaxElements) {
+                  vrdx::DescribePlan(p, &info);
+                  ok = ok && p.fits && p.rangeBegin == b && p.rangeWidth == width && p.oneWorkgroup && p.stepCount == 1 && p.launches == 1 &&
+                       p.steps[0].what == vrdx::Step::kSmallSortBits && p.steps[0].slot == 14 && p.steps[0].name != nullptr &&
+                       info.plan == VRDX_HIP_PLAN_ONE_WORKGROUP && info.bits == 0 && info.launches == 1 &&
+                       info.bytesPerElement == (kv ? 16u : 8u) && info.fallbackBytesPerElement == info.bytesPerElement &&
+                       vrdx::LayoutFits(p.layout, n);
+                  // the knobs play no part: but for the range and its one step, PlanSort's plan under the default knobs
+                  vrdx::SortPlan whole = vrdx::PlanSort(defaults, kv, n, 0), same = p;
+                  same.rangeBegin = same.rangeWidth = 0;
+                  ok = ok && whole.oneWorkgroup && whole.stepCount == 1 && whole.steps[0].what == vrdx::Step::kSmallSort;
+                  same.steps[0].what = vrdx::Step::kSmallSort;
+                  ok = ok && SamePlan(same, whole);
+                  std::snprintf(now, sizeof(now), "one-workgroup");
+                } else {
+                  ok = ok && !p.fits && p.refusal != nullptr && p.stepCount == 0 && p.launches == 0 && !p.oneWorkgroup;
+                  std::snprintf(now, sizeof(now), "refused");
+                }
+                if (!ok) Fail("range plan", n, atomic, keyValue, b, e);
+                // one answer per (n, ranking, value mode), whatever the range and whatever the knobs
+                if (geometry[0] == 0) std::snprintf(geometry, sizeof(geometry), "%s", now);
+                if (std::strcmp(geometry, now) != 0) Fail("the plan depends on the range or on a knob", n, atomic, keyValue, b, e);
+              }
           }
         std::printf("plan %u %d %d %s\n", n, atomic, keyValue, geometry);
       }

@@ -15,7 +15,7 @@ TWINS = {call.facts[1:4]: call for call in api.RECORDING_CALLS if call.facts[0] 
 
 def ordered_call(torch, sorter, keys, values=None, *, order, offsets=None, count=None, device_count=None, keys_off=0,
                  values_off=0, offsets_off=0, indirect_off=0, storage_off=0, storage=None, pool=None, expect_status=0,
-                 expect_refused=False, twin=False, keep_before=False):
+                 expect_refused=False, twin=False, keep_before=False, device="cuda"):
     """keys: uint32, the FULL host array; count: elementCount / maxElementCount (default: all of keys), which also sizes the
     storage requirement; offsets: the segmented calls; device_count: the indirect calls.  The checks are guarded_call's: the
     guard bytes around keys, values, count word and offsets, the bytes in front of the storage offset and behind the
@@ -25,20 +25,21 @@ def ordered_call(torch, sorter, keys, values=None, *, order, offsets=None, count
     facts = (offsets is not None, device_count is not None, values is not None)
     call = (TWINS if twin else ROWS)[facts]
     count = len(keys) if count is None else count
-    stream = torch.cuda.current_stream().cuda_stream
-    dk = to_device(torch, keys, FRONT + keys_off, TAIL)
+    on_gpu = torch.device(device).type == "cuda"   # (anything else: a sorter that works on host memory, stream 0)
+    stream = torch.cuda.current_stream().cuda_stream if on_gpu else 0
+    dk = to_device(torch, keys, FRONT + keys_off, TAIL, device)
     dv = do = dc = None
     if values is not None:
-        dv = to_device(torch, np.asarray(values).astype(np.uint32), FRONT + values_off, TAIL)
+        dv = to_device(torch, np.asarray(values).astype(np.uint32), FRONT + values_off, TAIL, device)
     if offsets is not None:
         offsets = np.asarray(offsets).astype(np.uint32)
-        do = to_device(torch, offsets, FRONT + offsets_off, NEIGHBOURS)
+        do = to_device(torch, offsets, FRONT + offsets_off, NEIGHBOURS, device)
     if device_count is not None:
-        dc = to_device(torch, np.array([device_count], np.uint32), FRONT + indirect_off, NEIGHBOURS)
+        dc = to_device(torch, np.array([device_count], np.uint32), FRONT + indirect_off, NEIGHBOURS, device)
     req = sorter.key_value_storage_requirements(count) if values is not None else sorter.storage_requirements(count)
     end = storage_off + req.size
     if storage is None:
-        storage = poisoned_storage(torch, req.size, storage_off)
+        storage = poisoned_storage(torch, req.size, storage_off, device=device)
     assert storage.data_ptr() % 16 == 0 and storage_off % 16 == 0
     before = storage.clone() if keep_before or expect_refused else None
     front, behind = storage[:storage_off].clone(), storage[end:].clone()
@@ -49,7 +50,8 @@ def ordered_call(torch, sorter, keys, values=None, *, order, offsets=None, count
     for name, t in (("keys", dk), ("values", dv), ("offsets", do), ("indirect", dc)):
         given[name], given[name + "_offset"] = address(t) if t is not None else (None, None)
     getattr(sorter, call.method)(*(given[name] for name, _ in call.parameters))
-    torch.cuda.synchronize()
+    if on_gpu:
+        torch.cuda.synchronize()
 
     if expect_refused:
         assert sorter.read_sorter_status(stream) == api.STATUS_ENQUEUE_REFUSED, "a call that must be refused was not"

@@ -18,6 +18,8 @@ BALLOT_TABLE = [(16_384, "one-workgroup", 0, 0, 0, 1), (524_288, "hybrid-8", 8, 
 FOUR_PASSES = ("four-passes", 0, 0, 0, 5)
 
 Row = collections.namedtuple("Row", "name bits hybrid_cap msd_cap launches config")
+# ... and under knobs: the plan of a sort by the bits [8, 16), the form of the wide-value sort, its oneWorkgroupMax
+KnobRow = collections.namedtuple("KnobRow", Row._fields + ("bits_plan", "wide_form", "wide_one_workgroup_max"))
 
 
 @functools.lru_cache(maxsize=1)
@@ -26,15 +28,23 @@ def executable():
     return os.path.join(NATIVE, "plan_check")
 
 
-def describe(compute_units, atomic_rank, sizes):
-    """{(n, key_value): Row} of the plan the host records for each size, keys-only and key+value"""
+def describe(compute_units, atomic_rank, sizes, knobs=None):
+    """{(n, key_value): Row} of the plan the host records for each size, keys-only and key+value.  knobs: the planning knobs
+    as the environment spells them ({"VRDX_SMALL_SORT": "0"}, tests/knob_cases.py SETTINGS; VRDX_RANK is not one: the ranking
+    is `atomic_rank`); with them -- an empty dict included -- every row is a KnobRow."""
     sizes = sorted(set(int(n) for n in sizes))
-    out = subprocess.run([executable(), "describe", str(compute_units), "1" if atomic_rank else "0"] + [str(n) for n in sizes],
-                         check=True, capture_output=True, text=True).stdout
+    spelled = []
+    if knobs is not None:   # (the default spelled out: what turns on the three fields of a KnobRow)
+        spelled = [f"{name}={value}" for name, value in sorted(knobs.items()) if name != "VRDX_RANK"] or ["VRDX_SMALL_SORT=1"]
+    out = subprocess.run([executable(), "describe", str(compute_units), "1" if atomic_rank else "0"] + spelled
+                         + [str(n) for n in sizes], check=True, capture_output=True, text=True).stdout
     table = {}
     for line in out.splitlines():
-        n, key_value, name, bits, hybrid_cap, msd_cap, launches, config = line.split()
-        table[int(n), key_value == "1"] = Row(name, int(bits), int(hybrid_cap), int(msd_cap), int(launches), config)
+        n, key_value, name, bits, hybrid_cap, msd_cap, launches, config, *more = line.split()
+        row = Row(name, int(bits), int(hybrid_cap), int(msd_cap), int(launches), config)
+        if knobs is not None:
+            row = KnobRow(*row, more[0], more[1], int(more[2]))
+        table[int(n), key_value == "1"] = row
     assert len(table) == 2 * len(sizes)
     return table
 

@@ -1,6 +1,7 @@
 """Without a GPU: the plan of the bit-range sorts (vrdx_plan.h, PlanSortBits) through tests/native/sort_bits_plan_check.cpp,
 compiled here -- every range at the sizes of the GPU tests, both rankings, keys-only and key+value: one workgroup and one
-launch up to 16384 elements, refused beyond, the full range equal to the whole-key plan -- and the size lists of
+launch up to 16384 elements, refused beyond, under every setting of VRDX_SMALL_SORT and VRDX_TILE_CONFIG (a range over part
+of the key is planned by size alone), the full range equal to the whole-key plan under the same knobs -- and the size lists of
 tests/test_sort_bits_gpu.py held to what the planner prints.  The same program also runs under ASan + UBSan."""
 import os
 import subprocess
@@ -31,8 +32,9 @@ def report(tmp_path_factory):
 
 def test_every_range_at_the_sizes_of_the_gpu_tests(report):
     assert report.returncode == 0 and ", 0 failures" in report.stdout, report.stdout[-3000:] + report.stderr[-2000:]
-    # 33 x 34 / 2 + 33 (b, e) pairs with b <= e <= 33 per size, ranking and value mode
-    assert f"sort bits plan: {len(SIZES) * 4 * (33 * 34 // 2 + 33)} cases" in report.stdout
+    # 33 x 34 / 2 + 33 (b, e) pairs with b <= e <= 33 per size, ranking, value mode and setting of the knobs (smallSort on and
+    # off times forcedConfig -1, 0 ... 3)
+    assert f"sort bits plan: {len(SIZES) * 4 * 10 * (33 * 34 // 2 + 33)} cases" in report.stdout
 
 
 def test_the_gpu_tests_sizes_take_the_plan_they_claim(report):

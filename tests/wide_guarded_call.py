@@ -13,7 +13,7 @@ ROWS = {call.facts[2]: call for call in api.WIDE_VALUE_CALLS}   # indirect or no
 
 
 def wide_call(torch, sorter, keys, values, *, count=None, device_count=None, count_behind_keys=None, keys_off=0, values_off=0,
-              indirect_off=0, storage_off=0, storage=None, pool=None, expect_status=0, keep_before=False):
+              indirect_off=0, storage_off=0, storage=None, pool=None, expect_status=0, keep_before=False, device="cuda"):
     """keys: uint32, values: uint64, the FULL host arrays; count: elementCount / maxElementCount (default: all of keys), which
     also sizes the storage requirement; device_count: the indirect call, the word the device reads -- in a buffer of its own at
     `indirect_off`, or with count_behind_keys = g in the keys' buffer, g guard bytes behind the last key.  The checks are
@@ -24,23 +24,24 @@ def wide_call(torch, sorter, keys, values, *, count=None, device_count=None, cou
     assert len(keys) == len(values) and values_off % 8 == 0 and keys_off % 4 == 0 and count_behind_keys in (None, 0, 4, 8, 12)
     call = ROWS[device_count is not None]
     count = len(keys) if count is None else count
-    stream = torch.cuda.current_stream().cuda_stream
+    on_gpu = torch.device(device).type == "cuda"   # (anything else: a sorter that works on host memory, stream 0)
+    stream = torch.cuda.current_stream().cuda_stream if on_gpu else 0
     body = keys.view(np.uint8)
     word = np.array([0 if device_count is None else device_count], np.uint32)
     if count_behind_keys is not None:
         body = np.concatenate([body, np.full(count_behind_keys, GUARD_BYTE, np.uint8), word.view(np.uint8)])
-    dk = to_device(torch, body, FRONT + keys_off, TAIL)
-    dv = to_device(torch, values, FRONT + values_off, TAIL)
+    dk = to_device(torch, body, FRONT + keys_off, TAIL, device)
+    dv = to_device(torch, values, FRONT + values_off, TAIL, device)
     dc = None
     if count_behind_keys is not None:
         dc = dk[len(body) - 4:]
     elif device_count is not None:
-        dc = to_device(torch, word, FRONT + indirect_off, NEIGHBOURS)
+        dc = to_device(torch, word, FRONT + indirect_off, NEIGHBOURS, device)
     req = sorter.wide_value_storage_requirements(count)
     assert req.usage == api.STORAGE_USAGE
     end = storage_off + req.size
     if storage is None:
-        storage = poisoned_storage(torch, req.size, storage_off)
+        storage = poisoned_storage(torch, req.size, storage_off, device=device)
     assert storage.data_ptr() % 16 == 0 and storage_off % 16 == 0
     before = storage.clone() if keep_before else None
     front, behind = storage[:storage_off].clone(), storage[end:].clone()
@@ -50,7 +51,8 @@ def wide_call(torch, sorter, keys, values, *, count=None, device_count=None, cou
     for name, t in (("keys", dk), ("values", dv), ("indirect", dc)):
         given[name], given[name + "_offset"] = address(t) if t is not None else (None, None)
     getattr(sorter, call.method)(*(given[name] for name, _ in call.parameters))
-    torch.cuda.synchronize()
+    if on_gpu:
+        torch.cuda.synchronize()
 
     if count > 0 and expect_status is not None:
         status = sorter.read_status(stream, storage.data_ptr(), storage_off)

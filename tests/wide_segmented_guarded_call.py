@@ -13,7 +13,8 @@ from vulkan_radix_sort_amd import api
 
 
 def wide_segmented_call(torch, sorter, keys, values, offsets, *, count=None, keys_off=0, values_off=0, offsets_off=0,
-                        storage_off=0, storage=None, pool=None, expect_status=0, sticky=None, keep_before=False):
+                        storage_off=0, storage=None, pool=None, expect_status=0, sticky=None, keep_before=False,
+                        device="cuda"):
     """keys: uint32, values: uint64, the FULL host arrays; offsets: segment_count + 1 words as they go to the device; count:
     maxElementCount (default: all of keys), which also sizes the storage requirement.  The checks are guarded_call's: the guard
     bytes around keys, values and offsets, the offsets unchanged, the bytes in front of the storage offset and behind the
@@ -23,15 +24,16 @@ def wide_segmented_call(torch, sorter, keys, values, offsets, *, count=None, key
     offsets = np.ascontiguousarray(offsets).astype(np.uint32)
     assert len(keys) == len(values) and values_off % 8 == 0 and keys_off % 4 == 0 and offsets_off % 4 == 0
     count = len(keys) if count is None else count
-    stream = torch.cuda.current_stream().cuda_stream
-    dk = to_device(torch, keys, FRONT + keys_off, TAIL)
-    dv = to_device(torch, values, FRONT + values_off, TAIL)
-    do = to_device(torch, offsets, FRONT + offsets_off, NEIGHBOURS)
+    on_gpu = torch.device(device).type == "cuda"   # (anything else: a sorter that works on host memory, stream 0)
+    stream = torch.cuda.current_stream().cuda_stream if on_gpu else 0
+    dk = to_device(torch, keys, FRONT + keys_off, TAIL, device)
+    dv = to_device(torch, values, FRONT + values_off, TAIL, device)
+    do = to_device(torch, offsets, FRONT + offsets_off, NEIGHBOURS, device)
     req = sorter.wide_value_storage_requirements(count)
     assert req.usage == api.STORAGE_USAGE
     end = storage_off + req.size
     if storage is None:
-        storage = poisoned_storage(torch, req.size, storage_off)
+        storage = poisoned_storage(torch, req.size, storage_off, device=device)
     assert storage.data_ptr() % 16 == 0 and storage_off % 16 == 0 and storage.numel() >= end
     assert all(address(t)[0] % 16 == 0 for t in (dk, dv, do))
     before = storage.clone() if keep_before else None
@@ -42,7 +44,8 @@ def wide_segmented_call(torch, sorter, keys, values, offsets, *, count=None, key
     for name, t in (("keys", dk), ("values", dv), ("offsets", do)):
         given[name], given[name + "_offset"] = address(t)
     getattr(sorter, CALL.method)(*(given[name] for name, _ in CALL.parameters))
-    torch.cuda.synchronize()
+    if on_gpu:
+        torch.cuda.synchronize()
 
     if count > 0 and len(offsets) > 1:
         if expect_status is not None:

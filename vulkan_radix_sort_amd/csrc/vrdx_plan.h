@@ -316,10 +316,10 @@ static inline SortPlan PlanSort(const PlanContext& c, bool keyValue, uint32_t el
 }
 
 // The plan of a bit-range sort (vrdxHipCmdSortBits; include/vk_radix_sort.h) by the bits [beginBit, endBit) of the key: one
-// workgroup ranking ceil((endBit - beginBit) / 8) digits in one launch -- wherever PlanSort takes one workgroup, i.e. up to
-// kSmallSortMaxElements elements.  Larger range sorts are NOT built: the plan then has no step and
-// fits == false, and the recorder refuses the call like a layout that does not fit.
-// The range of all 32 bits is PlanSort itself; an empty range has no step, like an empty sort; an invalid one (beginBit >
+// workgroup ranking ceil((endBit - beginBit) / 8) digits in one launch -- up to kSmallSortMaxElements elements, whatever
+// PlanContext::smallSort and forcedConfig say.  Larger range sorts are NOT built: the plan then has
+// no step and fits == false, and the recorder refuses the call like a layout that does not fit.
+// The range of all 32 bits is PlanSort itself, knobs and all; an empty range has no step, like an empty sort; an invalid one (beginBit >
 // endBit, endBit > 32) has none either and is refused.
 constexpr const char* kBitRangeRefused = "bit range (0 <= beginBit <= endBit <= 32)";
 static inline SortPlan PlanSortBits(const PlanContext& c, bool keyValue, uint32_t elementCount, uint32_t beginBit, uint32_t endBit,
@@ -332,13 +332,17 @@ static inline SortPlan PlanSortBits(const PlanContext& c, bool keyValue, uint32_
   p.fits = beginBit <= endBit && endBit <= 32;
   if (!p.fits) p.refusal = kBitRangeRefused;
   if (!p.fits || beginBit == endBit || elementCount == 0) return p;
-  const SortPlan whole = PlanSort(c, keyValue, elementCount, storageAddress);
-  if (!whole.oneWorkgroup) {
+  if (elementCount > kSmallSortMaxElements) {
     p.fits = false;  // beyond one workgroup: not built
     p.refusal = "bit range over more than 16384 elements (not built)";
     return p;
   }
-  p = whole;
+  // By size alone: a range sort has no general-path form that VRDX_SMALL_SORT=0 or VRDX_TILE_CONFIG could select, so the plan
+  // is the one-workgroup plan PlanSort records with those two knobs at their defaults.
+  PlanContext sizeOnly = c;
+  sizeOnly.smallSort = true;
+  sizeOnly.forcedConfig = -1;
+  p = PlanSort(sizeOnly, keyValue, elementCount, storageAddress);
   p.rangeBegin = beginBit;
   p.rangeWidth = endBit - beginBit;  // 1 ... 31: the kernel extracts with v_bfe_u32, which takes a width modulo 32
   p.stepCount = p.launches = 0;
