@@ -503,14 +503,18 @@ constexpr uint32_t MsdScatterGrid(uint32_t tiles, bool keyValue, uint32_t bits) 
   return 8u * ((units + 7u) / 8u);
 }
 
-// Workgroups of the plan's bucket launch.  The full-size kernel (one workgroup per CU) takes TWO buckets per workgroup, one
-// after the other (BucketSort2Body): half as many workgroups to start and to drain -- 107.4 instead of 110.9 us keys-only at
-// 2^25, 175-178 instead of 179-180 key+value (tools/r06/bucket_grid.sh, bucket_grid2.sh, removed, last at commit
-// 3645810).  The half-size kernel (two workgroups per CU) keeps one: 47.7 against 47.0 us keys-only at 2^24 with two.
+// Workgroups of the plan's bucket launch.  The full-size kernel (one workgroup per CU): 2^bits / 2, the grid of round 6, when
+// a workgroup took TWO fixed buckets one after the other -- half as many workgroups to start and to drain, 107.4 instead of
+// 110.9 us keys-only at 2^25, 175-178 instead of 179-180 key+value (tools/r06/bucket_grid.sh, bucket_grid2.sh, removed, last
+// at commit 3645810).  Since round 8 its workgroups draw their buckets by ticket (BucketSort2Body) and the grid only bounds how
+// many may draw: the ones resident first, one per CU, take all 2^bits buckets, the others draw once and return.
+// The half-size kernel (two workgroups per CU) keeps one fixed bucket per workgroup: 47.7 against 47.0 us keys-only at 2^24
+// with two, and 6-7 % of a sort of 2^24 lost with drawn ones (profiles/r08_bucket_tickets.txt).
 constexpr uint32_t MsdBucketGrid(uint32_t bits, bool halfSizeKernel) { return halfSizeKernel ? 1u << bits : (1u << bits) / 2u; }
 
 // MsdArgs::plainTail: the buckets at the end of the bucket launch that keep plain output stores -- one per CU, the last
-// bucket each CU sorts.  Only their stores lie on the kernel's tail; the write-back of every earlier bucket streams out
+// bucket each CU sorts (buckets are handed out in index order, bucket = ticket, so the last `CUs` tickets drawn are the
+// highest indices, one for each resident workgroup).  Only their stores lie on the kernel's tail; the write-back of every earlier bucket streams out
 // behind the LDS work of the buckets that follow it on the same CU (vrdx_kernels.hip, BucketSort2Body).  Only from
 // kMsdStreamedOutputFrom = 2^25 elements, the size the rule was measured at, to the end of the ten-bit plan: buckets of
 // 32 K keys and more, whose LDS work is at least as long as the measured one.  Below it (18.1 M ... 2^25: buckets down to

@@ -3088,15 +3088,18 @@ __device__ __forceinline__ void ScatterMsdRole(const MsdArgs a) {
 }
 
 // ---- the plan's bucket role -------------------------------------------------------------------------
-// Workgroup b sorts bucket b = [bucketBase[b], + bucketCount[b]) of the scratch arrays by the 32 - BITS bits below the
+// A workgroup sorts bucket b = [bucketBase[b], + bucketCount[b]) of the scratch arrays by the 32 - BITS bits below the
 // scatter's, in two stable passes (11 bits, then the rest) with 2048 packed counters per wave, and writes it to the same
 // range of the caller's arrays.  Keys (and values) stay in registers between the passes; the staging buffer -- up to
 // 144 KiB -- takes the counters' place inside each pass like in the scatter role; key+value stages the values through
 // the same slots after the keys.  A wave takes only as many slots as the bucket needs (like SortInWorkgroup).
 // LDS: BucketSort2LdsWords (vrdx_kernels.h).
 
-template <uint32_t BITS, int KPT, bool KV, int THREADS = 1024>
-__device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_t bucket, const uint32_t below, const bool streamOut) {
+// DRAW: the bucket also draws the workgroup's NEXT ticket from *ticketWord into *nextDrawn (BucketSort2Body, the full-size
+// launches); false: the half-size kernel, whose workgroups have fixed buckets -- both pointers are unused then (nullptr).
+template <uint32_t BITS, int KPT, bool KV, int THREADS = 1024, bool DRAW = true>
+__device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_t bucket, const uint32_t below, const bool streamOut,
+                                                  uint32_t* const ticketWord, uint32_t* const nextDrawn) {
   constexpr int WAVES = THREADS / 64;
   static_assert(THREADS == 1024 || THREADS == 512, "one or two words of a counter row per thread");
   constexpr uint32_t TILE = THREADS * KPT;
@@ -3120,7 +3123,15 @@ __device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_
   constexpr uint32_t passes = 2u;
   const uint32_t myBase = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.bucketBase[bucket]);
   const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.bucketCount[bucket]);
-  if (n == 0) return;
+  if (n == 0) {  // no pass, so no barrier of a pass that the workgroup's next ticket could travel behind (BucketSort2Body)
+    if constexpr (DRAW) {
+      // (a plain draw: the answer is needed at once, so the wait that the compiler's atomic optimiser puts behind it -- the
+      // reason the draw in the last pass below hides its address -- costs nothing here)
+      if (tid == 0) *nextDrawn = atomicAdd(ticketWord, 1u);
+      LdsBarrier();
+    }
+    return;
+  }
   const uint32_t* const keysIn = a.keysScratch + myBase;
   uint32_t* const keysOut = a.keysCaller + myBase;
   const uint32_t* const valuesIn = KV ? a.valuesScratch + myBase : nullptr;
@@ -3185,6 +3196,17 @@ __device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_
     LdsBarrier();
     PositionsPacked16<KPT, TILE, DYN>(key, shift, width, myRow, rank, slots);
     LdsBarrier();  // the counters are dead: the staging buffer takes their place
+    // The workgroup's NEXT ticket (BucketSort2Body) is drawn here in the last pass: the wave has no load or store in flight,
+    // the answer arrives behind the regrouping below, and the pass's last barrier hands it to every wave.
+    // (The word's address has a part in a register the compiler cannot see through: for an address it knows to be uniform its
+    // atomic optimiser draws for the whole wave and reads the answer with readfirstlane -- a vmcnt(0) right here, one memory
+    // round trip of wave 0 that the other fifteen then wait for at the next barrier; profiles/HISTORY.md §5.1.)
+    uint32_t drawn = 0;
+    if (DRAW && pass + 1u == passes && tid == 0) {
+      uint32_t none = 0;  // (an index, not the pointer: the access stays a global one, outside lgkmcnt)
+      asm volatile("" : "+v"(none));
+      drawn = atomicAdd(ticketWord + none, 1u);
+    }
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
       if (DYN && i % 4 == 0 && (uint32_t)i >= slots) break;
@@ -3210,6 +3232,7 @@ __device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_
         val[i] = staged[StagingSlot<TILE>(firstNow + 64 * i)];
       }
     }
+    if (DRAW && pass + 1u == passes && tid == 0) *nextDrawn = drawn;  // (pass 0's scan scratch: dead since that pass's barriers)
     LdsBarrier();  // the next pass clears its counters where the staging buffer is
   }
   // Key+value sorts of more than 2^24 pairs write their result with NON-TEMPORAL stores: 256 MiB and more of output is the
@@ -3245,29 +3268,53 @@ __device__ __forceinline__ void BucketSort2Bucket(const MsdArgs a, const uint32_
   }
 }
 
-// The bucket launch: workgroup b sorts bucket b, b + workgroups, ... -- one bucket per workgroup when there are 2^BITS of them
-// (the half-size kernel), two when half that: the keys-only launch that is also pass 1 of the fallback then carries no
-// workgroups the pass has no tile for (1024 workgroups of 144 KiB of LDS for 512 tiles cost a turned-down sort 3-6 us).
+// The full-size bucket launch: the workgroups DRAW their buckets (round 8).  Lane 0 of a workgroup takes a ticket from the word of the
+// pass whose launch this is -- pass 1: the histogram kernel zeroes it for every sort, and of the two roles of a launch only
+// one runs -- and sorts bucket = ticket until the ticket reaches 2^BITS.  The workgroups that become resident first (one per CU
+// of these 1024-thread kernels) take all buckets between them, in index order; every workgroup that starts later draws once
+// and returns.  (Reading the word next to the verdict, so that such a workgroup returns without a draw, was measured and
+// dropped: the load stands in front of the pass role as well -- a turned-down keys-only sort 0.3705-0.3737 ms against
+// 0.3650-0.3687 -- and the key+value bucket role ran 169.6 us against the parent's 165.0; profiles/r08_bucket_tickets.txt.)
+// Per CU and launch there is one workgroup start, one load of the verdict and one drain, where the
+// strided loop before (512 workgroups of two buckets) had two, and a CU that is done with a short bucket takes the next one
+// whoever it would have belonged to.  (The half-size kernel keeps one bucket per workgroup: below.)
+// The ticket's way to the sixteen waves: two words of the scan scratch taken in turns (pass 0's sums, dead in the last pass,
+// and not written again before every wave has passed the next bucket's first barrier).  The FIRST ticket is drawn here, with a
+// barrier of its own; every later one inside the bucket in front of it (BucketSort2Bucket): in its last pass, handed on by
+// that pass's last barrier -- no barrier is added to a bucket with keys -- or, for a bucket without keys, which has no pass,
+// with one barrier.  Two words because of those: a wave that runs ahead through an empty bucket writes the ticket after the
+// one a slower wave has yet to read (tests/test_bucket_ticket_draw.py).
 // (Every pass of a bucket ends with a barrier: the next bucket may clear its counters where the staging buffer was.)
-template <uint32_t BITS, int KPT, bool KV, int THREADS = 1024>
-__device__ __forceinline__ void BucketSort2Body(const MsdArgs a, const uint32_t workgroups) {
+template <uint32_t BITS, int KPT, bool KV>
+__device__ __forceinline__ void BucketSort2Body(const MsdArgs a) {
+  constexpr int THREADS = 1024;
   const uint32_t verdict = *a.planWord;
   if ((verdict & kMsdVerdictMask) != kMsdVerdictRuns) return;  // the plan does not apply (the four passes are running), or nothing needs sorting
   const uint32_t below = (verdict >> kMsdShiftShift) & kMsdShiftMask;
   // The output policy of KEYS-ONLY sorts, per bucket (key+value: BucketSort2Bucket).  The full-size kernel by ten bits, above
-  // kStreamingLoadsAbove elements: a CU sorts four buckets one after the other (512 workgroups of two), and only the LAST
-  // one's stores lie on the kernel's tail, where a single sort waits for their write-back.  The buckets in front of it are
-  // followed by the LDS work of the next bucket on the same CU, behind which a streamed write-back disappears, so they take
-  // non-temporal stores and leave nothing dirty for the next kernel's reads to push out; the last a.plainTail buckets in the
-  // launch's order (the highest indices) keep plain stores.  The host sets plainTail (vrdx_kernels.h, MsdPlainTail): one
+  // kStreamingLoadsAbove elements: a CU sorts four buckets one after the other, and only the LAST one's stores lie on the
+  // kernel's tail, where a single sort waits for their write-back.  The buckets in front of it are followed by the LDS work of
+  // the next bucket on the same CU, behind which a streamed write-back disappears, so they take non-temporal stores and leave
+  // nothing dirty for the next kernel's reads to push out; the last a.plainTail buckets in the launch's order -- the order of
+  // the tickets: the highest indices -- keep plain stores.  The host sets plainTail (vrdx_kernels.h, MsdPlainTail): one
   // bucket per CU in the range of sizes where this measured a gain, every bucket outside it.
   // (The half-size kernel and the eleven-bit plan keep plain stores throughout: not measured with this rule.)
   uint32_t streamedBuckets = 0u;
-  if constexpr (!KV && THREADS == 1024 && BITS == 10)
+  if constexpr (!KV && BITS == 10)
     if (a.maxCount > kStreamingLoadsAbove) streamedBuckets = (1u << BITS) - min(a.plainTail, 1u << BITS);
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  uint32_t* const drawn = smem + THREADS * KPT;  // [2]: the first words of BucketSort2Bucket's scanScratch
+  uint32_t* const ticketWord = a.tickets + 1;
+  // (Whether to go on is decided by the drawn ticket alone, which every wave reads behind a barrier: a wave that looked at the
+  // word itself and returned on what it saw would leave the others without a ticket -- the word moves between two waves' loads.)
+  if (threadIdx.x == 0) drawn[0] = atomicAdd(ticketWord, 1u);
+  LdsBarrier();
 #pragma unroll 1
-  for (uint32_t bucket = blockIdx.x; bucket < (1u << BITS); bucket += workgroups)
-    BucketSort2Bucket<BITS, KPT, KV, THREADS>(a, bucket, below, bucket < streamedBuckets);
+  for (uint32_t turn = 0;; turn ^= 1u) {
+    const uint32_t bucket = (uint32_t)__builtin_amdgcn_readfirstlane((int)drawn[turn]);  // wave-uniform: scalar loads of its header
+    if (bucket >= (1u << BITS)) return;
+    BucketSort2Bucket<BITS, KPT, KV, THREADS>(a, bucket, below, bucket < streamedBuckets, ticketWord, drawn + (turn ^ 1u));
+  }
 }
 
 // Buckets of no more than 18432 elements (sorts of up to 18.1 M elements by ten bits): workgroups of 512 threads and
@@ -3276,9 +3323,17 @@ __device__ __forceinline__ void BucketSort2Body(const MsdArgs a, const uint32_t 
 // and with one workgroup per CU nothing runs beside it.
 // (__launch_bounds__' second argument is WAVES PER SIMD here: two workgroups of eight waves on four SIMDs = 4, i.e. at most
 // 128 registers; the kernels take 85 keys-only and 121 key+value.)
+// Workgroup b sorts bucket b, without a ticket: with two workgroups on a CU the start of one lies behind the other's work
+// already, and the drawn form measured 6-7 % SLOWER on a whole sort of 2^24 keys (0.1319-0.1356 against 0.1235-0.1255 ms,
+// key+value 0.1925-0.1944 against 0.1844-0.1872; profiles/r08_bucket_tickets.txt) -- like two buckets per workgroup in round 6.
 template <uint32_t BITS, bool KV>
 __global__ __launch_bounds__(512, 4) void bucket_sort2_half_kernel(MsdArgs a) {
-  BucketSort2Body<BITS, kMsdHalfCap / 512, KV, 512>(a, gridDim.x);
+  const uint32_t verdict = *a.planWord;
+  if ((verdict & kMsdVerdictMask) != kMsdVerdictRuns) return;  // the plan does not apply (the four passes are running), or nothing needs sorting
+  const uint32_t below = (verdict >> kMsdShiftShift) & kMsdShiftMask;
+#pragma unroll 1
+  for (uint32_t bucket = blockIdx.x; bucket < (1u << BITS); bucket += gridDim.x)
+    BucketSort2Bucket<BITS, kMsdHalfCap / 512, KV, 512, false>(a, bucket, below, false, nullptr, nullptr);
 }
 
 // ---- the plan's launches double as the first two launches of its fallback ------------------------------
@@ -3324,11 +3379,9 @@ __global__ __launch_bounds__(1024) void msd_buckets_or_pass1_kernel(MsdArgs m, O
     FallbackPassBody<BITS, KV, DYN>(p);
     return;
   }
-  // (two buckets per workgroup whatever the pass's grid is: with key+value tiles of 32768 the pass has as many tiles as the plan
-  // has buckets, and 1032 workgroups of one bucket each measured 182 us where 512 of two take 173)
-  const uint32_t workgroups = min(gridDim.x, (1u << BITS) / 2u);
-  if (verdict == kMsdVerdictRuns && blockIdx.x < workgroups)
-    BucketSort2Body<BITS, (KV ? kMsdCapKeyValue : kMsdCapKeys) / 1024, KV>(m, workgroups);
+  // (every workgroup of the pass's grid may draw, 512 keys-only and 1032 key+value at 2^25: those that start when the tickets
+  // are gone return -- 1032 workgroups of one FIXED bucket each measured 182 us where 512 of two took 173)
+  if (verdict == kMsdVerdictRuns) BucketSort2Body<BITS, (KV ? kMsdCapKeyValue : kMsdCapKeys) / 1024, KV>(m);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -548,8 +548,9 @@ hipError_t LaunchMsdFused(hipStream_t stream, bool bucketLaunch, bool keyValue, 
   const bool split = p.slots != 0;  // the pass's run-time slot counts, checked like LaunchOnesweep does
   if (split && !SlotsFit(p, 32)) return hipErrorInvalidValue;
   // the larger of the two roles' grids, a multiple of 8 (the scatter derives its tile from the grid: eight chunks of tiles,
-  // one per XCD; a workgroup beyond its role's range returns).  The bucket launch takes two buckets per workgroup
-  // (MsdBucketGrid): a pass of up to 2^bits / 2 tiles then has no idle workgroups.
+  // one per XCD; a workgroup beyond its role's range returns).  The bucket launch asks for 2^bits / 2 workgroups
+  // (MsdBucketGrid): a pass of up to that many tiles has no idle workgroups, and in the bucket role every workgroup of the
+  // grid, whichever role's it is, may draw a bucket.
   const uint32_t planGrid = bucketLaunch ? MsdBucketGrid(m.bits, false) : MsdScatterGrid(m.tiles, keyValue, m.bits);
   const uint32_t grid = 8u * (((planGrid > passGrid ? planGrid : passGrid) + 7u) / 8u);
   const int form = 8 * ((int)m.bits - 10) + 4 * keyValue + 2 * bucketLaunch + split;
