@@ -458,8 +458,9 @@ void vrdxHipCmdSortSegmented64OrderedKeyValue(VkCommandBuffer commandBuffer, Vrd
  * VRDX_TILE_CONFIG: size alone decides; only the range [0, 32), which is the whole-key sort, follows them.
  * Timestamps: the 15-slot contract as for ONE_WORKGROUP above.
  *
- * Out of scope: range sorts of more than 16384 elements (the range forms of the histogram and pass kernels are not part of
- * this library yet: DESIGN.md section 4.13); ranges for the 64-bit sorts; a range combined with a descending, signed or
+ * Beyond 16384 elements: vrdxHipCmdRangeSort* below take the same arguments and sort every size (these calls keep their
+ * refusal: the range forms of the histogram and pass kernels are not part of this library).
+ * Out of scope: ranges for the 64-bit sorts; a range combined with a descending, signed or
  * floating-point order (whole 32-bit keys have those orders: vrdxHipCmdOrderedSort* below).
  * Ranges for the segmented sort: vrdxHipCmdSortSegmentedBits below.
  */
@@ -479,6 +480,66 @@ void vrdxHipCmdSortBitsKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorte
                                         VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
                                         uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset,
                                         VkQueryPool queryPool, uint32_t query);
+
+/**
+ * Range sort at every size (not part of the reference API): vrdxHipCmdSortBits[KeyValue][Indirect]
+ * with no size at which a range is refused.  The argument lists are those of vrdxHipCmdSortBits*, name for name and position
+ * for position, and so are the semantics, word for word: ascending and stable by f(k) = (k >> beginBit) & (2^(endBit -
+ * beginBit) - 1); keys move whole and values travel with their keys; storage
+ * vrdxGetSorter[KeyValue]StorageRequirements(maxElementCount); the same alignment rules and bounds (nothing written outside
+ * [0, n) of the caller's arrays or outside the storage requirement); the indirect count read on the device, clamped to the
+ * bound and never written; the clamp at 2^30 - 4; capture and replay on other data and, indirect, on other counts up to the
+ * bound; all 15 timestamp slots; word 1 of the storage reading VRDX_HIP_VERDICT_NONE afterwards; [0, 32) recording the
+ * matching whole-key call, the empty range only the timestamps, an invalid range refused
+ * (VRDX_HIP_STATUS_ENQUEUE_REFUSED) with nothing else touched.
+ * Two differences:
+ *   up to 16384 elements (maxElementCount for the indirect forms) the call records exactly what vrdxHipCmdSortBits* records:
+ *   the same one-workgroup launch in the same slot, byte-identical results;
+ *   beyond 16384 elements it records the CHUNKED form instead of refusing: the array is cut into up to one contiguous chunk
+ *   per compute unit (at least 8192 keys each), and every digit of the range (P = ceil((endBit - beginBit) / 8), the last one
+ *   of the bits that are left) takes three launches -- count per chunk, scan, stable scatter per chunk -- between the
+ *   caller's arrays and the storage's scratch arrays, with one streaming copy back at the end when the number of passes that
+ *   moved keys is odd.  A digit that is the same in every key moves nothing (its launches return at once); a field that is the
+ *   same in every key writes neither the arrays nor the scratch arrays.  No launch waits for another workgroup.
+ * Timestamps of the chunked form: slot 1 the fill, slots 2 + 3 p / 3 + 3 p / 4 + 3 p the count, scan and scatter of digit p,
+ * slot 14 the copy back; the slots no step ends coincide with the one before.
+ * vrdxHipDescribeRangeSortPlan reports the form, the chunks, the launches (3 P + 1) and the HBM bytes per element.
+ * Range sorts ignore the planning knobs (VRDX_SMALL_SORT, VRDX_TILE_CONFIG, VRDX_HYBRID, VRDX_MSD): size alone decides; only
+ * the range [0, 32), which is the whole-key sort, follows them.
+ */
+void vrdxHipCmdRangeSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                         VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                         VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdRangeSortKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                                 VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset, uint32_t beginBit,
+                                 uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                                 uint32_t query);
+void vrdxHipCmdRangeSortIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                 VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                 VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                                 VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
+void vrdxHipCmdRangeSortKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                         VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                         VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                         uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                         VkQueryPool queryPool, uint32_t query);
+#define VRDX_HIP_RANGE_SORT_NONE 0u          /* nothing is recorded: no elements, an empty range; refused: an invalid range */
+#define VRDX_HIP_RANGE_SORT_ONE_WORKGROUP 1u /* up to 16384 elements: what vrdxHipCmdSortBits* records */
+#define VRDX_HIP_RANGE_SORT_WHOLE_KEY 2u     /* the range [0, 32): what vrdxCmdSort* records (vrdxHipDescribePlan says which plan) */
+#define VRDX_HIP_RANGE_SORT_CHUNKED 3u       /* beyond 16384 elements: count, scan, scatter per digit */
+typedef struct VrdxHipRangeSortPlanInfo {
+  uint32_t form;                    /* VRDX_HIP_RANGE_SORT_* */
+  uint32_t chunks;                  /* CHUNKED: workgroups of the count and scatter launches; otherwise 1 */
+  uint32_t keysPerChunk;            /* CHUNKED: keys per chunk (a multiple of 256; the last chunk holds the rest); otherwise the count */
+  uint32_t digits;                  /* P: digits ranked (WHOLE_KEY: 4) */
+  uint32_t launches;                /* kernels recorded (CHUNKED: 3 P + 1) */
+  uint32_t bytesPerElementPerPass;  /* CHUNKED: HBM bytes per element of one ACTIVE pass (12 keys-only, 20 key+value: the count
+                                       reads the keys, the scatter reads and writes everything); otherwise of the whole sort */
+  uint32_t bytesPerElementCopyBack; /* CHUNKED: of the copy back, which runs after an odd number of active passes; otherwise 0 */
+} VrdxHipRangeSortPlanInfo;
+/* What vrdxHipCmdRangeSort[KeyValue][Indirect] records on `sorter` for elementCount (the bound of an indirect call). */
+void vrdxHipDescribeRangeSortPlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, uint32_t beginBit, uint32_t endBit,
+                                  VrdxHipRangeSortPlanInfo* info);
 
 /**
  * Segmented sort by a bit range of the key (not part of the reference API; CUB's DeviceSegmentedRadixSort with begin_bit /
@@ -502,7 +563,8 @@ void vrdxHipCmdSortBitsKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorte
  * P = ceil((endBit - beginBit) / 8) digits of the range; a larger segment is sorted by one workgroup through memory, one walk
  * of the segment per digit of the range that differs between its keys (at most P, where the whole-key form takes up to four).
  * So a single array of more than 16384 elements CAN be range-sorted as one segment, but then by one workgroup: correct, and
- * slow.  vrdxHipCmdSortBits beyond 16384 elements stays refused.
+ * slow: vrdxHipCmdRangeSort above sorts such an array with every compute unit.  vrdxHipCmdSortBits beyond 16384 elements
+ * stays refused.
  */
 void vrdxHipCmdSortSegmentedBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
                                  uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,

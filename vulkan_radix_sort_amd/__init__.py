@@ -45,6 +45,9 @@ from .api import (  # noqa: F401
     VrdxHipWideValuePlanInfo,
     WIDE_VALUE_FORM_NAMES,
     WIDE_VALUE_SEGMENTED_CALLS,
+    VrdxHipRangeSortPlanInfo,
+    RANGE_SORT_FORM_NAMES,
+    RANGE_SORT_CALLS,
 )
 from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
@@ -53,6 +56,7 @@ from .sort_bits import sort_bits  # noqa: F401
 from .segmented_bits import sort_segments_bits  # noqa: F401
 from .ordered import sort_ordered, sort_segments_ordered  # noqa: F401
 from .wide_value import sort_key_value64, sort_segments_key_value64  # noqa: F401
+from .range_sort import sort_range  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -100,4 +104,8 @@ __all__ = [
     "sort_key_value64",
     "sort_segments_key_value64",
     "WIDE_VALUE_SEGMENTED_CALLS",
+    "VrdxHipRangeSortPlanInfo",
+    "RANGE_SORT_FORM_NAMES",
+    "RANGE_SORT_CALLS",
+    "sort_range",
 ]

@@ -22,6 +22,7 @@ Known differences between the front ends.  They are behaviour -- a caller sees t
   values and storage live where the keys live, then the storage's alignment and size, and only then that the place is a GPU.
 * sort_segments_bits checks the bit range before the tensors, sort_bits behind keys and values; only sort_bits bounds the
   number of keys of a partial range (``check_range_count``).
+* sort_range (range_sort.py) is sort_bits check for check, in its order, without ``check_range_count``: no size is refused.
 """
 from __future__ import annotations
 

@@ -62,6 +62,9 @@ class RecordingCall(NamedTuple):
         """(key bits, segmented, indirect, key+value, None | "Bits" | "Ordered"), parsed from the C name"""
         ordered32 = re.fullmatch(r"vrdxHipCmdOrderedSort(Segmented)?(KeyValue)?(Indirect)?", self.c_name)
         wide_value = re.fullmatch(r"vrdxHipCmdWideValueSort(Indirect)?", self.c_name)
+        range_sort = re.fullmatch(r"vrdxHipCmdRangeSort(KeyValue)?(Indirect)?", self.c_name)
+        if range_sort:   # the rows of RANGE_SORT_CALLS: the arguments of vrdxHipCmdSortBits*
+            return 32, False, bool(range_sort.group(2)), bool(range_sort.group(1)), "Bits"
         if self.c_name == "vrdxHipCmdWideValueSortSegmented":   # the row of WIDE_VALUE_SEGMENTED_CALLS
             return 32, True, False, True, None
         if wide_value:   # the rows of WIDE_VALUE_CALLS: uint32 keys, always with values (of 8 bytes: the argument list is the same)
@@ -209,6 +212,22 @@ WIDE_VALUE_SEGMENTED_CALLS = (
           "``wide_value_storage_requirements(max_element_count)`` bytes."),
 )
 
+# by a bit range of the key at every size: a table of its own next to the others (RECORDING_CALLS stays as it is), the same
+# kind of row; the arguments are those of vrdxHipCmdSortBits[KeyValue][Indirect], name for name
+RANGE_SORT_CALLS = (
+    _CALL("vrdxHipCmdRangeSort", "cmd_range_sort",
+          "``cmd_sort_bits`` with no size at which a range is refused: up to 16384 elements the same launch, beyond that "
+          "count, scan and scatter per digit of the range over up to one chunk per compute unit; storage of "
+          "``storage_requirements(n)`` bytes."),
+    _CALL("vrdxHipCmdRangeSortKeyValue", "cmd_range_sort_key_value",
+          "the same with values that travel with their keys; storage of ``key_value_storage_requirements(n)`` bytes."),
+    _CALL("vrdxHipCmdRangeSortIndirect", "cmd_range_sort_indirect",
+          "``cmd_range_sort`` of the first min(count, ``max_element_count``) keys, the count one uint32 at "
+          "``indirect + indirect_offset`` that is read on the device."),
+    _CALL("vrdxHipCmdRangeSortKeyValueIndirect", "cmd_range_sort_key_value_indirect",
+          "the same with values that travel with their keys."),
+)
+
 
 def _exported_symbols():
     """Everything the library exports, in the order this tuple has always had: the entry points that record no sort, by hand,
@@ -231,6 +250,9 @@ def _exported_symbols():
         yield from names
         yield from (next(rows).c_name for _ in range(recording))
     assert next(rows, None) is None, "a row of RECORDING_CALLS is missing from EXPORTED_SYMBOLS"
+    # the range sorts at every size: behind the rows of RECORDING_CALLS (the groups below keep their distance from the end)
+    yield from (call.c_name for call in RANGE_SORT_CALLS)
+    yield "vrdxHipDescribeRangeSortPlan"
     # uint32 keys with 8-byte values: the segmented call, then the flat group
     yield from (call.c_name for call in WIDE_VALUE_SEGMENTED_CALLS)
     yield "vrdxHipGetSorterWideValueStorageRequirements"
@@ -290,6 +312,16 @@ def record_sort(sorter, key_bits, stream, count, offsets, segment_count, indirec
 
 
 _ORDERED_RECORDERS = {_takes(*call.facts)[1:4]: _recorder(call) for call in ORDERED_SORT_CALLS}
+
+
+_RANGE_RECORDERS = {_takes(*call.facts)[2:4]: _recorder(call) for call in RANGE_SORT_CALLS}
+
+
+def record_range_sort(sorter, stream, count, indirect, keys, values, bit_range, storage):
+    """``record_sort`` for the rows of RANGE_SORT_CALLS: records the one range sort that takes what the caller has.
+    ``bit_range``: (begin_bit, end_bit), always handed on; ``indirect`` / ``values``: ``None`` selects the call without."""
+    _RANGE_RECORDERS[(indirect is not None, values is not None)](sorter, stream, count, None, None, indirect, keys, values,
+                                                                  bit_range, None, storage)
 
 
 def record_ordered_sort(sorter, stream, count, offsets, segment_count, indirect, keys, values, order, storage):
@@ -399,6 +431,21 @@ class VrdxHipWideValuePlanInfo(ctypes.Structure):
         return WIDE_VALUE_FORM_NAMES.get(int(self.form), "?")
 
 
+# VRDX_HIP_RANGE_SORT_* (include/vk_radix_sort.h)
+RANGE_SORT_FORM_NAMES = {0: "none", 1: "one-workgroup", 2: "whole-key", 3: "chunked"}
+
+
+class VrdxHipRangeSortPlanInfo(ctypes.Structure):
+    # include/vk_radix_sort.h
+    _fields_ = [("form", ctypes.c_uint32), ("chunks", ctypes.c_uint32), ("keysPerChunk", ctypes.c_uint32),
+                ("digits", ctypes.c_uint32), ("launches", ctypes.c_uint32), ("bytesPerElementPerPass", ctypes.c_uint32),
+                ("bytesPerElementCopyBack", ctypes.c_uint32)]
+
+    @property
+    def name(self) -> str:
+        return RANGE_SORT_FORM_NAMES.get(int(self.form), "?")
+
+
 def in_tree_library_path() -> str:
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvrdx_hip.so")
 
@@ -454,7 +501,7 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = None
         fn.argtypes = [vp, u32, ctypes.POINTER(VrdxSorterStorageRequirements)]
-    for call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS:
+    for call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS + RANGE_SORT_CALLS:
         fn = getattr(lib, call.c_name)
         fn.restype = None
         fn.argtypes = call.argtypes
@@ -462,6 +509,8 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxHipDescribeWideValueSortPlan.argtypes = [vp, u32, ctypes.POINTER(VrdxHipWideValuePlanInfo)]
     lib.vrdxHipDescribeOrderedSortPlan.restype = None
     lib.vrdxHipDescribeOrderedSortPlan.argtypes = [vp, u32, ctypes.c_int, u32, ctypes.POINTER(VrdxHipPlanInfo)]
+    lib.vrdxHipDescribeRangeSortPlan.restype = None
+    lib.vrdxHipDescribeRangeSortPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipRangeSortPlanInfo)]
     lib.vrdxHipDescribeSortBitsPlan.restype = None
     lib.vrdxHipDescribeSortBitsPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
@@ -627,6 +676,15 @@ class Sorter:
                                               ctypes.byref(info))
         return info
 
+    def describe_range_sort_plan(self, element_count: int, key_value: bool, begin_bit: int,
+                                 end_bit: int) -> VrdxHipRangeSortPlanInfo:
+        """``vrdxHipDescribeRangeSortPlan``: the form ``cmd_range_sort*`` records for that many elements and that range
+        (``.name``), its chunks, digits and launches, and the HBM bytes per element of an active pass and of the copy back."""
+        info = VrdxHipRangeSortPlanInfo()
+        self._lib.vrdxHipDescribeRangeSortPlan(self.handle, element_count, 1 if key_value else 0, begin_bit, end_bit,
+                                               ctypes.byref(info))
+        return info
+
     def describe_ordered_sort_plan(self, element_count: int, key_value: bool, order: int) -> VrdxHipPlanInfo:
         """``vrdxHipDescribeOrderedSortPlan``: the plan ``cmd_ordered_sort*`` records for that many elements and that order word
         (beyond one workgroup: ``describe_plan``'s, plus two launches and 16 bytes per element)."""
@@ -692,5 +750,5 @@ def _recording_method(call: RecordingCall):
     return method
 
 
-for _call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS:
+for _call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS + RANGE_SORT_CALLS:
     setattr(Sorter, _call.method, _recording_method(_call))

@@ -502,6 +502,69 @@ void RecordSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t eleme
   if (plan.stepCount > 1) MaybeRecheckOrder(sorter, r.stream, plan.atomicRank);  // (the general path)
 }
 
+static_assert(VRDX_HIP_RANGE_SORT_NONE == (uint32_t)vrdx::RangeSortForm::kNone &&
+                  VRDX_HIP_RANGE_SORT_ONE_WORKGROUP == (uint32_t)vrdx::RangeSortForm::kOneWorkgroup &&
+                  VRDX_HIP_RANGE_SORT_WHOLE_KEY == (uint32_t)vrdx::RangeSortForm::kWholeKey &&
+                  VRDX_HIP_RANGE_SORT_CHUNKED == (uint32_t)vrdx::RangeSortForm::kChunked,
+              "the forms of the header are the planner's");
+
+// The range sorts at every size (include/vk_radix_sort.h, vrdxHipCmdRangeSort[KeyValue][Indirect]): PlanRangeSort
+// (vrdx_plan.h).  Every form but the chunked one IS what vrdxHipCmdSortBits* records and goes through RecordSort, refusals
+// included; the chunked form records its own step list on the storage of MakeRangeSortLayout.  Indirect: elementCount is the
+// bound; layout and grids come from it alone, and every launch reads the count from the caller's word when it runs.
+void RecordRangeSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer indirectBuffer,
+                     VkDeviceSize indirectOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                     VkDeviceSize valuesOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                     VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  const bool keyValue = valuesBuffer != nullptr;
+  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
+  const vrdx::RangeSortPlan plan =
+      vrdx::PlanRangeSort(PlanContextOf(sorter), keyValue, std::min<uint32_t>(elementCount, VRDX_MAX_ELEMENTS), beginBit, endBit,
+                          (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (plan.form != vrdx::RangeSortForm::kChunked && plan.refusal == nullptr)
+    return RecordSort(commandBuffer, sorter, elementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, valuesBuffer,
+                      valuesOffset, storageBuffer, storageOffset, queryPool, query, beginBit, endBit);
+  Recording r(commandBuffer, sorter, elementCount, queryPool, query);
+  if (r.NothingToRecord(sorter, plan.refusal, plan.stepCount)) return;
+  const auto words = [storage](uint64_t offset) { return reinterpret_cast<uint32_t*>(storage + offset); };
+  vrdx::RangeSortArgs a;
+  a.keys = reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset));
+  a.values = keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
+  a.keysScratch = words(plan.layout.keysScratchOffset);
+  a.valuesScratch = keyValue ? words(plan.layout.valuesScratchOffset) : nullptr;
+  a.maxCount = r.count;
+  a.countPtr = indirectBuffer != nullptr ? reinterpret_cast<const uint32_t*>(BufferAddress(indirectBuffer, indirectOffset)) : nullptr;
+  a.totals = words(plan.layout.totalsOffset);
+  a.counts = words(plan.layout.countsOffset);
+  a.state = words(VRDX_OFF_MSD_OVERFLOW);
+  a.grid = plan.grid;
+  a.beginBit = plan.rangeBegin;
+  a.width = plan.rangeWidth;
+  a.pass = 0;
+  for (uint32_t i = 0; i < plan.stepCount; ++i) {
+    const vrdx::RangeSortStep& step = plan.steps[i];
+    a.pass = step.pass;
+    hipError_t e = hipErrorInvalidValue;
+    switch (step.what) {
+      case vrdx::StepRange::kFill:
+        // header (count, VRDX_HIP_VERDICT_NONE, the mask of active passes, failure word) and the totals, as RecordSort fills
+        // them; indirect: the count is copied to where the reference keeps it
+        EnqueueCheck(sorter, "hipMemsetAsync(state)", hipMemsetAsync(storage, 0, plan.layout.clearBytes, r.stream));
+        e = a.countPtr == nullptr ? hipSuccess
+                                  : hipMemcpyAsync(storage + VRDX_OFF_COUNT, a.countPtr, sizeof(uint32_t), hipMemcpyDeviceToDevice, r.stream);
+        break;
+      case vrdx::StepRange::kCount: e = vrdx::LaunchRangeCount(r.stream, a); break;
+      case vrdx::StepRange::kScan: e = vrdx::LaunchRangeScan(r.stream, a); break;
+      case vrdx::StepRange::kScatter: e = vrdx::LaunchRangeScatter(r.stream, keyValue, plan.atomicRank, a); break;
+      case vrdx::StepRange::kCopyBack: e = vrdx::LaunchRangeCopyBack(r.stream, keyValue, a); break;
+    }
+    EnqueueCheck(sorter, step.name, e);
+    r.stamps.AdvanceTo(step.slot);
+  }
+  r.stamps.Finish();
+  MaybeRecheckOrder(sorter, r.stream, plan.atomicRank);
+}
+
 static_assert(VRDX_HIP_KEY_UINT64 == vrdx::kKeyOrderUint64 && VRDX_HIP_KEY_INT64 == vrdx::kKeyOrderInt64 &&
                   VRDX_HIP_KEY_FLOAT64 == vrdx::kKeyOrderFloat64 && VRDX_HIP_ORDER_DESCENDING == vrdx::kKeyOrderDescending,
               "the order word of the header is the kernels'");
@@ -955,6 +1018,38 @@ void vrdxHipCmdSortBitsKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorte
              valuesOffset, storageBuffer, storageOffset, queryPool, query, beginBit, endBit);
 }
 
+void vrdxHipCmdRangeSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                         VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                         VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordRangeSort(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, nullptr, 0, beginBit, endBit,
+                  storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdRangeSortKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t elementCount, VkBuffer keysBuffer,
+                                 VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset, uint32_t beginBit,
+                                 uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset, VkQueryPool queryPool,
+                                 uint32_t query) {
+  RecordRangeSort(commandBuffer, sorter, elementCount, nullptr, 0, keysBuffer, keysOffset, valuesBuffer, valuesOffset, beginBit,
+                  endBit, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdRangeSortIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                 VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                 VkDeviceSize keysOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
+                                 VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordRangeSort(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, nullptr, 0,
+                  beginBit, endBit, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdRangeSortKeyValueIndirect(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                         VkBuffer indirectBuffer, VkDeviceSize indirectOffset, VkBuffer keysBuffer,
+                                         VkDeviceSize keysOffset, VkBuffer valuesBuffer, VkDeviceSize valuesOffset,
+                                         uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                         VkQueryPool queryPool, uint32_t query) {
+  RecordRangeSort(commandBuffer, sorter, maxElementCount, indirectBuffer, indirectOffset, keysBuffer, keysOffset, valuesBuffer,
+                  valuesOffset, beginBit, endBit, storageBuffer, storageOffset, queryPool, query);
+}
+
 void vrdxHipGetSorter64StorageRequirements(VrdxSorter sorter, uint32_t maxElementCount,
                                            VrdxSorterStorageRequirements* requirements) {
   requirements->size = vrdx::MakeSort64Layout(maxElementCount, sorter->minStorageBufferOffsetAlignment).keysOnlySize;
@@ -1251,6 +1346,15 @@ void vrdxHipDescribeSortBitsPlan(VrdxSorter sorter, uint32_t elementCount, int k
   if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
   const SortPlan plan = vrdx::PlanSortBits(PlanContextOf(sorter), keyValue != 0, elementCount, beginBit, endBit, 0);
   if (plan.stepCount != 0) vrdx::DescribePlan(plan, info);  // (no step: refused -- an invalid range, one beyond one workgroup -- or empty)
+}
+
+void vrdxHipDescribeRangeSortPlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, uint32_t beginBit, uint32_t endBit,
+                                  VrdxHipRangeSortPlanInfo* info) {
+  if (info == nullptr) return;
+  std::memset(info, 0, sizeof(*info));
+  if (sorter == nullptr) return;
+  if (elementCount > VRDX_MAX_ELEMENTS) elementCount = VRDX_MAX_ELEMENTS;
+  vrdx::DescribeRangeSortPlan(vrdx::PlanRangeSort(PlanContextOf(sorter), keyValue != 0, elementCount, beginBit, endBit, 0), info);
 }
 
 void vrdxHipDescribeOrderedSortPlan(VrdxSorter sorter, uint32_t elementCount, int keyValue, uint32_t order, VrdxHipPlanInfo* info) {

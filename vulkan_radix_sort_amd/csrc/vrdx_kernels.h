@@ -262,6 +262,32 @@ enum SegmentClass { kSegmentSmall = 0, kSegmentMid = 1, kSegmentLarge = 2 };  //
 hipError_t LaunchSegmented(hipStream_t stream, SegmentClass sizeClass, uint32_t grid, bool keyValue, bool atomicRank,
                            const SegmentedArgs& args, uint32_t beginBit, uint32_t width);
 
+// ---- range sorts beyond one workgroup (vrdxHipCmdRangeSort[KeyValue][Indirect]; vrdx_kernels.hip, "range sort") ----
+// Count, scan, scatter per digit of the field, a copy back after an odd number of active passes (PlanRangeSort in
+// vrdx_plan.h lists the launches; MakeRangeSortLayout in vrdx_layout.h places the arrays).  `grid` workgroups take the chunks
+// of RangeChunkKeys (vrdx_layout.h): the host sizes it from maxCount, the kernels cut the count they read with it.
+struct RangeSortArgs {
+  uint32_t* keys;
+  uint32_t* values;            // KV only
+  uint32_t* keysScratch;
+  uint32_t* valuesScratch;     // KV only
+  uint32_t maxCount;           // element count (direct) or upper bound (indirect)
+  const uint32_t* countPtr;    // device-side element count (indirect) or nullptr
+  uint32_t* totals;            // uint[4][256]: the field's digits over the whole array (zeroed by the fill in front)
+  uint32_t* counts;            // uint[grid][256]: per chunk, the pass's counts, then its positions
+  uint32_t* state;             // header word 2: the mask of active passes (the first scan launch writes it)
+  uint32_t grid;               // workgroups of the count and scatter launches = rows of `counts`
+  uint32_t beginBit, width;    // the range: 1 <= width <= 31, beginBit + width <= 32
+  uint32_t pass;               // the digit this launch works on (the copy back: unused)
+};
+constexpr uint32_t kRangeCopyThreads = 256;
+// pass 0: also the totals of every digit; reads the caller's keys
+hipError_t LaunchRangeCount(hipStream_t stream, const RangeSortArgs& args);
+// one workgroup; pass 0: also the mask of active passes
+hipError_t LaunchRangeScan(hipStream_t stream, const RangeSortArgs& args);
+hipError_t LaunchRangeScatter(hipStream_t stream, bool keyValue, bool atomicRank, const RangeSortArgs& args);
+hipError_t LaunchRangeCopyBack(hipStream_t stream, bool keyValue, const RangeSortArgs& args);
+
 // ---- key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered*, vrdxHipCmdSortSegmented64Ordered*; vrdx_kernels.hip, "key
 // orders of the 64-bit sorts") ----
 // The order word of include/vk_radix_sort.h: a key type, VRDX_HIP_ORDER_DESCENDING or-ed in or not.  The kernels sort
@@ -452,6 +478,11 @@ constexpr size_t SmallSortLdsWords(int threads, int kpt, bool kv) {
 constexpr size_t SegmentLargeLdsWords(bool kv) {
   // staging (keys, values) | wave counters 16 x 256 | scan scratch 16 | bases 4 x 256 | tile starts 256 | tile counts 256 | 16
   return (size_t)kSegLargeTile * (kv ? 2 : 1) + 16 * 256 + 16 + 4 * 256 + 256 + 256 + 16;
+}
+
+constexpr size_t RangeScatterLdsWords(bool kv) {
+  // staging (keys, values) | wave counters 16 x 256 | scan scratch 16 | base 256 | tile starts 256 | tile counts 256 | 16
+  return (size_t)kSegLargeTile * (kv ? 2 : 1) + 16 * 256 + 16 + 256 + 256 + 256 + 16;
 }
 
 // SortInWorkgroup64: one staging plane per key word (and one for the values) | wave counters | scan scratch and the two

@@ -4749,6 +4749,273 @@ __global__ __launch_bounds__(1024) void segmented_large_wide_kernel(SegmentedWid
 }
 
 // ---------------------------------------------------------------------------------------------
+// range sort beyond one workgroup (vrdxHipCmdRangeSort*): count, scan, scatter -- DESIGN.md section 4.21
+// ---------------------------------------------------------------------------------------------
+// A stable LSD sort by the P = ceil(width / 8) digits of the field (RangeDigit), every pass three launches that each finish on
+// their own inputs: no ticket, no look-back, no status row, nothing that waits for another workgroup.
+//   range_count_kernel    workgroup c counts the pass's digit over ITS chunk of the array the pass reads (RangeChunkKeys,
+//                         vrdx_layout.h) into row c of the counts table.  After pass p - 1 a chunk holds other keys than it
+//                         did in the input, so every pass counts again.  The first launch also adds up the totals of all P
+//                         digits over the whole array, which do not depend on the order of the keys;
+//   range_scan_kernel     one workgroup: its first launch derives the mask of ACTIVE passes from the totals (a pass whose
+//                         digit is the same in every key moves nothing) and leaves it in header word 2; every launch turns
+//                         the rows of counts into positions: counts[c][d] = the digit's start + the counts of d in the chunks
+//                         in front of c;
+//   range_scatter_kernel  workgroup c walks its chunk tile by tile IN ORDER, SegmentLsd's step 2 with base[] starting from
+//                         row c of the table;
+//   range_copy_back_kernel  after an odd number of ACTIVE passes the result lies in the scratch arrays.
+// Pass p reads the caller's arrays when an even number of active passes ran in front of it and the scratch arrays otherwise:
+// every launch derives that from the mask.  Launches of a pass that is not active return at once and flip nothing.
+// Nothing here trusts the table: a scatter checks every position against n before it stores.
+__device__ __forceinline__ bool RangePassReadsScratch(uint32_t active, uint32_t pass) {
+  return (__popc(active & ((1u << pass) - 1u)) & 1) != 0;
+}
+
+// This workgroup's chunk: false when it has none (a count far below the bound of an indirect call).
+__device__ __forceinline__ bool RangeChunkOf(const RangeSortArgs& a, uint32_t n, uint32_t* begin, uint32_t* length) {
+  const uint32_t chunkKeys = RangeChunkKeys(n, a.grid);
+  const uint64_t first = (uint64_t)blockIdx.x * chunkKeys;
+  if (first >= n) return false;
+  *begin = (uint32_t)first;
+  *length = min(chunkKeys, n - (uint32_t)first);
+  return true;
+}
+
+// FIRST: the launch of pass 0 -- it reads the caller's keys, counts all P digits and adds their totals up.
+template <bool FIRST>
+__global__ __launch_bounds__(1024) void range_count_kernel(RangeSortArgs a) {
+  constexpr uint32_t THREADS = 1024;
+  __shared__ uint32_t bins[(FIRST ? 4 : 1) * 256 * kSegHistCopies];  // [digit index][digit][copy]
+  const uint32_t tid = threadIdx.x;
+  const uint32_t n = ElementCount(a.maxCount, a.countPtr);
+  const uint32_t digits = (a.width + 7u) / 8u;
+  bool fromScratch = false;
+  if constexpr (!FIRST) {
+    const uint32_t active = *a.state;
+    if (((active >> a.pass) & 1u) == 0) return;  // uniform
+    fromScratch = RangePassReadsScratch(active, a.pass);
+  }
+  uint32_t begin = 0, length = 0;
+  if (!RangeChunkOf(a, n, &begin, &length)) return;  // uniform
+  const uint32_t* const keys = (fromScratch ? a.keysScratch : a.keys) + begin;
+  for (uint32_t i = tid; i < (FIRST ? 4u : 1u) * 256u * kSegHistCopies; i += THREADS) bins[i] = 0;
+  LdsBarrier();
+  const uint32_t copy = tid & (kSegHistCopies - 1);
+  auto count = [&](uint32_t key) {
+    if constexpr (FIRST) {
+#pragma unroll
+      for (uint32_t p = 0; p < 4; ++p) {
+        if (p >= digits) break;  // uniform
+        atomicAdd(&bins[(p * 256 + VRDX_DIGIT(true, 0xFFu, key, RangeDigit(a.beginBit, a.width, p))) * kSegHistCopies + copy], 1u);
+      }
+    } else {
+      atomicAdd(&bins[VRDX_DIGIT(true, 0xFFu, key, RangeDigit(a.beginBit, a.width, a.pass)) * kSegHistCopies + copy], 1u);
+    }
+  };
+  {
+    constexpr uint32_t U = 8;  // loads in flight per lane
+    uint32_t i = tid;
+    for (; i + (U - 1) * THREADS < length; i += U * THREADS) {
+      uint32_t k[U];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) k[u] = keys[i + u * THREADS];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) count(k[u]);
+    }
+    for (; i < length; i += THREADS) count(keys[i]);
+  }
+  LdsBarrier();
+  // thread t: digit index t / 256, digit t % 256
+  const uint32_t p = tid >> 8, d = tid & 255u;
+  if (!FIRST && p != 0) return;
+  uint32_t c = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < kSegHistCopies; ++r) c += bins[(p * 256 + d) * kSegHistCopies + ((r + tid) & (kSegHistCopies - 1))];
+  if (p == 0) a.counts[(size_t)blockIdx.x * 256 + d] = c;
+  if constexpr (FIRST) {
+    if (p < digits && c != 0) atomicAdd(&a.totals[p * 256 + d], c);
+  }
+}
+
+__global__ __launch_bounds__(1024) void range_scan_kernel(RangeSortArgs a) {
+  __shared__ uint32_t partial[4 * 256];
+  __shared__ uint32_t start[256];
+  __shared__ uint32_t scanScratch[16];
+  __shared__ uint32_t varied;
+  const int tid = threadIdx.x;
+  const uint32_t g = (uint32_t)tid >> 8, d = (uint32_t)tid & 255u;
+  const uint32_t n = ElementCount(a.maxCount, a.countPtr);
+  uint32_t active;
+  if (a.pass == 0) {  // uniform
+    // a pass moves keys when its digit takes two values at least: some bin is neither empty nor everything
+    const uint32_t digits = (a.width + 7u) / 8u;
+    if (tid == 0) varied = 0;
+    LdsBarrier();
+    const uint32_t t = g < digits ? a.totals[g * 256 + d] : 0u;
+    if (t != 0 && t != n) atomicOr(&varied, 1u << g);
+    LdsBarrier();
+    active = varied;
+    if (tid == 0) *a.state = active;
+  } else {
+    active = *a.state;
+  }
+  if (((active >> a.pass) & 1u) == 0) return;  // uniform
+  const uint32_t total = tid < 256 ? a.totals[a.pass * 256 + d] : 0u;
+  const uint32_t exclusive = BlockExclusiveScan256(total, scanScratch, tid);
+  if (tid < 256) start[d] = exclusive;
+  // the rows in four groups, group g by the threads [256 g, 256 g + 256): sums first, then the running positions
+  const uint32_t chunks = RangeChunks(n, a.grid);
+  const uint32_t rows = (chunks + 3u) / 4u;
+  const uint32_t lo = min(g * rows, chunks), hi = min(lo + rows, chunks);
+  constexpr uint32_t B = 16;  // loads in flight per lane
+  uint32_t sum = 0;
+  for (uint32_t r0 = lo; r0 < hi; r0 += B) {
+    uint32_t v[B];
+#pragma unroll
+    for (uint32_t k = 0; k < B; ++k) v[k] = r0 + k < hi ? a.counts[(size_t)(r0 + k) * 256 + d] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < B; ++k) sum += v[k];
+  }
+  partial[g * 256 + d] = sum;
+  LdsBarrier();
+  uint32_t run = start[d];
+  for (uint32_t h = 0; h < g; ++h) run += partial[h * 256 + d];
+  for (uint32_t r0 = lo; r0 < hi; r0 += B) {
+    uint32_t v[B];
+#pragma unroll
+    for (uint32_t k = 0; k < B; ++k) v[k] = r0 + k < hi ? a.counts[(size_t)(r0 + k) * 256 + d] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < B; ++k) {
+      if (r0 + k < hi) a.counts[(size_t)(r0 + k) * 256 + d] = run;
+      run += v[k];
+    }
+  }
+}
+
+// LDS: RangeScatterLdsWords (vrdx_kernels.h).
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void range_scatter_kernel(RangeSortArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr int THREADS = 1024, KPT = 16, WAVES = THREADS / 64;
+  constexpr uint32_t TILE = kSegLargeTile;
+  uint32_t* const stagedKeys = smem;
+  uint32_t* const stagedValues = smem + TILE;  // KV only
+  uint32_t* const waveHist = smem + TILE * (KV ? 2 : 1);
+  uint32_t* const scanScratch = waveHist + WAVES * 256;
+  uint32_t* const base = scanScratch + 16;      // where the next key of digit d goes
+  uint32_t* const tileStart = base + 256;       // tile-local position of digit d's first key
+  uint32_t* const tileCount = tileStart + 256;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t n = ElementCount(a.maxCount, a.countPtr);
+  const uint32_t active = *a.state;
+  if (((active >> a.pass) & 1u) == 0) return;  // uniform
+  uint32_t begin = 0, length = 0;
+  if (!RangeChunkOf(a, n, &begin, &length)) return;  // uniform
+  const bool fromScratch = RangePassReadsScratch(active, a.pass);
+  const uint32_t* const src = (fromScratch ? a.keysScratch : a.keys) + begin;
+  uint32_t* const dst = fromScratch ? a.keys : a.keysScratch;
+  const uint32_t* const srcV = KV ? (fromScratch ? a.valuesScratch : a.values) + begin : nullptr;
+  uint32_t* const dstV = fromScratch ? a.values : a.valuesScratch;
+  if (tid < 256) base[tid] = a.counts[(size_t)blockIdx.x * 256 + tid];  // (first read two barriers into the first tile)
+  const uint32_t shift = RangeDigit(a.beginBit, a.width, a.pass);
+  uint32_t* const myHist = waveHist + wave * 256;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+#pragma unroll 1
+  for (uint32_t t0 = 0; t0 < length; t0 += TILE) {
+    const uint32_t m = min(TILE, length - t0);
+    // the chunks of four 64-key slots dealt out evenly over the waves, as in SegmentLsd: pads (the largest key) only in the
+    // last chunk, behind every real key of the tile -- and only in the array's last tile (chunkKeys is a multiple of 256)
+    const uint32_t chunks = (m + 255u) / 256u;
+    const uint32_t per = chunks / WAVES, extra = chunks % WAVES;
+    const uint32_t slots = 4u * (per + (w < extra ? 1u : 0u));
+    const uint32_t first = 256u * (w * per + (w < extra ? w : extra)) + lane;
+    uint32_t key[KPT];
+    uint32_t val[KV ? KPT : 1];
+    LoadStriped<KPT, false, true>(src + t0, first, m, false, 0xFFFFFFFFu, key, slots);
+    if constexpr (KV) LoadStriped<KPT, false, true>(srcV + t0, first, m, false, 0u, val, slots);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;
+    uint32_t rank[KPT];
+    if constexpr (ATOMIC_RANK)
+      RankAtomic<KPT, false, true, 0xFFu, true>(key, shift, myHist, lane, rank, slots);
+    else
+      RankBallot<KPT, false, true, true>(key, shift, myHist, lane, rank, slots);
+    LdsBarrier();
+    uint32_t c = 0;
+    if (tid < 256) {
+#pragma unroll
+      for (int v = 0; v < WAVES; ++v) c += waveHist[v * 256 + tid];
+    }
+    const uint32_t exclusive = BlockExclusiveScan256(tid < 256 ? c : 0u, scanScratch, tid);
+    if (tid < 256) {
+      uint32_t run = exclusive;
+#pragma unroll
+      for (int v = 0; v < WAVES; ++v) {
+        const uint32_t h = waveHist[v * 256 + tid];
+        waveHist[v * 256 + tid] = run;
+        run += h;
+      }
+      tileStart[tid] = exclusive;
+      // (the pads are the last keys of the digit of all ones, 2^w - 1 in a digit of w bits)
+      tileCount[tid] = (uint32_t)tid == (1u << (shift >> 8)) - 1u ? c - (256u * chunks - m) : c;
+    }
+    LdsBarrier();
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      if (i % 4 == 0 && (uint32_t)i >= slots) break;
+      const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[VRDX_DIGIT(true, 0xFFu, key[i], shift)]);
+      stagedKeys[slot] = key[i];
+      if constexpr (KV) stagedValues[slot] = val[i];
+    }
+    LdsBarrier();
+    // sorted position q of the tile -> base[d] + q - tileStart[d]: runs of one digit land contiguously
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      if (i % 4 == 0 && (uint32_t)i >= slots) break;
+      const uint32_t q = first + 64 * i;
+      if (q < m) {
+        const uint32_t slot = StagingSlot<TILE>(q);
+        const uint32_t k = stagedKeys[slot];
+        const uint32_t d = VRDX_DIGIT(true, 0xFFu, k, shift);
+        const uint32_t to = base[d] + q - tileStart[d];
+        // always < n when the table holds this pass's positions; whatever it holds, nothing is written outside [0, n)
+        if (to < n) {
+          dst[to] = k;
+          if constexpr (KV) dstV[to] = stagedValues[slot];
+        }
+      }
+    }
+    LdsBarrier();  // every lane has read base[] and tileStart[] of this tile
+    if (tid < 256) base[tid] += tileCount[tid];
+    // (the next tile reads base[] two barriers later, and writes the staging buffer and tileStart[] one barrier later)
+  }
+}
+
+// One thread per four elements of the bound, 256 elements apart (the caller's arrays may be aligned to 4 bytes only).
+template <bool KV>
+__global__ __launch_bounds__(kRangeCopyThreads) void range_copy_back_kernel(RangeSortArgs a) {
+  const uint32_t n = ElementCount(a.maxCount, a.countPtr);
+  if ((__popc(*a.state & 0xFu) & 1) == 0) return;  // an even number of active passes: the result is in place
+  const uint32_t first = blockIdx.x * (4u * kRangeCopyThreads) + threadIdx.x;
+  uint32_t k[4], v[KV ? 4 : 1];
+  (void)v;
+#pragma unroll
+  for (uint32_t u = 0; u < 4; ++u) {
+    const uint32_t i = first + u * kRangeCopyThreads;
+    k[u] = i < n ? a.keysScratch[i] : 0u;
+    if constexpr (KV) v[u] = i < n ? a.valuesScratch[i] : 0u;
+  }
+#pragma unroll
+  for (uint32_t u = 0; u < 4; ++u) {
+    const uint32_t i = first + u * kRangeCopyThreads;
+    if (i < n) {
+      a.keys[i] = k[u];
+      if constexpr (KV) a.values[i] = v[u];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs
 // ---------------------------------------------------------------------------------------------
 #include "vrdx_launch.inc"

@@ -363,6 +363,32 @@
   X(kSegmentedOrderedLargeVA, (&segmented_large_ordered_kernel<true, true>), 1024, SegmentLargeLdsWords(true) * 4, \
     "_ZN4vrdx30segmented_large_ordered_kernelILb1ELb1EEEvNS_13SegmentedArgsEj")
 
+// The kernels of the range sorts beyond one workgroup (vrdxHipCmdRangeSort*): a fourth list for the same reason.  Its ids
+// follow the wide-value list's (VRDX_ALL_KERNELS below); the text stands in front of that list, whose names stay the last of
+// this file.
+#define VRDX_RANGE_SORT_KERNELS(X) \
+  /* range_count_kernel [later passes | the first launch] */ \
+  X(kRangeCount, (&range_count_kernel<false>), 1024, 0, \
+    "_ZN4vrdx18range_count_kernelILb0EEEvNS_13RangeSortArgsE") \
+  X(kRangeCountFirst, (&range_count_kernel<true>), 1024, 0, \
+    "_ZN4vrdx18range_count_kernelILb1EEEvNS_13RangeSortArgsE") \
+  X(kRangeScan, (&range_scan_kernel), 1024, 0, \
+    "_ZN4vrdx17range_scan_kernelENS_13RangeSortArgsE") \
+  /* range_scatter_kernel [key-value][atomic rank] */ \
+  X(kRangeScatter, (&range_scatter_kernel<false, false>), 1024, RangeScatterLdsWords(false) * 4, \
+    "_ZN4vrdx20range_scatter_kernelILb0ELb0EEEvNS_13RangeSortArgsE") \
+  X(kRangeScatterA, (&range_scatter_kernel<false, true>), 1024, RangeScatterLdsWords(false) * 4, \
+    "_ZN4vrdx20range_scatter_kernelILb0ELb1EEEvNS_13RangeSortArgsE") \
+  X(kRangeScatterV, (&range_scatter_kernel<true, false>), 1024, RangeScatterLdsWords(true) * 4, \
+    "_ZN4vrdx20range_scatter_kernelILb1ELb0EEEvNS_13RangeSortArgsE") \
+  X(kRangeScatterVA, (&range_scatter_kernel<true, true>), 1024, RangeScatterLdsWords(true) * 4, \
+    "_ZN4vrdx20range_scatter_kernelILb1ELb1EEEvNS_13RangeSortArgsE") \
+  /* range_copy_back_kernel [key-value] */ \
+  X(kRangeCopyBack, (&range_copy_back_kernel<false>), kRangeCopyThreads, 0, \
+    "_ZN4vrdx22range_copy_back_kernelILb0EEEvNS_13RangeSortArgsE") \
+  X(kRangeCopyBackV, (&range_copy_back_kernel<true>), kRangeCopyThreads, 0, \
+    "_ZN4vrdx22range_copy_back_kernelILb1EEEvNS_13RangeSortArgsE")
+
 // The kernels of the sorts of 32-bit keys with 64-bit values (vrdxHipCmdWideValueSort*), in a third list behind the other two
 // for the same reason.
 #define VRDX_WIDE_VALUE_KERNELS(X) \
@@ -399,7 +425,8 @@
     "_ZN4vrdx27segmented_large_wide_kernelILb0EEEvNS_17SegmentedWideArgsE") \
   X(kSegmentedWideLargeA, (&segmented_large_wide_kernel<true>), 1024, SegmentWideLargeLdsWords() * 4, \
     "_ZN4vrdx27segmented_large_wide_kernelILb1EEEvNS_17SegmentedWideArgsE")
-#define VRDX_ALL_KERNELS(X) VRDX_KERNELS(X) VRDX_ORDERED32_KERNELS(X) VRDX_WIDE_VALUE_KERNELS(X)
+
+#define VRDX_ALL_KERNELS(X) VRDX_KERNELS(X) VRDX_ORDERED32_KERNELS(X) VRDX_WIDE_VALUE_KERNELS(X) VRDX_RANGE_SORT_KERNELS(X)
 
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
@@ -408,6 +435,7 @@ enum KernelId : int {
   kLastListedKernel = kNumKernels - 1,  // (the ordered list's first id is kNumKernels)
   VRDX_ORDERED32_KERNELS(VRDX_KERNEL_ID)
   VRDX_WIDE_VALUE_KERNELS(VRDX_KERNEL_ID)
+  VRDX_RANGE_SORT_KERNELS(VRDX_KERNEL_ID)
 #undef VRDX_KERNEL_ID
   kNumAllKernels
 };
@@ -735,4 +763,34 @@ hipError_t LaunchSegmentedWide(hipStream_t stream, SegmentClass sizeClass, uint3
                                const SegmentedWideArgs& args) {
   if (grid == 0) return hipErrorInvalidValue;
   return Launch(KernelId(kSegmentedWideSmall + 2 * sizeClass + atomicRank), grid, stream, args);
+}
+
+// ---- range sorts beyond one workgroup (VRDX_RANGE_SORT_KERNELS) ---------------------------------------
+// widths 1 ... 31 only (v_bfe_u32 takes a width modulo 32; the planner forwards the one range of 32 bits to the whole-key
+// sort); at most one chunk per 8192 keys of the bound, so that the rows of counts fit where MakeRangeSortLayout puts them
+static_assert(RangeScatterLdsWords(true) * 4 <= 160u * 1024u, "range_scatter_kernel's key+value form");
+static bool RangeSortFits(const RangeSortArgs& a, bool passLaunch) {
+  return a.width >= 1u && a.width <= 31u && a.beginBit + a.width <= 32u && a.maxCount != 0 && a.maxCount <= VRDX_MAX_ELEMENTS &&
+         a.grid != 0 && a.grid == RangeSortGrid(a.maxCount, a.grid) && (!passLaunch || 8u * a.pass < a.width);
+}
+
+hipError_t LaunchRangeCount(hipStream_t stream, const RangeSortArgs& args) {
+  if (!RangeSortFits(args, true)) return hipErrorInvalidValue;
+  return Launch(args.pass == 0 ? kRangeCountFirst : kRangeCount, args.grid, stream, args);
+}
+
+hipError_t LaunchRangeScan(hipStream_t stream, const RangeSortArgs& args) {
+  if (!RangeSortFits(args, true)) return hipErrorInvalidValue;
+  return Launch(kRangeScan, 1, stream, args);
+}
+
+hipError_t LaunchRangeScatter(hipStream_t stream, bool keyValue, bool atomicRank, const RangeSortArgs& args) {
+  if (!RangeSortFits(args, true) || keyValue != (args.values != nullptr)) return hipErrorInvalidValue;
+  return Launch(Form(kRangeScatter, keyValue, atomicRank), args.grid, stream, args);
+}
+
+hipError_t LaunchRangeCopyBack(hipStream_t stream, bool keyValue, const RangeSortArgs& args) {
+  if (!RangeSortFits(args, false) || keyValue != (args.values != nullptr)) return hipErrorInvalidValue;
+  const uint32_t grid = (args.maxCount + 4u * kRangeCopyThreads - 1u) / (4u * kRangeCopyThreads);
+  return Launch(keyValue ? kRangeCopyBackV : kRangeCopyBack, grid, stream, args);
 }

@@ -314,6 +314,61 @@ static inline SegmentedLayout MakeSegmentedWideLayout(uint32_t maxElementCount, 
   return s;
 }
 
+// The chunks of a range sort beyond one workgroup (vrdxHipCmdRangeSort*; PlanRangeSort in vrdx_plan.h; vrdx_kernels.hip,
+// "range sort"): workgroup c of every count and scatter launch owns the contiguous keys [c * chunkKeys, min(n, (c + 1) *
+// chunkKeys)).  ONE formula for the host and the kernels: the host sizes the grid from the element count (the bound of an
+// indirect call), the kernels evaluate RangeChunkKeys with the count they read and their own grid size -- a count of 5 under
+// a bound of 8 M is one short chunk and 255 workgroups that return.
+//   grid      = min(CUs, n / 8192), at least 1
+//   chunkKeys = ceil(n / min(grid, n / 8192)) rounded up to a multiple of 256: at least 8192 keys (the last chunk holds what
+//               is left), so that only the array's very last tile ever has pad keys and chunks <= n / 8192 rows of counts fit
+//               half of the reference's partition-histogram area.
+constexpr uint32_t kRangeChunkMinKeys = 8192u;
+static constexpr uint32_t RangeSortGrid(uint32_t elementCount, uint32_t cus) {
+  const uint32_t most = elementCount / kRangeChunkMinKeys;
+  const uint32_t grid = cus < most ? cus : most;
+  return grid != 0 ? grid : 1u;
+}
+static constexpr uint32_t RangeChunkKeys(uint32_t n, uint32_t grid) {
+  const uint32_t g = RangeSortGrid(n, grid);
+  return Align(RoundUp(n, g), 256u);
+}
+static constexpr uint32_t RangeChunks(uint32_t n, uint32_t grid) { return n != 0 ? RoundUp(n, RangeChunkKeys(n, grid)) : 0u; }
+
+// The chunked range sort's carving of the 32-bit storage (vrdxGetSorter[KeyValue]StorageRequirements(maxElementCount)):
+//   [0, 16)                        header: count, word 1 = VRDX_HIP_VERDICT_NONE, word 2 = the mask of ACTIVE passes (written
+//                                  by the first scan launch), failure word -- zeroed by the fill with the totals behind them
+//   histogramOffset                uint32 totals[4][256]: the counts of the field's P digits over the whole array, added up
+//                                  by the first count launch (rows P ... 3 stay zero)
+//   countsOffset                   first 128-byte line behind the totals: uint32 counts[grid][256], reused by every pass --
+//                                  the count launch leaves chunk c's counts of the pass's digit, the scan launch turns them
+//                                  into the absolute position of chunk c's first key of each digit.  grid KiB <= n / 8192
+//                                  KiB, at most half of the reference's partition-histogram area (ceil(n / 4096) KiB)
+//   keysScratchOffset              uint[N] on the first 128-byte line behind the table
+//   valuesScratchOffset            uint[N] behind it (128-byte aligned), key+value only
+struct RangeSortLayout {
+  uint64_t totalsOffset, countsOffset, countsBytes;
+  uint64_t keysScratchOffset, valuesScratchOffset;
+  uint64_t clearBytes;  // header + totals: what the fill zeroes
+  bool fits;            // every region lies inside the storage requirement of the requested form (keys-only | key+value)
+};
+
+static inline RangeSortLayout MakeRangeSortLayout(uint32_t maxElementCount, uint32_t align, uint32_t grid, bool keyValue,
+                                                  uint64_t storageAddress = 0) {
+  const StorageLayout l = MakeLayout(maxElementCount, align, 0, storageAddress);
+  RangeSortLayout r;
+  r.totalsOffset = l.histogramOffset;
+  r.countsOffset = l.msdBucketOffset;
+  r.countsBytes = (uint64_t)grid * VRDX_RADIX * sizeof(uint32_t);
+  r.clearBytes = l.clearBytes;
+  const uint64_t tableEnd = r.countsOffset + r.countsBytes;
+  r.keysScratchOffset = tableEnd + ((0 - (storageAddress + tableEnd)) & 127u);
+  r.valuesScratchOffset = r.keysScratchOffset + (((uint64_t)maxElementCount * sizeof(uint32_t) + 127u) & ~(uint64_t)127u);
+  const uint64_t bytes = (uint64_t)maxElementCount * sizeof(uint32_t);
+  r.fits = r.keysScratchOffset + bytes <= l.keysOnlySize && (!keyValue || r.valuesScratchOffset + bytes <= l.keyValueSize);
+  return r;
+}
+
 // The MSD plan's scatter (msd_scatter_or_pass0_kernel, one workgroup per CU and tile) cuts the sort into EQUAL tiles that fill whole
 // rounds of `cus` tiles: keys per tile, a multiple of 4096 (four 64-key slots per wave of its 1024 threads), at most 32768.
 // 520 tiles of 32768 keys would cost three rounds, the third for eight tiles; 768 tiles of 24576 cost three rounds of three

@@ -350,6 +350,85 @@ static inline SortPlan PlanSortBits(const PlanContext& c, bool keyValue, uint32_
   return p;
 }
 
+// The plan of a range sort at every size (vrdxHipCmdRangeSort[KeyValue][Indirect]; include/vk_radix_sort.h).  Up to
+// kSmallSortMaxElements elements, and for the full, the empty and an invalid range, it IS PlanSortBits' plan (`inner`, which the
+// recorder hands to the recorder of vrdxHipCmdSortBits*: the same launches, the same slots).  Beyond that, where PlanSortBits
+// refuses, the chunked form (vrdx_kernels.hip, "range sort") with a step list of its own -- SortPlan
+// and kMaxSortSteps stay what they are:
+//   fill (header and totals; an indirect count is copied)                        slot 1
+//   digit p = 0 ... P - 1, P = ceil(width / 8):  range_count_kernel              slot 2 + 3 p
+//                                                 range_scan_kernel               slot 3 + 3 p
+//                                                 range_scatter_kernel            slot 4 + 3 p
+//   range_copy_back_kernel                                                        slot 14
+// 3 P + 1 launches, known from the range alone; which passes are active and whether the copy back copies is decided on the
+// device.  `grid` workgroups take the chunks of RangeChunkKeys (vrdx_layout.h), sized from elementCount -- the bound of an
+// indirect call.  Like PlanSortBits the chunked form is chosen by size alone: no planning knob selects anything in it.
+enum class RangeSortForm : uint8_t { kNone, kOneWorkgroup, kWholeKey, kChunked };  // VRDX_HIP_RANGE_SORT_*
+enum class StepRange : uint8_t { kFill, kCount, kScan, kScatter, kCopyBack };
+struct RangeSortStep { StepRange what; uint8_t pass, slot; const char* name; };
+constexpr uint32_t kMaxRangeSortSteps = 2 + 3 * VRDX_PASSES;
+struct RangeSortPlan {
+  RangeSortForm form = RangeSortForm::kNone;
+  SortPlan inner{};               // every form but kChunked: PlanSortBits' plan, refusal included
+  bool keyValue = false;
+  uint32_t elementCount = 0;
+  bool atomicRank = false;
+  uint32_t rangeBegin = 0, rangeWidth = 0;
+  // kChunked only
+  uint32_t digits = 0;            // P
+  uint32_t grid = 0;              // chunks = workgroups of the count and scatter launches
+  uint32_t chunkKeys = 0;         // keys per chunk for elementCount itself (an indirect count: RangeChunkKeys on the device)
+  RangeSortLayout layout{};
+  const char* refusal = nullptr;  // the layout does not fit (cannot happen: see MakeRangeSortLayout)
+  RangeSortStep steps[kMaxRangeSortSteps];
+  uint32_t stepCount = 0;
+  uint32_t launches = 0;          // kernels among the steps
+};
+
+static inline RangeSortPlan PlanRangeSort(const PlanContext& c, bool keyValue, uint32_t elementCount, uint32_t beginBit,
+                                          uint32_t endBit, uint64_t storageAddress) {
+  RangeSortPlan p;
+  p.keyValue = keyValue;
+  p.elementCount = elementCount;
+  p.atomicRank = c.atomicRank;
+  const bool valid = beginBit <= endBit && endBit <= 32;
+  const bool partial = valid && beginBit != endBit && endBit - beginBit != 32;
+  if (!partial || elementCount <= kSmallSortMaxElements) {
+    p.inner = PlanSortBits(c, keyValue, elementCount, beginBit, endBit, storageAddress);
+    p.rangeBegin = p.inner.rangeBegin;
+    p.rangeWidth = p.inner.rangeWidth;
+    p.launches = p.inner.launches;
+    p.form = p.inner.stepCount == 0 ? RangeSortForm::kNone
+             : partial              ? RangeSortForm::kOneWorkgroup
+                                    : RangeSortForm::kWholeKey;
+    return p;
+  }
+  p.form = RangeSortForm::kChunked;
+  p.rangeBegin = beginBit;
+  p.rangeWidth = endBit - beginBit;  // 1 ... 31
+  p.digits = (p.rangeWidth + 7u) / 8u;
+  p.grid = RangeSortGrid(elementCount, (uint32_t)c.computeUnits);
+  p.chunkKeys = RangeChunkKeys(elementCount, p.grid);
+  p.layout = MakeRangeSortLayout(elementCount, c.minStorageBufferOffsetAlignment, p.grid, keyValue, storageAddress);
+  if (!p.layout.fits) {
+    p.form = RangeSortForm::kNone;
+    p.refusal = "range sort storage layout";
+    return p;
+  }
+  const auto add = [&p](StepRange what, const char* name, uint32_t slot, uint32_t pass = 0) {
+    p.steps[p.stepCount++] = RangeSortStep{what, (uint8_t)pass, (uint8_t)slot, name};
+    if (what != StepRange::kFill) ++p.launches;
+  };
+  add(StepRange::kFill, "hipMemcpyAsync(count)", 1);
+  for (uint32_t pass = 0; pass < p.digits; ++pass) {
+    add(StepRange::kCount, "range_count_kernel", 2 + 3 * pass, pass);
+    add(StepRange::kScan, "range_scan_kernel", 3 + 3 * pass, pass);
+    add(StepRange::kScatter, "range_scatter_kernel", 4 + 3 * pass, pass);
+  }
+  add(StepRange::kCopyBack, "range_copy_back_kernel", 14);
+  return p;
+}
+
 // The plan of an ordered 32-bit sort (vrdxHipCmdOrderedSort[KeyValue][Indirect]; include/vk_radix_sort.h) in the order of the
 // word `order` (vrdx_kernels.h, kKeyOrder*): kKeyOrderUint32 is PlanSort itself; an invalid word has no step and is refused.
 // Otherwise the plan is PlanSort's with its steps listed again: one workgroup runs small_sort_ordered_kernel, and beyond that
@@ -654,6 +733,27 @@ static inline void DescribeWideValuePlan(const PlanContext& c, const WideValuePl
     info->launches = 2 + 2 * inner.launches;
     info->bytesPerElement = 24 + 2 * inner.bytesPerElement + 16;  // split | two sorts | merge
   }
+}
+
+// What vrdxHipDescribeRangeSortPlan reports of a plan (include/vk_radix_sort.h); *info zeroed by the caller.
+static inline void DescribeRangeSortPlan(const RangeSortPlan& plan, VrdxHipRangeSortPlanInfo* info) {
+  info->form = (uint32_t)plan.form;
+  info->launches = plan.launches;
+  if (plan.form != RangeSortForm::kChunked) {
+    if (plan.form == RangeSortForm::kNone) return;
+    VrdxHipPlanInfo inner{};
+    DescribePlan(plan.inner, &inner);
+    info->chunks = 1;
+    info->keysPerChunk = plan.elementCount;
+    info->digits = plan.form == RangeSortForm::kOneWorkgroup ? (plan.rangeWidth + 7u) / 8u : VRDX_PASSES;
+    info->bytesPerElementPerPass = inner.bytesPerElement;  // the whole sort: the digits are ranked between one load and one store
+    return;
+  }
+  info->chunks = plan.grid;
+  info->keysPerChunk = plan.chunkKeys;
+  info->digits = plan.digits;
+  info->bytesPerElementPerPass = plan.keyValue ? 20u : 12u;  // count (keys read) + scatter (read + write)
+  info->bytesPerElementCopyBack = plan.keyValue ? 16u : 8u;
 }
 
 }  // namespace vrdx
