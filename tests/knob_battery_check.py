@@ -3,9 +3,9 @@ per process (vrdx_api.cpp, EnvKnobs), so tests/test_knobs_gpu.py starts this scr
 environment.  argv[1] is the setting's name.
 
 First the plans: for every (n, mode) of the setting's cases, what describe_plan, describe_ordered_sort_plan,
-describe_sort_bits_plan and describe_wide_value_sort_plan report against knob_cases.expected_plan -- a mismatch is a failure,
-and a child whose environment did not arrive fails here.  Then every case through guarded_call / ordered_call / wide_call /
-wide_segmented_call on poisoned storage: guard bytes, failure word, the sorter's sticky word, and the arrays bit for bit
+describe_sort_bits_plan, describe_range_sort_plan and describe_wide_value_sort_plan report against knob_cases.expected_plan -- a
+mismatch is a failure, and a child whose environment did not arrive fails here.  Then every case through guarded_call /
+range_call / ordered_call / wide_call / wide_segmented_call on poisoned storage: guard bytes, failure word, the sorter's sticky word, and the arrays bit for bit
 against the case's reference.  No case is skipped; a refusal is a failure except where the case is marked refused.
 
 One line per plan point and per case; the last line is "<cases> cases, <failures> failures".  Exit status 0 only with 0
@@ -23,6 +23,7 @@ import numpy as np
 import knob_cases
 from guarded_call import guarded_call
 from ordered_guarded_call import ordered_call
+from range_guarded_call import AsRangeSort
 from vulkan_radix_sort_amd import api
 from wide_guarded_call import wide_call
 from wide_segmented_guarded_call import wide_segmented_call
@@ -37,6 +38,12 @@ def check_plans(sorter, setting, rows):
             info = sorter.describe_wide_value_sort_plan(n)
             got, want = (info.name, int(info.oneWorkgroupMax)), (want, knob_cases.expected_wide_one_workgroup_max(setting))
             what = f"wide-value plan n={n}"
+        elif kind == "range":   # part of the key: the form alone; the whole key: PlanSort's launches under this setting
+            info = sorter.describe_range_sort_plan(n, key_value, *extra)
+            want = knob_cases.expected_plan(setting, n, key_value, kind, bit_range=extra)
+            got, what = info.name, "range-sort plan n=%d bits=[%d,%d)" % (n, *extra)
+            if want == "whole-key":
+                got, want = (got, int(info.launches)), (want, knob_cases.expected_launches(setting, n, key_value))
         elif isinstance(extra, tuple):
             got, what = sorter.describe_sort_bits_plan(n, key_value, *extra).name, "sort-bits plan n=%d bits=[%d,%d)" % (n, *extra)
         elif extra is not None:
@@ -63,7 +70,9 @@ def run_case(torch, sorter, case, device="cuda"):
                                offsets=offsets, device_count=case.count, **common)
         else:
             order = knob_cases.key_order_cases.order_word(*case.order[:2]) if case.order is not None else None
-            got = guarded_call(torch, sorter, keys, values, offsets=offsets, device_count=case.count,
+            ranged = "RangeSort" in case.entry   # (the arguments of vrdxHipCmdSortBits*, name for name: range_guarded_call.py)
+            got = guarded_call(torch, AsRangeSort(sorter) if ranged else sorter, keys, values, offsets=offsets,
+                               device_count=case.count,
                                bit_range=case.bit_range, order=order, expect_refused=case.refused, **common)
     except AssertionError as e:
         # the sorter's word is read whatever happened, so that it is this case's alone; a refused call leaves the poisoned

@@ -1,14 +1,16 @@
 """What tests/test_knobs_gpu.py (on the GPU, through tests/knob_battery_check.py) and tests/test_knob_cases.py (without one)
 share: the planning knobs of the library as SETTINGS, the plan the host must report under each of them (expected_plan, written
 out from the rules of vrdx_plan.h and held to the compiled planner by tests/test_knob_cases.py), and cases(setting), the
-battery of composed sorts -- 64-bit, ordered, by a bit range, with 8-byte values -- that runs under that setting.  A plain
+battery of composed sorts -- 64-bit, ordered, by a bit range (vrdxHipCmdSortBits* and vrdxHipCmdRangeSort*), with 8-byte
+values: all twenty-two flat vrdxHipCmd* entry points -- that runs under that setting.  A plain
 module next to storage_reuse_cases.py, imported the same way; it needs numpy only.
 
 The knobs are read once per process (vrdx_api.cpp, EnvKnobs), so a setting is the environment of a fresh child.  They send the
 32-bit sorts INSIDE the composed sorts down kernels the size-adaptive choice never takes at that size: the general path at
 1 ... 16384 elements (VRDX_SMALL_SORT=0, any VRDX_TILE_CONFIG), four passes at the hybrid plan's sizes (VRDX_HYBRID=0) and at
-the MSD plan's (VRDX_MSD=0: block sums; with VRDX_BLOCK_SUMS=0 the classic look-back).  The segmented sorts and the range
-sorts over part of the key take no notice of them; the battery holds them to that.
+the MSD plan's (VRDX_MSD=0: block sums; with VRDX_BLOCK_SUMS=0 the classic look-back).  The segmented sorts and the sorts
+over part of the key take no notice of them -- vrdxHipCmdSortBits* and, at every size, the chunked form included,
+vrdxHipCmdRangeSort* --; the battery holds them to that.  A range sort over (0, 32) is the whole-key sort, knobs and all.
 
 Keys, values and references are those of the case modules of each family -- sort64_model / key_order_cases,
 key_order32_cases, sort_bits_cases, wide_value_cases, segmented_cases, segmented64_cases, segmented_bits_cases,
@@ -36,6 +38,7 @@ WIDE_ONE_WORKGROUP_MAX = wide_value_cases.ONE_WORKGROUP_MAX   # kWideSmallMaxEle
 WIDE_TWO_SORTS_FROM = 1 << 24       # kWideValueTwoSortsFrom (vrdx_plan.h)
 HYBRID_LAST = {True: 8_144_384, False: 4_072_192}   # HybridCapacity's last size: one-atomic ranking, ballot ranking
 MSD_LAST = 67_108_864               # MsdBits' last size (one-atomic ranking only)
+MSD_HALF_LAST = 18_149_376          # ... with the half-size bucket kernel, one launch more
 
 SETTINGS = {
     "default": {},
@@ -54,11 +57,13 @@ SETTINGS = {
 KNOBS = ("VRDX_SMALL_SORT", "VRDX_HYBRID", "VRDX_MSD", "VRDX_BLOCK_SUMS", "VRDX_TILE_CONFIG")   # (VRDX_RANK picks the sorter)
 
 
-def expected_plan(setting, n, key_value, kind="sort", atomic=None):
+def expected_plan(setting, n, key_value, kind="sort", atomic=None, bit_range=None):
     """The name the host must report for n elements under a setting.  kind "sort": vrdxHipDescribePlan,
     vrdxHipDescribeOrderedSortPlan and vrdxHipDescribeSortBitsPlan over (0, 32) (api.PLAN_NAMES; the same with and without
     values); "bits": vrdxHipDescribeSortBitsPlan over part of the key; "wide": the form of vrdxHipDescribeWideValueSortPlan
-    (api.WIDE_VALUE_FORM_NAMES).  atomic: the ranking (default: the setting's sorter)."""
+    (api.WIDE_VALUE_FORM_NAMES); "range": the form of vrdxHipDescribeRangeSortPlan over `bit_range`
+    (api.RANGE_SORT_FORM_NAMES) -- over (0, 32) "whole-key", whose launches are those of kind "sort" under the same
+    setting (expected_launches).  atomic: the ranking (default: the setting's sorter)."""
     env = SETTINGS[setting]
     atomic = env.get("VRDX_RANK") != "ballot" if atomic is None else atomic
     small_sort = env.get("VRDX_SMALL_SORT") != "0"
@@ -69,6 +74,10 @@ def expected_plan(setting, n, key_value, kind="sort", atomic=None):
         return "none"
     if kind == "bits":     # by size alone: no knob reaches a range sort (PlanSortBits)
         return "one-workgroup" if n <= ONE_WORKGROUP_MAX else "none"
+    if kind == "range":    # PlanRangeSort: the whole key is PlanSort itself; part of it by size alone, and never refused
+        if bit_range == (0, 32):
+            return "whole-key"
+        return "one-workgroup" if n <= ONE_WORKGROUP_MAX else "chunked"
     if kind == "wide":     # PlanWideValueSort looks at VRDX_SMALL_SORT only: a forced tile geometry keeps one workgroup
         if n <= WIDE_ONE_WORKGROUP_MAX and small_sort:
             return "one-workgroup"
@@ -83,6 +92,15 @@ def expected_plan(setting, n, key_value, kind="sort", atomic=None):
     if n <= HYBRID_LAST[atomic]:
         return "hybrid-8"
     return "msd" if msd and atomic and n <= MSD_LAST else "four-passes"
+
+
+LAUNCHES = {"none": 0, "one-workgroup": 1, "four-passes": 5, "hybrid-8": 6}   # (plan_check_tool's tables; msd: 7 | 6)
+
+
+def expected_launches(setting, n, key_value, atomic=None):
+    """the launches of the whole-key plan (kind "sort") under a setting, which a range sort over (0, 32) must report as its own"""
+    name = expected_plan(setting, n, key_value, "sort", atomic)
+    return (7 if n <= MSD_HALF_LAST else 6) if name == "msd" else LAUNCHES[name]
 
 
 def expected_wide_one_workgroup_max(setting):
@@ -133,9 +151,10 @@ def seed_of(case):
 
 
 def _flat(group, family, n, count=None, key_value=False, bit_range=None, order=None):
-    """One flat call of a family: "Sort64" | "Sort64Ordered" | "OrderedSort" | "SortBits" | "WideValueSort" """
+    """One flat call of a family: "Sort64" | "Sort64Ordered" | "OrderedSort" | "SortBits" | "RangeSort" | "WideValueSort" """
     entry = "vrdxHipCmd" + family + ("KeyValue" if key_value else "") + ("Indirect" if count is not None else "")
-    refused = bit_range is not None and bit_range != (0, 32) and n > ONE_WORKGROUP_MAX
+    # (vrdxHipCmdSortBits* refuse part of the key beyond one workgroup; vrdxHipCmdRangeSort* refuse no size)
+    refused = family == "SortBits" and bit_range != (0, 32) and n > ONE_WORKGROUP_MAX
     return Case(group, entry, n, count, bit_range, order, refused)
 
 
@@ -147,6 +166,7 @@ def _family_rows(group, n, count=None):
         rows += [_flat(group, "Sort64Ordered", n, count, key_value, order=order) for order in ORDERS64]
         rows += [_flat(group, "OrderedSort", n, count, key_value, order=order) for order in ORDERS32]
         rows += [_flat(group, "SortBits", n, count, key_value, bit_range=r) for r in RANGES]
+        rows += [_flat(group, "RangeSort", n, count, key_value, bit_range=r) for r in RANGES]
     rows.append(_flat(group, "WideValueSort", n, count))
     return rows
 
@@ -180,6 +200,8 @@ def _mid_cases():
     for n in MID:
         rows += [_flat("mid", "Sort64", n, key_value=True), _flat("mid", "OrderedSort", n, key_value=True, order=FLOAT32_DESCENDING),
                  _flat("mid", "SortBits", n, bit_range=(0, 32)), _flat("mid", "WideValueSort", n)]
+    # the range sorts beyond one workgroup: the chunked form, which no knob may reach, and the whole key at the hybrid plan's size
+    rows += [_flat("mid", "RangeSort", 40_001, bit_range=(5, 22)), _flat("mid", "RangeSort", H, bit_range=(0, 32))]
     return rows
 
 
@@ -216,6 +238,8 @@ def plan_points(rows):
             point = (case.n, "wide", True, None)
         elif "SortBits" in case.entry:
             point = (case.n, "sort" if case.bit_range == (0, 32) else "bits", key_value, case.bit_range)
+        elif "RangeSort" in case.entry:
+            point = (case.n, "range", key_value, case.bit_range)
         else:
             point = (case.n, "sort", key_value, key_order32_cases.order_word(*case.order[:2]))
         if point not in points:
@@ -253,7 +277,7 @@ def inputs_of(case):
     elif "OrderedSort" in entry:  # (key+value: seven keys of both signs, every element with many equals)
         builder = "duplicates" if key_value and case.group == "small" else case.order[2]
         keys = key_order32_cases.make_keys(builder, total, rng, *case.order[:2])
-    elif "Bits" in entry:
+    elif "Bits" in entry or "RangeSort" in entry:
         keys = sort_bits_cases.make_keys("few" if key_value else "uniform", total, *case.bit_range, rng)
     else:
         keys = segmented_cases.make_keys("uniform", total, rng)
@@ -290,5 +314,5 @@ def expected_of(case):
         return key_order_cases.expected(keys, values, *order, count=n)
     if "OrderedSort" in entry:
         return key_order32_cases.expected(keys, values, *case.order[:2], count=n)
-    assert "SortBits" in entry, entry
+    assert "SortBits" in entry or "RangeSort" in entry, entry
     return sort_bits_cases.reference(keys, values, *case.bit_range, n)

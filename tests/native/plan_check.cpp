@@ -11,9 +11,11 @@
 //                                           tile geometry -- what the Python tests hold their hand-kept numbers to.
 //   plan_check describe <cus> <atomic> NAME=VALUE... <n>...   the same under planning knobs, spelled as in the environment
 //                                           (VRDX_SMALL_SORT=0, VRDX_HYBRID=0, VRDX_MSD=0, VRDX_BLOCK_SUMS=0, VRDX_TILE_CONFIG=1024x8
-//                                           ...; read as EnvKnobs of vrdx_api.cpp reads them), with three more fields per line:
+//                                           ...; read as EnvKnobs of vrdx_api.cpp reads them), with six more fields per line:
 //                                           the plan's name of a sort by the bits [8, 16), the form of the wide-value sort
-//                                           (api.py, WIDE_VALUE_FORM_NAMES) and its oneWorkgroupMax.
+//                                           (api.py, WIDE_VALUE_FORM_NAMES) and its oneWorkgroupMax, the form of the range sort
+//                                           by the bits [8, 16) (api.py, RANGE_SORT_FORM_NAMES) and the form and the
+//                                           launches of the range sort over [0, 32).
 // Built by tests/native/Makefile; nothing of HIP is linked (vrdx_kernels.h needs one of its headers).
 #include <algorithm>
 #include <cstdint>
@@ -80,6 +82,15 @@ bool SetKnob(vrdx::PlanContext& c, std::string_view knob) {
   return true;
 }
 
+const char* RangeFormName(vrdx::RangeSortForm form) {
+  switch (form) {
+    case vrdx::RangeSortForm::kOneWorkgroup: return "one-workgroup";
+    case vrdx::RangeSortForm::kWholeKey: return "whole-key";
+    case vrdx::RangeSortForm::kChunked: return "chunked";
+    default: return "none";
+  }
+}
+
 const char* WideFormName(vrdx::WideValueForm form) {
   switch (form) {
     case vrdx::WideValueForm::kOneWorkgroup: return "one-workgroup";
@@ -127,6 +138,9 @@ int Describe(int argc, char** argv) {
         const vrdx::WideValuePlan w = vrdx::PlanWideValueSort(c, n, 0);
         vrdx::DescribeWideValuePlan(c, w, &wide);
         std::printf(" %s %s %u", PlanName(rangedInfo.plan), WideFormName(w.form), wide.oneWorkgroupMax);
+        const vrdx::RangeSortPlan partial = vrdx::PlanRangeSort(c, keyValue != 0, n, 8, 16, 0);  // (as vrdxHipDescribeRangeSortPlan)
+        const vrdx::RangeSortPlan whole = vrdx::PlanRangeSort(c, keyValue != 0, n, 0, 32, 0);
+        std::printf(" %s %s %u", RangeFormName(partial.form), RangeFormName(whole.form), whole.launches);
       }
       std::printf("\n");
     }

@@ -18,8 +18,10 @@ BALLOT_TABLE = [(16_384, "one-workgroup", 0, 0, 0, 1), (524_288, "hybrid-8", 8, 
 FOUR_PASSES = ("four-passes", 0, 0, 0, 5)
 
 Row = collections.namedtuple("Row", "name bits hybrid_cap msd_cap launches config")
-# ... and under knobs: the plan of a sort by the bits [8, 16), the form of the wide-value sort, its oneWorkgroupMax
-KnobRow = collections.namedtuple("KnobRow", Row._fields + ("bits_plan", "wide_form", "wide_one_workgroup_max"))
+# ... and under knobs: the plan of a sort by the bits [8, 16), the form of the wide-value sort, its oneWorkgroupMax, the form
+# of the range sort by the bits [8, 16), form and launches of the range sort over [0, 32)
+KnobRow = collections.namedtuple("KnobRow", Row._fields + ("bits_plan", "wide_form", "wide_one_workgroup_max", "range_form",
+                                                            "range_whole_form", "range_whole_launches"))
 
 
 @functools.lru_cache(maxsize=1)
@@ -43,7 +45,7 @@ def describe(compute_units, atomic_rank, sizes, knobs=None):
         n, key_value, name, bits, hybrid_cap, msd_cap, launches, config, *more = line.split()
         row = Row(name, int(bits), int(hybrid_cap), int(msd_cap), int(launches), config)
         if knobs is not None:
-            row = KnobRow(*row, more[0], more[1], int(more[2]))
+            row = KnobRow(*row, more[0], more[1], int(more[2]), more[3], more[4], int(more[5]))
         table[int(n), key_value == "1"] = row
     assert len(table) == 2 * len(sizes)
     return table

@@ -121,11 +121,20 @@ def case_inputs(builder, n, begin, end):
 SCRATCH_KEY = 0xA5A5A5A5   # what the model's scratch arrays hold before the sort (the GPU tests' poison)
 
 
-def sort_range_model(keys, values, begin, end, cus, count=None, bound=None, fault=None, tile=TILE):
+def sort_range_model(keys, values, begin, end, cus, count=None, bound=None, fault=None, tile=TILE, stale_totals=None,
+                     stale_mask=None, stale_counts=None):
     """(keys, values, info) as the call leaves the caller's arrays; info: "form", and for the chunked form "active" (the mask),
-    "chunks", "chunk_keys", "copy_back" and "scratch_written".  bound: maxElementCount (default: all of keys); count: what the
-    device reads (default: the bound).  tile: kSegLargeTile as built; a tile that is no multiple of 256 has pads in every tile
-    of a chunk, not only in its last one (fault 6)."""
+    "chunks", "chunk_keys", "copy_back" and "scratch_written", and what the call leaves in the storage: "totals" ([4][256])
+    and "counts" (the table of per-chunk counts as the last active pass's scan left it, one row per chunk).  bound:
+    maxElementCount (default: all of keys); count: what the device reads (default: the bound).  tile: kSegLargeTile as built; a
+    tile that is no multiple of 256 has pads in every tile of a chunk, not only in its last one (fault 6).
+
+    What the storage held before, each for a device that has lost the clear or the store that makes it harmless (the device as
+    it stands zeroes the totals with the header, stores the mask in its first scan launch and STORES each row of counts):
+      stale_totals  [4][256] (or one word for every bin): the fill does not reach the totals, the count launch adds to them;
+      stale_mask    header word 2 as another sort left it, and the first scan launch does not store its own: that launch still
+                    decides from the totals whether it has anything to scan, every other launch reads the stale word;
+      stale_counts  rows of the table of per-chunk counts: the count launch adds to its row instead of storing it."""
     assert fault is None or fault in FAULTS, fault
     keys = np.asarray(keys, np.uint32)
     bound = len(keys) if bound is None else bound
@@ -162,7 +171,13 @@ def sort_range_model(keys, values, begin, end, cus, count=None, bound=None, faul
     # the first count launch: the totals of every digit, from the input; the first scan launch: the active passes
     bins = 512
     totals = [np.bincount(digit_of(keys[:n], p)[0], minlength=bins) for p in range(digits)]
-    active = [bool(((t != 0) & (t != n)).any()) for t in totals]
+    if stale_totals is not None:
+        before = np.broadcast_to(np.asarray(stale_totals, np.int64), (4, 256))
+        for p in range(digits):
+            totals[p][:256] += before[p]
+    derived = [bool(((t != 0) & (t != n)).any()) for t in totals]   # what the first scan launch finds
+    active = derived if stale_mask is None else [bool((stale_mask >> p) & 1) for p in range(digits)]   # ... every other launch
+    left_counts = np.zeros((0, 256), np.int64)
     for p in range(digits):
         if not active[p]:
             continue
@@ -170,9 +185,13 @@ def sort_range_model(keys, values, begin, end, cus, count=None, bound=None, faul
         counts = np.zeros((max(chunks, 1), bins), np.int64)
         for c in range(chunks):
             counts[c] = np.bincount(digit_of(counted[c * per_chunk:(c + 1) * per_chunk], p)[0], minlength=bins)
+            if stale_counts is not None and c < len(stale_counts):
+                counts[c][:256] += np.asarray(stale_counts[c], np.int64)
         start = np.concatenate([[0], np.cumsum(totals[p])[:-1]])
         table = counts.copy()
         scanned = -(-n // scan_chunk)   # rows the scan launch turns into positions
+        if p == 0 and not derived[0]:
+            scanned = 0                 # (under a stale mask: the first scan launch returns, the scatter meets raw counts)
         run = start.copy()
         for c in range(min(scanned, chunks)):
             table[c] = start if fault == "bases-ignore-chunks" else run
@@ -201,8 +220,11 @@ def sort_range_model(keys, values, begin, end, cus, count=None, bound=None, faul
                 if fault != "base-not-advanced":
                     base = base + with_pads
         scratch_written = scratch_written or in_caller
+        left_counts = table[:chunks, :256]
         src_k, dst_k, src_v, dst_v, in_caller = dst_k, src_k, dst_v, src_v, not in_caller
     copy_back = digits % 2 == 1 if fault == "copy-back-by-digits" else not in_caller
+    if stale_mask is not None:
+        copy_back = bin(stale_mask & 0xF).count("1") % 2 == 1
     caller_k, caller_v = (src_k, src_v) if in_caller else (dst_k, dst_v)
     scratch_k, scratch_v = (dst_k, dst_v) if in_caller else (src_k, src_v)
     if copy_back:
@@ -210,5 +232,7 @@ def sort_range_model(keys, values, begin, end, cus, count=None, bound=None, faul
     out_keys = np.concatenate([caller_k, keys[n:]]).astype(np.uint32)
     out_values = None if values is None else np.concatenate([caller_v, np.asarray(values[n:], np.uint32)]).astype(np.uint32)
     info = {"form": "chunked", "active": sum(1 << p for p in range(digits) if active[p]), "chunks": chunks,
-            "chunk_keys": per_chunk, "copy_back": copy_back, "scratch_written": scratch_written}
+            "chunk_keys": per_chunk, "copy_back": copy_back, "scratch_written": scratch_written,
+            "totals": np.array([totals[p][:256] if p < digits else np.zeros(256, np.int64) for p in range(4)]),
+            "counts": left_counts}
     return out_keys, out_values, info

@@ -3,7 +3,7 @@
 expected_plan against the compiled planner (tests/native/plan_check `describe` with the setting's knobs as arguments) at every
 (n, mode) the battery uses, for 256 CUs and both rankings; the case lists: deterministic, non-empty, together naming every flat
 vrdxHipCmd* entry point; and the battery itself -- run_battery of the child script -- over the default setting's small cases
-against HostSorter, a sorter on host memory in the manner of test_guarded_call.FakeSorter that covers the rows of all four
+against HostSorter, a sorter on host memory in the manner of test_guarded_call.FakeSorter that covers the rows of all five
 tables and can be told to misbehave: a clean one passes every case, and each planted fault makes the battery report failures
 that name the cases it must hit."""
 import ctypes
@@ -26,7 +26,9 @@ import wide_value_cases
 import wide_value_segmented_cases
 from vulkan_radix_sort_amd import api
 
-ALL_CALLS = api.RECORDING_CALLS + api.ORDERED_SORT_CALLS + api.WIDE_VALUE_CALLS + api.WIDE_VALUE_SEGMENTED_CALLS
+ALL_CALLS = (api.RECORDING_CALLS + api.ORDERED_SORT_CALLS + api.WIDE_VALUE_CALLS + api.WIDE_VALUE_SEGMENTED_CALLS
+             + api.RANGE_SORT_CALLS)
+RANGE_SORT_NAMES = {call.c_name for call in api.RANGE_SORT_CALLS}
 WIDE_VALUE_NAMES = {call.c_name for call in api.WIDE_VALUE_CALLS + api.WIDE_VALUE_SEGMENTED_CALLS}
 ORDERED32_NAMES = {call.c_name for call in api.ORDERED_SORT_CALLS}
 HEADER = 16   # HostSorter's storage: four words, the failure word the last of them
@@ -66,7 +68,30 @@ def test_expected_plan_is_what_the_compiled_planner_records(setting, atomic):
                     knob_cases.expected_plan(setting, n, key_value, "wide", atomic),
                     knob_cases.expected_wide_one_workgroup_max(setting))
             assert got == want, (setting, atomic, n, key_value)
+            # the range sorts: part of the key by size alone, the whole key with the launches of the whole-key plan
+            got = (row.range_form, row.range_whole_form, row.range_whole_launches, row.launches)
+            launches = knob_cases.expected_launches(setting, n, key_value, atomic)
+            want = (knob_cases.expected_plan(setting, n, key_value, "range", atomic, bit_range=(8, 16)),
+                    knob_cases.expected_plan(setting, n, key_value, "range", atomic, bit_range=(0, 32)), launches, launches)
+            assert got == want, (setting, atomic, n, key_value)
     assert all(kind == "wide" or (n, key_value) in table for n, kind, key_value in points)
+    assert any(kind == "range" and n > knob_cases.ONE_WORKGROUP_MAX for n, kind, _ in points)
+
+
+def test_a_partial_range_sort_is_planned_by_size_alone():
+    """one workgroup up to 16384 elements, chunked beyond, under every setting; never "none": no size is refused"""
+    for setting in knob_cases.SETTINGS:
+        for key_value in (False, True):
+            for r in knob_cases.RANGES[1:]:
+                assert knob_cases.expected_plan(setting, 1, key_value, "range", bit_range=r) == "one-workgroup"
+                assert knob_cases.expected_plan(setting, 16384, key_value, "range", bit_range=r) == "one-workgroup"
+                assert knob_cases.expected_plan(setting, 16385, key_value, "range", bit_range=r) == "chunked"
+                assert knob_cases.expected_plan(setting, knob_cases.M, key_value, "range", bit_range=r) == "chunked"
+            assert knob_cases.expected_plan(setting, 100, key_value, "range", bit_range=(0, 32)) == "whole-key"
+    launches = knob_cases.expected_launches
+    assert launches("default", 100, False) == 1 and launches("small-sort-off", 100, False) == 5
+    assert launches("default", knob_cases.H, True) == 6 and launches("hybrid-off", knob_cases.H, True) == 5
+    assert launches("default", knob_cases.M, True) == 7 and launches("msd-off", knob_cases.M, True) == 5
 
 
 def test_describe_without_knobs_is_what_it_was():
@@ -122,6 +147,12 @@ def test_the_batteries_by_group():
         (b, k) for b in knob_cases.INDIRECT_BOUNDS for k in (0, 1, b - 1, b, b + 7)}
     refused = [c for c in small if c.refused]
     assert refused and all(c.n == 16385 and c.bit_range != (0, 32) and "SortBits" in c.entry for c in refused)
+    # the range sorts: the four RANGES at every size and count of the sweep, keys-only and key+value, none of them refused
+    ranged = [c for c in small if "RangeSort" in c.entry]
+    assert {(c.n, c.count, c.bit_range, "KeyValue" in c.entry) for c in ranged} == {
+        (c.n, c.count, c.bit_range, "KeyValue" in c.entry) for c in small if "SortBits" in c.entry and c.n != 100}
+    assert {c.bit_range for c in ranged} == set(knob_cases.RANGES) and not any(c.refused for c in ranged)
+    assert any(c.n == 16385 and c.bit_range == (8, 16) for c in ranged)   # ... the chunked form under every small setting
     assert any(c.entry == "vrdxHipCmdSortBits" and c.bit_range == (8, 16) and c.count is None for c in refused)
     segmented = [c for c in knob_cases.cases("small-sort-off") if c.group == "segmented"]
     assert [c.entry.replace("vrdxHipCmd", "") for c in segmented] == [
@@ -133,12 +164,14 @@ def test_the_batteries_by_group():
         ("vrdxHipCmdSort64", knob_cases.M, None), ("vrdxHipCmdSort64KeyValueIndirect", knob_cases.M, knob_cases.M - 3),
         ("vrdxHipCmdOrderedSortKeyValue", knob_cases.M, None), ("vrdxHipCmdWideValueSort", knob_cases.M, None)]
     assert {c.n for c in knob_cases.cases("hybrid-off")} == {16385, 40_001, 300_001}
+    mid = [(c.entry, c.n, c.bit_range) for c in knob_cases.cases("hybrid-off") if "RangeSort" in c.entry]
+    assert mid == [("vrdxHipCmdRangeSort", 40_001, (5, 22)), ("vrdxHipCmdRangeSort", knob_cases.H, (0, 32))]
 
 
 def test_together_the_settings_name_every_flat_hip_entry_point():
-    flat = {call.c_name for call in api.RECORDING_CALLS + api.ORDERED_SORT_CALLS + api.WIDE_VALUE_CALLS
+    flat = {call.c_name for call in api.RECORDING_CALLS + api.ORDERED_SORT_CALLS + api.WIDE_VALUE_CALLS + api.RANGE_SORT_CALLS
             if call.c_name.startswith("vrdxHipCmd") and not call.facts[1]}
-    assert len(flat) == 18
+    assert len(flat) == 22 and RANGE_SORT_NAMES <= flat
     named = {case.entry for setting in knob_cases.SETTINGS for case in knob_cases.cases(setting)}
     assert flat <= named, sorted(flat - named)
     for setting in knob_cases.SMALL_SETTINGS:   # ... and every setting that reaches small sizes names them all by itself
@@ -154,11 +187,13 @@ def _view(address, count, dtype):
 
 FAULTS = ("dropped-scalar-tail",        # a streaming step of the 64-bit and wide-value sorts leaves out the last n % 4 elements
           "value-words-swapped",        # the 8-byte values come back with their words swapped
-          "small-range-sorts-refused")  # a sort by part of the key is refused at a size it must be sorted at
+          "small-range-sorts-refused",  # a sort by part of the key is refused at a size it must be sorted at
+          "range-sorts-follow-small-sort")  # vrdxHipCmdRangeSort* over part of the key is planned through the knob-dependent
+#                                             answer: refused where VRDX_SMALL_SORT=0 leaves it no one-workgroup plan
 
 
 class HostSorter:
-    """The cmd_* methods of every row of the four tables and what the helpers and check_plans ask of a sorter, on host
+    """The cmd_* methods of every row of the five tables and what the helpers and check_plans ask of a sorter, on host
     memory, sorting with the families' own references.  setting: the knobs it plans under (describe_*); fault: one of FAULTS."""
 
     def __init__(self, setting="default", fault=None):
@@ -207,6 +242,10 @@ class HostSorter:
     def describe_wide_value_sort_plan(self, n):
         return self._plan(n, True, "wide")
 
+    def describe_range_sort_plan(self, n, key_value, begin, end):
+        return SimpleNamespace(name=knob_cases.expected_plan(self.setting, n, key_value, "range", bit_range=(begin, end)),
+                               launches=knob_cases.expected_launches(self.setting, n, key_value))
+
     def record(self, call, command_buffer, storage, storage_offset, query_pool, query, keys, keys_offset, element_count=None,
                max_element_count=None, segment_count=None, offsets=None, offsets_offset=None, indirect=None,
                indirect_offset=None, values=None, values_offset=None, begin_bit=None, end_bit=None, order=None):
@@ -215,8 +254,12 @@ class HostSorter:
         wide_value = call.c_name in WIDE_VALUE_NAMES
         bound = max_element_count if segmented or is_indirect else element_count
         partial = extra == "Bits" and (begin_bit, end_bit) != (0, 32)
-        refuse = partial and not segmented and bound > knob_cases.ONE_WORKGROUP_MAX
-        if self.fault == "small-range-sorts-refused" and partial and not segmented:
+        ranged = call.c_name in RANGE_SORT_NAMES   # (no size is refused)
+        refuse = partial and not segmented and not ranged and bound > knob_cases.ONE_WORKGROUP_MAX
+        if self.fault == "small-range-sorts-refused" and partial and not segmented and not ranged:
+            refuse = True
+        if (self.fault == "range-sorts-follow-small-sort" and partial and ranged and bound <= knob_cases.ONE_WORKGROUP_MAX
+                and knob_cases.SETTINGS[self.setting].get("VRDX_SMALL_SORT") == "0"):
             refuse = True
         if refuse:
             self.sticky |= api.STATUS_ENQUEUE_REFUSED
@@ -325,6 +368,7 @@ def test_a_refusal_that_should_not_be_is_reported_by_case():
     rows = [c for c in SMALL_ROWS if "Bits" in c.entry]
     failures, lines = _run(HostSorter(fault="small-range-sorts-refused"), "default", rows)
     hit = {knob_cases.name_of(c) for c in rows if "Segmented" not in c.entry and c.bit_range != (0, 32) and not c.refused}
+    assert all("SortBits" in name for name in hit)
     assert _failed(lines) == hit and failures == len(hit) > 0
     assert all("the call was refused" in line for line in lines if line.startswith("FAIL"))
     assert "vrdxHipCmdSortBits n=255 bits=[8,16)" in hit
@@ -339,6 +383,40 @@ def test_a_refusal_that_should_not_be_is_reported_by_case():
 
     failures, lines = _run(Sorts(), "default", control)
     assert failures == len(control) == 1 and "must be refused" in lines[-2]
+
+
+@pytest.mark.parametrize("setting", list(knob_cases.SETTINGS))
+def test_the_range_sorts_of_every_setting_pass_on_a_correct_sorter(setting):
+    """every vrdxHipCmdRangeSort* case of the setting's battery, plans included, against a sorter that plans under that
+    setting: part of the key by size alone, the whole key with the launches of the setting's whole-key plan"""
+    rows = [c for c in knob_cases.cases(setting) if "RangeSort" in c.entry]
+    small, mid = setting in knob_cases.SMALL_SETTINGS, setting in knob_cases.MID_SETTINGS
+    assert len(rows) == 200 * small + 2 * mid and not any(c.refused for c in rows)
+    if not rows:   # (the settings of the large group alone: the range sorts are not part of their battery)
+        return
+    failures, lines = _run(HostSorter(setting), setting, rows)
+    assert failures == 0, [line for line in lines if line.startswith("FAIL")][:5]
+    assert sum(line.startswith("ok   range-sort plan") for line in lines) == len(knob_cases.plan_points(rows))
+    if small:   # the whole-key plan's launches follow the knobs; the partial ranges do not notice them
+        sorter = HostSorter(setting)
+        assert sorter.describe_range_sort_plan(16385, False, 8, 16).name == "chunked"
+        assert sorter.describe_range_sort_plan(100, False, 0, 32).launches == knob_cases.expected_launches(setting, 100, False)
+
+
+def test_a_range_sort_refused_without_the_small_sort_is_reported_by_case():
+    """PlanSortBits' regression, on the entry points that took its place at every size: the one-workgroup range sorts refused
+    under VRDX_SMALL_SORT=0.  The default setting does not show it; small-sort-off names every case."""
+    rows = [c for c in knob_cases.cases("small-sort-off") if "RangeSort" in c.entry and c.n in (5, 255, 8192, 16384, 16385)]
+    assert any(c.count is not None for c in rows) and any(c.n > knob_cases.ONE_WORKGROUP_MAX for c in rows)
+    assert _run(HostSorter("small-sort-off"), "small-sort-off", rows)[0] == 0
+    default_rows = [c for c in SMALL_ROWS if "RangeSort" in c.entry and c.n in (5, 255, 8192, 16384, 16385)]
+    assert _run(HostSorter("default", fault="range-sorts-follow-small-sort"), "default", default_rows)[0] == 0
+    failures, lines = _run(HostSorter("small-sort-off", fault="range-sorts-follow-small-sort"), "small-sort-off", rows)
+    hit = {knob_cases.name_of(c) for c in rows if c.bit_range != (0, 32) and c.n <= knob_cases.ONE_WORKGROUP_MAX}
+    assert _failed(lines) == hit and failures == len(hit) > 0
+    assert all("the call was refused" in line for line in lines if line.startswith("FAIL"))
+    assert {"vrdxHipCmdRangeSort n=255 bits=[8,16)", "vrdxHipCmdRangeSortKeyValueIndirect n=8192 count=0 bits=[5,22)"} <= hit
+    assert "vrdxHipCmdRangeSort n=16385 bits=[8,16)" not in hit   # (the chunked form never went through that answer)
 
 
 def test_a_setting_that_did_not_arrive_fails_on_the_plan_lines():

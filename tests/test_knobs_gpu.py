@@ -1,4 +1,5 @@
-"""The composed sorts -- 64-bit, ordered, by a bit range, with 8-byte values -- under every planning knob, on the device: one
+"""The composed sorts -- 64-bit, ordered, by a bit range (the range sorts at every size among them), with 8-byte values -- under
+every planning knob, on the device: one
 test per setting of tests/knob_cases.py, each ONE fresh child (tests/knob_battery_check.py) with the setting's environment,
 because the library reads the knobs once per process.  The child checks the plans first, so a setting that did not arrive
 fails there; then every case of the setting, guarded and bit for bit.  Children never run concurrently, and after one that

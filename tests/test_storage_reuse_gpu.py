@@ -41,10 +41,50 @@ verdicts they must leave are checked against tests/plan_model.py without a GPU b
   64-bit: A, B | I, T behind the inner      split64 / gather_hi64 / permute64 write [0, n) of each       (sort64-pairs, sort64-indirect): half the count
   storage                                   before the inner sorts, merge64 and copy_back64 read it      over the leaver's arrays; (msd-runs-pairs,
                                                                                                          sort64-pairs): they lie in 32-bit key scratch
+  words 1-3 behind the newer one-workgroup  small_sort_bits_kernel, small_sort_ordered_kernel and       (msd-runs-keys | hybrid-runs | segmented-invalid,
+  sorts                                     small_sort_wide_kernel, each on its own (as                  bits-one-workgroup | ordered-small |
+                                            small_sort_kernel does)                                      wide-one-workgroup): stale verdict, stale
+                                                                                                         "turned down", stale failure word; fills
+                                                                                                         0x00000001 and 0xFFFFFFFF
+  range sort: word 2, the mask of active    the range sort's fill zeroes it with the header;             (msd-declined-keys, range-chunked-keys): a "turned
+  passes (the MSD plan's word elsewhere)    range_scan_kernel's first launch stores it before any        down" read as passes; (range-chunked-pairs-copy-
+                                            other launch reads it                                        back, msd-runs-keys): a mask read as "turned
+                                                                                                         down", verdict NONE; (range-chunked-pairs-copy-
+                                                                                                         back, range-equal-field); fill 0xFFFFFFFF
+  range sort: totals[4][256]                the range sort's fill (the first count launch adds with      (hybrid-runs | segmented, range-chunked-keys): the
+                                            atomics)                                                     global histogram and the two list counters lie
+                                                                                                         there; (range-chunked-pairs-copy-back, range-gap-
+                                                                                                         in-mask): a constant digit becomes a pass; and
+                                                                                                         back: (range-chunked-keys, hybrid-declined |
+                                                                                                         segmented); fill 0x00000001
+  range sort: counts[chunks][256]           range_count_kernel STORES the row of every chunk that        (msd-runs-keys, range-chunked-keys): bucketCount
+                                            holds keys; range_scan_kernel and the scatter read those     and bucketBase lie there; (range-chunked-pairs-
+                                            rows only (rows behind an indirect count keep what they      copy-back, range-indirect-small): two rows under
+                                            held)                                                        eight of a longer sort; back: (range-chunked-keys,
+                                                                                                         msd-runs-pairs): doubled buckets; random fill
+  range sort: key and value scratch         every active pass's scatter writes all n elements before     (msd-runs-pairs, range-chunked-pairs-copy-back);
+                                            the next pass or the copy back reads them; no active pass:   (range-chunked-keys, range-equal-field): the
+                                            not a byte                                                   scratch stays byte for byte the leaver's; random
+                                                                                                         fill
+  wide values: A, B, C | A, T behind the    iota_wide_kernel writes A[0, n), gather_wide_kernel T[0, n)  (wide-gather, wide-two-sorts-indirect) and back: T
+  inner storage                             before copy_back_wide_kernel reads it; split_wide_kernel     lies over B and C; (sort64-pairs, wide-gather),
+                                            writes A, B, C [0, n) before the inner sorts and             (wide-gather, sort64-ordered-pairs): the 64-bit
+                                            merge_wide_kernel read them                                  sorts' A, B | I, T lie in the same bytes;
+                                                                                                         (msd-runs-pairs, wide-gather): 32-bit scratch
+  wide values, segmented: counters, lists   segmented_clear_kernel; segmented_small_wide_kernel writes   (wide-gather | hybrid-runs, wide-segmented): the
+  and scratch                               slot [0, count) before the mid and the large kernel read     counters lie in the global histogram; (segmented-
+                                            them; a large segment's pass writes its range of the         invalid, wide-segmented): other ids in the slots;
+                                            scratch (over A and T) before the next one reads it          (wide-two-sorts-indirect, wide-segmented)
+  by a bit range, in a key order            no region of their own: the segmented forms use the          (segmented, segmented-bits | ordered-segmented),
+                                            segmented regions above, the 64-bit ones those of the        (segmented64, segmented64-ordered), (sort64-pairs,
+                                            64-bit sorts; order32_kernel works on the caller's keys,     sort64-ordered-pairs), (msd-declined-keys,
+                                            in place, around the plan's own steps                        ordered-msd) and each of them back
 
 No region is left without a pair.  The one-workgroup path is the one that touched too little: small_sort_kernel cleared the
 failure word alone, so a sort of up to 16384 elements behind an MSD or hybrid sort reported that sort's verdict
-(vrdxHipReadPlanVerdict, Sorter.plan_taken()); the kernel now zeroes words 1-3.
+(vrdxHipReadPlanVerdict, Sorter.plan_taken()); the kernel now zeroes words 1-3.  The families added since -- by a bit range,
+in a key order, with 8-byte values, range sorts at every size -- joined the matrix later, every writer above named from the
+recorder and the kernels; the battery found nothing in them.
 
 Every wait in the kernels is bounded by their spin limit, so a clear that went missing shows up as STATUS_LOOKBACK_GAVE_UP or
 as a mismatch, never as a hang.  Only booleans and header words cross to the host per run: the inputs and the expected
@@ -60,6 +100,7 @@ import storage_reuse_cases as cases
 from guarded_call import ballot_sorter, sorter, to_device, torch_mod  # noqa: F401 (fixtures)
 from storage_reuse_cases import CALLS, INHERITED, NAMES
 from test_plan_choice_gpu import expected_word, plan_storage_word
+from test_range_sort_gpu import scratch_from
 from vulkan_radix_sort_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -91,6 +132,8 @@ def world(torch_mod, sorter, ballot_sorter):
             info = s.describe_plan(call.bound, True if wide else key_value)
             assert info.name == call.plan, (call.name, info.name)
             assert call.plan != "msd" or int(info.bits) == cases.MSD_BITS, (call.name, int(info.bits))
+            assert call.plan != "msd" or int(info.bits) == cases.msd_constants(call)[0], (call.name, int(info.bits))
+        chunks = _family_plan(s, call, key_value)
         if call.inputs not in shared:
             keys, values, offsets = cases.input_set(call.inputs)
             pristine = SimpleNamespace(keys=to_device(torch, cases.padded(keys)),
@@ -101,7 +144,7 @@ def world(torch_mod, sorter, ballot_sorter):
                 values=pristine.values.clone() if values is not None else None,
                 offsets=pristine.offsets.clone() if offsets is not None else None, expected={})
         d = shared[call.inputs]
-        which = (key_value, cases.sorted_count(call))
+        which = (key_value, cases.sorted_count(call), call.bits, call.order, cases.is_segmented(call))
         if which not in d.expected:
             want_keys, want_values = cases.expected_of(call)
             d.expected[which] = (to_device(torch, cases.padded(want_keys)),
@@ -109,8 +152,10 @@ def world(torch_mod, sorter, ballot_sorter):
         required = {"keys": lambda: s.storage_requirements(call.bound),
                     "key-value": lambda: s.key_value_storage_requirements(call.bound),
                     "keys64": lambda: s.storage_requirements64(call.bound, False),
-                    "key-value64": lambda: s.storage_requirements64(call.bound, True)}[call.requirement]().size
-        assert required % 16 == 0
+                    "key-value64": lambda: s.storage_requirements64(call.bound, True),
+                    "wide-value": lambda: s.wide_value_storage_requirements(call.bound)}[call.requirement]().size
+        # (the wide-value requirement is the inner one plus 12 bytes per element plus 112 + 2 x 124: a multiple of 4 only)
+        assert required % (4 if call.requirement == "wide-value" else 16) == 0
         verdict, shift = cases.verdict_of(call) if call.verdict != INHERITED else (INHERITED, None)
         assert verdict == call.verdict, (call.name, verdict)
         count = None
@@ -119,6 +164,8 @@ def world(torch_mod, sorter, ballot_sorter):
         w.device[call.name] = SimpleNamespace(
             buffers=d, key_value=key_value, expected_keys=d.expected[which][0], expected_values=d.expected[which][1],
             required=required, count=count, count_pristine=count.clone() if count is not None else None,
+            bits=call.bits if call.bits is not None else (None, None), order=cases.order_word(call),
+            scratch_from=scratch_from(chunks) if call.name == "range-equal-field" else None,
             plan_word=expected_word(verdict, shift) if cases.records_msd_plan(call) else None)
     w.largest = max(d.required for d in w.device.values())
     w.storage = torch.empty(FRONT + w.largest + BAND, dtype=torch.uint8, device="cuda")
@@ -131,6 +178,33 @@ def world(torch_mod, sorter, ballot_sorter):
     print(f"storage-reuse fixture: {time.perf_counter() - started:.1f} s, storage of {w.largest} bytes")
     yield w
     del w.storage, w.device, shared
+
+
+def _family_plan(s, call, key_value):
+    """The plan of a call of the newer families against the family's own describe call, before anything runs; returns the
+    chunks of a chunked range sort (else None)."""
+    if cases.is_segmented(call):
+        return None
+    if cases.is_range_sort(call):
+        info = s.describe_range_sort_plan(call.bound, key_value, *call.bits)
+        cus = int(s.describe_range_sort_plan(0x3FFFFFFC, False, 0, 8).chunks)   # (the device's CU count)
+        assert (info.name, int(info.digits)) == (call.form, -(-(call.bits[1] - call.bits[0]) // 8)), (call.name, info.name)
+        assert int(info.chunks) == min(cus, call.bound // 8192), (call.name, int(info.chunks))
+        assert cus >= cases.RANGE_FACTS[call.name].most_chunks, cus   # (every chunk RANGE_FACTS counts on holds keys here)
+        return int(info.chunks)
+    if call.bits is not None:
+        info = s.describe_sort_bits_plan(call.bound, key_value, *call.bits)
+        assert info.name == call.form and int(info.launches) == 1, (call.name, info.name)
+    elif cases.is_ordered32(call):
+        info = s.describe_ordered_sort_plan(call.bound, key_value, cases.order_word(call))
+        assert info.name == call.plan, (call.name, info.name)
+        assert call.plan != "msd" or int(info.bits) == cases.msd_constants(call)[0], (call.name, int(info.bits))
+    elif cases.has_wide_values(call):
+        info = s.describe_wide_value_sort_plan(call.bound)
+        assert info.name == call.form, (call.name, info.name)
+        assert (int(info.oneWorkgroupMax), int(info.twoSortsFrom)) == (cases.WIDE_ONE_WORKGROUP_N, cases.WIDE_TWO_SORTS_N)
+        assert call.form == "one-workgroup" or api.PLAN_NAMES[int(info.innerPlan)] == call.plan, (call.name, int(info.innerPlan))
+    return None
 
 
 def _prepare_storage(w, off, word=None, random=False):
@@ -148,16 +222,19 @@ def _prepare_storage(w, off, word=None, random=False):
     w.storage[off + w.largest:] = BAND_BYTE
 
 
-ROWS = {row.c_name: row for row in api.RECORDING_CALLS}
+ROWS = {row.c_name: row for row in api.RECORDING_CALLS + api.ORDERED_SORT_CALLS + api.WIDE_VALUE_CALLS
+        + api.WIDE_VALUE_SEGMENTED_CALLS + api.RANGE_SORT_CALLS}
 
 
 def _record(s, stream, call, d, storage, off):
-    """the row of RECORDING_CALLS that `call.entry` names, on the world's buffers at byte offset 0"""
+    """the row of RECORDING_CALLS, ORDERED_SORT_CALLS, WIDE_VALUE_CALLS, WIDE_VALUE_SEGMENTED_CALLS or RANGE_SORT_CALLS that
+    `call.entry` names, on the world's buffers at byte offset 0"""
     b = d.buffers
     row = ROWS[call.entry]
     given = {"command_buffer": stream, "element_count": call.bound, "max_element_count": call.bound,
              "segment_count": len(b.offsets) - 1 if b.offsets is not None else None, "offsets": b.offsets, "indirect": d.count,
-             "keys": b.keys, "values": b.values if d.key_value else None}
+             "keys": b.keys, "values": b.values if d.key_value else None, "begin_bit": d.bits[0], "end_bit": d.bits[1],
+             "order": d.order}
     given = {name: t.data_ptr() if hasattr(t, "data_ptr") else t for name, t in given.items()}
     given.update(storage=storage, storage_offset=off, offsets_offset=0, indirect_offset=0, keys_offset=0, values_offset=0)
     getattr(s, row.method)(*(given[name] for name, _ in row.parameters[:-2]))   # (no query pool)
@@ -176,9 +253,15 @@ def run(w, call, off):
     end = off + d.required
     header = w.storage[off:off + 16].clone()
     behind = w.storage[end:end + BEHIND].clone()   # (up to the end of the band for the largest call)
+    scratch = w.storage[off + d.scratch_from:end].clone() if d.scratch_from is not None else None
     _record(s, stream, call, d, w.storage.data_ptr(), off)
     torch.cuda.synchronize()
     problems = []
+    # 0. a range sort over a field that is the same in every key writes neither of its scratch arrays
+    if scratch is not None:
+        assert scratch.numel() > 4 * call.bound
+        if not torch.equal(w.storage[off + d.scratch_from:end], scratch):
+            problems.append("an equal field wrote the scratch arrays")
     # 1. keys and values bit for bit, the elements from the count on and the guard behind the arrays included
     if not torch.equal(b.keys, d.expected_keys):
         problems.append("keys differ")
