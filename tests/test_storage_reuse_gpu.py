@@ -88,7 +88,8 @@ recorder and the kernels; the battery found nothing in them.
 
 Every wait in the kernels is bounded by their spin limit, so a clear that went missing shows up as STATUS_LOOKBACK_GAVE_UP or
 as a mismatch, never as a hang.  Only booleans and header words cross to the host per run: the inputs and the expected
-outputs are made once and kept on the device.
+outputs are made once and kept on the device.  What one call needs -- its plan, its device buffers, the recording, the
+checks of its arrays and header words -- is tests/recorded_call.py, which tests/test_in_flight_gpu.py runs two at a time.
 """
 import time
 from types import SimpleNamespace
@@ -96,20 +97,15 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import recorded_call
 import storage_reuse_cases as cases
-from guarded_call import ballot_sorter, sorter, to_device, torch_mod  # noqa: F401 (fixtures)
+from guarded_call import ballot_sorter, sorter, torch_mod  # noqa: F401 (fixtures)
+from recorded_call import BAND, BAND_BYTE, BEHIND, FRONT, FRONT_BYTE, OFFSETS, POISON
 from storage_reuse_cases import CALLS, INHERITED, NAMES
-from test_plan_choice_gpu import expected_word, plan_storage_word
-from test_range_sort_gpu import scratch_from
-from vulkan_radix_sort_amd import api
+from test_plan_choice_gpu import plan_storage_word
 
 pytestmark = pytest.mark.gpu
 
-OFFSETS = (0, 48)     # storageOffset: the layout moves with the low seven bits of the storage's address
-FRONT = max(OFFSETS)
-BAND = 256            # 0x5A behind the largest requirement
-BEHIND = 4096         # bytes right behind a call's own requirement that it must leave alone
-POISON, FRONT_BYTE, BAND_BYTE = 0xA5, 0x3C, 0x5A
 FILLS = [("zero", 0x00000000), ("ones", 0xFFFFFFFF), ("one", 0x00000001), ("aggregate-1", 0x40000001),
          ("inclusive-1", 0x80000001), ("block-arrival-1", 0x04000001), ("random", None)]
 
@@ -125,48 +121,9 @@ def world(torch_mod, sorter, ballot_sorter):
     w = SimpleNamespace(torch=torch, sorters={"atomic": sorter, "ballot": ballot_sorter}, device={})
     shared = {}
     for call in CALLS:
-        s = w.sorters[call.sorter]
-        key_value, wide = cases.is_key_value(call), cases.is_wide(call)
         # what the host records is what the table of CALLS assumes
-        if call.plan is not None:
-            info = s.describe_plan(call.bound, True if wide else key_value)
-            assert info.name == call.plan, (call.name, info.name)
-            assert call.plan != "msd" or int(info.bits) == cases.MSD_BITS, (call.name, int(info.bits))
-            assert call.plan != "msd" or int(info.bits) == cases.msd_constants(call)[0], (call.name, int(info.bits))
-        chunks = _family_plan(s, call, key_value)
-        if call.inputs not in shared:
-            keys, values, offsets = cases.input_set(call.inputs)
-            pristine = SimpleNamespace(keys=to_device(torch, cases.padded(keys)),
-                                       values=to_device(torch, cases.padded(values)) if values is not None else None,
-                                       offsets=to_device(torch, offsets) if offsets is not None else None)
-            shared[call.inputs] = SimpleNamespace(
-                pristine=pristine, keys=pristine.keys.clone(),
-                values=pristine.values.clone() if values is not None else None,
-                offsets=pristine.offsets.clone() if offsets is not None else None, expected={})
-        d = shared[call.inputs]
-        which = (key_value, cases.sorted_count(call), call.bits, call.order, cases.is_segmented(call))
-        if which not in d.expected:
-            want_keys, want_values = cases.expected_of(call)
-            d.expected[which] = (to_device(torch, cases.padded(want_keys)),
-                                 to_device(torch, cases.padded(want_values)) if key_value else None)
-        required = {"keys": lambda: s.storage_requirements(call.bound),
-                    "key-value": lambda: s.key_value_storage_requirements(call.bound),
-                    "keys64": lambda: s.storage_requirements64(call.bound, False),
-                    "key-value64": lambda: s.storage_requirements64(call.bound, True),
-                    "wide-value": lambda: s.wide_value_storage_requirements(call.bound)}[call.requirement]().size
-        # (the wide-value requirement is the inner one plus 12 bytes per element plus 112 + 2 x 124: a multiple of 4 only)
-        assert required % (4 if call.requirement == "wide-value" else 16) == 0
-        verdict, shift = cases.verdict_of(call) if call.verdict != INHERITED else (INHERITED, None)
-        assert verdict == call.verdict, (call.name, verdict)
-        count = None
-        if call.count is not None:
-            count = to_device(torch, np.array([call.count, 0, 0, 0], np.uint32))
-        w.device[call.name] = SimpleNamespace(
-            buffers=d, key_value=key_value, expected_keys=d.expected[which][0], expected_values=d.expected[which][1],
-            required=required, count=count, count_pristine=count.clone() if count is not None else None,
-            bits=call.bits if call.bits is not None else (None, None), order=cases.order_word(call),
-            scratch_from=scratch_from(chunks) if call.name == "range-equal-field" else None,
-            plan_word=expected_word(verdict, shift) if cases.records_msd_plan(call) else None)
+        required, chunks = recorded_call.planned(w.sorters[call.sorter], call)
+        w.device[call.name] = recorded_call.device_call(torch, call, shared, required, chunks)
     w.largest = max(d.required for d in w.device.values())
     w.storage = torch.empty(FRONT + w.largest + BAND, dtype=torch.uint8, device="cuda")
     assert w.storage.data_ptr() % 128 == 0
@@ -178,33 +135,6 @@ def world(torch_mod, sorter, ballot_sorter):
     print(f"storage-reuse fixture: {time.perf_counter() - started:.1f} s, storage of {w.largest} bytes")
     yield w
     del w.storage, w.device, shared
-
-
-def _family_plan(s, call, key_value):
-    """The plan of a call of the newer families against the family's own describe call, before anything runs; returns the
-    chunks of a chunked range sort (else None)."""
-    if cases.is_segmented(call):
-        return None
-    if cases.is_range_sort(call):
-        info = s.describe_range_sort_plan(call.bound, key_value, *call.bits)
-        cus = int(s.describe_range_sort_plan(0x3FFFFFFC, False, 0, 8).chunks)   # (the device's CU count)
-        assert (info.name, int(info.digits)) == (call.form, -(-(call.bits[1] - call.bits[0]) // 8)), (call.name, info.name)
-        assert int(info.chunks) == min(cus, call.bound // 8192), (call.name, int(info.chunks))
-        assert cus >= cases.RANGE_FACTS[call.name].most_chunks, cus   # (every chunk RANGE_FACTS counts on holds keys here)
-        return int(info.chunks)
-    if call.bits is not None:
-        info = s.describe_sort_bits_plan(call.bound, key_value, *call.bits)
-        assert info.name == call.form and int(info.launches) == 1, (call.name, info.name)
-    elif cases.is_ordered32(call):
-        info = s.describe_ordered_sort_plan(call.bound, key_value, cases.order_word(call))
-        assert info.name == call.plan, (call.name, info.name)
-        assert call.plan != "msd" or int(info.bits) == cases.msd_constants(call)[0], (call.name, int(info.bits))
-    elif cases.has_wide_values(call):
-        info = s.describe_wide_value_sort_plan(call.bound)
-        assert info.name == call.form, (call.name, info.name)
-        assert (int(info.oneWorkgroupMax), int(info.twoSortsFrom)) == (cases.WIDE_ONE_WORKGROUP_N, cases.WIDE_TWO_SORTS_N)
-        assert call.form == "one-workgroup" or api.PLAN_NAMES[int(info.innerPlan)] == call.plan, (call.name, int(info.innerPlan))
-    return None
 
 
 def _prepare_storage(w, off, word=None, random=False):
@@ -222,39 +152,18 @@ def _prepare_storage(w, off, word=None, random=False):
     w.storage[off + w.largest:] = BAND_BYTE
 
 
-ROWS = {row.c_name: row for row in api.RECORDING_CALLS + api.ORDERED_SORT_CALLS + api.WIDE_VALUE_CALLS
-        + api.WIDE_VALUE_SEGMENTED_CALLS + api.RANGE_SORT_CALLS}
-
-
-def _record(s, stream, call, d, storage, off):
-    """the row of RECORDING_CALLS, ORDERED_SORT_CALLS, WIDE_VALUE_CALLS, WIDE_VALUE_SEGMENTED_CALLS or RANGE_SORT_CALLS that
-    `call.entry` names, on the world's buffers at byte offset 0"""
-    b = d.buffers
-    row = ROWS[call.entry]
-    given = {"command_buffer": stream, "element_count": call.bound, "max_element_count": call.bound,
-             "segment_count": len(b.offsets) - 1 if b.offsets is not None else None, "offsets": b.offsets, "indirect": d.count,
-             "keys": b.keys, "values": b.values if d.key_value else None, "begin_bit": d.bits[0], "end_bit": d.bits[1],
-             "order": d.order}
-    given = {name: t.data_ptr() if hasattr(t, "data_ptr") else t for name, t in given.items()}
-    given.update(storage=storage, storage_offset=off, offsets_offset=0, indirect_offset=0, keys_offset=0, values_offset=0)
-    getattr(s, row.method)(*(given[name] for name, _ in row.parameters[:-2]))   # (no query pool)
-
-
 def run(w, call, off):
     """One call on the storage as it is: fresh copies of the inputs, the call, and every check of the module's docstring.
     Returns (problems, failure word the call must leave): the problems as a list of short strings, empty when all is well."""
     torch = w.torch
     s, d = w.sorters[call.sorter], w.device[call.name]
-    b = d.buffers
     stream = torch.cuda.current_stream().cuda_stream
-    b.keys.copy_(b.pristine.keys)
-    if b.values is not None:
-        b.values.copy_(b.pristine.values)
+    recorded_call.restore_inputs(d)
     end = off + d.required
     header = w.storage[off:off + 16].clone()
     behind = w.storage[end:end + BEHIND].clone()   # (up to the end of the band for the largest call)
     scratch = w.storage[off + d.scratch_from:end].clone() if d.scratch_from is not None else None
-    _record(s, stream, call, d, w.storage.data_ptr(), off)
+    recorded_call.record(s, stream, call, d, w.storage.data_ptr(), off)
     torch.cuda.synchronize()
     problems = []
     # 0. a range sort over a field that is the same in every key writes neither of its scratch arrays
@@ -263,33 +172,15 @@ def run(w, call, off):
         if not torch.equal(w.storage[off + d.scratch_from:end], scratch):
             problems.append("an equal field wrote the scratch arrays")
     # 1. keys and values bit for bit, the elements from the count on and the guard behind the arrays included
-    if not torch.equal(b.keys, d.expected_keys):
-        problems.append("keys differ")
-    if d.key_value and not torch.equal(b.values, d.expected_values):
-        problems.append("values differ")
-    if b.values is not None and not d.key_value and not torch.equal(b.values, b.pristine.values):
-        problems.append("a keys-only call wrote the values")
-    if d.count is not None and not torch.equal(d.count, d.count_pristine):
-        problems.append("the count word changed")
-    if b.offsets is not None and not torch.equal(b.offsets, b.pristine.offsets):
-        problems.append("the offsets changed")
+    problems += [message for message, left, wanted in recorded_call.array_checks(d) if not torch.equal(left, wanted)]
     # 2. and 3. the failure word, the verdict, and word 1 as a whole where the MSD plan is recorded
-    want_status, want_verdict = call.failure, call.verdict
+    before = after = None
     if call.verdict == INHERITED:   # an empty sort records nothing: the header is the call before's
-        words = header.cpu().numpy().view(np.uint32)
-        want_status, want_verdict = int(words[3]), int(words[1]) & 0xFF
-        if not torch.equal(w.storage[off:off + 16], header):
-            problems.append("an empty sort wrote the header")
-    status = s.read_status(stream, w.storage.data_ptr(), off)
-    if status != want_status:
-        problems.append(f"failure word {status:#x}, not {want_status:#x}")
-    verdict = s.read_plan_verdict(stream, w.storage.data_ptr(), off)
-    if verdict != want_verdict:
-        problems.append(f"verdict {verdict}, not {want_verdict}")
-    if d.plan_word is not None:
-        word = plan_storage_word(w.storage[off:])
-        if word != d.plan_word:
-            problems.append(f"plan word {word:#x}, not {d.plan_word:#x}")
+        before = header.cpu().numpy().view(np.uint32)
+        after = w.storage[off:off + 16].cpu().numpy().view(np.uint32)
+    problems += recorded_call.header_problems(
+        call, d, s.read_status(stream, w.storage.data_ptr(), off), s.read_plan_verdict(stream, w.storage.data_ptr(), off),
+        lambda: plan_storage_word(w.storage[off:]), before, after)
     # 4. nothing outside the call's own requirement
     if not bool((w.storage[off + w.largest:] == BAND_BYTE).all()):
         problems.append("wrote the band behind the storage")
@@ -297,7 +188,7 @@ def run(w, call, off):
         problems.append("wrote in front of the storage offset")
     if not torch.equal(w.storage[end:end + BEHIND], behind):
         problems.append("wrote behind its own storage requirement")
-    return problems, (0 if call.failure == INHERITED else call.failure)
+    return problems, recorded_call.failure_left(call)
 
 
 def _sticky_problems(w, left):
