@@ -576,6 +576,9 @@ void vrdxHipCmdSortSegmentedBitsKeyValue(VkCommandBuffer commandBuffer, VrdxSort
                                          VkDeviceSize valuesOffset, uint32_t beginBit, uint32_t endBit, VkBuffer storageBuffer,
                                          VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query);
 
+/* The balanced segmented sort -- vrdxHipCmdSortSegmented[KeyValue] with huge segments spread over every compute unit -- is
+ * declared in vk_radix_sort_balanced.h, next to this file. */
+
 /**
  * Key orders of the 32-bit sorts (not part of the reference API): int32 and float32 keys, ascending or descending.  The four
  * flat calls and the two segmented calls with one order word, `order`, in front of storageBuffer -- the position it has in

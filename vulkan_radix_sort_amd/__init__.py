@@ -48,6 +48,11 @@ from .api import (  # noqa: F401
     VrdxHipRangeSortPlanInfo,
     RANGE_SORT_FORM_NAMES,
     RANGE_SORT_CALLS,
+    VrdxHipBalancedSegmentedPlanInfo,
+    VrdxHipBalancedSplitInfo,
+    BALANCED_FORM_NAMES,
+    BALANCED_SEGMENTED_CALLS,
+    BALANCED_EXPORTED_SYMBOLS,
 )
 from .segmented import sort_segments  # noqa: F401
 from .sort64 import sort64  # noqa: F401
@@ -57,6 +62,7 @@ from .segmented_bits import sort_segments_bits  # noqa: F401
 from .ordered import sort_ordered, sort_segments_ordered  # noqa: F401
 from .wide_value import sort_key_value64, sort_segments_key_value64  # noqa: F401
 from .range_sort import sort_range  # noqa: F401
+from .segmented_balanced import sort_segments_balanced  # noqa: F401
 
 __all__ = [
     "VK_SUCCESS",
@@ -108,4 +114,10 @@ __all__ = [
     "RANGE_SORT_FORM_NAMES",
     "RANGE_SORT_CALLS",
     "sort_range",
+    "VrdxHipBalancedSegmentedPlanInfo",
+    "VrdxHipBalancedSplitInfo",
+    "BALANCED_FORM_NAMES",
+    "BALANCED_SEGMENTED_CALLS",
+    "BALANCED_EXPORTED_SYMBOLS",
+    "sort_segments_balanced",
 ]

@@ -63,6 +63,9 @@ class RecordingCall(NamedTuple):
         ordered32 = re.fullmatch(r"vrdxHipCmdOrderedSort(Segmented)?(KeyValue)?(Indirect)?", self.c_name)
         wide_value = re.fullmatch(r"vrdxHipCmdWideValueSort(Indirect)?", self.c_name)
         range_sort = re.fullmatch(r"vrdxHipCmdRangeSort(KeyValue)?(Indirect)?", self.c_name)
+        balanced = re.fullmatch(r"vrdxHipCmdBalancedSortSegmented(KeyValue)?", self.c_name)
+        if balanced:   # the rows of BALANCED_SEGMENTED_CALLS: the arguments of vrdxHipCmdSortSegmented[KeyValue]
+            return 32, True, False, bool(balanced.group(1)), None
         if range_sort:   # the rows of RANGE_SORT_CALLS: the arguments of vrdxHipCmdSortBits*
             return 32, False, bool(range_sort.group(2)), bool(range_sort.group(1)), "Bits"
         if self.c_name == "vrdxHipCmdWideValueSortSegmented":   # the row of WIDE_VALUE_SEGMENTED_CALLS
@@ -228,6 +231,16 @@ RANGE_SORT_CALLS = (
           "the same with values that travel with their keys."),
 )
 
+# the segmented sort that spreads huge segments over every compute unit: a table of its own (RECORDING_CALLS stays as it is);
+# the arguments are those of vrdxHipCmdSortSegmented[KeyValue], name for name
+BALANCED_SEGMENTED_CALLS = (
+    _CALL("vrdxHipCmdBalancedSortSegmented", "cmd_balanced_sort_segmented",
+          "``cmd_sort_segmented`` with one difference: a segment that is long and longer than its share of the chip is cut "
+          "into pieces that many workgroups sort together; the result is the same bit for bit."),
+    _CALL("vrdxHipCmdBalancedSortSegmentedKeyValue", "cmd_balanced_sort_segmented_key_value",
+          "the same with values that travel with their keys; storage of ``key_value_storage_requirements(n)`` bytes."),
+)
+
 
 def _exported_symbols():
     """Everything the library exports, in the order this tuple has always had: the entry points that record no sort, by hand,
@@ -264,6 +277,9 @@ def _exported_symbols():
 
 
 EXPORTED_SYMBOLS = tuple(_exported_symbols())
+# what include/vk_radix_sort_balanced.h declares: a tuple of its own, EXPORTED_SYMBOLS is what include/vk_radix_sort.h declares
+BALANCED_EXPORTED_SYMBOLS = tuple(call.c_name for call in BALANCED_SEGMENTED_CALLS) + (
+    "vrdxHipDescribeBalancedSegmentedPlan", "vrdxHipReadBalancedSplit")
 
 
 def _compiled(name, source, **names):
@@ -446,6 +462,27 @@ class VrdxHipRangeSortPlanInfo(ctypes.Structure):
         return RANGE_SORT_FORM_NAMES.get(int(self.form), "?")
 
 
+# VRDX_HIP_BALANCED_* (include/vk_radix_sort_balanced.h)
+BALANCED_FORM_NAMES = {0: "none", 1: "twin", 2: "balanced"}
+
+
+class VrdxHipBalancedSegmentedPlanInfo(ctypes.Structure):
+    # include/vk_radix_sort_balanced.h
+    _fields_ = [("form", ctypes.c_uint32), ("launches", ctypes.c_uint32), ("spreadFrom", ctypes.c_uint32),
+                ("spreadShares", ctypes.c_uint32), ("spreadCap", ctypes.c_uint32), ("pieceCap", ctypes.c_uint32),
+                ("minPieceKeys", ctypes.c_uint32)]
+
+    @property
+    def name(self) -> str:
+        return BALANCED_FORM_NAMES.get(int(self.form), "?")
+
+
+class VrdxHipBalancedSplitInfo(ctypes.Structure):
+    # include/vk_radix_sort_balanced.h
+    _fields_ = [("listedSegments", ctypes.c_uint32), ("spreadSegments", ctypes.c_uint32), ("pieces", ctypes.c_uint32),
+                ("pieceKeys", ctypes.c_uint32)]
+
+
 def in_tree_library_path() -> str:
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvrdx_hip.so")
 
@@ -478,7 +515,7 @@ def load_library() -> ctypes.CDLL:
         # A stale VRDX_LIBRARY (left behind by a tuning script, or the test build with its injection hooks) silently
         # changes what production code runs: say so, and insist on the same version and ABI.
         import sys
-        missing = [name for name in EXPORTED_SYMBOLS if not hasattr(lib, name)]
+        missing = [name for name in EXPORTED_SYMBOLS + BALANCED_EXPORTED_SYMBOLS if not hasattr(lib, name)]
         if missing:
             raise ImportError(f"VRDX_LIBRARY={path} does not export {', '.join(missing)}: not a build of this library")
         lib.vrdxHipVersionString.restype = ctypes.c_char_p
@@ -501,7 +538,8 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = None
         fn.argtypes = [vp, u32, ctypes.POINTER(VrdxSorterStorageRequirements)]
-    for call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS + RANGE_SORT_CALLS:
+    for call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS + RANGE_SORT_CALLS + \
+        BALANCED_SEGMENTED_CALLS:
         fn = getattr(lib, call.c_name)
         fn.restype = None
         fn.argtypes = call.argtypes
@@ -511,6 +549,10 @@ def load_library() -> ctypes.CDLL:
     lib.vrdxHipDescribeOrderedSortPlan.argtypes = [vp, u32, ctypes.c_int, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipDescribeRangeSortPlan.restype = None
     lib.vrdxHipDescribeRangeSortPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipRangeSortPlanInfo)]
+    lib.vrdxHipDescribeBalancedSegmentedPlan.restype = None
+    lib.vrdxHipDescribeBalancedSegmentedPlan.argtypes = [vp, u32, u32, ctypes.c_int, ctypes.POINTER(VrdxHipBalancedSegmentedPlanInfo)]
+    lib.vrdxHipReadBalancedSplit.restype = ctypes.c_int32
+    lib.vrdxHipReadBalancedSplit.argtypes = [vp, vp, vp, u64, u32, ctypes.POINTER(VrdxHipBalancedSplitInfo)]
     lib.vrdxHipDescribeSortBitsPlan.restype = None
     lib.vrdxHipDescribeSortBitsPlan.argtypes = [vp, u32, ctypes.c_int, u32, u32, ctypes.POINTER(VrdxHipPlanInfo)]
     lib.vrdxHipCreateQueryPool.restype = ctypes.c_int32
@@ -685,6 +727,27 @@ class Sorter:
                                                ctypes.byref(info))
         return info
 
+    def describe_balanced_segmented_plan(self, max_element_count: int, segment_count: int,
+                                         key_value: bool) -> VrdxHipBalancedSegmentedPlanInfo:
+        """``vrdxHipDescribeBalancedSegmentedPlan``: the form ``cmd_balanced_sort_segmented*`` records under that bound
+        (``.name``), its launches, the two constants of the rule, the caps of spread segments and pieces, and the smallest
+        piece length."""
+        info = VrdxHipBalancedSegmentedPlanInfo()
+        self._lib.vrdxHipDescribeBalancedSegmentedPlan(self.handle, max_element_count, segment_count, 1 if key_value else 0,
+                                                       ctypes.byref(info))
+        return info
+
+    def read_balanced_split(self, command_buffer, storage, max_element_count: int, storage_offset=0) -> VrdxHipBalancedSplitInfo:
+        """``vrdxHipReadBalancedSplit``: what the device decided in the last ``cmd_balanced_sort_segmented*`` on this storage,
+        recorded with this ``max_element_count``: listed segments, spread segments, pieces, piece length.  Synchronises the
+        stream."""
+        info = VrdxHipBalancedSplitInfo()
+        r = self._lib.vrdxHipReadBalancedSplit(_handle(command_buffer), self.handle, _handle(storage), storage_offset,
+                                               max_element_count, ctypes.byref(info))
+        if r != VK_SUCCESS:
+            raise VrdxError("vrdxHipReadBalancedSplit", r)
+        return info
+
     def describe_ordered_sort_plan(self, element_count: int, key_value: bool, order: int) -> VrdxHipPlanInfo:
         """``vrdxHipDescribeOrderedSortPlan``: the plan ``cmd_ordered_sort*`` records for that many elements and that order word
         (beyond one workgroup: ``describe_plan``'s, plus two launches and 16 bytes per element)."""
@@ -750,5 +813,6 @@ def _recording_method(call: RecordingCall):
     return method
 
 
-for _call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS + RANGE_SORT_CALLS:
+for _call in RECORDING_CALLS + ORDERED_SORT_CALLS + WIDE_VALUE_CALLS + WIDE_VALUE_SEGMENTED_CALLS + RANGE_SORT_CALLS + \
+        BALANCED_SEGMENTED_CALLS:
     setattr(Sorter, _call.method, _recording_method(_call))

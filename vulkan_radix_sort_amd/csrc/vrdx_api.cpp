@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/vk_radix_sort.h"
+#include "../../include/vk_radix_sort_balanced.h"
 #include "vrdx_kernels.h"
 #include "vrdx_layout.h"
 #include "vrdx_plan.h"
@@ -627,6 +628,91 @@ void RecordSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint3
 constexpr auto RecordSegmentedSort32 = RecordSegmentedSort<vrdx::SegmentedArgs, uint32_t>;
 constexpr auto RecordSegmentedSort64 = RecordSegmentedSort<vrdx::Segmented64Args, uint64_t>;
 
+static_assert(VRDX_HIP_BALANCED_NONE == (uint32_t)vrdx::BalancedForm::kNone &&
+                  VRDX_HIP_BALANCED_TWIN == (uint32_t)vrdx::BalancedForm::kTwin &&
+                  VRDX_HIP_BALANCED_BALANCED == (uint32_t)vrdx::BalancedForm::kBalanced &&
+                  VRDX_HIP_BALANCED_SPREAD_FROM == vrdx::kSegSpreadFrom && VRDX_HIP_BALANCED_SPREAD_SHARES == vrdx::kSegSpreadShares,
+              "the forms and constants of the header are the planner's");
+
+// The balanced segmented sorts (include/vk_radix_sort.h, vrdxHipCmdBalancedSortSegmented[KeyValue]):
+// PlanBalancedSegmentedSort (vrdx_plan.h).  Every form but the balanced one IS what vrdxHipCmdSortSegmented* records and goes
+// through RecordSegmentedSort32; the balanced form records its own step list on the storage of MakeBalancedSegmentedLayout.
+void RecordBalancedSegmentedSort(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount,
+                                 VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset, VkBuffer keysBuffer, VkDeviceSize keysOffset,
+                                 VkBuffer valuesBuffer, VkDeviceSize valuesOffset, VkBuffer storageBuffer,
+                                 VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  const bool keyValue = valuesBuffer != nullptr;
+  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
+  const vrdx::BalancedSegmentedPlan plan =
+      vrdx::PlanBalancedSegmentedSort(PlanContextOf(sorter), keyValue, std::min<uint32_t>(maxElementCount, VRDX_MAX_ELEMENTS),
+                                      segmentCount, (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (plan.form != vrdx::BalancedForm::kBalanced && plan.refusal == nullptr)
+    return RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
+                                 keysOffset, valuesBuffer, valuesOffset, {}, storageBuffer, storageOffset, queryPool, query);
+  Recording r(commandBuffer, sorter, maxElementCount, queryPool, query);
+  if (r.NothingToRecord(sorter, plan.refusal, plan.stepCount)) return;
+  const auto words = [storage](uint64_t offset) { return reinterpret_cast<uint32_t*>(storage + offset); };
+  const vrdx::SegmentedLayout& lists = plan.layout.lists;
+  vrdx::BalancedSegmentedArgs a;
+  vrdx::SegmentedArgs& s = a.segmented;
+  s.keys = reinterpret_cast<uint32_t*>(BufferAddress(keysBuffer, keysOffset));
+  s.values = keyValue ? reinterpret_cast<uint32_t*>(BufferAddress(valuesBuffer, valuesOffset)) : nullptr;
+  s.keysScratch = words(lists.keysScratchOffset);
+  s.valuesScratch = keyValue ? words(lists.valuesScratchOffset) : nullptr;
+  s.offsets = reinterpret_cast<const uint32_t*>(BufferAddress(offsetsBuffer, offsetsOffset));
+  s.segmentCount = segmentCount;
+  s.maxCount = r.count;
+  s.midCount = words(lists.midCountOffset);
+  s.midList = words(lists.midListOffset);
+  s.midCap = lists.midCap;
+  s.largeCount = words(lists.largeCountOffset);
+  s.largeList = words(lists.largeListOffset);
+  s.largeCap = lists.largeCap;
+  s.failure = words(VRDX_OFF_FAILURE);
+  s.stickyFailure = sorter->stickyStatus;
+  a.split = words(plan.layout.splitOffset);
+  a.restCount = a.split + 4;
+  a.restList = words(plan.layout.restListOffset);
+  a.spreadTable = words(plan.layout.spreadTableOffset);
+  a.pieceTable = words(plan.layout.pieceTableOffset);
+  a.rows = words(plan.layout.rowsOffset);
+  a.spreadCap = plan.layout.spreadCap;
+  a.pieceCap = plan.layout.pieceCap;
+  a.computeUnits = plan.computeUnits;
+  a.pass = 0;
+  // the twin's large kernel, unchanged, on the segments that are not spread: only the list and its count differ
+  vrdx::SegmentedArgs rest = s;
+  rest.largeCount = a.restCount;
+  rest.largeList = a.restList;
+  for (uint32_t i = 0; i < plan.stepCount; ++i) {
+    const vrdx::BalancedSegmentedStep& step = plan.steps[i];
+    a.pass = step.pass;
+    hipError_t e = hipErrorInvalidValue;
+    switch (step.what) {
+      case vrdx::StepBalanced::kClear: e = vrdx::LaunchSegmentedClear(r.stream, s); break;
+      case vrdx::StepBalanced::kSmall:
+        e = vrdx::LaunchSegmented(r.stream, vrdx::kSegmentSmall, step.grid, keyValue, plan.atomicRank, s, 0, 0);
+        break;
+      case vrdx::StepBalanced::kMid:
+        e = vrdx::LaunchSegmented(r.stream, vrdx::kSegmentMid, step.grid, keyValue, plan.atomicRank, s, 0, 0);
+        break;
+      case vrdx::StepBalanced::kSplit: e = vrdx::LaunchSegmentedSplit(r.stream, a); break;
+      case vrdx::StepBalanced::kLargeRest:
+        e = vrdx::LaunchSegmented(r.stream, vrdx::kSegmentLarge, step.grid, keyValue, plan.atomicRank, rest, 0, 0);
+        break;
+      case vrdx::StepBalanced::kCount: e = vrdx::LaunchSegmentedPieceCount(r.stream, a); break;
+      case vrdx::StepBalanced::kScan: e = vrdx::LaunchSegmentedPieceScan(r.stream, a); break;
+      case vrdx::StepBalanced::kScatter: e = vrdx::LaunchSegmentedPieceScatter(r.stream, keyValue, plan.atomicRank, a); break;
+      case vrdx::StepBalanced::kCopyBack: e = vrdx::LaunchSegmentedPieceCopyBack(r.stream, keyValue, a); break;
+    }
+    EnqueueCheck(sorter, step.name, e);
+    // (a step that shares its slot with the next one -- the split, a count -- leaves the stamp to it)
+    if (i + 1 == plan.stepCount || plan.steps[i + 1].slot != step.slot) r.stamps.AdvanceTo(step.slot);
+  }
+  r.stamps.Finish();
+  MaybeRecheckOrder(sorter, r.stream, plan.atomicRank);
+}
+
 // The 64-bit sorts (include/vk_radix_sort.h, vrdxHipCmdSort64[Ordered][KeyValue][Indirect]): the steps of PlanSort64
 // (vrdx_plan.h).  The inner sorts go through RecordSort, without a query pool, on word arrays inside the storage.
 // Indirect (indirectBuffer != nullptr): elementCount is the bound; layout, plans and grids come from it alone, and every
@@ -933,6 +1019,56 @@ void vrdxHipCmdSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter s
                                      VkQueryPool queryPool, uint32_t query) {
   RecordSegmentedSort32(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer, keysOffset,
                         valuesBuffer, valuesOffset, {}, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdBalancedSortSegmented(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                     uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                     VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer storageBuffer,
+                                     VkDeviceSize storageOffset, VkQueryPool queryPool, uint32_t query) {
+  RecordBalancedSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
+                              keysOffset, nullptr, 0, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipCmdBalancedSortSegmentedKeyValue(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,
+                                             uint32_t segmentCount, VkBuffer offsetsBuffer, VkDeviceSize offsetsOffset,
+                                             VkBuffer keysBuffer, VkDeviceSize keysOffset, VkBuffer valuesBuffer,
+                                             VkDeviceSize valuesOffset, VkBuffer storageBuffer, VkDeviceSize storageOffset,
+                                             VkQueryPool queryPool, uint32_t query) {
+  RecordBalancedSegmentedSort(commandBuffer, sorter, maxElementCount, segmentCount, offsetsBuffer, offsetsOffset, keysBuffer,
+                              keysOffset, valuesBuffer, valuesOffset, storageBuffer, storageOffset, queryPool, query);
+}
+
+void vrdxHipDescribeBalancedSegmentedPlan(VrdxSorter sorter, uint32_t maxElementCount, uint32_t segmentCount, int keyValue,
+                                          VrdxHipBalancedSegmentedPlanInfo* info) {
+  if (info == nullptr) return;
+  std::memset(info, 0, sizeof(*info));
+  if (sorter == nullptr) return;
+  if (maxElementCount > VRDX_MAX_ELEMENTS) maxElementCount = VRDX_MAX_ELEMENTS;
+  vrdx::DescribeBalancedSegmentedPlan(
+      vrdx::PlanBalancedSegmentedSort(PlanContextOf(sorter), keyValue != 0, maxElementCount, segmentCount, 0), info);
+}
+
+VkResult vrdxHipReadBalancedSplit(VkCommandBuffer commandBuffer, VrdxSorter sorter, VkBuffer storageBuffer,
+                                  VkDeviceSize storageOffset, uint32_t maxElementCount, VrdxHipBalancedSplitInfo* info) {
+  if (info == nullptr || sorter == nullptr) return VK_ERROR_INITIALIZATION_FAILED;
+  std::memset(info, 0, sizeof(*info));
+  if (maxElementCount > VRDX_MAX_ELEMENTS) maxElementCount = VRDX_MAX_ELEMENTS;
+  uint8_t* const storage = BufferAddress(storageBuffer, storageOffset);
+  // (the offset of the words depends on neither the form of the values nor the segment count)
+  const vrdx::BalancedSegmentedPlan plan = vrdx::PlanBalancedSegmentedSort(PlanContextOf(sorter), false, maxElementCount, 1,
+                                                                           (uint64_t)reinterpret_cast<uintptr_t>(storage));
+  if (plan.form != vrdx::BalancedForm::kBalanced) return VK_SUCCESS;
+  DeviceScope deviceScope(sorter->device);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(commandBuffer);
+  uint32_t words[4];
+  if (hipMemcpyAsync(words, storage + plan.layout.splitOffset, sizeof(words), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return VK_ERROR_DEVICE_LOST;
+  info->listedSegments = words[0];
+  info->spreadSegments = words[1];
+  info->pieces = words[2];
+  info->pieceKeys = words[3];
+  return VK_SUCCESS;
 }
 
 void vrdxHipCmdSortSegmentedBits(VkCommandBuffer commandBuffer, VrdxSorter sorter, uint32_t maxElementCount,

@@ -288,6 +288,30 @@ hipError_t LaunchRangeScan(hipStream_t stream, const RangeSortArgs& args);
 hipError_t LaunchRangeScatter(hipStream_t stream, bool keyValue, bool atomicRank, const RangeSortArgs& args);
 hipError_t LaunchRangeCopyBack(hipStream_t stream, bool keyValue, const RangeSortArgs& args);
 
+// ---- the balanced segmented sort (vrdxHipCmdBalancedSortSegmented[KeyValue]; vrdx_kernels.hip, "balanced segmented sort")
+// ---- The segmented sort's fill, small and mid launches as they are; then segmented_split_kernel (one workgroup) cuts the
+// large list into the SPREAD segments and the rest (vrdx_layout.h, MakeBalancedSegmentedLayout), the unchanged
+// segmented_large_kernel runs on the rest list, and the pieces of the spread segments are sorted by count, scan and scatter
+// launches per byte of the key and a copy back (PlanBalancedSegmentedSort in vrdx_plan.h lists the launches).
+struct BalancedSegmentedArgs {
+  SegmentedArgs segmented;     // what the twin's kernels take; the large launch gets restCount / restList in its place
+  uint32_t* restCount;         // written by the split kernel
+  uint32_t* restList;          // [segmented.largeCap] segment ids
+  uint32_t* split;             // [kSegSplitWords]: listed, spread, pieces, L; written by the split kernel
+  uint32_t* spreadTable;       // [spreadCap][kSegSpreadEntryWords]
+  uint32_t* pieceTable;        // [pieceCap][kSegPieceEntryWords]
+  uint32_t* rows;              // [pieceCap][256]: per piece, the pass's counts, then its positions
+  uint32_t spreadCap, pieceCap;
+  uint32_t computeUnits;       // the divisor of the share and of the piece length
+  uint32_t pass;               // the byte this launch works on (the split and the copy back: unused)
+};
+hipError_t LaunchSegmentedSplit(hipStream_t stream, const BalancedSegmentedArgs& args);
+// one workgroup per piece slot | per spread slot | per piece slot | per piece slot; a slot without a piece or a segment returns
+hipError_t LaunchSegmentedPieceCount(hipStream_t stream, const BalancedSegmentedArgs& args);
+hipError_t LaunchSegmentedPieceScan(hipStream_t stream, const BalancedSegmentedArgs& args);
+hipError_t LaunchSegmentedPieceScatter(hipStream_t stream, bool keyValue, bool atomicRank, const BalancedSegmentedArgs& args);
+hipError_t LaunchSegmentedPieceCopyBack(hipStream_t stream, bool keyValue, const BalancedSegmentedArgs& args);
+
 // ---- key orders of the 64-bit sorts (vrdxHipCmdSort64Ordered*, vrdxHipCmdSortSegmented64Ordered*; vrdx_kernels.hip, "key
 // orders of the 64-bit sorts") ----
 // The order word of include/vk_radix_sort.h: a key type, VRDX_HIP_ORDER_DESCENDING or-ed in or not.  The kernels sort

@@ -5016,6 +5016,350 @@ __global__ __launch_bounds__(kRangeCopyThreads) void range_copy_back_kernel(Rang
 }
 
 // ---------------------------------------------------------------------------------------------
+// balanced segmented sort (vrdxHipCmdBalancedSortSegmented*): huge segments in pieces -- DESIGN.md section 4.23
+// ---------------------------------------------------------------------------------------------
+// The segmented sort with one launch more behind the mid launch and the range sort's count / scan / scatter over PIECES of
+// the segments that are long and longer than their share of the chip (vrdx_layout.h, MakeBalancedSegmentedLayout, has the
+// rule, the piece length and the caps):
+//   segmented_split_kernel            one workgroup: reads the large list the small kernel wrote, adds up the lengths, and
+//                                     sends every listed segment to the spread table or to the rest list, which the unchanged
+//                                     segmented_large_kernel then takes; cuts the spread segments into pieces;
+//   segmented_piece_count_kernel      workgroup per piece: the counts of byte p over the piece, on the side the segment's
+//                                     pass p reads -- again in every pass, a piece holds other keys after a pass;
+//   segmented_piece_scan_kernel       workgroup per spread segment: adds the rows of its pieces up, marks pass p active in
+//                                     the SEGMENT's mask when some bin is neither empty nor everything, and turns each row
+//                                     into segment begin + start of the digit + the digit's counts in the earlier pieces;
+//   segmented_piece_scatter_kernel    workgroup per piece: returns for an inactive pass, else range_scatter_kernel's tile body
+//                                     from the piece's row, every store checked against the segment's bounds;
+//   segmented_piece_copy_back_kernel  workgroup per piece: after an odd number of active passes of its segment.
+// The side pass p reads follows per segment from the bits below p of its mask (RangePassReadsScratch); bit p is written by
+// scan p alone, which does not read it.  No launch waits for another workgroup.  The tables lie in the caller's storage:
+// whatever they hold, every index is checked against maxCount and the segment's bounds before it is used.
+__device__ __forceinline__ uint32_t ListedLength(const SegmentedArgs& s, uint32_t i, uint32_t* id, uint32_t* begin, uint32_t* end) {
+  const uint32_t segment = s.largeList[i];
+  *id = segment;
+  if (segment >= s.segmentCount) return 0u;
+  const uint32_t b = s.offsets[segment], e = s.offsets[segment + 1];
+  if (!(b <= e && e <= s.maxCount) || e - b <= kSegMidMax) return 0u;  // (what segmented_large_kernel skips as well)
+  *begin = b;
+  *end = e;
+  return e - b;
+}
+
+__global__ __launch_bounds__(1024) void segmented_split_kernel(BalancedSegmentedArgs a) {
+  constexpr uint32_t THREADS = 1024;
+  __shared__ unsigned long long totalLarge, totalSpread;
+  __shared__ uint32_t restN, spreadN, pieceN;
+  __shared__ uint32_t segBegin[kSegSpreadMaxSlots], segEnd[kSegSpreadMaxSlots], segId[kSegSpreadMaxSlots];
+  __shared__ uint32_t segFirst[kSegSpreadMaxSlots], segPieces[kSegSpreadMaxSlots];
+  const SegmentedArgs& s = a.segmented;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t spreadCap = min(a.spreadCap, kSegSpreadMaxSlots);
+  if (tid == 0) {
+    totalLarge = 0;
+    totalSpread = 0;
+    restN = 0;
+    spreadN = 0;
+    pieceN = 0;
+  }
+  __syncthreads();
+  const uint32_t listed = min(*s.largeCount, s.largeCap);
+  uint32_t id = 0, begin = 0, end = 0;
+  unsigned long long mine = 0;
+  for (uint32_t i = tid; i < listed; i += THREADS) mine += ListedLength(s, i, &id, &begin, &end);
+  if (mine != 0) atomicAdd(&totalLarge, mine);
+  __syncthreads();
+  const unsigned long long share = (totalLarge + a.computeUnits - 1u) / a.computeUnits;
+  const unsigned long long from = max((unsigned long long)kSegSpreadFrom, kSegSpreadShares * share);
+  for (uint32_t i = tid; i < listed; i += THREADS) {
+    const uint32_t length = ListedLength(s, i, &id, &begin, &end);
+    if (length == 0) continue;
+    if (length > from) {
+      const uint32_t slot = atomicAdd(&spreadN, 1u);
+      if (slot < spreadCap) {
+        segBegin[slot] = begin;
+        segEnd[slot] = end;
+        segId[slot] = id;
+        atomicAdd(&totalSpread, (unsigned long long)length);
+        continue;
+      }
+    }
+    a.restList[atomicAdd(&restN, 1u)] = id;  // (at most `listed` <= largeCap entries)
+  }
+  __syncthreads();
+  const uint32_t spread = min(spreadN, spreadCap);
+  const unsigned long long perCu = (totalSpread + a.computeUnits - 1u) / a.computeUnits;
+  const unsigned long long rounded = (perCu + 255u) & ~255ull;
+  const uint32_t pieceKeys = (uint32_t)min(max(rounded, (unsigned long long)kSegPieceMinKeys), 0x40000000ull);
+  if (tid == 0) {
+    // a segment whose pieces find no room (only overlapping segments can ask for more than pieceCap) stays with one workgroup
+    uint32_t first = 0;
+    for (uint32_t k = 0; k < spread; ++k) {
+      uint32_t pieces = (segEnd[k] - segBegin[k] + pieceKeys - 1u) / pieceKeys;
+      if (first + pieces > a.pieceCap) {
+        pieces = 0;
+        a.restList[restN++] = segId[k];
+      }
+      segFirst[k] = first;
+      segPieces[k] = pieces;
+      first += pieces;
+    }
+    pieceN = first;
+  }
+  __syncthreads();
+  if (tid < spread) {
+    uint32_t* const entry = a.spreadTable + (size_t)tid * kSegSpreadEntryWords;
+    entry[0] = segBegin[tid];
+    entry[1] = segEnd[tid];
+    entry[2] = segFirst[tid];
+    entry[3] = segPieces[tid];
+    entry[4] = 0u;  // the mask of active passes
+    entry[5] = segId[tid];
+    for (uint32_t k = 0; k < segPieces[tid]; ++k) {
+      uint32_t* const piece = a.pieceTable + (size_t)(segFirst[tid] + k) * kSegPieceEntryWords;
+      const uint32_t pieceBegin = segBegin[tid] + k * pieceKeys;
+      piece[0] = tid;
+      piece[1] = pieceBegin;
+      piece[2] = segEnd[tid] - pieceBegin > pieceKeys ? pieceBegin + pieceKeys : segEnd[tid];
+    }
+  }
+  if (tid == 0) {
+    a.split[0] = listed;
+    a.split[1] = spread;
+    a.split[2] = pieceN;
+    a.split[3] = pieceKeys;
+    *a.restCount = restN;
+  }
+}
+
+// What a piece's workgroup works on: false when this slot has no piece.  Everything read from the tables is checked.
+struct SegmentPiece {
+  uint32_t begin, end;        // the piece
+  uint32_t segBegin, segEnd;  // its segment
+  uint32_t active;            // the segment's mask
+};
+__device__ __forceinline__ bool PieceOf(const BalancedSegmentedArgs& a, SegmentPiece* p) {
+  if (blockIdx.x >= min(a.split[2], a.pieceCap)) return false;
+  const uint32_t* const piece = a.pieceTable + (size_t)blockIdx.x * kSegPieceEntryWords;
+  const uint32_t slot = piece[0];
+  if (slot >= a.spreadCap) return false;
+  const uint32_t* const entry = a.spreadTable + (size_t)slot * kSegSpreadEntryWords;
+  p->begin = piece[1];
+  p->end = piece[2];
+  p->segBegin = entry[0];
+  p->segEnd = entry[1];
+  p->active = entry[4];
+  return p->segBegin <= p->begin && p->begin < p->end && p->end <= p->segEnd && p->segEnd <= a.segmented.maxCount;
+}
+
+__global__ __launch_bounds__(1024) void segmented_piece_count_kernel(BalancedSegmentedArgs a) {
+  constexpr uint32_t THREADS = 1024;
+  __shared__ uint32_t bins[256 * kSegHistCopies];  // [digit][copy]
+  const uint32_t tid = threadIdx.x;
+  SegmentPiece p;
+  if (!PieceOf(a, &p)) return;  // uniform
+  const uint32_t* const keys = (RangePassReadsScratch(p.active, a.pass) ? a.segmented.keysScratch : a.segmented.keys) + p.begin;
+  const uint32_t length = p.end - p.begin;
+  const uint32_t shift = 8u * a.pass;
+  for (uint32_t i = tid; i < 256u * kSegHistCopies; i += THREADS) bins[i] = 0;
+  LdsBarrier();
+  const uint32_t copy = tid & (kSegHistCopies - 1);
+  auto count = [&](uint32_t key) { atomicAdd(&bins[((key >> shift) & 0xFFu) * kSegHistCopies + copy], 1u); };
+  {
+    constexpr uint32_t U = 8;  // loads in flight per lane
+    uint32_t i = tid;
+    for (; i + (U - 1) * THREADS < length; i += U * THREADS) {
+      uint32_t k[U];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) k[u] = keys[i + u * THREADS];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) count(k[u]);
+    }
+    for (; i < length; i += THREADS) count(keys[i]);
+  }
+  LdsBarrier();
+  if (tid >= 256) return;
+  uint32_t c = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < kSegHistCopies; ++r) c += bins[tid * kSegHistCopies + ((r + tid) & (kSegHistCopies - 1))];
+  a.rows[(size_t)blockIdx.x * 256 + tid] = c;
+}
+
+__global__ __launch_bounds__(1024) void segmented_piece_scan_kernel(BalancedSegmentedArgs a) {
+  __shared__ uint32_t partial[4 * 256];
+  __shared__ uint32_t start[256];
+  __shared__ uint32_t scanScratch[16];
+  __shared__ uint32_t varied;
+  const int tid = threadIdx.x;
+  const uint32_t g = (uint32_t)tid >> 8, d = (uint32_t)tid & 255u;
+  if (blockIdx.x >= min(a.split[1], a.spreadCap)) return;  // uniform
+  uint32_t* const entry = a.spreadTable + (size_t)blockIdx.x * kSegSpreadEntryWords;
+  const uint32_t begin = entry[0], end = entry[1], first = entry[2], pieces = entry[3];
+  if (pieces == 0 || first >= a.pieceCap || pieces > a.pieceCap - first || begin >= end) return;  // uniform
+  uint32_t* const rows = a.rows + (size_t)first * 256;
+  if (tid == 0) varied = 0;
+  // the rows in four groups, group g by the threads [256 g, 256 g + 256): sums first, then the running positions
+  const uint32_t per = (pieces + 3u) / 4u;
+  const uint32_t lo = min(g * per, pieces), hi = min(lo + per, pieces);
+  constexpr uint32_t B = 16;  // loads in flight per lane
+  uint32_t sum = 0;
+  for (uint32_t r0 = lo; r0 < hi; r0 += B) {
+    uint32_t v[B];
+#pragma unroll
+    for (uint32_t k = 0; k < B; ++k) v[k] = r0 + k < hi ? rows[(size_t)(r0 + k) * 256 + d] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < B; ++k) sum += v[k];
+  }
+  partial[g * 256 + d] = sum;
+  LdsBarrier();
+  // a pass moves keys when its digit takes two values at least: some bin is neither empty nor everything
+  const uint32_t total = tid < 256 ? partial[d] + partial[256 + d] + partial[512 + d] + partial[768 + d] : 0u;
+  if (total != 0 && total != end - begin) varied = 1u;
+  const uint32_t exclusive = BlockExclusiveScan256(total, scanScratch, tid);
+  if (tid < 256) start[d] = exclusive;
+  LdsBarrier();
+  if (varied == 0) return;  // uniform: bit `pass` of the mask stays 0
+  if (tid == 0) entry[4] |= 1u << a.pass;
+  uint32_t run = begin + start[d];
+  for (uint32_t h = 0; h < g; ++h) run += partial[h * 256 + d];
+  for (uint32_t r0 = lo; r0 < hi; r0 += B) {
+    uint32_t v[B];
+#pragma unroll
+    for (uint32_t k = 0; k < B; ++k) v[k] = r0 + k < hi ? rows[(size_t)(r0 + k) * 256 + d] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < B; ++k) {
+      if (r0 + k < hi) rows[(size_t)(r0 + k) * 256 + d] = run;
+      run += v[k];
+    }
+  }
+}
+
+// LDS: RangeScatterLdsWords (vrdx_kernels.h).
+template <bool KV, bool ATOMIC_RANK>
+__global__ __launch_bounds__(1024) void segmented_piece_scatter_kernel(BalancedSegmentedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr int THREADS = 1024, KPT = 16, WAVES = THREADS / 64;
+  constexpr uint32_t TILE = kSegLargeTile;
+  uint32_t* const stagedKeys = smem;
+  uint32_t* const stagedValues = smem + TILE;  // KV only
+  uint32_t* const waveHist = smem + TILE * (KV ? 2 : 1);
+  uint32_t* const scanScratch = waveHist + WAVES * 256;
+  uint32_t* const base = scanScratch + 16;      // where the next key of digit d goes
+  uint32_t* const tileStart = base + 256;       // tile-local position of digit d's first key
+  uint32_t* const tileCount = tileStart + 256;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  SegmentPiece p;
+  if (!PieceOf(a, &p)) return;                     // uniform
+  if (((p.active >> a.pass) & 1u) == 0) return;  // uniform
+  const SegmentedArgs& s = a.segmented;
+  const bool fromScratch = RangePassReadsScratch(p.active, a.pass);
+  const uint32_t length = p.end - p.begin;
+  const uint32_t* const src = (fromScratch ? s.keysScratch : s.keys) + p.begin;
+  uint32_t* const dst = fromScratch ? s.keys : s.keysScratch;
+  const uint32_t* const srcV = KV ? (fromScratch ? s.valuesScratch : s.values) + p.begin : nullptr;
+  uint32_t* const dstV = fromScratch ? s.values : s.valuesScratch;
+  if (tid < 256) base[tid] = a.rows[(size_t)blockIdx.x * 256 + tid];  // (first read two barriers into the first tile)
+  const uint32_t shift = 8u * a.pass;
+  uint32_t* const myHist = waveHist + wave * 256;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+#pragma unroll 1
+  for (uint32_t t0 = 0; t0 < length; t0 += TILE) {
+    const uint32_t m = min(TILE, length - t0);
+    // the chunks of four 64-key slots dealt out evenly over the waves, as in SegmentLsd: pads (the largest key) only in the
+    // last chunk, behind every real key of the tile
+    const uint32_t chunks = (m + 255u) / 256u;
+    const uint32_t per = chunks / WAVES, extra = chunks % WAVES;
+    const uint32_t slots = 4u * (per + (w < extra ? 1u : 0u));
+    const uint32_t first = 256u * (w * per + (w < extra ? w : extra)) + lane;
+    uint32_t key[KPT];
+    uint32_t val[KV ? KPT : 1];
+    LoadStriped<KPT, false, true>(src + t0, first, m, false, 0xFFFFFFFFu, key, slots);
+    if constexpr (KV) LoadStriped<KPT, false, true>(srcV + t0, first, m, false, 0u, val, slots);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) myHist[lane + 64 * i] = 0;
+    uint32_t rank[KPT];
+    if constexpr (ATOMIC_RANK)
+      RankAtomic<KPT, false, true, 0xFFu, false>(key, shift, myHist, lane, rank, slots);
+    else
+      RankBallot<KPT, false, true, false>(key, shift, myHist, lane, rank, slots);
+    LdsBarrier();
+    uint32_t c = 0;
+    if (tid < 256) {
+#pragma unroll
+      for (int v = 0; v < WAVES; ++v) c += waveHist[v * 256 + tid];
+    }
+    const uint32_t exclusive = BlockExclusiveScan256(tid < 256 ? c : 0u, scanScratch, tid);
+    if (tid < 256) {
+      uint32_t run = exclusive;
+#pragma unroll
+      for (int v = 0; v < WAVES; ++v) {
+        const uint32_t h = waveHist[v * 256 + tid];
+        waveHist[v * 256 + tid] = run;
+        run += h;
+      }
+      tileStart[tid] = exclusive;
+      tileCount[tid] = tid == 255 ? c - (256u * chunks - m) : c;  // (the pads are digit 255's last keys)
+    }
+    LdsBarrier();
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      if (i % 4 == 0 && (uint32_t)i >= slots) break;
+      const uint32_t slot = StagingSlot<TILE>(rank[i] + myHist[VRDX_DIGIT(false, 0xFFu, key[i], shift)]);
+      stagedKeys[slot] = key[i];
+      if constexpr (KV) stagedValues[slot] = val[i];
+    }
+    LdsBarrier();
+    // sorted position q of the tile -> base[d] + q - tileStart[d]: runs of one digit land contiguously
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      if (i % 4 == 0 && (uint32_t)i >= slots) break;
+      const uint32_t q = first + 64 * i;
+      if (q < m) {
+        const uint32_t slot = StagingSlot<TILE>(q);
+        const uint32_t k = stagedKeys[slot];
+        const uint32_t d = VRDX_DIGIT(false, 0xFFu, k, shift);
+        const uint32_t to = base[d] + q - tileStart[d];
+        // inside the segment when the row holds this pass's positions; whatever it holds, nothing is written outside it
+        if (to >= p.segBegin && to < p.segEnd) {
+          dst[to] = k;
+          if constexpr (KV) dstV[to] = stagedValues[slot];
+        }
+      }
+    }
+    LdsBarrier();  // every lane has read base[] and tileStart[] of this tile
+    if (tid < 256) base[tid] += tileCount[tid];
+    // (the next tile reads base[] two barriers later, and writes the staging buffer and tileStart[] one barrier later)
+  }
+}
+
+template <bool KV>
+__global__ __launch_bounds__(1024) void segmented_piece_copy_back_kernel(BalancedSegmentedArgs a) {
+  constexpr uint32_t THREADS = 1024, U = 4;
+  SegmentPiece p;
+  if (!PieceOf(a, &p)) return;                    // uniform
+  if ((__popc(p.active & 0xFu) & 1) == 0) return;  // an even number of active passes: the segment is in place
+  const SegmentedArgs& s = a.segmented;
+  for (uint32_t i0 = p.begin + threadIdx.x; i0 < p.end; i0 += U * THREADS) {
+    uint32_t k[U], v[KV ? U : 1];
+    (void)v;
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+      const uint32_t i = i0 + u * THREADS;
+      k[u] = i < p.end ? s.keysScratch[i] : 0u;
+      if constexpr (KV) v[u] = i < p.end ? s.valuesScratch[i] : 0u;
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+      const uint32_t i = i0 + u * THREADS;
+      if (i < p.end) {
+        s.keys[i] = k[u];
+        if constexpr (KV) s.values[i] = v[u];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side: the launch layer (vrdx_launch.inc) on the kernels' host stubs
 // ---------------------------------------------------------------------------------------------
 #include "vrdx_launch.inc"

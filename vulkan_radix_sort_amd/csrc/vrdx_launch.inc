@@ -389,6 +389,30 @@
   X(kRangeCopyBackV, (&range_copy_back_kernel<true>), kRangeCopyThreads, 0, \
     "_ZN4vrdx22range_copy_back_kernelILb1EEEvNS_13RangeSortArgsE")
 
+// The kernels of the balanced segmented sort (vrdxHipCmdBalancedSortSegmented*): a fifth list for the same reason.  Its ids
+// follow the range-sort list's; the text stands here, in front of the wide-value list.
+#define VRDX_BALANCED_SEGMENTED_KERNELS(X) \
+  X(kSegmentedSplit, (&segmented_split_kernel), 1024, 0, \
+    "_ZN4vrdx22segmented_split_kernelENS_21BalancedSegmentedArgsE") \
+  X(kSegmentedPieceCount, (&segmented_piece_count_kernel), 1024, 0, \
+    "_ZN4vrdx28segmented_piece_count_kernelENS_21BalancedSegmentedArgsE") \
+  X(kSegmentedPieceScan, (&segmented_piece_scan_kernel), 1024, 0, \
+    "_ZN4vrdx27segmented_piece_scan_kernelENS_21BalancedSegmentedArgsE") \
+  /* segmented_piece_scatter_kernel [key-value][atomic rank] */ \
+  X(kSegmentedPieceScatter, (&segmented_piece_scatter_kernel<false, false>), 1024, RangeScatterLdsWords(false) * 4, \
+    "_ZN4vrdx30segmented_piece_scatter_kernelILb0ELb0EEEvNS_21BalancedSegmentedArgsE") \
+  X(kSegmentedPieceScatterA, (&segmented_piece_scatter_kernel<false, true>), 1024, RangeScatterLdsWords(false) * 4, \
+    "_ZN4vrdx30segmented_piece_scatter_kernelILb0ELb1EEEvNS_21BalancedSegmentedArgsE") \
+  X(kSegmentedPieceScatterV, (&segmented_piece_scatter_kernel<true, false>), 1024, RangeScatterLdsWords(true) * 4, \
+    "_ZN4vrdx30segmented_piece_scatter_kernelILb1ELb0EEEvNS_21BalancedSegmentedArgsE") \
+  X(kSegmentedPieceScatterVA, (&segmented_piece_scatter_kernel<true, true>), 1024, RangeScatterLdsWords(true) * 4, \
+    "_ZN4vrdx30segmented_piece_scatter_kernelILb1ELb1EEEvNS_21BalancedSegmentedArgsE") \
+  /* segmented_piece_copy_back_kernel [key-value] */ \
+  X(kSegmentedPieceCopyBack, (&segmented_piece_copy_back_kernel<false>), 1024, 0, \
+    "_ZN4vrdx32segmented_piece_copy_back_kernelILb0EEEvNS_21BalancedSegmentedArgsE") \
+  X(kSegmentedPieceCopyBackV, (&segmented_piece_copy_back_kernel<true>), 1024, 0, \
+    "_ZN4vrdx32segmented_piece_copy_back_kernelILb1EEEvNS_21BalancedSegmentedArgsE")
+
 // The kernels of the sorts of 32-bit keys with 64-bit values (vrdxHipCmdWideValueSort*), in a third list behind the other two
 // for the same reason.
 #define VRDX_WIDE_VALUE_KERNELS(X) \
@@ -426,7 +450,8 @@
   X(kSegmentedWideLargeA, (&segmented_large_wide_kernel<true>), 1024, SegmentWideLargeLdsWords() * 4, \
     "_ZN4vrdx27segmented_large_wide_kernelILb1EEEvNS_17SegmentedWideArgsE")
 
-#define VRDX_ALL_KERNELS(X) VRDX_KERNELS(X) VRDX_ORDERED32_KERNELS(X) VRDX_WIDE_VALUE_KERNELS(X) VRDX_RANGE_SORT_KERNELS(X)
+#define VRDX_ALL_KERNELS(X) VRDX_KERNELS(X) VRDX_ORDERED32_KERNELS(X) VRDX_WIDE_VALUE_KERNELS(X) VRDX_RANGE_SORT_KERNELS(X) \
+  VRDX_BALANCED_SEGMENTED_KERNELS(X)
 
 enum KernelId : int {
 #define VRDX_KERNEL_ID(id, stub, threads, ldsBytes, name) id,
@@ -436,6 +461,7 @@ enum KernelId : int {
   VRDX_ORDERED32_KERNELS(VRDX_KERNEL_ID)
   VRDX_WIDE_VALUE_KERNELS(VRDX_KERNEL_ID)
   VRDX_RANGE_SORT_KERNELS(VRDX_KERNEL_ID)
+  VRDX_BALANCED_SEGMENTED_KERNELS(VRDX_KERNEL_ID)
 #undef VRDX_KERNEL_ID
   kNumAllKernels
 };
@@ -793,4 +819,39 @@ hipError_t LaunchRangeCopyBack(hipStream_t stream, bool keyValue, const RangeSor
   if (!RangeSortFits(args, false) || keyValue != (args.values != nullptr)) return hipErrorInvalidValue;
   const uint32_t grid = (args.maxCount + 4u * kRangeCopyThreads - 1u) / (4u * kRangeCopyThreads);
   return Launch(keyValue ? kRangeCopyBackV : kRangeCopyBack, grid, stream, args);
+}
+
+// ---- the balanced segmented sort (VRDX_BALANCED_SEGMENTED_KERNELS) ------------------------------------
+// the caps are those of vrdx_layout.h for this bound and CU count: the tables and rows lie where MakeBalancedSegmentedLayout
+// puts them, sized by the same two functions
+static bool BalancedSegmentedFits(const BalancedSegmentedArgs& a, bool passLaunch) {
+  const SegmentedArgs& s = a.segmented;
+  return s.maxCount > kSegSpreadFrom && s.maxCount <= VRDX_MAX_ELEMENTS && s.segmentCount != 0 && a.computeUnits != 0 &&
+         a.spreadCap != 0 && a.spreadCap == SegSpreadCap(s.maxCount, a.computeUnits) &&
+         a.pieceCap == SegPieceCap(s.maxCount, a.computeUnits) && (!passLaunch || a.pass < VRDX_PASSES);
+}
+
+hipError_t LaunchSegmentedSplit(hipStream_t stream, const BalancedSegmentedArgs& args) {
+  if (!BalancedSegmentedFits(args, false)) return hipErrorInvalidValue;
+  return Launch(kSegmentedSplit, 1, stream, args);
+}
+
+hipError_t LaunchSegmentedPieceCount(hipStream_t stream, const BalancedSegmentedArgs& args) {
+  if (!BalancedSegmentedFits(args, true)) return hipErrorInvalidValue;
+  return Launch(kSegmentedPieceCount, args.pieceCap, stream, args);
+}
+
+hipError_t LaunchSegmentedPieceScan(hipStream_t stream, const BalancedSegmentedArgs& args) {
+  if (!BalancedSegmentedFits(args, true)) return hipErrorInvalidValue;
+  return Launch(kSegmentedPieceScan, args.spreadCap, stream, args);
+}
+
+hipError_t LaunchSegmentedPieceScatter(hipStream_t stream, bool keyValue, bool atomicRank, const BalancedSegmentedArgs& args) {
+  if (!BalancedSegmentedFits(args, true) || keyValue != (args.segmented.values != nullptr)) return hipErrorInvalidValue;
+  return Launch(Form(kSegmentedPieceScatter, keyValue, atomicRank), args.pieceCap, stream, args);
+}
+
+hipError_t LaunchSegmentedPieceCopyBack(hipStream_t stream, bool keyValue, const BalancedSegmentedArgs& args) {
+  if (!BalancedSegmentedFits(args, false) || keyValue != (args.segmented.values != nullptr)) return hipErrorInvalidValue;
+  return Launch(keyValue ? kSegmentedPieceCopyBackV : kSegmentedPieceCopyBack, args.pieceCap, stream, args);
 }

@@ -369,6 +369,82 @@ static inline RangeSortLayout MakeRangeSortLayout(uint32_t maxElementCount, uint
   return r;
 }
 
+// The balanced segmented sort (vrdxHipCmdBalancedSortSegmented[KeyValue]; PlanBalancedSegmentedSort in vrdx_plan.h;
+// vrdx_kernels.hip, "balanced segmented sort").  segmented_split_kernel decides on the device which
+// segments of the large list are SPREAD -- cut into pieces that many workgroups sort together -- and which stay with one
+// workgroup each (the rest list):
+//   totalLarge = the lengths of all listed segments added up (64 bits: offsets that overlap can exceed 2^32)
+//   share      = ceil(totalLarge / CUs)
+//   spread     <=> len > max(kSegSpreadFrom, kSegSpreadShares * share)
+//   L          = max(kSegPieceMinKeys, ceil(totalSpread / CUs) rounded up to a multiple of 256), the piece length;
+//                a spread segment [b, e) is cut into [b + k L, min(e, b + (k + 1) L))
+// kSegSpreadFrom: four tiles of the large kernel -- below that one workgroup takes about 110 us, what a dozen launches cost
+// anyway.  kSegSpreadShares: one workgroup sorts 0.58 keys/ns, the chunked form 55 keys/ns with 256 CUs, so the two break even
+// where a segment is 2.8 shares long; 3 is that, rounded up.  Both are derived from recorded runs and may be changed only with
+// the measurement of tools/segmented_balanced_bench.py recorded in profiles/.
+// The caps, from maxElementCount and the CU count alone (valid offsets: segments are disjoint):
+//   spread segments  S <= N / (kSegSpreadFrom + 1): each holds more than kSegSpreadFrom of the N elements; and
+//                    S <= (CUs - 1) / kSegSpreadShares: S x 3 x share < totalSpread <= totalLarge <= CUs x share, so S < CUs / 3
+//                    (this one holds for overlapping segments too)
+//   pieces           sum of ceil(len / L) <= floor(totalSpread / L) + S, and totalSpread / L <= CUs (L >= totalSpread / CUs)
+//                    and <= N / kSegPieceMinKeys (L >= kSegPieceMinKeys): min(CUs, N / kSegPieceMinKeys) + the cap of S
+// Only offsets that already raise VRDX_HIP_STATUS_SEGMENTS_INVALID can exceed a cap; a segment that finds no room in a table
+// goes to the rest list, which holds every listed segment.
+constexpr uint32_t kSegSpreadFrom = 65536u;
+constexpr uint32_t kSegSpreadShares = 3u;
+constexpr uint32_t kSegPieceMinKeys = 16384u;
+constexpr uint32_t kSegSpreadEntryWords = 8u;  // begin, end, firstPiece, pieceCount, mask of active passes, segment id, -, -
+constexpr uint32_t kSegPieceEntryWords = 4u;   // the segment's slot, begin, end, -
+constexpr uint32_t kSegSplitWords = 8u;        // listed, spread, pieces, L (vrdxHipReadBalancedSplit); the rest list's count; -
+constexpr uint32_t kSegSpreadMaxSlots = 256u;  // the split kernel keeps the spread table in LDS while it builds it (769 CUs)
+static constexpr uint32_t SegSpreadCap(uint32_t maxElementCount, uint32_t cus) {
+  const uint32_t bySize = maxElementCount / (kSegSpreadFrom + 1u);
+  const uint32_t shares = cus != 0 ? (cus - 1u) / kSegSpreadShares : 0u;
+  const uint32_t byShare = shares < kSegSpreadMaxSlots ? shares : kSegSpreadMaxSlots;
+  return bySize < byShare ? bySize : byShare;
+}
+static constexpr uint32_t SegPieceCap(uint32_t maxElementCount, uint32_t cus) {
+  const uint32_t spread = SegSpreadCap(maxElementCount, cus);
+  const uint32_t bySize = maxElementCount / kSegPieceMinKeys;
+  return spread != 0 ? (cus < bySize ? cus : bySize) + spread : 0u;
+}
+
+// Its carving of the 32-bit storage: MakeSegmentedLayout's header, counters and lists where they are, and behind the lists,
+// still inside the reference's partition-histogram area (ceil(N / 4096) KiB):
+//   restListOffset    uint32[largeCap]: the listed segments that are not spread
+//   splitOffset       uint32[kSegSplitWords]
+//   spreadTableOffset uint32[spreadCap][kSegSpreadEntryWords]
+//   pieceTableOffset  uint32[pieceCap][kSegPieceEntryWords]
+//   rowsOffset        on a 128-byte line: uint32[pieceCap][256], per piece the pass's counts, then its positions -- at most
+//                     N / 16384 + N / 65537 KiB
+//   keysScratch, valuesScratch  behind them, 128-byte aligned as ever
+struct BalancedSegmentedLayout {
+  SegmentedLayout lists;  // counters, lists, caps, the scratch arrays and `fits`
+  uint64_t restListOffset, splitOffset, spreadTableOffset, pieceTableOffset, rowsOffset;
+  uint32_t spreadCap, pieceCap;
+};
+
+static inline BalancedSegmentedLayout MakeBalancedSegmentedLayout(uint32_t maxElementCount, uint32_t align, uint32_t cus,
+                                                                  bool keyValue, uint64_t storageAddress = 0) {
+  const StorageLayout l = MakeLayout(maxElementCount, align, 0, storageAddress);
+  BalancedSegmentedLayout b;
+  SegmentedLayout& s = b.lists;
+  b.restListOffset = PlaceSegmentLists(s, l, maxElementCount, 1024u * 16u + 1u);
+  b.spreadCap = SegSpreadCap(maxElementCount, cus);
+  b.pieceCap = SegPieceCap(maxElementCount, cus);
+  b.splitOffset = b.restListOffset + 4ull * s.largeCap;
+  b.spreadTableOffset = b.splitOffset + 4ull * kSegSplitWords;
+  b.pieceTableOffset = b.spreadTableOffset + 4ull * kSegSpreadEntryWords * b.spreadCap;
+  const uint64_t tablesEnd = b.pieceTableOffset + 4ull * kSegPieceEntryWords * b.pieceCap;
+  b.rowsOffset = tablesEnd + ((0 - (storageAddress + tablesEnd)) & 127u);
+  const uint64_t rowsEnd = b.rowsOffset + (uint64_t)b.pieceCap * VRDX_RADIX * sizeof(uint32_t);  // (a multiple of 128 again)
+  s.keysScratchOffset = rowsEnd;
+  s.valuesScratchOffset = s.keysScratchOffset + (((uint64_t)maxElementCount * sizeof(uint32_t) + 127u) & ~(uint64_t)127u);
+  const uint64_t bytes = (uint64_t)maxElementCount * sizeof(uint32_t);
+  s.fits = s.keysScratchOffset + bytes <= l.keysOnlySize && (!keyValue || s.valuesScratchOffset + bytes <= l.keyValueSize);
+  return b;
+}
+
 // The MSD plan's scatter (msd_scatter_or_pass0_kernel, one workgroup per CU and tile) cuts the sort into EQUAL tiles that fill whole
 // rounds of `cus` tiles: keys per tile, a multiple of 4096 (four 64-key slots per wave of its 1024 threads), at most 32768.
 // 520 tiles of 32768 keys would cost three rounds, the third for eight tiles; 768 tiles of 24576 cost three rounds of three

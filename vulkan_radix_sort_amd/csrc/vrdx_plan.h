@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "../../include/vk_radix_sort.h"
+#include "../../include/vk_radix_sort_balanced.h"
 #include "vrdx_kernels.h"
 #include "vrdx_layout.h"
 
@@ -531,6 +532,78 @@ static inline SegmentedPlan PlanSegmentedSort(const PlanContext& c, uint32_t key
   return p;
 }
 
+// ---- the balanced segmented sort (vrdxHipCmdBalancedSortSegmented[KeyValue]; include/vk_radix_sort.h) ----
+// Up to kSegSpreadFrom elements -- and where the CU count admits no spread segment -- no segment can be spread and the plan IS
+// PlanSegmentedSort's (`twin`, which the recorder hands to the recorder of vrdxHipCmdSortSegmented*: the same launches, the same
+// slots).  Beyond that a step list of its own on the storage of MakeBalancedSegmentedLayout (vrdx_kernels.hip, "balanced
+// segmented sort") -- SegmentedPlan stays what it is:
+//   segmented_clear_kernel                                              slot 1
+//   segmented_small_kernel                                              slot 2
+//   segmented_mid_kernel                                                slot 3
+//   segmented_split_kernel, segmented_large_kernel on the rest list     slot 4
+//   byte p = 0 ... 3:  segmented_piece_count_kernel, _scan_kernel       slot 5 + 2 p
+//                      segmented_piece_scatter_kernel                   slot 6 + 2 p
+//   segmented_piece_copy_back_kernel                                    slot 13 (slot 14 coincides)
+// 18 launches, known from the bound alone; which segments are spread, which passes are active and whether the copy back copies
+// is decided on the device.  Grids depend on segmentCount, maxElementCount and the CU count only, so a captured call replays
+// on any segmentation with the same segmentCount.  Chosen by size alone: no planning knob selects anything in it.
+enum class BalancedForm : uint8_t { kNone, kTwin, kBalanced };  // VRDX_HIP_BALANCED_*
+enum class StepBalanced : uint8_t { kClear, kSmall, kMid, kSplit, kLargeRest, kCount, kScan, kScatter, kCopyBack };
+struct BalancedSegmentedStep { StepBalanced what; uint8_t pass, slot; const char* name; uint32_t grid; };
+constexpr uint32_t kMaxBalancedSteps = 6 + 3 * VRDX_PASSES;
+struct BalancedSegmentedPlan {
+  BalancedForm form = BalancedForm::kNone;
+  SegmentedPlan twin{};             // every form but kBalanced: PlanSegmentedSort's plan
+  bool keyValue = false;
+  bool atomicRank = false;
+  uint32_t computeUnits = 0;
+  const char* refusal = nullptr;    // the layout does not fit (cannot happen: see MakeBalancedSegmentedLayout)
+  BalancedSegmentedLayout layout{};  // kBalanced only
+  BalancedSegmentedStep steps[kMaxBalancedSteps];
+  uint32_t stepCount = 0;
+  uint32_t launches = 0;            // kernels among the steps (the fill is one)
+};
+
+static inline BalancedSegmentedPlan PlanBalancedSegmentedSort(const PlanContext& c, bool keyValue, uint32_t maxElementCount,
+                                                              uint32_t segmentCount, uint64_t storageAddress) {
+  BalancedSegmentedPlan p;
+  p.keyValue = keyValue;
+  p.atomicRank = c.atomicRank;
+  p.computeUnits = (uint32_t)c.computeUnits;
+  if (maxElementCount <= kSegSpreadFrom || segmentCount == 0 || SegSpreadCap(maxElementCount, p.computeUnits) == 0) {
+    p.twin = PlanSegmentedSort(c, 4, keyValue, maxElementCount, segmentCount, SegmentedKey{}, storageAddress);
+    p.refusal = p.twin.refusal;
+    p.launches = p.twin.stepCount;
+    p.form = p.twin.stepCount != 0 ? BalancedForm::kTwin : BalancedForm::kNone;
+    return p;
+  }
+  p.layout = MakeBalancedSegmentedLayout(maxElementCount, c.minStorageBufferOffsetAlignment, p.computeUnits, keyValue, storageAddress);
+  if (!p.layout.lists.fits) {
+    p.refusal = "balanced segmented storage layout";
+    return p;
+  }
+  p.form = BalancedForm::kBalanced;
+  const auto add = [&p](StepBalanced what, const char* name, uint32_t slot, uint32_t grid, uint32_t pass = 0) {
+    p.steps[p.stepCount++] = BalancedSegmentedStep{what, (uint8_t)pass, (uint8_t)slot, name, grid};
+    ++p.launches;
+  };
+  // the twin's grids (PlanSegmentedSort): beyond kSegSpreadFrom elements both lists hold a segment at least, so none is 0
+  const uint32_t resident = 2u * p.computeUnits;
+  const SegmentedLayout& s = p.layout.lists;
+  add(StepBalanced::kClear, "segmented_clear_kernel", 1, 1u);
+  add(StepBalanced::kSmall, "segmented_small_kernel", 2, std::min<uint32_t>(segmentCount, 1u << 20));
+  add(StepBalanced::kMid, "segmented_mid_kernel", 3, std::min<uint32_t>(std::min<uint32_t>(segmentCount, s.midCap), resident));
+  add(StepBalanced::kSplit, "segmented_split_kernel", 4, 1u);
+  add(StepBalanced::kLargeRest, "segmented_large_kernel", 4, std::min<uint32_t>(std::min<uint32_t>(segmentCount, s.largeCap), resident));
+  for (uint32_t pass = 0; pass < VRDX_PASSES; ++pass) {
+    add(StepBalanced::kCount, "segmented_piece_count_kernel", 5 + 2 * pass, p.layout.pieceCap, pass);
+    add(StepBalanced::kScan, "segmented_piece_scan_kernel", 5 + 2 * pass, p.layout.spreadCap, pass);
+    add(StepBalanced::kScatter, "segmented_piece_scatter_kernel", 6 + 2 * pass, p.layout.pieceCap, pass);
+  }
+  add(StepBalanced::kCopyBack, "segmented_piece_copy_back_kernel", 13, p.layout.pieceCap);
+  return p;
+}
+
 // ---- the 64-bit sorts (vrdxHipCmdSort64[Ordered][KeyValue][Indirect]) ----
 // Two stable 32-bit key+value sorts, low words first and high words second, on word arrays inside the storage (vrdx_layout.h,
 // MakeSort64Layout), with the streaming kernels of vrdx_kernels.hip ("64-bit keys") around them:
@@ -754,6 +827,18 @@ static inline void DescribeRangeSortPlan(const RangeSortPlan& plan, VrdxHipRange
   info->digits = plan.digits;
   info->bytesPerElementPerPass = plan.keyValue ? 20u : 12u;  // count (keys read) + scatter (read + write)
   info->bytesPerElementCopyBack = plan.keyValue ? 16u : 8u;
+}
+
+// What vrdxHipDescribeBalancedSegmentedPlan reports of a plan (include/vk_radix_sort.h); *info zeroed by the caller.
+static inline void DescribeBalancedSegmentedPlan(const BalancedSegmentedPlan& plan, VrdxHipBalancedSegmentedPlanInfo* info) {
+  info->form = (uint32_t)plan.form;
+  info->launches = plan.launches;
+  info->spreadFrom = kSegSpreadFrom;
+  info->spreadShares = kSegSpreadShares;
+  info->minPieceKeys = kSegPieceMinKeys;
+  if (plan.form != BalancedForm::kBalanced) return;
+  info->spreadCap = plan.layout.spreadCap;
+  info->pieceCap = plan.layout.pieceCap;
 }
 
 }  // namespace vrdx
